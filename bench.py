@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- scans/sec of the urban_road_filter classification hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scans S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scans S] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One STEP = one pass of the whole hot path (all kernels of urf_classify_batch_soa: ROI, ring
@@ -23,9 +23,22 @@ The default backend is nccl (= RCCL on ROCm).  --force-dist initialises the proc
 and runs the same barrier and all-reduces on device tensors: the RCCL plumbing (communicator, device
 tensors, destroy) on the one GPU a test box has.
 
-Rank 0 at N = 1 also measures, each behind its own parity gate and in a few seconds, the other
-BASELINE.json configurations (`other_configs`: cfg2 single sweep, cfg5 128x4096, the reference's
-default ROI); `value` / `config` / `roofline` are cfg3's.
+A plain run does only what `value` needs: generate and upload the batch, W warm-up steps, K timed
+steps, the line.  Everything else is behind --full (off by default): the parity gate against the CPU
+oracle before the warm-up, a second pass of the K steps with per-kernel event brackets (`kernel_ms`,
+`roofline`), the optional outputs' timings and, on rank 0 at N = 1 for cfg3, the reference's CPU
+path (`cpu_baseline`), the callback path and the C++ adapter (`e2e_*`, `adapter_e2e`) and, each
+behind its own parity gate, the other BASELINE.json configurations (`other_configs`: cfg2 single
+sweep, cfg5 128x4096, the reference's default ROI, ...); `value` / `config` / `roofline` are cfg3's.
+Without --full, `roofline`, `kernel_ms`, `outputs_ms_per_batch` and `cpu_baseline` are null,
+`parity_checked_scans` is empty and the other keys named above are absent.  The --no-* options and
+--parity-scans trim a --full run.
+
+--dump-outputs DIR writes, right after the timed steps, what the last of them handed the caller
+(rank 0's batch): DIR/labels.npy (float32 [k, points]: the labels of k scans, a fixed seeded sample
+of at most 32 MiB), DIR/labels_scans.npy (float64 [k]: which scans) and DIR/info.npy (float64 [S, 8]:
+every scan's struct urf_scan_info).  The inputs depend on the arguments alone, so two builds run
+with the same arguments can be compared file by file.
 """
 import argparse
 import concurrent.futures as cf
@@ -341,6 +354,21 @@ def _timed_steps(torch, stream, fn, steps, warmup):
     return 1e3 * (time.perf_counter() - t0) / steps
 
 
+DUMP_LABEL_BYTES = 32 << 20   # the labels' share of --dump-outputs (float32); info adds 64 B per scan
+
+
+def dump_outputs(torch, out_dir, dl, di, S):
+    """--dump-outputs: the arrays the timed step hands its caller, as float32 / float64 .npy files -- the labels of
+    a fixed seeded sample of scans (all of them when they fit DUMP_LABEL_BYTES) and every scan's urf_scan_info."""
+    os.makedirs(out_dir, exist_ok=True)
+    k = min(S, max(1, DUMP_LABEL_BYTES // (4 * N_PTS)))
+    scans = np.arange(S) if k == S else np.sort(np.random.default_rng(20261016).choice(S, k, replace=False))
+    rows = dl.index_select(0, torch.from_numpy(scans).to(dl.device))
+    np.save(os.path.join(out_dir, "labels.npy"), rows.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "labels_scans.npy"), scans.astype(np.float64))
+    np.save(os.path.join(out_dir, "info.npy"), di.cpu().numpy().astype(np.float64))
+
+
 def other_configs(u, O, torch, ctx, stream, dev, dx, dy, dz, dl, di, X, Y, Z, S):
     """The remaining BASELINE.json configurations that fit one GPU, each behind its own parity gate (labels ==
     CPU oracle on sampled scans) and timed like the headline (inputs resident, whole pipeline per step):
@@ -503,6 +531,52 @@ def other_configs(u, O, torch, ctx, stream, dev, dx, dy, dz, dl, di, X, Y, Z, S)
     return res
 
 
+def kernel_figures(kms, kcalls, front_scans, S, ms_step):
+    """--full: `roofline`, `kernel_ms` and `kernel_ms_note` of the line from the pass with per-kernel event brackets."""
+    if front_scans == S:   # every scan took the fused front end: the three brackets hold its kernels (urf_front.hpp)
+        kms = {FRONT_NAMES.get(k, k): v for k, v in kms.items()}
+    dom = max(kms, key=lambda k: kms[k])
+    dom_ms = kms[dom] / max(kcalls, 1)
+    alg_bytes_launch = ALG_BYTES_PER_SCAN * S
+    achieved = alg_bytes_launch / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+    whole = ALG_BYTES_PER_SCAN * S / (ms_step * 1e-3) / 1e9
+    out = {"roofline": {"bound": "hbm", "whole_pipeline_frac": round(whole / HBM_PEAK_GBS, 5), "whole_pipeline_achieved": round(whole, 2),
+                        "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
+                        "frac_note": "achieved / frac are the contract's: the WHOLE algorithm's bytes over the DOMINANT kernel's time; "
+                                     "whole_pipeline_frac divides the same bytes by the whole step and is the figure to compare with the north-star's 40 %",
+                        "kernel": dom, "kernel_ms": round(dom_ms, 4),
+                        "kernel_ms_source": "hipEvent pairs around the kernel on the launch stream, mean over the timed steps "
+                                            "(rocprofv3 --kernel-trace of the same command: profiles/*_kernel_stats.txt)",
+                        "algorithmic_bytes_per_launch": alg_bytes_launch},
+           "kernel_ms": {k: round(v / max(kcalls, 1), 4) for k, v in kms.items()},
+           "kernel_ms_note": FRONT_NOTE if front_scans else None}
+    traffic_file = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+    if os.path.exists(traffic_file):
+        try:
+            tr = json.load(open(traffic_file))
+            if tr.get("scans_per_launch") == S and tr.get("pipeline_bytes_per_step"):
+                out["roofline"]["traffic_pipeline"] = tr["pipeline_bytes_per_step"]   # all kernels of one step
+            if tr.get("kernel") == dom and tr.get("scans_per_launch") == S:
+                out["roofline"]["traffic"] = tr["hbm_bytes_per_launch"]
+                out["roofline"]["traffic_source"] = "profiles/hbm_traffic.json (rocprofv3 --pmc, reads corrected for gfx950: 2 x FETCH_SIZE)"
+            if tr.get("valu_insts_per_step") and tr.get("scans_per_launch") == S:
+                # The other ceiling: vector-instruction issue.  Measured on this chip (tools/bench_micro/valubench.hip,
+                # profiles/r4_valubench.txt): a SIMD issues 1.05 G wave64 instructions/s of the two-operand kind (2.3 cycles
+                # at 2.4 GHz -- the chip's documented two cycles, not the four DESIGN.md assumed until r3) and 0.57-0.63 G/s
+                # of the three-operand / compare / 64-bit kind (4 cycles); 256 CUs x 4 SIMDs.
+                n_inst, simds = float(tr["valu_insts_per_step"]), 1024.0
+                fast, slow = 1e3 * n_inst / (simds * 1.05e9), 1e3 * n_inst / (simds * 0.60e9)
+                out["roofline"]["valu_issue"] = {
+                    "insts_per_step": int(n_inst), "insts_source": "profiles/hbm_traffic.json (rocprofv3 --pmc SQ_INSTS_VALU, summed over the pipeline's kernels)",
+                    "rate_source": "profiles/r4_valubench.txt: 1.05e9 (two-operand VALU) .. 0.60e9 (three-operand, compare, f64) wave-instructions/s/SIMD",
+                    "ceiling_ms": round(fast, 4), "ceiling_ms_all_slow_encodings": round(slow, 4),
+                    "frac": round(fast / ms_step, 4), "frac_all_slow_encodings": round(slow / ms_step, 4)}
+        except Exception:
+            pass
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -519,6 +593,10 @@ def main():
     ap.add_argument("--front", type=int, default=-1, help="urf_set_front_mode: 0 legacy kernels only, 1 / 2 the fused front end (default: the library's)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (backend as given) even with one rank and run its barrier / all-reduces")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/*.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity gate, per-kernel times, roofline, CPU baseline, callback path and other configurations")
     args = ap.parse_args()
 
     import torch   # first: the HIP runtime torch bundles is the one the C-ABI library binds to
@@ -593,7 +671,9 @@ def main():
     step()
     torch.cuda.synchronize()
     front_scans = ctx.front_scans()   # scans of the batch that took the fused front end (urf_front.hpp)
-    picked = sorted(np.random.default_rng(20260925 + rank).choice(S, min(args.parity_scans, S), replace=False).tolist())
+    picked = []
+    if args.full:
+        picked = sorted(np.random.default_rng(20260925 + rank).choice(S, min(args.parity_scans, S), replace=False).tolist())
     for s in picked:   # a seeded random sample of the batch, not its first scans
         lb, _, _ = O.run_b(X[s], Y[s], Z[s], params)
         L = dl[s].cpu().numpy()
@@ -620,21 +700,25 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     step_ms = [ev[k].elapsed_time(ev[k + 1]) for k in range(args.steps)]
+    if args.dump_outputs and rank == 0:   # (before anything else writes dl / di)
+        dump_outputs(torch, args.dump_outputs, dl, di, S)
     # per-kernel times come from a SECOND pass of the same K steps with the library's event brackets on (hipEvent pairs
     # around every kernel on the launch stream): `value` above is from a pass without them
-    ctx.enable_kernel_timing(True)
-    ctx.kernel_timing()                     # reset
-    ctx.enable_kernel_timing(True)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    kms, kcalls = ctx.kernel_timing()
-    ctx.enable_kernel_timing(False)
+    kms, kcalls = None, 0
+    if args.full:
+        ctx.enable_kernel_timing(True)
+        ctx.kernel_timing()                     # reset
+        ctx.enable_kernel_timing(True)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        kms, kcalls = ctx.kernel_timing()
+        ctx.enable_kernel_timing(False)
 
     # the optional outputs of SURVEY.md 8f for the whole batch (not part of `value`): index sets,
     # published order, marker points
     outputs_ms = None
-    if world == 1 and args.workload == "cfg3" and not args.no_outputs:
+    if args.full and world == 1 and args.workload == "cfg3" and not args.no_outputs:
         idx = [torch.empty((S, N_PTS), dtype=torch.int32, device=dev) for _ in range(4)]
         cnt = torch.zeros((S, 4), dtype=torch.int32, device=dev)
         mpts = torch.empty((S, 361, 4), dtype=torch.float32, device=dev)
@@ -661,12 +745,6 @@ def main():
         total_scans = int(counters[0])
         value = total_scans / elapsed_max
         ms_step = 1e3 * elapsed_max / args.steps
-        if front_scans == S:   # every scan took the fused front end: the three brackets hold its kernels (urf_front.hpp)
-            kms = {FRONT_NAMES.get(k, k): v for k, v in kms.items()}
-        dom = max(kms, key=lambda k: kms[k])
-        dom_ms = kms[dom] / max(kcalls, 1)
-        alg_bytes_launch = ALG_BYTES_PER_SCAN * S
-        achieved = alg_bytes_launch / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
         whole = ALG_BYTES_PER_SCAN * S / (ms_step * 1e-3) / 1e9
         out = {
             "metric": "scans/sec (%d-ring x %d-column cloud)" % (RINGS, COLS),
@@ -686,17 +764,9 @@ def main():
                        "scans_per_gpu": S, "points_per_scan": N_PTS,
                        "sharding": "one batch per GPU (rank r classifies the contiguous seed block r*S+1 .. (r+1)*S), no data-path collective"},
             "hbm_roofline_frac_whole_pipeline": round(whole / HBM_PEAK_GBS, 5),   # 13 B/point x points/s over the WHOLE step / 8 TB/s: the honest figure
-            "roofline": {"bound": "hbm", "whole_pipeline_frac": round(whole / HBM_PEAK_GBS, 5), "whole_pipeline_achieved": round(whole, 2),
-                         "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
-                         "frac_note": "achieved / frac are the contract's: the WHOLE algorithm's bytes over the DOMINANT kernel's time; "
-                                      "whole_pipeline_frac divides the same bytes by the whole step and is the figure to compare with the north-star's 40 %",
-                         "kernel": dom, "kernel_ms": round(dom_ms, 4),
-                         "kernel_ms_source": "hipEvent pairs around the kernel on the launch stream, mean over the timed steps "
-                                             "(rocprofv3 --kernel-trace of the same command: profiles/*_kernel_stats.txt)",
-                         "algorithmic_bytes_per_launch": alg_bytes_launch},
-            "kernel_ms": {k: round(v / max(kcalls, 1), 4) for k, v in kms.items()},
-            "kernel_ms_note": FRONT_NOTE if front_scans else None,
+            "roofline": None,   # --full: per-kernel times from a pass of their own
+            "kernel_ms": None,
+            "kernel_ms_note": None,
             "outputs_ms_per_batch": outputs_ms,
             "counters": dict(zip(sharding.COUNTER_NAMES, [int(v) for v in counters])),
             "front_scans_per_gpu": front_scans,
@@ -707,39 +777,18 @@ def main():
             "h2d_seconds_per_batch": round(t_h2d, 4),
             "gen_seconds": round(t_gen, 2),
         }
-        traffic_file = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(traffic_file):
-            try:
-                tr = json.load(open(traffic_file))
-                if tr.get("scans_per_launch") == S and tr.get("pipeline_bytes_per_step"):
-                    out["roofline"]["traffic_pipeline"] = tr["pipeline_bytes_per_step"]   # all kernels of one step
-                if tr.get("kernel") == dom and tr.get("scans_per_launch") == S:
-                    out["roofline"]["traffic"] = tr["hbm_bytes_per_launch"]
-                    out["roofline"]["traffic_source"] = "profiles/hbm_traffic.json (rocprofv3 --pmc, corrected per MI355X_MICROARCH.md)"
-                if tr.get("valu_insts_per_step") and tr.get("scans_per_launch") == S:
-                    # The other ceiling: vector-instruction issue.  Measured on this chip (tools/bench_micro/valubench.hip,
-                    # profiles/r4_valubench.txt): a SIMD issues 1.05 G wave64 instructions/s of the two-operand kind (2.3 cycles
-                    # at 2.4 GHz -- MI355X_MICROARCH.md's "two cycles", not the four DESIGN.md assumed until r3) and 0.57-0.63 G/s
-                    # of the three-operand / compare / 64-bit kind (4 cycles); 256 CUs x 4 SIMDs.
-                    n_inst, simds = float(tr["valu_insts_per_step"]), 1024.0
-                    fast, slow = 1e3 * n_inst / (simds * 1.05e9), 1e3 * n_inst / (simds * 0.60e9)
-                    out["roofline"]["valu_issue"] = {
-                        "insts_per_step": int(n_inst), "insts_source": "profiles/hbm_traffic.json (rocprofv3 --pmc SQ_INSTS_VALU, summed over the pipeline's kernels)",
-                        "rate_source": "profiles/r4_valubench.txt: 1.05e9 (two-operand VALU) .. 0.60e9 (three-operand, compare, f64) wave-instructions/s/SIMD",
-                        "ceiling_ms": round(fast, 4), "ceiling_ms_all_slow_encodings": round(slow, 4),
-                        "frac": round(fast / ms_step, 4), "frac_all_slow_encodings": round(slow / ms_step, 4)}
-            except Exception:
-                pass
-        if world == 1 and not args.no_cpu_baseline and args.workload == "cfg3":
+        if kms is not None:
+            out.update(kernel_figures(kms, kcalls, front_scans, S, ms_step))
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "cfg3":
             out["cpu_baseline"] = cpu_baseline(params)
         else:
             out["cpu_baseline"] = None
-        if world == 1 and args.workload == "cfg3" and not args.no_other_configs:
+        if args.full and world == 1 and args.workload == "cfg3" and not args.no_other_configs:
             # (the outputs above read ring-sorted intermediate results: the context ran the batch again through the general kernels and
             # would stay with them -- include/urf.h; the configurations below are timed as a caller without those outputs sees them)
             ctx.set_front_mode(args.front if args.front >= 0 else 1)
             out["other_configs"] = other_configs(u, O, torch, ctx, stream, dev, dx, dy, dz, dl, di, X, Y, Z, S)
-        if world == 1 and not args.no_e2e and args.workload == "cfg3":
+        if args.full and world == 1 and not args.no_e2e and args.workload == "cfg3":
             ctx.close()   # the batch context's scratch is not needed any more
             e2e = e2e_callback_path(u, O, params)
             out.update(e2e)

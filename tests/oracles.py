@@ -3,9 +3,15 @@
 oracle B = oracle/liburf_oracle.so   (C restatement, travels to the GPU box)
 oracle A = oracle/_ref/urf_ref       (the reference's own sources; built only where
                                       /root/reference exists, the binary travels too)
+Where oracle A's binary is absent, run_a replays its recorded outputs (tests/golden/oracle_a/, keyed by
+the exact input bytes): tests/golden/make_oracle_a_records.py records them where the binary exists.
 """
+import atexit
 import ctypes as C
+import glob
+import hashlib
 import os
+import lzma
 import struct
 import subprocess
 import tempfile
@@ -19,6 +25,9 @@ ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_B = os.path.join(ORACLE_DIR, "liburf_oracle.so")
 ORACLE_A = os.path.join(ORACLE_DIR, "_ref", "urf_ref")
 ORACLE_A_LIBM = os.path.join(ORACLE_DIR, "_ref", "urf_ref_libm")   # same sources, float acos/asin/atan2 -> include/urf_libm.h
+RECORDS_A = os.path.join(ROOT, "tests", "golden", "oracle_a")   # oracle A's recorded outputs (*.npz: input key -> output bytes)
+RECORD_ENV = "URF_RECORD_ORACLE_A"   # set (to 1) while the tests run with oracle A: every live output is recorded
+RECORD_FILE_BYTES = 900 << 10       # one records file stays below the repository's 1 MiB limit
 REFERENCE = "/root/reference"
 
 
@@ -159,6 +168,52 @@ def run_b(x, y, z, params, debug=False):
     return labels, info.as_dict(), st
 
 
+_records = None    # key -> records file
+_recorded = {}     # key -> output bytes recorded in this process (RECORD_ENV)
+
+
+def _record_key(inp, libm):
+    return hashlib.sha256((b"libm:" if libm else b"host:") + inp).hexdigest()[:32]
+
+
+def _replay_a(key):
+    global _records
+    if _records is None:
+        _records = {}
+        for f in sorted(glob.glob(os.path.join(RECORDS_A, "*.npz"))):
+            with np.load(f) as z:
+                _records.update(dict.fromkeys(z.files, f))
+    assert key in _records, ("oracle A's binary is not built here and no recorded output matches this input "
+                             "(tests/golden/make_oracle_a_records.py records them where it is)")
+    with np.load(_records[key]) as z:
+        return lzma.decompress(z[key].tobytes())
+
+
+def write_records():
+    """RECORD_ENV: the outputs recorded by this process, merged into tests/golden/oracle_a/ (files below 1 MiB)."""
+    if not _recorded:
+        return
+    allr = {}
+    for f in sorted(glob.glob(os.path.join(RECORDS_A, "*.npz"))):
+        with np.load(f) as z:
+            allr.update({k: z[k] for k in z.files})
+        os.remove(f)
+    allr.update({k: np.frombuffer(lzma.compress(b, preset=9 | lzma.PRESET_EXTREME), np.uint8) for k, b in _recorded.items()})
+    os.makedirs(RECORDS_A, exist_ok=True)
+    part, size, n = {}, 0, 0
+    for k in sorted(allr):
+        if part and size + allr[k].nbytes > RECORD_FILE_BYTES:
+            np.savez(os.path.join(RECORDS_A, "records_%02d.npz" % n), **part)
+            part, size, n = {}, 0, n + 1
+        part[k] = allr[k]
+        size += allr[k].nbytes
+    np.savez(os.path.join(RECORDS_A, "records_%02d.npz" % n), **part)
+
+
+if os.environ.get(RECORD_ENV):
+    atexit.register(write_records)
+
+
 def run_a(scans, params, repeat=1, timeout=1200, marker_params=None, libm=False):
     """scans: list of (x, y, z) with equal length.  Returns (list of labels, list of info dicts,
     ms_per_scan_steady, ms_first).  The RING bit is not observable from the reference.
@@ -168,24 +223,30 @@ def run_a(scans, params, repeat=1, timeout=1200, marker_params=None, libm=False)
     libm=True runs the variant whose float acos / asin / atan2 calls are mapped onto include/urf_libm.h
     (oracle/shim/urf_libm_override.h): same reference sources, the product's definition of the three
     functions instead of the host's glibc."""
-    assert has_oracle_a(), "oracle A (reference build) not available"
     n = len(scans[0][0])
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(b"URFREFIN")
-            f.write(struct.pack("<4I", len(scans), n, repeat, 1 if marker_params is not None else 0))
-            f.write(bytes(params))
-            if marker_params is not None:
-                f.write(bytes(marker_params))
-            for x, y, z in scans:
-                assert len(x) == n
-                f.write(np.ascontiguousarray(x, np.float32).tobytes())
-                f.write(np.ascontiguousarray(y, np.float32).tobytes())
-                f.write(np.ascontiguousarray(z, np.float32).tobytes())
-        subprocess.run([ORACLE_A_LIBM if libm else ORACLE_A, fin, fout], check=True, timeout=timeout)
-        with open(fout, "rb") as f:
-            blob = f.read()
+    body = [bytes(params)]
+    if marker_params is not None:
+        body.append(bytes(marker_params))
+    for x, y, z in scans:
+        assert len(x) == n
+        body += [np.ascontiguousarray(a, np.float32).tobytes() for a in (x, y, z)]
+    body = b"".join(body)
+    flags = 1 if marker_params is not None else 0
+    key = _record_key(struct.pack("<4I", len(scans), n, 1, flags) + body, libm)   # (repeat only changes the timings)
+    if not has_oracle_a():
+        blob = _replay_a(key)
+    else:
+        with tempfile.TemporaryDirectory() as td:
+            fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
+            with open(fin, "wb") as f:
+                f.write(b"URFREFIN")
+                f.write(struct.pack("<4I", len(scans), n, repeat, flags))
+                f.write(body)
+            subprocess.run([ORACLE_A_LIBM if libm else ORACLE_A, fin, fout], check=True, timeout=timeout)
+            with open(fout, "rb") as f:
+                blob = f.read()
+        if os.environ.get(RECORD_ENV):
+            _recorded[key] = blob
     assert blob[:8] == b"URFREFOU"
     ns, nn = struct.unpack_from("<2I", blob, 8)
     ms_steady, ms_first = struct.unpack_from("<2d", blob, 16)

@@ -14,7 +14,6 @@ from fuzz import case
 GLIBC_DEPENDENT = {49: 1, 78: 2}   # (78: a tie-bearing cloud, x / y on a 1/16 m grid: many points share a vertical angle)
 
 
-@pytest.mark.skipif(not O.has_oracle_a(), reason="oracle A binary (reference build) not available")
 @pytest.mark.parametrize("seed", range(100))
 def test_oracle_b_equals_reference_on_random_input(seed):
     (x, y, z), p = case(1000 + seed, for_reference=True)
@@ -32,7 +31,6 @@ def test_oracle_b_equals_reference_on_random_input(seed):
             assert ia[0][k] == ib[k], k
 
 
-@pytest.mark.skipif(not O.has_oracle_a(), reason="oracle A binary (reference build) not available")
 @pytest.mark.parametrize("seed", range(0, 140))
 def test_oracle_b_equals_reference_with_shared_libm(seed):
     """Same comparison against the reference sources built with the product's definition of
@@ -48,7 +46,6 @@ def test_oracle_b_equals_reference_with_shared_libm(seed):
             assert np.array_equal(ia[0][key], st[key]), key
 
 
-@pytest.mark.skipif(not O.has_oracle_a(), reason="oracle A binary (reference build) not available")
 @pytest.mark.parametrize("seed,pairs", [(201, 1500), (202, 40), (203, 1500)])
 def test_oracle_b_equals_reference_with_nan_slopes(seed, pairs):
     """Identical points in a star sector: the slope between them is 0 / 0, which the reference counts and skips
@@ -64,7 +61,6 @@ def test_oracle_b_equals_reference_with_nan_slopes(seed, pairs):
         assert ia[0][k] == ib[k], k
 
 
-@pytest.mark.skipif(not O.has_oracle_a(), reason="oracle A binary (reference build) not available")
 @pytest.mark.parametrize("scene,cfg,seed", [(3, "cfg2", 11), (3, "cfg2", 12), (4, "narrow", 13), (3, "default_roi", 14)])
 def test_oracle_b_equals_reference_on_sensor_like_sweeps(scene, cfg, seed):
     """Sweeps as a sensor's driver delivers them (range noise, 2 mm range steps, drop-outs; ~10 000 exact planar-range ties
@@ -80,7 +76,6 @@ def test_oracle_b_equals_reference_on_sensor_like_sweeps(scene, cfg, seed):
         assert np.array_equal(ia[0][key], st[key]), key
 
 
-@pytest.mark.skipif(not O.has_oracle_a(), reason="oracle A binary (reference build) not available")
 @pytest.mark.parametrize("n,dup", [(364, 0.0), (364, 0.1), (1024, 0.1), (4000, 0.05)])
 def test_oracle_b_equals_reference_when_std_sort_reaches_its_depth_limit(n, dup):
     """One star sector whose ranges, in input order, are an adversarial sequence for libstdc++'s introsort (McIlroy's

@@ -25,7 +25,7 @@ def run_bench(*args):
 
 def test_two_ranks_over_gloo_on_one_device():
     S, K = 48, 2
-    d = run_bench("--gpus", "2", "--backend", "gloo", "--scans", str(S), "--steps", str(K), "--warmup", "1",
+    d = run_bench("--full", "--gpus", "2", "--backend", "gloo", "--scans", str(S), "--steps", str(K), "--warmup", "1",
                   "--no-cpu-baseline", "--parity-scans", "2")
     assert d["n_gpus"] == 2 and d["backend"] == "gloo" and d["scaling"] == "weak"
     c = d["counters"]
@@ -36,7 +36,7 @@ def test_two_ranks_over_gloo_on_one_device():
 
 
 def test_single_rank_line_has_the_contract_keys():
-    d = run_bench("--scans", "32", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--front", "2")   # (mode 1 starts at 192 scans)
+    d = run_bench("--full", "--scans", "32", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--front", "2")   # (mode 1 starts at 192 scans)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "other_configs"):
         assert k in d, k
@@ -54,7 +54,7 @@ def test_single_rank_line_has_the_contract_keys():
 
 
 def test_row_major_workload():
-    d = run_bench("--workload", "ring_major", "--scans", "32", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--front", "2")
+    d = run_bench("--full", "--workload", "ring_major", "--scans", "32", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--front", "2")
     assert d["front_scans_per_gpu"] == 32 and d["value"] > 0 and "k_front" in d["kernel_ms"]
     assert "row-major" in d["config"]["workload"]
 
@@ -64,9 +64,38 @@ def test_rccl_with_one_rank():
     and world size 1, the barrier and both all-reduces run on device tensors, the group is destroyed.  What stays
     unproven without a multi-GPU node: RCCL between ranks."""
     S, K = 32, 2
-    d = run_bench("--force-dist", "--scans", str(S), "--steps", str(K), "--warmup", "1", "--no-cpu-baseline", "--no-e2e",
+    d = run_bench("--full", "--force-dist", "--scans", str(S), "--steps", str(K), "--warmup", "1", "--no-cpu-baseline", "--no-e2e",
                   "--no-other-configs", "--no-outputs")
     assert d["backend"] == "nccl" and d["n_gpus"] == 1
     c = d["counters"]   # unchanged by the reduction over one rank
     assert c["scans"] == S * K and c["points_in"] == S * K * 64 * 2048 and c["ok_scans"] == S * K
     assert 0 < c["curb"] < c["road"] < c["roi_points"] <= c["points_in"]
+
+
+def test_plain_run_dumps_what_the_timed_step_computed(tmp_path):
+    """A plain run (no --full) times the steps and prints the line without the extras; --dump-outputs writes the labels and
+    scan infos of the last timed step, the labels equal the CPU oracle's and a second run with the same arguments dumps the same."""
+    import numpy as np
+    import oracles as O
+    import urban_road_filter_amd as u
+    S, K = 8, 3
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d = run_bench("--scans", str(S), "--steps", str(K), "--warmup", "1", "--dump-outputs", str(out))
+        assert d["steps"] == K and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "scans/s" and d["higher_is_better"] is True
+        assert d["counters"]["scans"] == S * K and d["counters"]["ok_scans"] == S * K
+        assert d["kernel_ms"] is None and d["roofline"] is None and d["cpu_baseline"] is None and d["parity_checked_scans"] == []
+        assert "other_configs" not in d and "e2e_latency_ms" not in d and "adapter_e2e" not in d
+        dumps.append({n: np.load(out / (n + ".npy")) for n in ("labels", "labels_scans", "info")})
+    a, b = dumps
+    assert a["labels"].dtype == np.float32 and a["labels"].shape == (S, 64 * 2048)
+    assert a["labels_scans"].dtype == np.float64 and np.array_equal(a["labels_scans"], np.arange(S))
+    assert a["info"].dtype == np.float64 and a["info"].shape == (S, 8)
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+    p = O.cfg_params("cfg2")
+    for s in (0, S - 1):   # scan s of rank 0 is seed s + 1 (sharding.shard_seeds)
+        lb, ib, _ = O.run_b(*u.synth_cloud(64, 2048, 1, s + 1), p)
+        assert np.array_equal(a["labels"][s], lb.astype(np.float32)), s
+        assert (a["info"][s, 4], a["info"][s, 5]) == (ib["n_road"], ib["n_curb"]), s

@@ -29,7 +29,6 @@ def b_markers(seq, p, mp):
     return out
 
 
-@pytest.mark.skipif(not O.has_oracle_a(), reason="oracle A binary (reference build) not available")
 @pytest.mark.parametrize("simp,zavg", [(1, 1), (0, 0), (1, 0), (0, 1)])
 def test_oracle_b_markers_equal_reference(simp, zavg):
     mp = O.MarkerParams.default()
@@ -42,7 +41,6 @@ def test_oracle_b_markers_equal_reference(simp, zavg):
         assert O.markers_equal(ia[k]["markers"], mb), "sweep %d" % k
 
 
-@pytest.mark.skipif(not O.has_oracle_a(), reason="oracle A binary (reference build) not available")
 def test_no_markers_for_degenerate_sweeps():
     """Fewer than 3 marker points: the reference publishes no MarkerArray (lidar_segmentation.cpp:371)."""
     p = O.cfg_params("cfg1")      # z_zero only, no blind spots -> everything road ... but ROI cut to a sliver:

@@ -11,7 +11,7 @@ EXTRA=${AB_ARGS:-"--steps 8 --warmup 2 --no-cpu-baseline"}
 for round in 1 2; do
 for lib in "$@"; do
   name=$(basename "$lib" .so)
-  URF_LIB_PATH="$REPO/$lib" timeout 300 python bench.py $EXTRA > "$OUT/$name.$round.json" 2> "$OUT/$name.$round.err" || echo "FAILED $name: $(tail -2 $OUT/$name.$round.err)"
+  URF_LIB_PATH="$REPO/$lib" timeout 300 python bench.py --full $EXTRA > "$OUT/$name.$round.json" 2> "$OUT/$name.$round.err" || echo "FAILED $name: $(tail -2 $OUT/$name.$round.err)"
   python - "$OUT/$name.$round.json" "$name" <<'PY'
 import json, sys
 try:

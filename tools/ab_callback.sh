@@ -9,7 +9,7 @@ for round in 1 2; do
 for lib in "$@"; do
   name=$(basename "$lib" .so)
   echo "== $name (round $round)"
-  URF_LIB_PATH="$REPO/$lib" timeout 120 python bench.py --workload cfg2 --steps 50 --warmup 5 --no-cpu-baseline --no-e2e --no-outputs --no-other-configs 2>/dev/null | python -c '
+  URF_LIB_PATH="$REPO/$lib" timeout 120 python bench.py --full --workload cfg2 --steps 50 --warmup 5 --no-cpu-baseline --no-e2e --no-outputs --no-other-configs 2>/dev/null | python -c '
 import json, sys
 for l in sys.stdin:
     if l.startswith("{"):

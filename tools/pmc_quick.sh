@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 case "$OUT" in /*) ;; *) OUT="$REPO/$OUT";; esac
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--workload $W --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-other-configs --parity-scans 0"
+ARGS="--full --workload $W --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-other-configs --parity-scans 0"
 pass() {
   name=$1; shift
   timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/$name" -o "$name" -- python "$REPO/bench.py" $ARGS > "$OUT/$name.log" 2>&1

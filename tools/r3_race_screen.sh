@@ -11,7 +11,7 @@ for lib in "$@"; do
   URF_LIB_PATH="$REPO/$lib" timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_batches.py tests/test_gpu_fuzz.py tests/test_gpu_async.py -m gpu -q --maxfail=50 > "$OUT/$name.log" 2>&1
   echo "$name rc=$? $(tail -1 "$OUT/$name.log")"
 done
-timeout 900 python bench.py --steps 10 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 10 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
 python - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

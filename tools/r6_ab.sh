@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the fused front end inside one gpurun call: same box, same batch
 mkdir -p gpurun_out
-Q="--no-cpu-baseline --no-e2e --no-outputs --no-other-configs --steps 20 --warmup 5"
+Q="--full --no-cpu-baseline --no-e2e --no-outputs --no-other-configs --steps 20 --warmup 5"
 for wl in cfg3 sensor; do
   for f in 0 1; do
     python bench.py $Q --workload $wl --front $f > gpurun_out/r6_ab_${wl}_front$f.json 2> gpurun_out/r6_ab_${wl}_front$f.err

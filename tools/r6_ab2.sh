@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B inside one gpurun call: libraries x workloads x front mode.  tools/r6_ab2.sh "<lib or - ...>" "<workload ...>" "<front ...>"
 mkdir -p gpurun_out
-Q="--no-cpu-baseline --no-e2e --no-outputs --no-other-configs --steps 20 --warmup 5"
+Q="--full --no-cpu-baseline --no-e2e --no-outputs --no-other-configs --steps 20 --warmup 5"
 for lib in $1; do for wl in $2; do for f in $3; do
   tag=$(basename $lib .so)_${wl}_f$f
   if [ "$lib" = "-" ]; then unset URF_LIB_PATH; else export URF_LIB_PATH=$PWD/$lib; fi
