@@ -64,6 +64,9 @@ extern "C" {
  * 5 (round 6): urf_set_front_mode / urf_front_scans (the fused front end for batches of organised sweeps: firing order and
  * row-major); the entry points that read ring-sorted intermediate results may run the last batch call again, see there;
  * urf_callback_path_preset.
+ * Additions under 5, additive (no existing entry point, struct or value changed): urf_classify_batch_pc2_ragged (ragged
+ * PointCloud2 batches), urf_clouds_batch_soa / urf_clouds_batch_pc2 with struct urf_point_xyzi, URF_ORDER_INPUT and
+ * URF_ORDER_REFERENCE (the four published clouds of a batch as device-resident records).
  * WHICH std::sort (4 above): the one of libstdc++ as shipped with GCC 5 .. 13 (bits/stl_algo.h: __sort = __introsort_loop with
  * _S_threshold 16, __move_median_to_first on (first + 1, mid, last - 1), __unguarded_partition, depth limit 2 * floor(log2 n),
  * __partial_sort as the fallback, then __final_insertion_sort); tests/test_stdsort.py pins the restatement against the std::sort
@@ -284,6 +287,50 @@ int urf_classify_batch_pc2(urf_ctx* ctx, const uint8_t* d_data, uint32_t n_per_s
                            uint32_t point_step, uint32_t off_x, uint32_t off_y, uint32_t off_z,
                            uint8_t* d_labels, urf_scan_info* d_info);
 
+/* The same with ragged scans, as urf_classify_batch_soa_ragged: scan s is records [d_offsets[s], d_offsets[s+1])
+ * of d_data (device array of n_scans+1 uint32; every message has the same record layout, back to back), its labels
+ * go to the same indices of d_labels.  n_total = d_offsets[n_scans] as a host value (records unpacked; at most
+ * max_points * max_batch of the context, else URF_ERR_CAPACITY), max_len >= the longest scan.  A zero-length message
+ * gets status URF_TOO_FEW_POINTS (what urf::Detector answers for an empty message).  Labels and summaries equal
+ * those of urf_classify_batch_soa_ragged on the same points.  Messages of variable length: drivers that drop
+ * non-returns (Velodyne's non-organised mode, any is_dense cloud). */
+int urf_classify_batch_pc2_ragged(urf_ctx* ctx, const uint8_t* d_data, const uint32_t* d_offsets, uint64_t n_total, uint32_t max_len, uint32_t n_scans, uint32_t point_step, uint32_t off_x, uint32_t off_y, uint32_t off_z, uint8_t* d_labels, urf_scan_info* d_info);
+
+/* ---- the published clouds of a batch, on the device ---------------------------
+ * The four clouds the reference publishes per sweep (lidar_segmentation.cpp:354-367, 605-608, 618-621) for every
+ * scan of the LAST classify call, which must have been one of the four batch entry points above (after a sweep of
+ * the callback path, or before any call: URF_ERR_INVALID_ARG -- the callback path has urf::Detector).  One record
+ * per point, the layout of pcl::PointXYZI and of urf::PointXYZI: x, y, z, intensity copied bit for bit from the
+ * input (NaN payloads and -0 survive), w = 1.0f, pad = 0.
+ *   d_records   all clouds back to back: scan by scan, inside a scan road, curb, roi, road_probably (the order of
+ *               urf_compact_indices' counts); NULL: only counts and offsets are written.  capacity (records) must
+ *               be at least 3 * n_scans * max_len of the call (road + curb and road_probably are subsets of roi),
+ *               else URF_ERR_CAPACITY.
+ *   d_counts    [4 * n_scans]: d_counts[4*s+k] records of cloud k of scan s (0 for a scan whose status is not URF_OK);
+ *   d_offsets   [4 * n_scans]: where that cloud starts in d_records (exclusive prefix of d_counts, 64 bit).
+ * order: URF_ORDER_INPUT, all four clouds in input order (urf::Detector's default), or URF_ORDER_REFERENCE: road,
+ * curb and road_probably in exactly the sequence urf_ordered_indices_batch returns, roi in input order.  The
+ * reference order runs urf_ordered_indices_batch's kernels and so inherits what it does after a call that took the
+ * fused front end (the call runs once more through the general kernels, and the context stays with them); input
+ * order reads nothing but the labels and the inputs.  Layout and values do not depend on scheduling.  Asynchronous
+ * on the context's stream, results stay on the device.
+ * urf_clouds_batch_soa: the last call was urf_classify_batch_soa(_ragged); x / y / z are read from that call's
+ * arrays, intensity from d_intensity (device, laid out like x; NULL: intensity 0).
+ * urf_clouds_batch_pc2: the last call was urf_classify_batch_pc2(_ragged); the caller passes the same message
+ * bytes again, x / y / z / intensity are read from the records (off_intensity = -1: the messages have no FLOAT32
+ * intensity field, intensity 0 -- what pcl::fromROSMsg leaves; otherwise off_intensity + 4 <= point_step).
+ * LIFETIME (as for urf_ordered_indices* below): the last call's d_labels must still be alive and unmodified, and so
+ * must its inputs -- d_x / d_y / d_z of a SoA call, d_data of a PointCloud2 call -- until these calls have completed. */
+typedef struct urf_point_xyzi {
+    float x, y, z, w;       /* w = 1.0f */
+    float intensity;
+    float pad[3];           /* 0 */
+} urf_point_xyzi;           /* 32 bytes */
+#define URF_ORDER_INPUT     0
+#define URF_ORDER_REFERENCE 1
+int urf_clouds_batch_soa(urf_ctx* ctx, const float* d_intensity, int order, urf_point_xyzi* d_records, uint64_t capacity, uint32_t* d_counts, uint64_t* d_offsets);
+int urf_clouds_batch_pc2(urf_ctx* ctx, const uint8_t* d_data, uint32_t point_step, uint32_t off_x, uint32_t off_y, uint32_t off_z, int32_t off_intensity, int order, urf_point_xyzi* d_records, uint64_t capacity, uint32_t* d_counts, uint64_t* d_offsets);
+
 /* ---- index-set outputs -----------------------------------------------------
  * Compacts the label bytes of ONE scan (device) into ascending index lists
  * (device, each with room for n_points entries; any may be NULL) and writes
@@ -318,7 +365,8 @@ int urf_compact_indices_batch(urf_ctx* ctx, const uint8_t* d_labels, uint32_t n_
  * and, for calls with ragged offsets, nothing else -- the x / y / z these kernels need were copied
  * into the context's scratch by the call itself.  d_labels of the last classify call must therefore
  * stay allocated and unmodified until the last of these calls on it has completed (for a sweep of the
- * callback path the library owns that buffer: nothing to keep alive). */
+ * callback path the library owns that buffer: nothing to keep alive).  urf_clouds_batch_* (above) read the last batch
+ * call's inputs as well: x / y / z of a SoA call, the message bytes of a PointCloud2 call. */
 int urf_ordered_indices(urf_ctx* ctx, uint32_t scan, uint32_t* road, uint32_t* curb, uint32_t* ring10,
                         uint32_t* counts);
 /* Every scan of the last classify call at once, results on the DEVICE (asynchronous on the

@@ -53,7 +53,8 @@ int urf_selftest(urf_ctx* ctx, uint64_t* n_mismatches);
  * has room for 4 floats.  Synchronous. */
 int urf_selftest_fast(urf_ctx* ctx, uint64_t n_samples, float* err);
 /* Test hook: bit 2 (value 4) forces the general (comparison network) path of the star-shaped sort
- * for every sector; 0 in production.  Takes effect with the next classify call. */
+ * for every sector; 0 in production.  Takes effect with the next classify call.  Bit 4 (value 16): urf_clouds_batch_*
+ * store their records with non-temporal stores (an A/B switch for tools/batch_clouds_bench.py: measured slower). */
 int urf_set_debug_flags(urf_ctx* ctx, uint32_t flags);
 
 #ifdef __cplusplus

@@ -9,6 +9,7 @@ from .api import (  # noqa: F401
     MarkerParams,
     ParamDesc,
     Params,
+    PointXYZI,
     ScanInfo,
     UrfError,
     clamp_params,
@@ -21,6 +22,7 @@ from .api import (  # noqa: F401
     test_lib,
     synth_cloud,
     pc2_to_planes,
+    ORDER_INPUT, ORDER_REFERENCE,
     LABEL_MASK, LABEL_ROAD, LABEL_CURB, FLAG_ROI, FLAG_RING, FLAG_RING10,
     STAGE_VALPHA, STAGE_RING, STAGE_AZIMUTH, STAGE_RANGE2D, STAGE_DETECT, STAGE_SECTOR,
     STAGE_ANGLE_TABLE, STAGE_MAXDIST, STAGE_QUADRANTS, STAGE_BEAM_STOP,

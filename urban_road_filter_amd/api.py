@@ -18,6 +18,7 @@ FLAG_ROI, FLAG_RING, FLAG_RING10 = 0x04, 0x08, 0x10
  STAGE_ANGLE_TABLE, STAGE_MAXDIST, STAGE_QUADRANTS, STAGE_BEAM_STOP) = range(1, 11)
 
 OK, TOO_FEW_POINTS = 0, 1
+ORDER_INPUT, ORDER_REFERENCE = 0, 1   # urf_clouds_batch_*: input order / the reference's published order
 
 
 class UrfError(RuntimeError):
@@ -65,6 +66,12 @@ class ScanInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PointXYZI(C.Structure):
+    """struct urf_point_xyzi: one record of the published clouds, the layout of pcl::PointXYZI (32 bytes)."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("w", C.c_float),
+                ("intensity", C.c_float), ("pad", C.c_float * 3)]
 
 
 class MarkerParams(C.Structure):
@@ -128,6 +135,10 @@ def lib(hooks=False):
         "urf_classify_batch_soa": [vp, fp, fp, fp, C.c_uint32, C.c_uint32, u8p, vp],
         "urf_classify_batch_soa_ragged": [vp, fp, fp, fp, u32p, C.c_uint32, C.c_uint32, u8p, vp],
         "urf_classify_batch_pc2": [vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp],
+        "urf_classify_batch_pc2_ragged": [vp, u8p, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.c_uint32, u8p, vp],
+        "urf_clouds_batch_soa": [vp, fp, C.c_int, vp, C.c_uint64, u32p, vp],
+        "urf_clouds_batch_pc2": [vp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int, vp, C.c_uint64, u32p, vp],
         "urf_compact_indices": [vp, u8p, C.c_uint32, u32p, u32p, u32p, u32p, u32p],
         "urf_compact_indices_batch": [vp, u8p, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p],
         "urf_ordered_indices_batch": [vp, u32p, u32p, u32p, C.c_uint32, u32p],
@@ -440,6 +451,26 @@ class Context:
         self._check(self._lib.urf_classify_batch_pc2(self._h, _ptr(d_data), n_per_scan, n_scans, point_step,
                                                      off_x, off_y, off_z, _ptr(d_labels), _ptr(d_info)),
                     "urf_classify_batch_pc2")
+
+    def classify_batch_pc2_ragged(self, d_data, d_offsets, n_total, max_len, n_scans, point_step, off_x, off_y, off_z, d_labels,
+                                  d_info=None):
+        """Ragged PointCloud2 batch: scan s = records [d_offsets[s], d_offsets[s+1]) of d_data; n_total = d_offsets[n_scans]."""
+        self._check(self._lib.urf_classify_batch_pc2_ragged(self._h, _ptr(d_data), _ptr(d_offsets), n_total, max_len, n_scans,
+                                                            point_step, off_x, off_y, off_z, _ptr(d_labels), _ptr(d_info)),
+                    "urf_classify_batch_pc2_ragged")
+
+    def clouds_batch_soa(self, d_intensity, order, d_records, capacity, d_counts, d_offsets):
+        """The four published clouds of every scan of the last (SoA) batch call as 32-byte records on the device:
+        d_counts / d_offsets [4 * n_scans] (uint32 / uint64), cloud order road, curb, roi, road_probably."""
+        self._check(self._lib.urf_clouds_batch_soa(self._h, _ptr(d_intensity), order, _ptr(d_records), capacity, _ptr(d_counts),
+                                                   _ptr(d_offsets)), "urf_clouds_batch_soa")
+
+    def clouds_batch_pc2(self, d_data, point_step, off_x, off_y, off_z, off_intensity, order, d_records, capacity, d_counts,
+                         d_offsets):
+        """The same after a PointCloud2 batch call: d_data = that call's message bytes; off_intensity -1: no intensity field."""
+        self._check(self._lib.urf_clouds_batch_pc2(self._h, _ptr(d_data), point_step, off_x, off_y, off_z, off_intensity, order,
+                                                   _ptr(d_records), capacity, _ptr(d_counts), _ptr(d_offsets)),
+                    "urf_clouds_batch_pc2")
 
     def compact_indices(self, d_labels, n_points, d_road, d_curb, d_roi, d_ring10, d_counts):
         self._check(self._lib.urf_compact_indices(self._h, _ptr(d_labels), n_points, _ptr(d_road), _ptr(d_curb),

@@ -1,6 +1,8 @@
 /* detector.cpp -- see detector.hpp.  Host code; all classification happens behind the C ABI. */
 #include "detector.hpp"
 
+#include <hip/hip_runtime_api.h>
+
 #include <cstring>
 
 namespace urf {
@@ -320,6 +322,168 @@ bool Detector::filtered(const PointCloud2& msg)
     uint64_t n = 0;
     resolve(msg, off, oi, n);
     return filtered(msg.data.data(), (uint32_t)n, msg.point_step, off[0], off[1], off[2], msg.header, oi);
+}
+
+/* ---- BatchDetector ------------------------------------------------------------------------------------- */
+BatchDetector::BatchDetector(int device, uint32_t max_points, uint32_t max_batch) : max_points_(max_points), max_batch_(max_batch)
+{
+    int rc = urf_create(&ctx_, device, max_points, max_batch);
+    if (rc != URF_OK)
+        throw Error(rc, std::string("urf_create: ") + urf_strerror(rc));
+    hipStream_t st = nullptr;   /* the uploads, the library's kernels and the read-backs in one stream order */
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+        urf_destroy(ctx_);
+        ctx_ = nullptr;
+        throw Error(URF_ERR_HIP, "BatchDetector: hipStreamCreate failed");
+    }
+    stream_ = st;
+    rc = urf_set_stream(ctx_, st);
+    if (rc != URF_OK) {
+        urf_destroy(ctx_);
+        ctx_ = nullptr;
+        (void)hipStreamDestroy(st);
+        throw Error(rc, std::string("urf_set_stream: ") + urf_strerror(rc));
+    }
+}
+
+BatchDetector::~BatchDetector()
+{
+    if (ctx_)
+        urf_destroy(ctx_);
+    for (void* p : { d_data_, d_records_, d_small_ })
+        if (p)
+            (void)hipFree(p);
+    if (stream_)
+        (void)hipStreamDestroy((hipStream_t)stream_);
+}
+
+void BatchDetector::check(int rc, const char* what) const
+{
+    if (rc < 0)
+        throw Error(rc, std::string(what) + ": " + urf_strerror(rc) + " " + urf_last_error(ctx_));
+}
+
+void BatchDetector::setParams(const urf_params& p) { check(urf_set_params(ctx_, &p), "urf_set_params"); }
+
+urf_params BatchDetector::params() const
+{
+    urf_params p;
+    check(urf_get_params(ctx_, &p), "urf_get_params");
+    return p;
+}
+
+void* BatchDetector::grow(void*& p, size_t& cap, size_t bytes)
+{
+    if (bytes > cap) {
+        if (p)
+            (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const size_t want = bytes + bytes / 4;
+        if (hipMalloc(&p, want) != hipSuccess) {
+            p = nullptr;
+            throw Error(URF_ERR_OOM, "BatchDetector: hipMalloc failed");
+        }
+        cap = want;
+    }
+    return p;
+}
+
+size_t BatchDetector::filtered(const std::vector<PointCloud2>& msgs)
+{
+    const size_t S = msgs.size();
+    infos_.assign(S, urf_scan_info{});
+    clouds_.resize(4 * S);
+    for (size_t i = 0; i < S; i++)
+        for (int k = 0; k < 4; k++) {
+            clouds_[4 * i + k].header = msgs[i].header;   /* lidar_segmentation.cpp:612-615 */
+            clouds_[4 * i + k].points.clear();
+        }
+    if (S == 0)
+        return 0;
+    if (S > max_batch_)
+        throw Error(URF_ERR_CAPACITY, "BatchDetector: more messages than max_batch");
+    /* one record layout for the whole batch, fields by name as Detector::resolve (pcl::fromROSMsg) finds them */
+    uint32_t off[3] = { 0, 0, 0 };
+    int64_t oi = -1;
+    std::vector<uint32_t> offsets(S + 1, 0);
+    uint32_t max_len = 0;
+    uint64_t total = 0;
+    for (size_t i = 0; i < S; i++) {
+        uint32_t o[3] = { 0, 0, 0 };
+        int64_t oii = -1;
+        uint64_t n = 0;
+        Detector::resolve(msgs[i], o, oii, n);
+        if (i == 0) {
+            std::memcpy(off, o, sizeof(off));
+            oi = oii;
+        } else if (std::memcmp(off, o, sizeof(off)) != 0 || oi != oii || msgs[i].point_step != msgs[0].point_step) {
+            throw Error(URF_ERR_INVALID_ARG, "BatchDetector: the messages of a batch must share their record layout");
+        }
+        if (n > max_points_)
+            throw Error(URF_ERR_CAPACITY, "BatchDetector: a message holds more than max_points points");
+        total += n;
+        max_len = n > max_len ? (uint32_t)n : max_len;
+        offsets[i + 1] = (uint32_t)total;
+    }
+    if (total > (uint64_t)max_points_ * max_batch_)
+        throw Error(URF_ERR_CAPACITY, "BatchDetector: more points than max_points * max_batch");
+    const uint32_t step = msgs[0].point_step;
+    if (total == 0) {   /* nothing but empty messages: what Detector answers for each */
+        for (auto& in : infos_)
+            in.status = URF_TOO_FEW_POINTS;
+        return 0;
+    }
+    /* the messages back to back, one upload */
+    h_data_.resize((size_t)total * step);
+    for (size_t i = 0; i < S; i++)
+        if (offsets[i + 1] > offsets[i])
+            std::memcpy(h_data_.data() + (size_t)offsets[i] * step, msgs[i].data.data(), (size_t)(offsets[i + 1] - offsets[i]) * step);
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_off = al((S + 1) * sizeof(uint32_t)), b_lab = al((size_t)total), b_info = al(S * sizeof(urf_scan_info)),
+                 b_cnt = al(4 * S * sizeof(uint32_t)), b_offs = al(4 * S * sizeof(uint64_t));
+    uint8_t* small = (uint8_t*)grow(d_small_, d_small_cap_, b_off + b_lab + b_info + b_cnt + b_offs);
+    uint32_t* d_offsets = (uint32_t*)small;
+    uint8_t* d_labels = small + b_off;
+    urf_scan_info* d_info = (urf_scan_info*)(small + b_off + b_lab);
+    uint32_t* d_counts = (uint32_t*)(small + b_off + b_lab + b_info);
+    uint64_t* d_roffs = (uint64_t*)(small + b_off + b_lab + b_info + b_cnt);
+    uint8_t* d_data = (uint8_t*)grow(d_data_, d_data_cap_, h_data_.size());
+    const uint64_t capacity = 3ull * S * max_len;
+    urf_point_xyzi* d_rec = (urf_point_xyzi*)grow(d_records_, d_records_cap_, (size_t)capacity * sizeof(urf_point_xyzi));
+    hipStream_t st = (hipStream_t)stream_;
+    if (hipMemcpyAsync(d_data, h_data_.data(), h_data_.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_offsets, offsets.data(), (S + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess)
+        throw Error(URF_ERR_HIP, "BatchDetector: upload failed");
+    check(urf_classify_batch_pc2_ragged(ctx_, d_data, d_offsets, total, max_len, (uint32_t)S, step, off[0], off[1], off[2], d_labels, d_info),
+          "urf_classify_batch_pc2_ragged");
+    check(urf_clouds_batch_pc2(ctx_, d_data, step, off[0], off[1], off[2], (int32_t)oi, reference_order_ ? URF_ORDER_REFERENCE : URF_ORDER_INPUT,
+                               d_rec, capacity, d_counts, d_roffs),
+          "urf_clouds_batch_pc2");
+    /* the counts, then exactly the records they add up to */
+    std::vector<uint32_t> counts(4 * S);
+    std::vector<uint64_t> roffs(4 * S);
+    if (hipMemcpyAsync(counts.data(), d_counts, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(roffs.data(), d_roffs, roffs.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(infos_.data(), d_info, S * sizeof(urf_scan_info), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        throw Error(URF_ERR_HIP, "BatchDetector: read-back failed");
+    const uint64_t n_rec = roffs[4 * S - 1] + counts[4 * S - 1];
+    h_records_.resize(n_rec);
+    if (n_rec && (hipMemcpyAsync(h_records_.data(), d_rec, n_rec * sizeof(urf_point_xyzi), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                  hipStreamSynchronize(st) != hipSuccess))
+        throw Error(URF_ERR_HIP, "BatchDetector: read-back failed");
+    size_t n_pub = 0;
+    for (size_t i = 0; i < S; i++) {
+        n_pub += infos_[i].status == URF_OK;
+        for (int k = 0; k < 4; k++) {
+            auto& pts = clouds_[4 * i + k].points;
+            pts.resize(counts[4 * i + k]);
+            if (!pts.empty())
+                std::memcpy((void*)pts.data(), h_records_.data() + roffs[4 * i + k], pts.size() * sizeof(PointXYZI));
+        }
+    }
+    return n_pub;
 }
 
 }   // namespace urf

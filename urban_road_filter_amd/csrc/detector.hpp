@@ -30,6 +30,7 @@
 #ifndef URF_DETECTOR_HPP
 #define URF_DETECTOR_HPP
 
+#include <cstddef>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -46,6 +47,12 @@ struct alignas(16) PointXYZI {
     float intensity = 0;
     float pad1[3] = { 0, 0, 0 };
 };
+static_assert(sizeof(PointXYZI) == sizeof(urf_point_xyzi) && offsetof(PointXYZI, x) == offsetof(urf_point_xyzi, x) &&
+                  offsetof(PointXYZI, y) == offsetof(urf_point_xyzi, y) && offsetof(PointXYZI, z) == offsetof(urf_point_xyzi, z) &&
+                  offsetof(PointXYZI, pad0) == offsetof(urf_point_xyzi, w) &&
+                  offsetof(PointXYZI, intensity) == offsetof(urf_point_xyzi, intensity) &&
+                  offsetof(PointXYZI, pad1) == offsetof(urf_point_xyzi, pad),
+              "urf::PointXYZI and urf_point_xyzi (include/urf.h) must share their layout: the batch clouds are copied as bytes");
 
 struct Header {
     uint32_t seq = 0;
@@ -155,6 +162,7 @@ private:
     void check(int rc, const char* what) const;
     void split(const Pending& m);
     static void resolve(const PointCloud2& msg, uint32_t off[3], int64_t& off_intensity, uint64_t& n);
+    friend class BatchDetector;
     urf_ctx* ctx_ = nullptr;
     bool reference_order_ = false;
     bool marker_on_ = false, marker_published_ = false;
@@ -167,6 +175,57 @@ private:
     PointCloud road_, curb_, roi_, road_probably_;
     std::vector<uint32_t> ord_;   /* 3 x max_points: the index lists of the reference order (sized once) */
     uint32_t max_points_ = 0;
+};
+
+/* The batch twin of Detector::filtered(const PointCloud2&), for recorded drives: a vector of wire messages -- of any lengths
+ * (drivers that drop non-returns publish variable-length clouds), all with the same record layout -- goes to the device in
+ * one copy, through urf_classify_batch_pc2_ragged and urf_clouds_batch_pc2, and the four clouds of every message come back
+ * in one copy.  road(i) ... road_probably(i) equal what Detector::filtered gives for message i on its own: the same points
+ * in the same order (input order, or the reference's after setReferenceOrder(true)), the same header.  Records carry
+ * x / y / z / intensity bit for bit with pcl::PointXYZI's w = 1 and zero padding (what pcl::fromROSMsg leaves; Detector
+ * copies a pcl::PointXYZI-layout message's padding bytes as they are, which a message from pcl::toROSMsg holds the same way).
+ * One context of max_batch scans of up to max_points points: a call with more messages, or a longer one, throws
+ * Error(URF_ERR_CAPACITY).  road_marker stays with Detector (its ghost deletion runs from sweep to sweep). */
+class BatchDetector {
+public:
+    BatchDetector(int device = 0, uint32_t max_points = 1u << 20, uint32_t max_batch = 64);
+    ~BatchDetector();
+    BatchDetector(const BatchDetector&) = delete;
+    BatchDetector& operator=(const BatchDetector&) = delete;
+
+    void setParams(const urf_params& p);
+    urf_params params() const;
+    void setReferenceOrder(bool on) { reference_order_ = on; }
+
+    /* Classifies every message; returns how many of them publish (the others: < 30 ROI points, or empty). */
+    size_t filtered(const std::vector<PointCloud2>& msgs);
+
+    size_t size() const { return infos_.size(); }
+    const PointCloud& road(size_t i) const { return clouds_.at(4 * i + 0); }
+    const PointCloud& curb(size_t i) const { return clouds_.at(4 * i + 1); }
+    const PointCloud& roi(size_t i) const { return clouds_.at(4 * i + 2); }
+    const PointCloud& road_probably(size_t i) const { return clouds_.at(4 * i + 3); }
+    const urf_scan_info& info(size_t i) const { return infos_.at(i); }
+    bool published(size_t i) const { return infos_.at(i).status == URF_OK; }
+
+private:
+    void check(int rc, const char* what) const;
+    void* grow(void*& p, size_t& cap, size_t bytes);
+    urf_ctx* ctx_ = nullptr;
+    void* stream_ = nullptr;
+    uint32_t max_points_ = 0, max_batch_ = 0;
+    bool reference_order_ = false;
+    /* device buffers (grown on demand) */
+    void* d_data_ = nullptr;
+    size_t d_data_cap_ = 0;
+    void* d_records_ = nullptr;
+    size_t d_records_cap_ = 0;
+    void* d_small_ = nullptr;    /* offsets, labels, infos, counts, record offsets */
+    size_t d_small_cap_ = 0;
+    std::vector<uint8_t> h_data_;
+    std::vector<PointXYZI> h_records_;
+    std::vector<urf_scan_info> infos_;
+    std::vector<PointCloud> clouds_;   /* 4 per message: road, curb, roi, road_probably */
 };
 
 }   // namespace urf

@@ -107,6 +107,11 @@ struct urf_ctx {
     uint32_t mk_scans = 0;
     float* mk_out = nullptr;        /* single-scan entry point: 361 x 4 floats + 1 count */
     uint32_t* compact_cnt = nullptr;   /* [max_batch][max_tiles][4] */
+    /* lazily: the published clouds of a batch (urf_clouds_batch_*) -- per (scan, tile) counts and bases, and the ordered lists of the
+     * reference order: 3 x cl_scans x cl_stride entries + 3 counts per scan */
+    void* cl_tiles = nullptr;          /* 2 x [max_batch][max_tiles] x 16 bytes */
+    uint32_t* cl_lists = nullptr;
+    size_t cl_lists_cap = 0;           /* entries */
     float* d_newY = nullptr;
     urf_beam* d_beams = nullptr;
     uint32_t beams_cap = 0;
@@ -146,6 +151,7 @@ struct urf_ctx {
     /* last call, for the entry points that read its intermediate results (urf_read_stage,
      * urf_ordered_indices, urf_marker_points): the kernel arguments and parameters it ran with */
     uint32_t last_scans = 0;
+    int last_batch = 0;             /* URF_LAST_*: the batch entry point that made the last call (0: none, or a sweep of the callback path) */
     urf_kargs last_a;
     urf_dev_params last_dp;
     std::string last_error;
@@ -154,6 +160,9 @@ struct urf_ctx {
     double ht[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     bool ht_on = false;
 };
+
+#define URF_LAST_SOA 1
+#define URF_LAST_PC2 2
 
 #define URF_HIP(ctx, call)                                                              \
     do {                                                                                \
@@ -414,7 +423,7 @@ static void free_lazy(urf_ctx* c)
     if (c->ev_main)
         (void)hipEventDestroy(c->ev_main);
     for (void* p : { (void*)c->mk_d, (void*)c->mk_pos, (void*)c->mk_red, (void*)c->mk_out, (void*)c->ord_keys,
-                     (void*)c->ord_pos, (void*)c->ord_cls, (void*)c->ord_lists })
+                     (void*)c->ord_pos, (void*)c->ord_cls, (void*)c->ord_lists, c->cl_tiles, (void*)c->cl_lists })
         if (p)
             (void)hipFree(p);
     if (c->sx) {
@@ -954,7 +963,10 @@ extern "C" int urf_classify_batch_soa(urf_ctx* c, const float* d_x, const float*
 {
     if (!c)
         return URF_ERR_INVALID_ARG;
-    return run_pipeline(c, d_x, d_y, d_z, nullptr, n_per_scan, n_per_scan, n_scans, d_labels, d_info);
+    const int rc = run_pipeline(c, d_x, d_y, d_z, nullptr, n_per_scan, n_per_scan, n_scans, d_labels, d_info);
+    if (rc == URF_OK && n_scans)
+        c->last_batch = URF_LAST_SOA;
+    return rc;
 }
 
 extern "C" int urf_classify_batch_soa_ragged(urf_ctx* c, const float* d_x, const float* d_y, const float* d_z,
@@ -963,7 +975,10 @@ extern "C" int urf_classify_batch_soa_ragged(urf_ctx* c, const float* d_x, const
 {
     if (!c || !d_offsets)
         return URF_ERR_INVALID_ARG;
-    return run_pipeline(c, d_x, d_y, d_z, d_offsets, 0, max_len, n_scans, d_labels, d_info);
+    const int rc = run_pipeline(c, d_x, d_y, d_z, d_offsets, 0, max_len, n_scans, d_labels, d_info);
+    if (rc == URF_OK && n_scans)
+        c->last_batch = URF_LAST_SOA;
+    return rc;
 }
 
 static int ensure_soa_staging(urf_ctx* c)
@@ -1009,7 +1024,39 @@ extern "C" int urf_classify_batch_pc2(urf_ctx* c, const uint8_t* d_data, uint32_
     const unsigned long long total = (unsigned long long)n_per_scan * n_scans;
     hipLaunchKernelGGL(k_pc2_to_soa, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, d_data, total,
                        point_step, off_x, off_y, off_z, c->sx, c->sy, c->sz);
-    return run_pipeline(c, c->sx, c->sy, c->sz, nullptr, n_per_scan, n_per_scan, n_scans, d_labels, d_info);
+    rc = run_pipeline(c, c->sx, c->sy, c->sz, nullptr, n_per_scan, n_per_scan, n_scans, d_labels, d_info);
+    if (rc == URF_OK)
+        c->last_batch = URF_LAST_PC2;
+    return rc;
+}
+
+/* Ragged PointCloud2 batches: the records [0, n_total) unpacked into the SoA staging at their own indices, then the ragged
+ * pipeline with the caller's offsets (which index records and staging alike).  A zero-length scan is one the pipeline already
+ * answers with URF_TOO_FEW_POINTS (urf_classify_batch_soa_ragged does the same). */
+extern "C" int urf_classify_batch_pc2_ragged(urf_ctx* c, const uint8_t* d_data, const uint32_t* d_offsets, uint64_t n_total,
+                                             uint32_t max_len, uint32_t n_scans, uint32_t point_step, uint32_t off_x,
+                                             uint32_t off_y, uint32_t off_z, uint8_t* d_labels, urf_scan_info* d_info)
+{
+    if (!c || !d_data || !d_offsets || !d_labels || !pc2_layout_ok(point_step, off_x, off_y, off_z))
+        return URF_ERR_INVALID_ARG;
+    if (n_scans > c->max_batch || max_len > c->max_points || n_total > (uint64_t)c->max_points * c->max_batch)
+        return URF_ERR_CAPACITY;
+    if (n_scans == 0)
+        return URF_OK;
+    URF_HIP(c, hipSetDevice(c->device));
+    int rc = ensure_soa_staging(c);
+    if (rc != URF_OK)
+        return rc;
+    rc = order_after_slots(c);   /* the staging arrays are shared with the callback path */
+    if (rc != URF_OK)
+        return rc;
+    if (n_total)
+        hipLaunchKernelGGL(k_pc2_to_soa, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, c->stream, d_data,
+                           (unsigned long long)n_total, point_step, off_x, off_y, off_z, c->sx, c->sy, c->sz);
+    rc = run_pipeline(c, c->sx, c->sy, c->sz, d_offsets, 0, max_len, n_scans, d_labels, d_info);
+    if (rc == URF_OK)
+        c->last_batch = URF_LAST_PC2;
+    return rc;
 }
 
 /* ---- the callback path: one sweep, host buffers ------------------------------- */
@@ -1361,6 +1408,7 @@ extern "C" int urf_classify_pc2_wait(urf_ctx* c, uint32_t ticket, uint8_t* label
     c->last_a = sl.cap_a;
     c->last_dp = sl.cap_dp;
     c->last_is_slot = true;
+    c->last_batch = 0;
     c->last_row = slot_row(c, sl);
     c->last_gen = sl.gen;
     if (labels_out)
@@ -1566,6 +1614,134 @@ extern "C" int urf_ordered_indices(urf_ctx* c, uint32_t scan, uint32_t* road, ui
     counts[1] = h[1];
     counts[2] = h[2];
     return URF_OK;
+}
+
+/* ---- the published clouds of a batch (urf_k_clouds.hpp) ---------------------------------------------- */
+#define URF_DBG_CLOUDS_NT 16u   /* test hook (urf_set_debug_flags): the records go out with non-temporal stores (A/B, tools/batch_clouds_bench.py) */
+
+static int ensure_clouds_scratch(urf_ctx* c, uint32_t n_scans, uint32_t stride, bool lists)
+{
+    if (!c->cl_tiles)
+        URF_HIP(c, hipMalloc(&c->cl_tiles, 2 * (size_t)c->max_batch * c->max_tiles * sizeof(urf_u32x4)));
+    const size_t need = 3 * (size_t)n_scans * stride + 3 * (size_t)n_scans;
+    if (lists && need > c->cl_lists_cap) {
+        URF_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->cl_lists)
+            (void)hipFree(c->cl_lists);
+        c->cl_lists = nullptr;
+        c->cl_lists_cap = 0;
+        void* p = nullptr;
+        URF_HIP(c, hipMalloc(&p, need * sizeof(uint32_t)));
+        c->cl_lists = (uint32_t*)p;
+        c->cl_lists_cap = need;
+    }
+    return URF_OK;
+}
+
+/* src: where the points come from (x / y / z / data and the layout fields; the rest is filled in here) */
+static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, urf_point_xyzi* d_records, uint64_t capacity,
+                        uint32_t* d_counts, uint64_t* d_offsets)
+{
+    if (!d_counts || !d_offsets || (order != URF_ORDER_INPUT && order != URF_ORDER_REFERENCE))
+        return URF_ERR_INVALID_ARG;
+    if (c->last_is_slot || c->last_batch != kind || c->last_scans == 0 || !c->last_a.labels) {
+        c->last_error = c->last_batch == 0 ? "the last classify call was no batch call (urf_classify_batch_*)"
+                                           : "the last batch call was of the other kind (SoA / PointCloud2)";
+        return URF_ERR_INVALID_ARG;
+    }
+    const uint32_t S = c->last_scans, max_len = c->last_a.max_len, stride = max_len ? max_len : 1u;
+    if (d_records && capacity < 3ull * S * max_len)
+        return URF_ERR_CAPACITY;
+    URF_HIP(c, hipSetDevice(c->device));
+    const bool ref = order == URF_ORDER_REFERENCE && d_records;
+    int rc = ensure_clouds_scratch(c, S, stride, ref);
+    if (rc != URF_OK)
+        return rc;
+    if (ref) {   /* urf_ordered_indices_batch's kernels (after a fused call: the documented rerun through the general kernels) */
+        rc = launch_ordered(c, 0, S, c->cl_lists, c->cl_lists + (size_t)S * stride, c->cl_lists + 2 * (size_t)S * stride, stride,
+                            c->cl_lists + 3 * (size_t)S * stride);
+    } else {
+        rc = order_after_slots(c);   /* cl_tiles is the context's */
+    }
+    if (rc != URF_OK)
+        return rc;
+    const urf_kargs& a = c->last_a;   /* (after a rerun: the same labels, inputs and offsets) */
+    src.labels = a.labels;
+    src.offsets = a.offsets;
+    src.info = a.info;
+    src.n_per_scan = a.n_per_scan;
+    src.max_len = a.max_len;
+    src.tiles = a.tiles;
+    src.n_scans = S;
+    src.tile_cnt = (urf_u32x4*)c->cl_tiles;
+    src.tile_base = src.tile_cnt + (size_t)c->max_batch * c->max_tiles;
+    src.counts = d_counts;
+    src.offs = (unsigned long long*)d_offsets;
+    src.rec = (urf_u32x4*)d_records;
+    src.lists = c->cl_lists;
+    src.list_cnt = c->cl_lists ? c->cl_lists + 3 * (size_t)S * stride : nullptr;
+    src.stride = stride;
+    hipStream_t st = c->stream;
+    const dim3 g_tiles(a.tiles, S);
+    hipLaunchKernelGGL(k_clouds_count, g_tiles, dim3(URF_CLOUDS_COUNT_THREADS), 0, st, src);
+    hipLaunchKernelGGL(k_clouds_scan, dim3(S), dim3(URF_CLOUDS_THREADS), 0, st, src);
+    hipLaunchKernelGGL(k_clouds_offsets, dim3(1), dim3(URF_CLOUDS_OFF_THREADS), 0, st, src);
+    if (d_records) {
+        const bool nt = (c->debug_flags & URF_DBG_CLOUDS_NT) != 0;
+        const unsigned which = ref ? 0x4u : 0xfu;
+        if (nt)
+            hipLaunchKernelGGL(k_clouds_write<true>, g_tiles, dim3(URF_CLOUDS_THREADS), 0, st, src, which);
+        else
+            hipLaunchKernelGGL(k_clouds_write<false>, g_tiles, dim3(URF_CLOUDS_THREADS), 0, st, src, which);
+        if (ref) {
+            const dim3 g_list((stride + URF_CLOUDS_THREADS - 1) / URF_CLOUDS_THREADS, S, 3);
+            if (nt)
+                hipLaunchKernelGGL(k_clouds_gather<true>, g_list, dim3(URF_CLOUDS_THREADS), 0, st, src);
+            else
+                hipLaunchKernelGGL(k_clouds_gather<false>, g_list, dim3(URF_CLOUDS_THREADS), 0, st, src);
+        }
+    }
+    URF_HIP(c, hipGetLastError());
+    return URF_OK;
+}
+
+extern "C" int urf_clouds_batch_soa(urf_ctx* c, const float* d_intensity, int order, urf_point_xyzi* d_records, uint64_t capacity,
+                                    uint32_t* d_counts, uint64_t* d_offsets)
+{
+    if (!c)
+        return URF_ERR_INVALID_ARG;
+    urf_clouds_args src{};
+    src.src = URF_SRC_SOA;
+    src.x = (const unsigned*)c->last_a.x;
+    src.y = (const unsigned*)c->last_a.y;
+    src.z = (const unsigned*)c->last_a.z;
+    src.in = (const unsigned*)d_intensity;
+    src.oi = -1;
+    return clouds_batch(c, URF_LAST_SOA, src, order, d_records, capacity, d_counts, d_offsets);
+}
+
+extern "C" int urf_clouds_batch_pc2(urf_ctx* c, const uint8_t* d_data, uint32_t point_step, uint32_t off_x, uint32_t off_y,
+                                    uint32_t off_z, int32_t off_intensity, int order, urf_point_xyzi* d_records, uint64_t capacity,
+                                    uint32_t* d_counts, uint64_t* d_offsets)
+{
+    if (!c || !d_data || !pc2_layout_ok(point_step, off_x, off_y, off_z) || off_intensity < -1 ||
+        (off_intensity >= 0 && (uint64_t)off_intensity + 4 > point_step))
+        return URF_ERR_INVALID_ARG;
+    urf_clouds_args src{};
+    src.data = d_data;
+    src.step = point_step;
+    src.ox = off_x;
+    src.oy = off_y;
+    src.oz = off_z;
+    src.oi = off_intensity;
+    const uint32_t oi = off_intensity >= 0 ? (uint32_t)off_intensity : 0u;
+    if (((uintptr_t)d_data | point_step) % 16 == 0 && off_x == 0 && off_y == 4 && off_z == 8 && oi % 4 == 0)
+        src.src = URF_SRC_PC2_XYZ;   /* pcl::PointXYZI, PointXYZ + intensity (Velodyne), Ouster records */
+    else if (((uintptr_t)d_data | point_step | off_x | off_y | off_z | oi) % 4 == 0)
+        src.src = URF_SRC_PC2;
+    else
+        src.src = URF_SRC_PC2_BYTES;
+    return clouds_batch(c, URF_LAST_PC2, src, order, d_records, capacity, d_counts, d_offsets);
 }
 
 static int launch_markers(urf_ctx* c, uint32_t s0, uint32_t n, float* d_pts, uint32_t* d_counts)

@@ -21,7 +21,8 @@
  *   k_label        road acceptance per point, label bytes       blind_spots.cpp:124-130,164-170, lidar_segmentation.cpp:354-367
  *
  * The kernels live in one header per family (r6), included below in this order: urf_k_table.hpp, urf_k_split.hpp,
- * urf_k_star.hpp, urf_k_ring.hpp, urf_k_beams_label.hpp, urf_k_outputs.hpp.  A batch of sweeps in firing order takes the
+ * urf_k_star.hpp, urf_k_ring.hpp, urf_k_beams_label.hpp, urf_k_outputs.hpp, urf_k_clouds.hpp (the
+ * published clouds of a batch as records).  A batch of sweeps in firing order takes the
  * fused front end of urf_front.hpp (k_front, k_front_finish, k_label_front) instead of k_split / k_ring / k_label.
  *
  * The reference's per-ring azimuth quicksort (lidar_segmentation.cpp:70-93,
@@ -60,5 +61,6 @@
 #include "urf_k_ring.hpp"
 #include "urf_k_beams_label.hpp"
 #include "urf_k_outputs.hpp"
+#include "urf_k_clouds.hpp"
 
 #endif /* URF_KERNELS_HPP */
