@@ -806,7 +806,10 @@ def test_batch_outputs_equal_the_single_scan_outputs():
             want = [np.nonzero((L[s] & 3) == 1)[0], np.nonzero((L[s] & 3) == 2)[0], np.nonzero(L[s] & 4)[0], np.nonzero(L[s] & 16)[0]]
             for k in range(4):
                 assert cnt[s, k] == len(want[k]) and np.array_equal(lists[k][s, :cnt[s, k]], want[k]), (s, k)
-        # published order and marker points: batch == scan by scan
+        # published order and marker points: batch == scan by scan (one scan asked for first: the context's
+        # scratch for both then grows from one scan to S)
+        ctx.ordered_indices(n, scan=0)
+        ctx.marker_points(scan=0)
         ob = [DevBuf(4 * S * n) for _ in range(3)]
         oc = DevBuf(12 * S)
         ctx.ordered_indices_batch(*ob, n, oc)

@@ -28,10 +28,62 @@
 #define URF_ASYNC_SLOTS 4
 static_assert(URF_ASYNC_SLOTS == URF_MAX_IN_FLIGHT, "include/urf.h documents the number of sweeps in flight");
 
+/* A lazily sized buffer of T -- device memory, or pinned host memory (Host) --: grow() makes it large enough for the largest
+ * request so far, and the context frees it with itself. */
+template <class T, bool Host = false>
+struct lazy_buf {
+    T* p = nullptr;
+    size_t cap = 0;   /* elements */
+    lazy_buf() = default;
+    lazy_buf(const lazy_buf&) = delete;
+    lazy_buf& operator=(const lazy_buf&) = delete;
+    ~lazy_buf() { release(); }
+    void release()
+    {
+        if (p)
+            (void)(Host ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+/* Every scratch array of urf_kargs, declared once with its elements per row: X(field, elements).  A row is one scan's slice of
+ * each array -- scan r of a batch call, or the sweep of the callback path that runs on row r -- and starts r * elements into it
+ * (kargs_row).  Most arrays have max_batch rows; the two per-call counters (SLOTS) have URF_ASYNC_SLOTS, one per sweep in flight,
+ * whatever max_batch is.  urf_create allocates SCANS and SLOTS; CAPTURE comes with the first urf_enable_stage_capture, ROW_MAJOR
+ * (the firing-order copies of row-major organised sweeps) once such a sweep has been sighted (rows_state_update).  sstride,
+ * max_tiles and front_cand_cap are the context's (scratch_walk). */
+#define URF_SCRATCH_SCANS(X)                                                                                                     \
+    X(rx, sstride) X(ry, sstride) X(rz, sstride) X(rec, sstride)                                                                 \
+    X(sr, sstride) X(sz, sstride) X(sslot, sstride) X(ssrt16, sstride) X(ssrt, sstride) X(wsg, sstride)                          \
+    X(big_r, sstride) X(big_z, sstride) X(big_i, sstride)                                                                        \
+    X(tile_roi, max_tiles) X(roi_bits, max_tiles * (URF_TILE / 64)) X(troff, max_tiles * (URF_MAX_CHANNELS + 1))                 \
+    X(tsoff, max_tiles * (URF_MAX_SECTORS + 1)) X(tmaxs, max_tiles * URF_MAX_CHANNELS)                                           \
+    X(rpre, URF_MAX_CHANNELS * (max_tiles + 1)) X(rstart, URF_MAX_CHANNELS * max_tiles)                                          \
+    X(angle, URF_MAX_CHANNELS) X(ring_thr, URF_MAX_CHANNELS * 4) X(ring_lut, URF_LUT_CELLS) X(ring_cnt, URF_MAX_CHANNELS)        \
+    X(ring_off, URF_MAX_CHANNELS + 1)                                                                                            \
+    X(sec_cnt, URF_MAX_SECTORS) X(sec_run, URF_MAX_SECTORS) X(sec_off, URF_MAX_SECTORS + 1) X(star_hit, URF_MAX_SECTORS)         \
+    X(star_first, URF_MAX_SECTORS) X(star_list_mid, URF_MAX_SECTORS) X(star_list_big, URF_MAX_SECTORS)                           \
+    X(star_list_runs, URF_MAX_SECTORS) X(tie_list, URF_MAX_SECTORS) X(tie_post, URF_MAX_SECTORS)                                 \
+    X(table_upto, 1) X(table_redo, 1) X(redo_list, 1) X(table_cause, 1)                                                          \
+    X(nan_mask, 4) X(nan_list, 2 * URF_MAX_CHANNELS) X(vis, URF_MAX_CHANNELS)                                                    \
+    X(maxdist, URF_MAX_CHANNELS) X(quad, 4)                                                                                      \
+    X(curb_cnt, URF_MAX_CHANNELS) X(curb_az, URF_MAX_CHANNELS * URF_CURB_LIST)                                                   \
+    X(sufmin, URF_MAX_CHANNELS * URF_DEG_CELLS) X(premax, URF_MAX_CHANNELS * URF_DEG_CELLS)                                      \
+    X(stop_f, URF_DEG_CELLS) X(stop_b, URF_DEG_CELLS)                                                                            \
+    X(win, URF_MAX_CHANNELS * URF_DEG_CELLS)                                                                                     \
+    X(info, 1)                                                                                                                   \
+    X(front_ok, 1) X(front_pres, max_tiles * 64) X(front_maxs, max_tiles * 64) X(front_lane_ring, 64)                            \
+    X(front_ring_lane, URF_MAX_CHANNELS) X(front_cand, front_cand_cap) X(front_all, front_cand_cap) X(front_ncand, 1)             \
+    X(front_list, 1) X(front_st, URF_FRONT_ST_WORDS)
+#define URF_SCRATCH_SLOTS(X) X(star_count, 8) X(ring_hint, 1)
+#define URF_SCRATCH_CAPTURE(X) X(valpha, sstride) X(seckey, sstride) X(ringkey, sstride) X(rd2, sstride) X(caz, sstride)
+#define URF_SCRATCH_ROW_MAJOR(X) X(tx, sstride) X(ty, sstride) X(tz, sstride) X(rows_v, 64) X(rows_ok, 1)
+enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR };
+
 struct urf_ctx {
     int device = 0;
     uint32_t max_points = 0, max_batch = 0;
-    size_t total = 0;               /* scratch elements: sstride * max_batch */
     uint32_t max_tiles = 0;
     uint32_t sstride = 0;           /* scratch elements per scan: max_tiles * URF_TILE + URF_SCAN_PAD */
     uint32_t debug_flags = 0;       /* urf_set_debug_flags */
@@ -40,22 +92,20 @@ struct urf_ctx {
     hipStream_t stream = nullptr;
     urf_params params;
     urf_dev_params dp;
-    urf_kargs k;                    /* device pointers (context-owned part) */
-    /* owned device memory */
+    urf_kargs k;                    /* device pointers (context-owned part): the scratch arrays (URF_SCRATCH_*) at row 0 */
+    /* owned device memory of fixed size: the scratch arrays and the tables, freed by urf_destroy */
     std::vector<void*> allocs;
-    float *sx = nullptr, *sy = nullptr, *sz = nullptr;   /* SoA staging for PointCloud2 input */
+    lazy_buf<float> sx, sy, sz;     /* SoA staging for PointCloud2 input: max_batch x max_points */
     /* The single-scan (callback) path: URF_ASYNC_SLOTS sweeps in flight, so that -- with a context created
      * for several scans -- the copies and kernels of several sweeps overlap on the device (a single sweep's
      * kernels are a few dozen workgroups each).  Per slot: pinned host staging for the message bytes and for the
      * results, device copies of both, the captured launch sequence. */
     struct slot_t {
-        uint8_t* h_in = nullptr;        /* pinned, h_in_cap bytes */
-        size_t h_in_cap = 0;
-        uint8_t* d_raw = nullptr;       /* device, d_raw_cap bytes */
-        size_t d_raw_cap = 0;
-        uint8_t* h_labels = nullptr;    /* pinned, max_points */
-        uint8_t* d_labels = nullptr;    /* device, max_points */
-        urf_scan_info* h_info = nullptr;   /* pinned */
+        lazy_buf<uint8_t, true> h_in;   /* the largest message so far */
+        lazy_buf<uint8_t> d_raw;        /* ... its device copy */
+        lazy_buf<uint8_t, true> h_labels;   /* max_points */
+        lazy_buf<uint8_t> d_labels;     /* max_points */
+        lazy_buf<urf_scan_info, true> h_info;
         hipEvent_t ev_done = nullptr;
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
@@ -94,24 +144,21 @@ struct urf_ctx {
     uint64_t last_gen = 0;                 /* ... which was the row's submission number last_gen */
     uint32_t next_ticket = 0;
     uint64_t epoch = 1;             /* bumped by everything a captured sequence depends on */
-    /* lazily, sized for the largest number of scans asked for so far: scratch of the index-list and
-     * marker-point outputs (sstride entries resp. channels x 361 cells per scan) */
-    unsigned long long* ord_keys = nullptr;
-    uint32_t* ord_pos = nullptr;
-    uint32_t* ord_cls = nullptr;   /* [scans][URF_MAX_CHANNELS][2] road / curb points per ring (k_ring_order -> k_ordered_lists) */
-    uint32_t ord_scans = 0;
-    uint32_t* ord_lists = nullptr;  /* single-scan entry point: 3 x sstride + 4 */
-    float* mk_d = nullptr;
-    uint32_t* mk_pos = nullptr;
-    uint8_t* mk_red = nullptr;
-    uint32_t mk_scans = 0;
-    float* mk_out = nullptr;        /* single-scan entry point: 361 x 4 floats + 1 count */
+    /* sized for the largest number of scans asked for so far: scratch of the index-list and marker-point outputs
+     * (sstride entries resp. channels x 361 cells per scan) */
+    lazy_buf<unsigned long long> ord_keys;
+    lazy_buf<uint32_t> ord_pos;
+    lazy_buf<uint32_t> ord_cls;     /* [scans][URF_MAX_CHANNELS][2] road / curb points per ring (k_ring_order -> k_ordered_lists) */
+    lazy_buf<uint32_t> ord_lists;   /* single-scan entry point: 3 x sstride + 4 */
+    lazy_buf<float> mk_d;
+    lazy_buf<uint32_t> mk_pos;
+    lazy_buf<uint8_t> mk_red;       /* ... and one flag per ring and scan behind the cells (k_marker_ring_literal) */
+    lazy_buf<float> mk_out;         /* single-scan entry point: 361 x 4 floats + 1 count */
     uint32_t* compact_cnt = nullptr;   /* [max_batch][max_tiles][4] */
-    /* lazily: the published clouds of a batch (urf_clouds_batch_*) -- per (scan, tile) counts and bases, and the ordered lists of the
-     * reference order: 3 x cl_scans x cl_stride entries + 3 counts per scan */
-    void* cl_tiles = nullptr;          /* 2 x [max_batch][max_tiles] x 16 bytes */
-    uint32_t* cl_lists = nullptr;
-    size_t cl_lists_cap = 0;           /* entries */
+    /* the published clouds of a batch (urf_clouds_batch_*): per (scan, tile) counts and bases, and the ordered lists of the
+     * reference order: 3 x scans x stride entries + 3 counts per scan */
+    lazy_buf<urf_u32x4> cl_tiles;   /* 2 x [max_batch][max_tiles] */
+    lazy_buf<uint32_t> cl_lists;
     float* d_newY = nullptr;
     urf_beam* d_beams = nullptr;
     uint32_t beams_cap = 0;
@@ -143,7 +190,7 @@ struct urf_ctx {
      * take the fused kernels too (row-major sweeps gain from them at any batch size, sweeps in firing order only from 192 per call on) */
     bool rows_used = false;
     uint32_t rows_probation = 0;
-    /* k_front_finish's first part runs on a stream of its own next to the star-shaped search (run_pipeline) */
+    /* k_front_finish's first part runs on a stream of its own next to the star-shaped search (run_pipeline): all three or none */
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool speculate = true;
@@ -181,6 +228,53 @@ static int dev_alloc(urf_ctx* c, T** p, size_t count)
     c->allocs.push_back(v);
     *p = (T*)v;
     return URF_OK;
+}
+
+/* b holds at least `count` elements afterwards.  To grow, it waits for `st` first when one is given (work in flight there may still
+ * read the old memory) and frees the old memory; a failed allocation leaves it empty. */
+template <class T, bool Host>
+static int grow(urf_ctx* c, lazy_buf<T, Host>& b, size_t count, hipStream_t st = nullptr)
+{
+    if (count <= b.cap)
+        return URF_OK;
+    if (st)
+        URF_HIP(c, hipStreamSynchronize(st));
+    b.release();
+    void* v = nullptr;
+    URF_HIP(c, Host ? hipHostMalloc(&v, count * sizeof(T), hipHostMallocDefault) : hipMalloc(&v, count * sizeof(T)));
+    b.p = (T*)v;
+    b.cap = count;
+    return URF_OK;
+}
+
+/* f(group, field, rows, elements per row) for every scratch array of `k` (URF_SCRATCH_*) */
+template <class F>
+static void scratch_walk(const urf_ctx* c, urf_kargs& k, F&& f)
+{
+    const size_t sstride = c->sstride, max_tiles = c->max_tiles, front_cand_cap = k.front_cand_cap;
+#define URF_X_SCANS(field, n) f(URF_SCR_ALWAYS, k.field, (size_t)c->max_batch, (size_t)(n));
+#define URF_X_SLOTS(field, n) f(URF_SCR_ALWAYS, k.field, (size_t)URF_ASYNC_SLOTS, (size_t)(n));
+#define URF_X_CAPTURE(field, n) f(URF_SCR_CAPTURE, k.field, (size_t)c->max_batch, (size_t)(n));
+#define URF_X_ROW_MAJOR(field, n) f(URF_SCR_ROW_MAJOR, k.field, (size_t)c->max_batch, (size_t)(n));
+    URF_SCRATCH_SCANS(URF_X_SCANS)
+    URF_SCRATCH_SLOTS(URF_X_SLOTS)
+    URF_SCRATCH_CAPTURE(URF_X_CAPTURE)
+    URF_SCRATCH_ROW_MAJOR(URF_X_ROW_MAJOR)
+#undef URF_X_SCANS
+#undef URF_X_SLOTS
+#undef URF_X_CAPTURE
+#undef URF_X_ROW_MAJOR
+}
+
+/* Allocates the arrays of `group` that are missing (URF_OK: all of them are there). */
+static int scratch_alloc(urf_ctx* c, urf_scratch_group group)
+{
+    int rc = URF_OK;
+    scratch_walk(c, c->k, [&](urf_scratch_group g, auto*& p, size_t rows, size_t n) {
+        if (g == group && !p && rc == URF_OK)
+            rc = dev_alloc(c, &p, rows * n);
+    });
+    return rc;
 }
 
 /* star_shaped_search.cpp:32-66 beam_init: per-sector constants of the
@@ -260,31 +354,6 @@ static int upload_params(urf_ctx* c)
     return URF_OK;
 }
 
-/* the firing-order copies of row-major organised sweeps (k_transpose): allocated when the first such sweep has been sighted */
-static int ensure_rows_arrays(urf_ctx* c)
-{
-    if (c->k.tx)
-        return URF_OK;
-    int rc;
-    if ((rc = dev_alloc(c, &c->k.rows_v, (size_t)c->max_batch * 64)) != URF_OK || (rc = dev_alloc(c, &c->k.rows_ok, (size_t)c->max_batch)) != URF_OK ||
-        (rc = dev_alloc(c, &c->k.ty, c->total)) != URF_OK || (rc = dev_alloc(c, &c->k.tz, c->total)) != URF_OK ||
-        (rc = dev_alloc(c, &c->k.tx, c->total)) != URF_OK)   /* (tx last: its pointer says that all of them are there) */
-        return rc;
-    return URF_OK;
-}
-
-static int ensure_capture_arrays(urf_ctx* c)
-{
-    if (c->k.valpha)
-        return URF_OK;
-    int rc;
-    if ((rc = dev_alloc(c, &c->k.valpha, c->total)) != URF_OK || (rc = dev_alloc(c, &c->k.seckey, c->total)) != URF_OK ||
-        (rc = dev_alloc(c, &c->k.ringkey, c->total)) != URF_OK || (rc = dev_alloc(c, &c->k.rd2, c->total)) != URF_OK ||
-        (rc = dev_alloc(c, &c->k.caz, c->total)) != URF_OK)
-        return rc;
-    return URF_OK;
-}
-
 extern "C" int urf_create(urf_ctx** out, int device_id, uint32_t max_points, uint32_t max_batch)
 {
     if (!out || max_points == 0 || max_batch == 0)
@@ -303,7 +372,6 @@ extern "C" int urf_create(urf_ctx** out, int device_id, uint32_t max_points, uin
     c->max_batch = max_batch;
     c->max_tiles = (uint32_t)max_tiles;
     c->sstride = (uint32_t)sstride;
-    c->total = (size_t)sstride * max_batch;
     int rc = URF_OK;
     auto fail = [&](int code) {
         urf_destroy(c);
@@ -323,34 +391,11 @@ extern "C" int urf_create(urf_ctx** out, int device_id, uint32_t max_points, uin
     std::memset(&c->k, 0, sizeof(c->k));
     std::memset(&c->last_a, 0, sizeof(c->last_a));
     urf_kargs& k = c->k;
-    const size_t T = c->total, S = max_batch, tiles = c->max_tiles;
-    const size_t C = URF_MAX_CHANNELS, K = URF_MAX_SECTORS;
-#define A(ptr, count)                                     \
-    if ((rc = dev_alloc(c, &(ptr), (count))) != URF_OK)   \
-        return fail(rc);
-    A(k.rx, T) A(k.ry, T) A(k.rz, T) A(k.rec, T)
-    A(k.sr, T) A(k.sz, T) A(k.sslot, T) A(k.ssrt16, T) A(k.ssrt, T) A(k.wsg, T)
-    A(k.big_r, T) A(k.big_z, T) A(k.big_i, T)
-    A(k.tile_roi, S * tiles) A(k.roi_bits, S * tiles * (URF_TILE / 64)) A(k.troff, S * tiles * (C + 1)) A(k.tsoff, S * tiles * (K + 1)) A(k.tmaxs, S * tiles * C)
-    A(k.rpre, S * C * (tiles + 1)) A(k.rstart, S * C * tiles)
-    A(k.angle, S * C) A(k.ring_thr, S * C * 4) A(k.ring_lut, S * URF_LUT_CELLS) A(k.ring_cnt, S * C) A(k.ring_off, S * (C + 1))
-    A(k.sec_cnt, S * K) A(k.sec_run, S * K) A(k.sec_off, S * (K + 1)) A(k.star_hit, S * K)
-    A(k.star_first, S * K) A(k.star_list_mid, S * K) A(k.star_list_big, S * K) A(k.star_list_runs, S * K) A(k.tie_list, S * K) A(k.tie_post, S * K) A(k.star_count, 8 * URF_ASYNC_SLOTS)   /* eight counters per scratch row in use at once */
-    A(k.table_upto, S) A(k.table_redo, S) A(k.redo_list, S) A(k.table_cause, S) A(k.ring_hint, URF_ASYNC_SLOTS)
-    A(k.nan_mask, S * 4) A(k.nan_list, 2 * S * C) A(k.vis, S * C)
-    A(k.maxdist, S * C) A(k.quad, S * 4)
-    A(k.curb_cnt, S * C) A(k.curb_az, S * C * URF_CURB_LIST)
-    A(k.sufmin, S * C * URF_DEG_CELLS) A(k.premax, S * C * URF_DEG_CELLS)
-    A(k.stop_f, S * URF_DEG_CELLS) A(k.stop_b, S * URF_DEG_CELLS)
-    A(k.win, S * C * URF_DEG_CELLS)
-    A(k.info, S)
     k.front_cand_cap = max_points / 8 > 4096 ? max_points / 8 : 4096;
-    A(k.front_ok, S) A(k.front_pres, S * tiles * 64) A(k.front_maxs, S * tiles * 64) A(k.front_lane_ring, S * 64) A(k.front_ring_lane, S * C)
-    A(k.front_cand, S * k.front_cand_cap) A(k.front_all, S * k.front_cand_cap) A(k.front_ncand, S) A(k.front_list, S) A(k.front_st, S * 72)
-    A(c->offsets_copy, S + 1)
-    A(c->compact_cnt, S * tiles * 4)
-    A(c->d_newY, (size_t)max_points) A(c->d_beams, K)
-#undef A
+    if ((rc = scratch_alloc(c, URF_SCR_ALWAYS)) != URF_OK || (rc = dev_alloc(c, &c->offsets_copy, (size_t)max_batch + 1)) != URF_OK ||
+        (rc = dev_alloc(c, &c->compact_cnt, (size_t)max_batch * c->max_tiles * 4)) != URF_OK ||
+        (rc = dev_alloc(c, &c->d_newY, (size_t)max_points)) != URF_OK || (rc = dev_alloc(c, &c->d_beams, (size_t)URF_MAX_SECTORS)) != URF_OK)
+        return fail(rc);
     {
         urf_wu* tab = nullptr;
         const size_t nt = (size_t)max_points + 32;
@@ -395,44 +440,6 @@ extern "C" int urf_create(urf_ctx** out, int device_id, uint32_t max_points, uin
     return URF_OK;
 }
 
-static void free_lazy(urf_ctx* c)
-{
-    if (c->h_spec_failed)
-        (void)hipHostFree(c->h_spec_failed);
-    for (auto& sl : c->slots) {
-        if (sl.exec)
-            (void)hipGraphExecDestroy(sl.exec);
-        if (sl.graph)
-            (void)hipGraphDestroy(sl.graph);
-        if (sl.ev_done)
-            (void)hipEventDestroy(sl.ev_done);
-        if (sl.h_in)
-            (void)hipHostFree(sl.h_in);
-        if (sl.h_labels)
-            (void)hipHostFree(sl.h_labels);
-        if (sl.h_info)
-            (void)hipHostFree(sl.h_info);
-        if (sl.d_raw)
-            (void)hipFree(sl.d_raw);
-        if (sl.d_labels)
-            (void)hipFree(sl.d_labels);
-    }
-    for (hipStream_t st : c->row_stream)
-        if (st)
-            (void)hipStreamDestroy(st);
-    if (c->ev_main)
-        (void)hipEventDestroy(c->ev_main);
-    for (void* p : { (void*)c->mk_d, (void*)c->mk_pos, (void*)c->mk_red, (void*)c->mk_out, (void*)c->ord_keys,
-                     (void*)c->ord_pos, (void*)c->ord_cls, (void*)c->ord_lists, c->cl_tiles, (void*)c->cl_lists })
-        if (p)
-            (void)hipFree(p);
-    if (c->sx) {
-        (void)hipFree(c->sx);
-        (void)hipFree(c->sy);
-        (void)hipFree(c->sz);
-    }
-}
-
 extern "C" int urf_destroy(urf_ctx* c)
 {
     if (!c)
@@ -443,10 +450,8 @@ extern "C" int urf_destroy(urf_ctx* c)
     if (c->side_stream) {
         (void)hipStreamSynchronize(c->side_stream);
         (void)hipStreamDestroy(c->side_stream);
-        if (c->ev_fork)
-            (void)hipEventDestroy(c->ev_fork);
-        if (c->ev_join)
-            (void)hipEventDestroy(c->ev_join);
+        (void)hipEventDestroy(c->ev_fork);
+        (void)hipEventDestroy(c->ev_join);
     }
     for (hipStream_t st : c->row_stream)
         if (st)
@@ -456,10 +461,24 @@ extern "C" int urf_destroy(urf_ctx* c)
             (void)hipEventDestroy(e);
     for (void* p : c->allocs)
         (void)hipFree(p);
-    free_lazy(c);
+    if (c->h_spec_failed)
+        (void)hipHostFree(c->h_spec_failed);
+    for (auto& sl : c->slots) {
+        if (sl.exec)
+            (void)hipGraphExecDestroy(sl.exec);
+        if (sl.graph)
+            (void)hipGraphDestroy(sl.graph);
+        if (sl.ev_done)
+            (void)hipEventDestroy(sl.ev_done);
+    }
+    for (hipStream_t st : c->row_stream)
+        if (st)
+            (void)hipStreamDestroy(st);
+    if (c->ev_main)
+        (void)hipEventDestroy(c->ev_main);
     if (c->own_stream)
         (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;   /* (the lazily sized buffers go with it: lazy_buf) */
     return URF_OK;
 }
 
@@ -520,7 +539,7 @@ extern "C" int urf_enable_stage_capture(urf_ctx* c, int mode)
         return URF_ERR_INVALID_ARG;
     if (mode) {
         URF_HIP(c, hipSetDevice(c->device));
-        const int rc = ensure_capture_arrays(c);
+        const int rc = scratch_alloc(c, URF_SCR_CAPTURE);
         if (rc != URF_OK)
             return rc;
     }
@@ -630,39 +649,17 @@ extern "C" int urf_kernel_timing(urf_ctx* c, double* ms_sum, uint32_t* n_calls)
 
 extern "C" const char* urf_last_error(const urf_ctx* c) { return c ? c->last_error.c_str() : ""; }
 
-/* The context's scratch with every per-scan array advanced by `row` scans (allocation strides): slot i of the
- * callback path (URF_MAX_IN_FLIGHT slots) runs on row i % min(max_batch, URF_MAX_IN_FLIGHT) and on that row's own
- * stream, so that the sweeps in flight overlap.  Row 0 = the context's own arguments. */
+/* The context's scratch at row `row` (URF_SCRATCH_*): slot i of the callback path (URF_MAX_IN_FLIGHT slots) runs on row
+ * i % min(max_batch, URF_MAX_IN_FLIGHT) and on that row's own stream, so that the sweeps in flight overlap.  Row 0 = the
+ * context's own arguments; a lazy group that is not there stays NULL. */
 static urf_kargs kargs_row(const urf_ctx* c, uint32_t row)
 {
     urf_kargs k = c->k;
-    if (row == 0)
-        return k;
-    const size_t P = (size_t)row * c->sstride, tiles = c->max_tiles, C = URF_MAX_CHANNELS, K = URF_MAX_SECTORS, r = row;
-    k.rx += P; k.ry += P; k.rz += P; k.rec += P;
-    k.sr += P; k.sz += P; k.sslot += P; k.ssrt16 += P; k.ssrt += P; k.wsg += P;
-    k.big_r += P; k.big_z += P; k.big_i += P;
-    if (k.valpha) {
-        k.valpha += P; k.seckey += P; k.ringkey += P; k.rd2 += P; k.caz += P;
-    }
-    k.tile_roi += r * tiles; k.roi_bits += r * tiles * (URF_TILE / 64); k.troff += r * tiles * (C + 1); k.tsoff += r * tiles * (K + 1); k.tmaxs += r * tiles * C;
-    k.rpre += r * C * (tiles + 1); k.rstart += r * C * tiles;
-    k.angle += r * C; k.ring_thr += r * C * 4; k.ring_lut += r * URF_LUT_CELLS; k.ring_cnt += r * C; k.ring_off += r * (C + 1);
-    k.sec_cnt += r * K; k.sec_run += r * K; k.sec_off += r * (K + 1); k.star_hit += r * K;
-    k.star_first += r * K; k.star_list_mid += r * K; k.star_list_big += r * K; k.star_list_runs += r * K; k.tie_list += r * K; k.tie_post += r * K; k.star_count += 8 * r;
-    k.table_upto += r; k.table_redo += r; k.redo_list += r; k.table_cause += r; k.ring_hint += r;
-    k.nan_mask += r * 4; k.nan_list += 2 * r * C; k.vis += r * C;
-    k.maxdist += r * C; k.quad += r * 4;
-    k.curb_cnt += r * C; k.curb_az += r * C * URF_CURB_LIST;
-    k.sufmin += r * C * URF_DEG_CELLS; k.premax += r * C * URF_DEG_CELLS;
-    k.stop_f += r * URF_DEG_CELLS; k.stop_b += r * URF_DEG_CELLS;
-    k.win += r * C * URF_DEG_CELLS;
-    k.info += r;
-    k.front_ok += r; k.front_pres += r * tiles * 64; k.front_maxs += r * tiles * 64; k.front_lane_ring += r * 64; k.front_ring_lane += r * C;
-    if (k.tx) {
-        k.tx += P; k.ty += P; k.tz += P; k.rows_v += r * 64; k.rows_ok += r;
-    }
-    k.front_cand += r * (size_t)k.front_cand_cap; k.front_all += r * (size_t)k.front_cand_cap; k.front_ncand += r; k.front_list += r; k.front_st += r * 72;
+    if (row)
+        scratch_walk(c, k, [&](urf_scratch_group, auto*& p, size_t, size_t n) {
+            if (p)
+                p += row * n;
+        });
     return k;
 }
 
@@ -701,7 +698,7 @@ static int rows_state_update(urf_ctx* c, hipStream_t st)
     if (c->front_mode != 0 && !c->front_rows && !c->rows_oom && c->h_spec_failed[4]) {
         /* the calls in flight finish first -- what they handed back (such sweeps, possibly all of them) says nothing about the calls to come */
         URF_HIP(c, hipStreamSynchronize(st));
-        if (ensure_rows_arrays(c) == URF_OK) {
+        if (scratch_alloc(c, URF_SCR_ROW_MAJOR) == URF_OK) {
             c->front_rows = true;
             c->rows_probation = 16;
             c->front_direct = c->front_off = false;
@@ -739,10 +736,12 @@ static int run_pipeline(urf_ctx* c, const float* d_x, const float* d_y, const fl
         return URF_ERR_CAPACITY;
     URF_HIP(c, hipSetDevice(c->device));
     hipStream_t st = on_stream ? on_stream : c->stream;
-    if (!on_stream) {
-        const int orc = order_after_slots(c);
-        if (orc != URF_OK)
-            return orc;
+    if (!on_stream) {   /* (a sweep of the callback path: urf_classify_pc2_async has done both, outside its stream capture) */
+        int rc = order_after_slots(c);
+        if (rc == URF_OK)
+            rc = rows_state_update(c, st);   /* (may allocate the row-major group: before the arguments are taken) */
+        if (rc != URF_OK)
+            return rc;
     }
     urf_kargs a = kargs_row(c, row);
     a.x = d_x;
@@ -793,18 +792,6 @@ static int run_pipeline(urf_ctx* c, const float* d_x, const float* d_y, const fl
     /* The fused front end (urf_front.hpp) for batches of sweeps in firing order: k_front tries every scan, the legacy kernels
      * skip the scans it kept.  64 lasers = 64 lanes, the detectors' window of curbPoints == 5 in registers, no stage capture
      * (its values are the legacy kernels'), not for the single sweeps of the callback path (sixteen waves on the whole device). */
-    if (!on_stream) {   /* (a sweep of the callback path: urf_classify_pc2_async has done it, outside its stream capture) */
-        const int rrc = rows_state_update(c, st);
-        if (rrc != URF_OK)
-            return rrc;
-    }
-    if (c->k.tx && !a.tx) {   /* (allocated after this call's arguments were copied: row 0's) */
-        a.tx = c->k.tx;
-        a.ty = c->k.ty;
-        a.tz = c->k.tz;
-        a.rows_v = c->k.rows_v;
-        a.rows_ok = c->k.rows_ok;
-    }
     if (c->h_spec_failed[2])
         c->front_direct = true;
     if (c->h_spec_failed[3] && c->front_mode != 2)
@@ -867,11 +854,20 @@ static int run_pipeline(urf_ctx* c, const float* d_x, const float* d_y, const fl
     bool side = false, part1 = false;
     const size_t finish_lds = (size_t)a.tiles * 384 + 2 * URF_FINISH_CHUNK * sizeof(urf_u2);
     if (a.front && !ev && !on_stream) {
-        if (!c->side_stream) {
-            if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)
-                c->side_stream = nullptr;
+        if (!c->side_stream) {   /* (all three or none: a later call tries again) */
+            hipStream_t s = nullptr;
+            hipEvent_t f = nullptr, j = nullptr;
+            if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&f, hipEventDisableTiming) == hipSuccess &&
+                hipEventCreateWithFlags(&j, hipEventDisableTiming) == hipSuccess) {
+                c->side_stream = s;
+                c->ev_fork = f;
+                c->ev_join = j;
+            } else {
+                if (f)
+                    (void)hipEventDestroy(f);
+                if (s)
+                    (void)hipStreamDestroy(s);
+            }
         }
         if (c->side_stream && hipEventRecord(c->ev_fork, st) == hipSuccess && hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) == hipSuccess) {
             hipLaunchKernelGGL(k_front_finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, c->side_stream, a, dp, 1u);
@@ -983,17 +979,11 @@ extern "C" int urf_classify_batch_soa_ragged(urf_ctx* c, const float* d_x, const
 
 static int ensure_soa_staging(urf_ctx* c)
 {
-    if (c->sx)
-        return URF_OK;
     const size_t n = (size_t)c->max_points * c->max_batch;
-    void *px = nullptr, *py = nullptr, *pz = nullptr;
-    URF_HIP(c, hipMalloc(&px, n * sizeof(float)));
-    URF_HIP(c, hipMalloc(&py, n * sizeof(float)));
-    URF_HIP(c, hipMalloc(&pz, n * sizeof(float)));
-    c->sx = (float*)px;
-    c->sy = (float*)py;
-    c->sz = (float*)pz;
-    return URF_OK;
+    int rc;
+    if ((rc = grow(c, c->sx, n)) != URF_OK || (rc = grow(c, c->sy, n)) != URF_OK)
+        return rc;
+    return grow(c, c->sz, n);
 }
 
 /* field offsets of a PointCloud2 record: every FLOAT32 field must lie inside the record
@@ -1004,6 +994,29 @@ static bool pc2_layout_ok(uint32_t point_step, uint32_t off_x, uint32_t off_y, u
     return ps >= 4 && (uint64_t)off_x + 4 <= ps && (uint64_t)off_y + 4 <= ps && (uint64_t)off_z + 4 <= ps;
 }
 
+/* PointCloud2 batches: the records [0, n_total) unpacked into the SoA staging at their own indices, then the pipeline (ragged: with
+ * the caller's offsets, which index records and staging alike) */
+static int classify_batch_pc2(urf_ctx* c, const uint8_t* d_data, const uint32_t* d_offsets, uint64_t n_total, uint32_t n_per_scan,
+                              uint32_t max_len, uint32_t n_scans, uint32_t point_step, uint32_t off_x, uint32_t off_y, uint32_t off_z,
+                              uint8_t* d_labels, urf_scan_info* d_info)
+{
+    if (n_scans == 0)
+        return URF_OK;
+    URF_HIP(c, hipSetDevice(c->device));
+    int rc = ensure_soa_staging(c);
+    if (rc == URF_OK)
+        rc = order_after_slots(c);   /* the staging arrays are shared with the callback path */
+    if (rc != URF_OK)
+        return rc;
+    if (n_total)
+        hipLaunchKernelGGL(k_pc2_to_soa, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, c->stream, d_data,
+                           (unsigned long long)n_total, point_step, off_x, off_y, off_z, c->sx.p, c->sy.p, c->sz.p);
+    rc = run_pipeline(c, c->sx.p, c->sy.p, c->sz.p, d_offsets, n_per_scan, max_len, n_scans, d_labels, d_info);
+    if (rc == URF_OK)
+        c->last_batch = URF_LAST_PC2;
+    return rc;
+}
+
 extern "C" int urf_classify_batch_pc2(urf_ctx* c, const uint8_t* d_data, uint32_t n_per_scan, uint32_t n_scans,
                                       uint32_t point_step, uint32_t off_x, uint32_t off_y, uint32_t off_z,
                                       uint8_t* d_labels, urf_scan_info* d_info)
@@ -1012,27 +1025,12 @@ extern "C" int urf_classify_batch_pc2(urf_ctx* c, const uint8_t* d_data, uint32_
         return URF_ERR_INVALID_ARG;
     if (n_scans > c->max_batch || n_per_scan > c->max_points)
         return URF_ERR_CAPACITY;
-    if (n_scans == 0)
-        return URF_OK;
-    URF_HIP(c, hipSetDevice(c->device));
-    int rc = ensure_soa_staging(c);
-    if (rc != URF_OK)
-        return rc;
-    rc = order_after_slots(c);   /* the staging arrays are shared with the callback path */
-    if (rc != URF_OK)
-        return rc;
-    const unsigned long long total = (unsigned long long)n_per_scan * n_scans;
-    hipLaunchKernelGGL(k_pc2_to_soa, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, d_data, total,
-                       point_step, off_x, off_y, off_z, c->sx, c->sy, c->sz);
-    rc = run_pipeline(c, c->sx, c->sy, c->sz, nullptr, n_per_scan, n_per_scan, n_scans, d_labels, d_info);
-    if (rc == URF_OK)
-        c->last_batch = URF_LAST_PC2;
-    return rc;
+    return classify_batch_pc2(c, d_data, nullptr, (uint64_t)n_per_scan * n_scans, n_per_scan, n_per_scan, n_scans, point_step, off_x, off_y,
+                              off_z, d_labels, d_info);
 }
 
-/* Ragged PointCloud2 batches: the records [0, n_total) unpacked into the SoA staging at their own indices, then the ragged
- * pipeline with the caller's offsets (which index records and staging alike).  A zero-length scan is one the pipeline already
- * answers with URF_TOO_FEW_POINTS (urf_classify_batch_soa_ragged does the same). */
+/* A zero-length scan of a ragged batch is one the pipeline already answers with URF_TOO_FEW_POINTS (urf_classify_batch_soa_ragged
+ * does the same). */
 extern "C" int urf_classify_batch_pc2_ragged(urf_ctx* c, const uint8_t* d_data, const uint32_t* d_offsets, uint64_t n_total,
                                              uint32_t max_len, uint32_t n_scans, uint32_t point_step, uint32_t off_x,
                                              uint32_t off_y, uint32_t off_z, uint8_t* d_labels, urf_scan_info* d_info)
@@ -1041,22 +1039,7 @@ extern "C" int urf_classify_batch_pc2_ragged(urf_ctx* c, const uint8_t* d_data, 
         return URF_ERR_INVALID_ARG;
     if (n_scans > c->max_batch || max_len > c->max_points || n_total > (uint64_t)c->max_points * c->max_batch)
         return URF_ERR_CAPACITY;
-    if (n_scans == 0)
-        return URF_OK;
-    URF_HIP(c, hipSetDevice(c->device));
-    int rc = ensure_soa_staging(c);
-    if (rc != URF_OK)
-        return rc;
-    rc = order_after_slots(c);   /* the staging arrays are shared with the callback path */
-    if (rc != URF_OK)
-        return rc;
-    if (n_total)
-        hipLaunchKernelGGL(k_pc2_to_soa, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, c->stream, d_data,
-                           (unsigned long long)n_total, point_step, off_x, off_y, off_z, c->sx, c->sy, c->sz);
-    rc = run_pipeline(c, c->sx, c->sy, c->sz, d_offsets, 0, max_len, n_scans, d_labels, d_info);
-    if (rc == URF_OK)
-        c->last_batch = URF_LAST_PC2;
-    return rc;
+    return classify_batch_pc2(c, d_data, d_offsets, n_total, 0, max_len, n_scans, point_step, off_x, off_y, off_z, d_labels, d_info);
 }
 
 /* ---- the callback path: one sweep, host buffers ------------------------------- */
@@ -1082,33 +1065,17 @@ static int slot_prepare(urf_ctx* c, urf_ctx::slot_t& sl, size_t bytes)
             URF_HIP(c, hipStreamCreateWithFlags(&c->row_stream[r], hipStreamNonBlocking));
         c->streams_made = true;
     }
-    if (!sl.ev_done) {
+    if (!sl.ev_done)
         URF_HIP(c, hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
-        void *hl = nullptr, *hi = nullptr, *dl = nullptr;
-        URF_HIP(c, hipHostMalloc(&hl, c->max_points, hipHostMallocDefault));
-        URF_HIP(c, hipHostMalloc(&hi, sizeof(urf_scan_info), hipHostMallocDefault));
-        URF_HIP(c, hipMalloc(&dl, c->max_points));
-        sl.h_labels = (uint8_t*)hl;
-        sl.h_info = (urf_scan_info*)hi;
-        sl.d_labels = (uint8_t*)dl;
-    }
-    if (bytes > sl.h_in_cap) {   /* grows to the largest message seen (a new buffer invalidates the captured sequence) */
-        URF_HIP(c, hipStreamSynchronize(slot_stream(c, sl)));   /* the slot's last sweep may still read d_raw */
-        if (sl.h_in)
-            (void)hipHostFree(sl.h_in);
-        if (sl.d_raw)
-            (void)hipFree(sl.d_raw);
-        sl.h_in = nullptr;
-        sl.d_raw = nullptr;
-        sl.h_in_cap = sl.d_raw_cap = 0;
+    int rc;
+    if ((rc = grow(c, sl.h_labels, c->max_points)) != URF_OK || (rc = grow(c, sl.h_info, 1)) != URF_OK ||
+        (rc = grow(c, sl.d_labels, c->max_points)) != URF_OK)
+        return rc;
+    if (bytes > sl.h_in.cap || bytes > sl.d_raw.cap) {   /* grows to the largest message seen (a new buffer invalidates the captured sequence) */
         sl.key[0] = 0;
-        void *h = nullptr, *d = nullptr;
-        URF_HIP(c, hipHostMalloc(&h, bytes, hipHostMallocDefault));
-        sl.h_in = (uint8_t*)h;
-        sl.h_in_cap = bytes;
-        URF_HIP(c, hipMalloc(&d, bytes));
-        sl.d_raw = (uint8_t*)d;
-        sl.d_raw_cap = bytes;
+        const hipStream_t st = slot_stream(c, sl);   /* the slot's last sweep may still read d_raw */
+        if ((rc = grow(c, sl.h_in, bytes, st)) != URF_OK || (rc = grow(c, sl.d_raw, bytes, st)) != URF_OK)
+            return rc;
     }
     return URF_OK;
 }
@@ -1190,25 +1157,25 @@ static int slot_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t n_points, uint3
     float *sx, *sy, *sz;
     if (sl.planes) {
         const size_t n4 = ((size_t)n_points + 3) & ~(size_t)3;
-        sx = (float*)sl.d_raw;
+        sx = (float*)sl.d_raw.p;
         sy = sx + n4;
         sz = sy + n4;
     } else {
-        sx = c->sx + (size_t)row * c->max_points;   /* (ensure_soa_staging: the caller) */
-        sy = c->sy + (size_t)row * c->max_points;
-        sz = c->sz + (size_t)row * c->max_points;
-        hipLaunchKernelGGL(k_pc2_to_soa, dim3((n_points + 255) / 256), dim3(256), 0, st, sl.d_raw, (unsigned long long)n_points,
+        sx = c->sx.p + (size_t)row * c->max_points;   /* (ensure_soa_staging: the caller) */
+        sy = c->sy.p + (size_t)row * c->max_points;
+        sz = c->sz.p + (size_t)row * c->max_points;
+        hipLaunchKernelGGL(k_pc2_to_soa, dim3((n_points + 255) / 256), dim3(256), 0, st, sl.d_raw.p, (unsigned long long)n_points,
                            point_step, off_x, off_y, off_z, sx, sy, sz);
     }
     urf_kargs a_run;
     urf_dev_params dp_run;   /* (dp_in may point at sl.cap_dp) */
-    const int rc = run_pipeline(c, sx, sy, sz, nullptr, n_points, n_points, 1, sl.d_labels, nullptr, row, st, &a_run, &dp_run, dp_in, capture_in);
+    const int rc = run_pipeline(c, sx, sy, sz, nullptr, n_points, n_points, 1, sl.d_labels.p, nullptr, row, st, &a_run, &dp_run, dp_in, capture_in);
     if (rc != URF_OK)
         return rc;
     sl.cap_a = a_run;
     sl.cap_dp = dp_run;
-    URF_HIP(c, hipMemcpyAsync(sl.h_labels, sl.d_labels, n_points, hipMemcpyDeviceToHost, st));
-    URF_HIP(c, hipMemcpyAsync(sl.h_info, kargs_row(c, row).info, sizeof(urf_scan_info), hipMemcpyDeviceToHost, st));
+    URF_HIP(c, hipMemcpyAsync(sl.h_labels.p, sl.d_labels.p, n_points, hipMemcpyDeviceToHost, st));
+    URF_HIP(c, hipMemcpyAsync(sl.h_info.p, kargs_row(c, row).info, sizeof(urf_scan_info), hipMemcpyDeviceToHost, st));
     return URF_OK;
 }
 
@@ -1223,7 +1190,7 @@ extern "C" int urf_pinned_input(urf_ctx* c, size_t bytes, uint8_t** ptr)
     const int rc = slot_prepare(c, sl, bytes);
     if (rc != URF_OK)
         return rc;
-    *ptr = sl.h_in;
+    *ptr = sl.h_in.p;
     return URF_OK;
 }
 
@@ -1242,9 +1209,9 @@ extern "C" int urf_classify_pc2_async(urf_ctx* c, const uint8_t* data, uint32_t 
     HT_START;
     /* a message inside the slot's pinned buffer must be the buffer urf_pinned_input() handed out, and
      * fit it: a larger one would make slot_prepare() free the very memory it is about to read */
-    if (sl.h_in && data >= sl.h_in && data < sl.h_in + sl.h_in_cap && (data != sl.h_in || bytes > sl.h_in_cap))
+    if (sl.h_in.p && data >= sl.h_in.p && data < sl.h_in.p + sl.h_in.cap && (data != sl.h_in.p || bytes > sl.h_in.cap))
         return URF_ERR_INVALID_ARG;
-    const bool planes = data != sl.h_in;   /* (a producer that filled the pinned buffer itself wrote records) */
+    const bool planes = data != sl.h_in.p;   /* (a producer that filled the pinned buffer itself wrote records) */
     const size_t n4 = ((size_t)n_points + 3) & ~(size_t)3;
     const size_t plane_bytes = 3 * sizeof(float) * n4;
     int rc = slot_prepare(c, sl, planes && plane_bytes > bytes ? plane_bytes : bytes);
@@ -1265,16 +1232,16 @@ extern "C" int urf_classify_pc2_async(urf_ctx* c, const uint8_t* data, uint32_t 
         /* gathered into the pinned planes (pc2_to_planes) in two halves, so that the first one is on its way while the
          * second one is gathered (one 2-D copy per half: its columns of the three planes; 35 us for the whole, 22 per
          * half).  (urf_pinned_input() lets a producer write its records into the pinned buffer directly: no staging.) */
-        float* X = (float*)sl.h_in;
+        float* X = (float*)sl.h_in.p;
         const uint32_t mid = n_points >= 32768 ? (uint32_t)((n4 / 2) & ~(size_t)3) : 0u;
         const uint32_t cut[3] = { 0u, mid, n_points };
         for (int h = mid ? 0 : 1; h < 2; h++) {
             pc2_to_planes(data, cut[h], cut[h + 1], point_step, off_x, off_y, off_z, X, X + n4, X + 2 * n4);
             const size_t w = (h == 1 ? n4 - cut[1] : cut[1]) * sizeof(float), o = cut[h] * sizeof(float);
-            URF_HIP(c, hipMemcpy2DAsync(sl.d_raw + o, n4 * sizeof(float), sl.h_in + o, n4 * sizeof(float), w, 3, hipMemcpyHostToDevice, st));
+            URF_HIP(c, hipMemcpy2DAsync(sl.d_raw.p + o, n4 * sizeof(float), sl.h_in.p + o, n4 * sizeof(float), w, 3, hipMemcpyHostToDevice, st));
         }
     } else {
-        URF_HIP(c, hipMemcpyAsync(sl.d_raw, sl.h_in, bytes, hipMemcpyHostToDevice, st));
+        URF_HIP(c, hipMemcpyAsync(sl.d_raw.p, sl.h_in.p, bytes, hipMemcpyHostToDevice, st));
     }
     if (planes != sl.planes)
         sl.key[0] = 0;   /* the captured sequence reads the other format */
@@ -1367,14 +1334,14 @@ extern "C" int urf_classify_pc2_wait(urf_ctx* c, uint32_t ticket, uint8_t* label
         return st == URF_STATUS_REDO_TABLE || st == URF_STATUS_REDO_LISTS || st == URF_STATUS_REDO_NAN || st == URF_STATUS_REDO_HINT ||
                st == URF_STATUS_REDO_TIES;
     };
-    for (int tries = 0; tries < 6 && redo(sl.h_info->status); tries++) {
-        if (sl.h_info->status == URF_STATUS_REDO_TABLE)
+    for (int tries = 0; tries < 6 && redo(sl.h_info.p->status); tries++) {
+        if (sl.h_info.p->status == URF_STATUS_REDO_TABLE)
             c->speculate = false;
-        else if (sl.h_info->status == URF_STATUS_REDO_HINT)
+        else if (sl.h_info.p->status == URF_STATUS_REDO_HINT)
             c->use_hint = false;
-        else if (sl.h_info->status == URF_STATUS_REDO_LISTS)
+        else if (sl.h_info.p->status == URF_STATUS_REDO_LISTS)
             c->slot_lists = true;
-        else if (sl.h_info->status == URF_STATUS_REDO_TIES)
+        else if (sl.h_info.p->status == URF_STATUS_REDO_TIES)
             c->slot_ties = true;
         else
             c->slot_nan = true;
@@ -1398,7 +1365,7 @@ extern "C" int urf_classify_pc2_wait(urf_ctx* c, uint32_t ticket, uint8_t* label
             return rc;
         }
     }
-    if (redo(sl.h_info->status)) {
+    if (redo(sl.h_info.p->status)) {
         sl.pending = false;
         return URF_ERR_HIP;   /* (cannot happen: the full sequence raises neither) */
     }
@@ -1412,9 +1379,9 @@ extern "C" int urf_classify_pc2_wait(urf_ctx* c, uint32_t ticket, uint8_t* label
     c->last_row = slot_row(c, sl);
     c->last_gen = sl.gen;
     if (labels_out)
-        std::memcpy(labels_out, sl.h_labels, sl.n_points);
+        std::memcpy(labels_out, sl.h_labels.p, sl.n_points);
     if (info)
-        *info = *sl.h_info;
+        *info = *sl.h_info.p;
     sl.pending = false;
     HT(5, ht0);
     return URF_OK;
@@ -1426,11 +1393,11 @@ extern "C" int urf_result_labels(urf_ctx* c, uint32_t ticket, const uint8_t** la
         return URF_ERR_INVALID_ARG;
     *labels = nullptr;
     const urf_ctx::slot_t& sl = c->slots[ticket % URF_ASYNC_SLOTS];
-    if (!sl.used || sl.ticket != ticket || !sl.h_labels)
+    if (!sl.used || sl.ticket != ticket || !sl.h_labels.p)
         return URF_ERR_INVALID_ARG;   /* never issued, or its slot has been used again since */
     if (sl.pending)
         return URF_ERR_BUSY;          /* not waited for yet: the buffer is still being written */
-    *labels = sl.h_labels;
+    *labels = sl.h_labels.p;
     return URF_OK;
 }
 
@@ -1528,27 +1495,11 @@ extern "C" int urf_compact_indices(urf_ctx* c, const uint8_t* d_labels, uint32_t
 
 static int ensure_order_scratch(urf_ctx* c, uint32_t n_scans)
 {
-    if (n_scans <= c->ord_scans)
-        return URF_OK;
-    URF_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->ord_keys) {
-        (void)hipFree(c->ord_keys);
-        (void)hipFree(c->ord_pos);
-        (void)hipFree(c->ord_cls);
-        c->ord_keys = nullptr;
-        c->ord_pos = nullptr;
-        c->ord_cls = nullptr;
-        c->ord_scans = 0;
-    }
-    void *p0 = nullptr, *p1 = nullptr, *p2 = nullptr;
-    URF_HIP(c, hipMalloc(&p0, (size_t)n_scans * c->sstride * sizeof(unsigned long long)));
-    URF_HIP(c, hipMalloc(&p1, (size_t)n_scans * c->sstride * sizeof(uint32_t)));
-    URF_HIP(c, hipMalloc(&p2, (size_t)n_scans * URF_MAX_CHANNELS * 2 * sizeof(uint32_t)));
-    c->ord_keys = (unsigned long long*)p0;
-    c->ord_pos = (uint32_t*)p1;
-    c->ord_cls = (uint32_t*)p2;
-    c->ord_scans = n_scans;
-    return URF_OK;
+    const size_t n = (size_t)n_scans * c->sstride;
+    int rc;
+    if ((rc = grow(c, c->ord_keys, n, c->stream)) != URF_OK || (rc = grow(c, c->ord_pos, n, c->stream)) != URF_OK)
+        return rc;
+    return grow(c, c->ord_cls, (size_t)n_scans * URF_MAX_CHANNELS * 2, c->stream);
 }
 
 /* scans [s0, s0 + n) of the last classify call, lists of `stride` entries per scan on the device */
@@ -1565,8 +1516,8 @@ static int launch_ordered(urf_ctx* c, uint32_t s0, uint32_t n, uint32_t* d_road,
     const urf_kargs a = c->last_a;   /* the call's own arguments and parameters, whatever was set since */
     const urf_dev_params dp = c->last_dp;
     hipLaunchKernelGGL(k_ring_order, dim3((unsigned)dp.p.channels, n), dim3(256), (2 * (size_t)a.tiles + 1) * sizeof(unsigned), c->stream, a, dp,
-                       s0, c->ord_keys, c->ord_pos, c->ord_cls);
-    hipLaunchKernelGGL(k_ordered_lists, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, c->ord_pos, c->ord_cls, d_road,
+                       s0, c->ord_keys.p, c->ord_pos.p, c->ord_cls.p);
+    hipLaunchKernelGGL(k_ordered_lists, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, c->ord_pos.p, c->ord_cls.p, d_road,
                        d_curb, d_r10, stride, d_counts);
     URF_HIP(c, hipGetLastError());
     return URF_OK;
@@ -1588,12 +1539,10 @@ extern "C" int urf_ordered_indices(urf_ctx* c, uint32_t scan, uint32_t* road, ui
         return URF_ERR_INVALID_ARG;
     URF_HIP(c, hipSetDevice(c->device));
     const size_t mp = c->sstride;
-    if (!c->ord_lists) {
-        void* p2 = nullptr;
-        URF_HIP(c, hipMalloc(&p2, (mp * 3 + 4) * sizeof(uint32_t)));
-        c->ord_lists = (uint32_t*)p2;
-    }
-    uint32_t* d_road = c->ord_lists;
+    const int grc = grow(c, c->ord_lists, mp * 3 + 4);
+    if (grc != URF_OK)
+        return grc;
+    uint32_t* d_road = c->ord_lists.p;
     uint32_t* d_curb = d_road + mp;
     uint32_t* d_r10 = d_curb + mp;
     uint32_t* d_cnt = d_r10 + mp;
@@ -1621,21 +1570,10 @@ extern "C" int urf_ordered_indices(urf_ctx* c, uint32_t scan, uint32_t* road, ui
 
 static int ensure_clouds_scratch(urf_ctx* c, uint32_t n_scans, uint32_t stride, bool lists)
 {
-    if (!c->cl_tiles)
-        URF_HIP(c, hipMalloc(&c->cl_tiles, 2 * (size_t)c->max_batch * c->max_tiles * sizeof(urf_u32x4)));
-    const size_t need = 3 * (size_t)n_scans * stride + 3 * (size_t)n_scans;
-    if (lists && need > c->cl_lists_cap) {
-        URF_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->cl_lists)
-            (void)hipFree(c->cl_lists);
-        c->cl_lists = nullptr;
-        c->cl_lists_cap = 0;
-        void* p = nullptr;
-        URF_HIP(c, hipMalloc(&p, need * sizeof(uint32_t)));
-        c->cl_lists = (uint32_t*)p;
-        c->cl_lists_cap = need;
-    }
-    return URF_OK;
+    const int rc = grow(c, c->cl_tiles, 2 * (size_t)c->max_batch * c->max_tiles);
+    if (rc != URF_OK || !lists)
+        return rc;
+    return grow(c, c->cl_lists, 3 * (size_t)n_scans * stride + 3 * (size_t)n_scans, c->stream);
 }
 
 /* src: where the points come from (x / y / z / data and the layout fields; the rest is filled in here) */
@@ -1658,8 +1596,8 @@ static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, ur
     if (rc != URF_OK)
         return rc;
     if (ref) {   /* urf_ordered_indices_batch's kernels (after a fused call: the documented rerun through the general kernels) */
-        rc = launch_ordered(c, 0, S, c->cl_lists, c->cl_lists + (size_t)S * stride, c->cl_lists + 2 * (size_t)S * stride, stride,
-                            c->cl_lists + 3 * (size_t)S * stride);
+        uint32_t* const l = c->cl_lists.p;
+        rc = launch_ordered(c, 0, S, l, l + (size_t)S * stride, l + 2 * (size_t)S * stride, stride, l + 3 * (size_t)S * stride);
     } else {
         rc = order_after_slots(c);   /* cl_tiles is the context's */
     }
@@ -1673,13 +1611,13 @@ static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, ur
     src.max_len = a.max_len;
     src.tiles = a.tiles;
     src.n_scans = S;
-    src.tile_cnt = (urf_u32x4*)c->cl_tiles;
+    src.tile_cnt = c->cl_tiles.p;
     src.tile_base = src.tile_cnt + (size_t)c->max_batch * c->max_tiles;
     src.counts = d_counts;
     src.offs = (unsigned long long*)d_offsets;
     src.rec = (urf_u32x4*)d_records;
-    src.lists = c->cl_lists;
-    src.list_cnt = c->cl_lists ? c->cl_lists + 3 * (size_t)S * stride : nullptr;
+    src.lists = c->cl_lists.p;
+    src.list_cnt = c->cl_lists.p ? c->cl_lists.p + 3 * (size_t)S * stride : nullptr;
     src.stride = stride;
     hipStream_t st = c->stream;
     const dim3 g_tiles(a.tiles, S);
@@ -1746,41 +1684,19 @@ extern "C" int urf_clouds_batch_pc2(urf_ctx* c, const uint8_t* d_data, uint32_t 
 
 static int launch_markers(urf_ctx* c, uint32_t s0, uint32_t n, float* d_pts, uint32_t* d_counts)
 {
-    {
-        const int irc = last_row_intact(c);
-        if (irc != URF_OK)
-            return irc;
-        const int orc = order_after_slots(c);
-        if (orc != URF_OK)
-            return orc;
-    }
     const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;
-    if (n > c->mk_scans) {
-        URF_HIP(c, hipStreamSynchronize(c->stream));
-        for (void* p : { (void*)c->mk_d, (void*)c->mk_pos, (void*)c->mk_red })
-            if (p)
-                (void)hipFree(p);
-        c->mk_d = nullptr;
-        c->mk_pos = nullptr;
-        c->mk_red = nullptr;
-        c->mk_scans = 0;
-        void *p0 = nullptr, *p1 = nullptr, *p2 = nullptr;
-        URF_HIP(c, hipMalloc(&p0, n * cells * sizeof(float)));
-        URF_HIP(c, hipMalloc(&p1, n * cells * sizeof(uint32_t)));
-        URF_HIP(c, hipMalloc(&p2, n * (cells + URF_MAX_CHANNELS)));   /* + one flag per ring: its order decides (k_marker_ring_literal) */
-        c->mk_d = (float*)p0;
-        c->mk_pos = (uint32_t*)p1;
-        c->mk_red = (uint8_t*)p2;
-        c->mk_scans = n;
-    }
+    int rc;
+    if ((rc = last_row_intact(c)) != URF_OK || (rc = order_after_slots(c)) != URF_OK || (rc = grow(c, c->mk_d, n * cells, c->stream)) != URF_OK ||
+        (rc = grow(c, c->mk_pos, n * cells, c->stream)) != URF_OK || (rc = grow(c, c->mk_red, n * (cells + URF_MAX_CHANNELS), c->stream)) != URF_OK)
+        return rc;
     const urf_kargs a = c->last_a;
     const urf_dev_params dp = c->last_dp;
-    uint8_t* const mk_lit = c->mk_red + (size_t)c->mk_scans * cells;
+    uint8_t* const mk_lit = c->mk_red.p + n * cells;
     hipLaunchKernelGGL(k_marker_ring, dim3((unsigned)dp.p.channels, n), dim3(256), (2 * (size_t)a.tiles + 1) * sizeof(unsigned), c->stream, a, dp, s0,
-                       c->mk_d, c->mk_pos, c->mk_red, mk_lit);
+                       c->mk_d.p, c->mk_pos.p, c->mk_red.p, mk_lit);
     /* rings in which the ORDER of equal azimuths decides a marker point (normally none: every workgroup returns at once) */
-    hipLaunchKernelGGL(k_marker_ring_literal, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, mk_lit, c->mk_d, c->mk_pos, c->mk_red);
-    hipLaunchKernelGGL(k_marker_bins, dim3(n), dim3(384), 0, c->stream, a, dp, s0, c->mk_d, c->mk_pos, c->mk_red, d_pts, d_counts);
+    hipLaunchKernelGGL(k_marker_ring_literal, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, mk_lit, c->mk_d.p, c->mk_pos.p, c->mk_red.p);
+    hipLaunchKernelGGL(k_marker_bins, dim3(n), dim3(384), 0, c->stream, a, dp, s0, c->mk_d.p, c->mk_pos.p, c->mk_red.p, d_pts, d_counts);
     URF_HIP(c, hipGetLastError());
     return URF_OK;
 }
@@ -1798,18 +1714,15 @@ extern "C" int urf_marker_points(urf_ctx* c, uint32_t scan, float* pts, uint32_t
     if (!c || !pts || !count || scan >= c->last_scans || !c->last_a.labels)
         return URF_ERR_INVALID_ARG;
     URF_HIP(c, hipSetDevice(c->device));
-    if (!c->mk_out) {
-        void* p3 = nullptr;
-        URF_HIP(c, hipMalloc(&p3, (URF_DEG_CELLS * 4 + 4) * sizeof(float)));
-        c->mk_out = (float*)p3;
-    }
-    hipStream_t st = c->stream;
-    unsigned* d_cnt = (unsigned*)(c->mk_out + URF_DEG_CELLS * 4);
-    const int rc = launch_markers(c, scan, 1, c->mk_out, d_cnt);
+    int rc = grow(c, c->mk_out, URF_DEG_CELLS * 4 + 4);
     if (rc != URF_OK)
         return rc;
+    hipStream_t st = c->stream;
+    unsigned* d_cnt = (unsigned*)(c->mk_out.p + URF_DEG_CELLS * 4);
+    if ((rc = launch_markers(c, scan, 1, c->mk_out.p, d_cnt)) != URF_OK)
+        return rc;
     std::vector<float> h(URF_DEG_CELLS * 4 + 4);
-    URF_HIP(c, hipMemcpyAsync(h.data(), c->mk_out, h.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    URF_HIP(c, hipMemcpyAsync(h.data(), c->mk_out.p, h.size() * sizeof(float), hipMemcpyDeviceToHost, st));
     URF_HIP(c, hipStreamSynchronize(st));
     uint32_t n = 0;
     std::memcpy(&n, &h[URF_DEG_CELLS * 4], sizeof(n));
