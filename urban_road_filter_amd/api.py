@@ -352,7 +352,9 @@ class Context:
         return n.value
 
     def set_front_mode(self, mode):
-        """The fused front end for batches of sweeps in firing order (include/urf.h): 0 never, 1 batches of >= 32 scans, 2 always."""
+        """The fused front end for batches of organised sweeps (include/urf.h): 0 never; 1 (default) batch calls of at least 192 scans
+        -- a context whose sweeps have turned out to be row-major takes it at any batch size, and on the callback path; 2 every batch
+        call it applies to."""
         self._check(self._lib.urf_set_front_mode(self._h, int(mode)), "urf_set_front_mode")
 
     def callback_path_preset(self, sequence_bits):

@@ -81,6 +81,104 @@ struct lazy_buf {
 #define URF_SCRATCH_ROW_MAJOR(X) X(tx, sstride) X(ty, sstride) X(tz, sstride) X(rows_v, 64) X(rows_ok, 1)
 enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR };
 
+/* The launch policy: which kernels a call launches, decided on the host from what the kernels of earlier calls reported through the
+ * host-mapped flag words (enum urf_flag).  fold() is the only reader of the words: a batch call runs it in run_pipeline, a sweep of the
+ * callback path in urf_classify_pc2_async, before either launches anything.  plan() turns the fields into a call's urf_kargs.  Every
+ * change of what plan() reads bumps `epoch` (set()), the key of the callback path's captured sequences: a replayed sequence launches
+ * what a fresh one would.  (Hidden: the library exports the C ABI, not this struct's functions.) */
+struct __attribute__((visibility("hidden"))) urf_policy {
+    uint32_t* flags = nullptr;      /* [URF_FLAG_WORDS] pinned, device-mapped (urf_kargs::flags) */
+    uint64_t epoch = 1;             /* bumped by everything a captured sequence depends on (the settings' entry points bump it too) */
+    /* k_ring_table speculates: it stops when no new ring has shown up for a while (speculate) and at the ring count of the row's previous
+     * call (use_hint).  k_split checks; a scan that proves a rule wrong is repaired in the same call and raises its flag word
+     * (URF_FLAG_LOOKAHEAD_FAILED / URF_FLAG_HINT_FAILED), and the context does without that rule from then on. */
+    bool speculate = true, use_hint = true;
+    /* the callback path's short sequence leaves out what normally finds nothing to do; a sweep that needed the kernels for the work lists
+     * of oversized star sectors (slot_lists), for rings with a point on the sensor's axis (slot_nan) or for equal planar ranges in a star
+     * sector (slot_ties: any real sensor's sweep) comes back with a URF_STATUS_REDO_* status and is run again with them, as are all later
+     * ones (on_redo) */
+    bool slot_lists = false, slot_nan = false, slot_ties = false;
+    /* the fused front end (urf_front.hpp, urf_set_front_mode): 0 never, 1 batches of at least URF_FRONT_MIN_SCANS scans (default), 2 every
+     * batch call it applies to.  After a read-back of ring-sorted results the context keeps to the general kernels (want_ring_sorted,
+     * last_row_intact). */
+    int front_mode = 1;
+    uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
+    bool want_ring_sorted = false;
+    /* k_front hands a scan without the shape back to the general kernels: launched list-driven until a call has done so
+     * (URF_FLAG_FRONT_HANDED_BACK: front_direct, full grids from then on); mode 1 stops trying once a whole batch has been handed back
+     * (URF_FLAG_FRONT_ALL_HANDED_BACK: front_off, unorganised clouds).  forget_front() starts over. */
+    bool front_direct = false, front_off = false;
+    /* row-major organised sweeps (k_ring_table's third rule): once one has been sighted (URF_FLAG_ROWS_SIGHTED) the firing-order copies are
+     * allocated and the sequences hold k_rows_probe and k_transpose (front_rows; rows_oom: the allocation failed).  Once a scan has taken
+     * the layout (URF_FLAG_ROWS_TAKEN: rows_used), or while the sighting is on probation, batches below mode 1's threshold and the
+     * callback path take the fused kernels too. */
+    bool front_rows = false, rows_oom = false, rows_used = false;
+    uint32_t rows_probation = 0;
+
+    template <class T>
+    void set(T& field, T value)
+    {
+        if (field != value) {
+            field = value;
+            epoch++;
+        }
+    }
+    /* urf_set_params with other parameters, urf_set_front_mode with another mode, the row-major sighting */
+    void forget_front()
+    {
+        set(front_direct, false);
+        set(front_off, false);
+        flags[URF_FLAG_FRONT_HANDED_BACK] = flags[URF_FLAG_FRONT_ALL_HANDED_BACK] = 0;
+    }
+    int fold(urf_ctx* c, hipStream_t st);
+    /* A sighting that no scan confirms (a sweep in firing order whose region of interest begins with a single laser) lapses after 16 calls
+     * that count: every submission on the callback path, whichever kernels it takes, but only those batch calls below mode 1's threshold
+     * that took the fused kernels on its strength. */
+    void probation_sweep() { lapse(front_rows); }
+    void probation_batch(const urf_kargs& a) { lapse(a.front && front_mode != 2 && a.n_scans < URF_FRONT_MIN_SCANS); }
+    void lapse(bool counts)
+    {
+        if (counts && !rows_used && rows_probation && --rows_probation == 0)
+            epoch++;
+    }
+    /* a sweep of the callback path that the short sequence voided: from now on the sequence holds what it needed (false: no such status) */
+    bool on_redo(int status)
+    {
+        switch (status) {
+        case URF_STATUS_REDO_TABLE: set(speculate, false); return true;
+        case URF_STATUS_REDO_HINT: set(use_hint, false); return true;
+        case URF_STATUS_REDO_LISTS: set(slot_lists, true); return true;
+        case URF_STATUS_REDO_NAN: set(slot_nan, true); return true;
+        case URF_STATUS_REDO_TIES: set(slot_ties, true); return true;
+        }
+        return false;
+    }
+    /* The launch decisions of one call (a.tiles, a.capture, a.n_scans set): slot, a sweep of the callback path; general_only, no fused
+     * kernels (last_row_intact). */
+    void plan(urf_kargs& a, const urf_dev_params& dp, bool slot, bool general_only) const
+    {
+        a.table_lookahead = speculate ? URF_TABLE_LOOKAHEAD : 0u;
+        a.table_hint = (speculate && use_hint) ? 1u : 0u;
+        /* A sweep of the callback path is waited for by the host before anybody sees its result: the kernels that normally find nothing
+         * to do -- the two repair kernels behind the speculative ring table, the two for the work lists of oversized star sectors, 20 of a
+         * sweep's 200 microseconds -- are left out, k_index voids a sweep that needed them, and urf_classify_pc2_wait() runs it again. */
+        a.optimistic = slot ? ((speculate ? URF_OPT_NO_REPAIR : 0u) | (slot_lists ? 0u : URF_OPT_NO_LISTS) | (slot_nan ? 0u : URF_OPT_NO_NAN) |
+                               (slot_ties ? 0u : URF_OPT_NO_TIES)) : 0u;
+        /* The fused front end: 64 lasers = 64 lanes, the detectors' window of curbPoints == 5 in registers, no stage capture (its values
+         * are the general kernels').  Row-major sweeps gain from it at any batch size (the general kernels need 0.64 ms for four such
+         * sweeps, the fused ones 0.26, tools/r6_min_scans.py --rows), sweeps in firing order only from 192 per call on, and not as single
+         * sweeps of the callback path (tools/r6_single_sweep.py). */
+        const bool shape = front_mode != 0 && !front_off && !general_only && !want_ring_sorted && a.capture == 0 &&
+                           (unsigned)dp.p.channels == URF_FRONT_LANES && dp.p.curbPoints == 5 && a.tiles <= URF_FRONT_MAX_TILES;
+        const bool small_ok = front_rows && (rows_used || rows_probation > 0);
+        a.front = (shape && (slot ? small_ok : (front_mode == 2 || small_ok || a.n_scans >= URF_FRONT_MIN_SCANS))) ? 1u : 0u;
+        a.front_sight = (shape && !a.front && !front_rows && !rows_oom) ? 1u : 0u;
+        a.front_tpb = front_tpb ? front_tpb : (a.n_scans >= URF_FRONT_TPB_SCANS ? URF_FRONT_TPB_LARGE : (a.n_scans >= 16u ? URF_FRONT_TPB_SMALL : 1u));
+        a.front_lists = (a.front && !front_direct && !slot) ? 1u : 0u;   /* (the callback path's sequence holds the general kernels as grids anyway) */
+        a.front_rows = (a.front && front_rows) ? 1u : 0u;   /* (independent of the two other speculations: the repair kernels come with it) */
+    }
+};
+
 struct urf_ctx {
     int device = 0;
     uint32_t max_points = 0, max_batch = 0;
@@ -119,12 +217,7 @@ struct urf_ctx {
         bool planes = false;            /* d_raw holds x[n] y[n] z[n] (a staged message) instead of the records */
     } slots[URF_ASYNC_SLOTS];
     bool streams_made = false;
-    /* the callback path launches a short sequence first: no repair kernels behind the speculative ring table, no
-     * kernels for the work lists of oversized star sectors (run_pipeline); a sweep that needed one of them comes back
-     * with an internal status and is run again with it, as are all later ones (urf_classify_pc2_wait) */
-    bool slot_lists = false;
-    bool slot_nan = false;          /* ... k_nan_rings (a sweep with a ring point on the sensor's axis) */
-    bool slot_ties = false;         /* ... k_star_ties (a sweep with equal planar ranges in a star sector: any real sensor's) */
+    urf_policy pol;                 /* which kernels a call launches */
     uint32_t n_rerun = 0;           /* sweeps urf_classify_pc2_wait had to run again */
     /* Slot i works on scratch row i % rows, rows = min(max_batch, URF_ASYNC_SLOTS); row 0 runs on the
      * context's stream, every other row on a stream of its own (slots that share a row share its
@@ -143,7 +236,6 @@ struct urf_ctx {
     uint32_t last_row = 0;                 /* ... on this row ... */
     uint64_t last_gen = 0;                 /* ... which was the row's submission number last_gen */
     uint32_t next_ticket = 0;
-    uint64_t epoch = 1;             /* bumped by everything a captured sequence depends on */
     /* sized for the largest number of scans asked for so far: scratch of the index-list and marker-point outputs
      * (sstride entries resp. channels x 361 cells per scan) */
     lazy_buf<unsigned long long> ord_keys;
@@ -167,34 +259,9 @@ struct urf_ctx {
     std::vector<std::vector<hipEvent_t>> timing_events;   /* sets of URF_NUM_KERNELS+1 events, created once and reused */
     size_t timing_used = 0;         /* sets recorded since the last urf_kernel_timing() */
     uint32_t* offsets_copy = nullptr;   /* [max_batch + 1] the ragged offsets of the last call (context-owned) */
-    /* k_ring_table speculates (stops when no new ring has shown up for a while, k_split checks);
-     * a scan that proves it wrong is repaired in the same call and raises this host-visible flag,
-     * after which the context builds its tables the long way */
-    uint32_t* h_spec_failed = nullptr;  /* pinned, device-mapped: [0] look-ahead, [1] ring-count hint */
-    /* the fused front end (urf_front.hpp, urf_set_front_mode): 0 never, 1 batches of at least URF_FRONT_MIN_SCANS scans (default),
-     * 2 every batch call it applies to.  The entry points that read ring-sorted intermediate results (urf_read_stage,
-     * urf_ordered_indices*, urf_marker_points*) run the last call again through the legacy kernels when it took the fused ones,
-     * and the context keeps to the legacy kernels from then on (want_ring_sorted). */
-    int front_mode = 1;
-    uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
-    bool want_ring_sorted = false;
-    /* k_front hands a scan without the shape back to the legacy kernels.  As long as no call has done so, those are launched
-     * list-driven (a few persistent workgroups that find an empty list) instead of as full grids of workgroups that look at the
-     * scan's flag and leave; after the first such scan (h_spec_failed[2]) they come as full grids, and once a whole batch has been
-     * handed back (h_spec_failed[3]: unorganised clouds) the context stops trying.  urf_set_params / urf_set_front_mode start over. */
-    bool front_direct = false, front_off = false;
-    /* row-major organised sweeps (k_ring_table's third rule): once one has been sighted (h_spec_failed[4]) the batch calls' sequence
-     * holds k_transpose and k_ring_table may choose the layout */
-    bool front_rows = false, rows_oom = false;
-    /* ... and once a scan has really taken the layout (h_spec_failed[6]) -- or for a few calls after the sighting -- batches below mode 1's threshold
-     * take the fused kernels too (row-major sweeps gain from them at any batch size, sweeps in firing order only from 192 per call on) */
-    bool rows_used = false;
-    uint32_t rows_probation = 0;
-    /* k_front_finish's first part runs on a stream of its own next to the star-shaped search (run_pipeline): all three or none */
+    /* k_front_finish's first part runs on a stream of its own next to the star-shaped search (side_fork): all three or none */
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool speculate = true;
-    bool use_hint = true;           /* k_ring_table also stops at the ring count of the row's previous call (until that fails once) */
     /* last call, for the entry points that read its intermediate results (urf_read_stage,
      * urf_ordered_indices, urf_marker_points): the kernel arguments and parameters it ran with */
     uint32_t last_scans = 0;
@@ -275,6 +342,35 @@ static int scratch_alloc(urf_ctx* c, urf_scratch_group group)
             rc = dev_alloc(c, &p, rows * n);
     });
     return rc;
+}
+
+/* What the kernels of earlier calls reported, taken into the policy before a call's launches (never inside a stream capture: the first
+ * row-major sighting lets the calls in flight on `st`, the stream the call launches on, finish -- what they handed back, possibly all
+ * of their sweeps, says nothing about the calls to come -- and allocates the firing-order copies before the call takes its arguments). */
+int urf_policy::fold(urf_ctx* c, hipStream_t st)
+{
+    if (front_mode != 0 && !front_rows && !rows_oom && flags[URF_FLAG_ROWS_SIGHTED]) {
+        URF_HIP(c, hipStreamSynchronize(st));
+        if (scratch_alloc(c, URF_SCR_ROW_MAJOR) == URF_OK) {
+            set(front_rows, true);
+            rows_probation = 16;
+            forget_front();
+        } else {
+            set(rows_oom, true);   /* (such sweeps keep to the general kernels) */
+            c->last_error.clear();
+        }
+    }
+    if (front_rows && flags[URF_FLAG_ROWS_TAKEN])
+        set(rows_used, true);
+    if (flags[URF_FLAG_LOOKAHEAD_FAILED])
+        set(speculate, false);
+    if (flags[URF_FLAG_HINT_FAILED])
+        set(use_hint, false);
+    if (flags[URF_FLAG_FRONT_HANDED_BACK])
+        set(front_direct, true);
+    if (flags[URF_FLAG_FRONT_ALL_HANDED_BACK] && front_mode != 2)
+        set(front_off, true);
+    return URF_OK;
 }
 
 /* star_shaped_search.cpp:32-66 beam_init: per-sector constants of the
@@ -406,21 +502,19 @@ extern "C" int urf_create(urf_ctx** out, int device_id, uint32_t max_points, uin
     }
     k.sstride = c->sstride;
     if (const char* e = std::getenv("URF_FRONT_TPB"))   /* tuning experiments: tiles per block of k_front */
-        c->front_tpb = (uint32_t)std::atoi(e) > 0 ? (uint32_t)std::atoi(e) : c->front_tpb;
+        c->pol.front_tpb = (uint32_t)std::atoi(e) > 0 ? (uint32_t)std::atoi(e) : c->pol.front_tpb;
     {
         void* hp = nullptr;
-        if (hipHostMalloc(&hp, 8 * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess)
+        if (hipHostMalloc(&hp, URF_FLAG_WORDS * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess)
             return fail(URF_ERR_HIP);
-        c->h_spec_failed = (uint32_t*)hp;   /* [2], [3]: the fused front end's two flags (front_direct, front_off); [4], [5]: row-major sweeps sighted / failed */
-        for (int i = 0; i < 8; i++)
-            c->h_spec_failed[i] = 0;
+        c->pol.flags = (uint32_t*)hp;
+        std::memset(hp, 0, URF_FLAG_WORDS * sizeof(uint32_t));
         if (hipMemset(k.ring_hint, 0, URF_ASYNC_SLOTS * sizeof(uint32_t)) != hipSuccess)
             return fail(URF_ERR_HIP);
         void* dp_ = nullptr;
         if (hipHostGetDevicePointer(&dp_, hp, 0) != hipSuccess)
             return fail(URF_ERR_HIP);
-        k.spec_failed = (uint32_t*)dp_;
-        k.front_state = k.spec_failed + 2;
+        k.flags = (uint32_t*)dp_;
     }
     /* x_zero_method.cpp:24-27: newY[j] = newY[j-1] + 0.0100 (float += double), a
      * data-independent table shared by all rings */
@@ -461,8 +555,8 @@ extern "C" int urf_destroy(urf_ctx* c)
             (void)hipEventDestroy(e);
     for (void* p : c->allocs)
         (void)hipFree(p);
-    if (c->h_spec_failed)
-        (void)hipHostFree(c->h_spec_failed);
+    if (c->pol.flags)
+        (void)hipHostFree(c->pol.flags);
     for (auto& sl : c->slots) {
         if (sl.exec)
             (void)hipGraphExecDestroy(sl.exec);
@@ -496,11 +590,10 @@ extern "C" int urf_set_params(urf_ctx* c, const urf_params* p)
     /* the ring counts of earlier calls say nothing about sweeps classified with OTHER parameters (region of interest, interval) */
     if (std::memcmp(&c->params, p, sizeof(*p)) != 0) {
         URF_HIP(c, hipMemsetAsync(c->k.ring_hint, 0, URF_ASYNC_SLOTS * sizeof(uint32_t), c->stream));
-        c->front_direct = c->front_off = false;   /* ... nor does what the fused front end made of them */
-        c->h_spec_failed[2] = c->h_spec_failed[3] = 0;
+        c->pol.forget_front();   /* ... nor does what the fused front end made of them */
     }
     c->params = *p;
-    c->epoch++;
+    c->pol.epoch++;
     return upload_params(c);
 }
 
@@ -517,7 +610,7 @@ extern "C" int urf_set_stream(urf_ctx* c, void* hip_stream)
     if (!c)
         return URF_ERR_INVALID_ARG;
     c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    c->epoch++;
+    c->pol.epoch++;
     return URF_OK;
 }
 
@@ -544,7 +637,7 @@ extern "C" int urf_enable_stage_capture(urf_ctx* c, int mode)
             return rc;
     }
     c->capture = mode;
-    c->epoch++;
+    c->pol.epoch++;
     return URF_OK;
 }
 
@@ -554,8 +647,9 @@ extern "C" int urf_callback_path_state(const urf_ctx* c, uint32_t* n_rerun, uint
         return URF_ERR_INVALID_ARG;
     if (n_rerun)
         *n_rerun = c->n_rerun;
+    const urf_policy& p = c->pol;
     if (sequence)
-        *sequence = (c->speculate ? 1u : 0u) | (c->slot_lists ? 2u : 0u) | (c->slot_nan ? 4u : 0u) | (c->speculate && c->use_hint ? 8u : 0u) | (c->slot_ties ? 16u : 0u);
+        *sequence = (p.speculate ? 1u : 0u) | (p.slot_lists ? 2u : 0u) | (p.slot_nan ? 4u : 0u) | (p.speculate && p.use_hint ? 8u : 0u) | (p.slot_ties ? 16u : 0u);
     return URF_OK;
 }
 
@@ -563,13 +657,10 @@ extern "C" int urf_callback_path_preset(urf_ctx* c, uint32_t sequence_bits)
 {
     if (!c || (sequence_bits & ~(2u | 4u | 16u)))
         return URF_ERR_INVALID_ARG;
-    const bool lists = c->slot_lists || (sequence_bits & 2u), nan = c->slot_nan || (sequence_bits & 4u), ties = c->slot_ties || (sequence_bits & 16u);
-    if (lists != c->slot_lists || nan != c->slot_nan || ties != c->slot_ties) {
-        c->slot_lists = lists;
-        c->slot_nan = nan;
-        c->slot_ties = ties;
-        c->epoch++;   /* the captured sequences are rebuilt */
-    }
+    urf_policy& p = c->pol;   /* (a change rebuilds the captured sequences) */
+    p.set(p.slot_lists, p.slot_lists || (sequence_bits & 2u) != 0);
+    p.set(p.slot_nan, p.slot_nan || (sequence_bits & 4u) != 0);
+    p.set(p.slot_ties, p.slot_ties || (sequence_bits & 16u) != 0);
     return URF_OK;
 }
 
@@ -582,14 +673,11 @@ extern "C" int urf_set_front_mode(urf_ctx* c, int mode)
 {
     if (!c || mode < 0 || mode > 2)
         return URF_ERR_INVALID_ARG;
-    if (mode != c->front_mode && mode != 0) {   /* (a new start: what earlier calls made of the fused front end is forgotten) */
-        c->front_direct = c->front_off = false;
-        c->h_spec_failed[2] = c->h_spec_failed[3] = 0;
-    }
-    c->front_mode = mode;
-    c->epoch++;   /* (the callback path's captured sequences depend on it) */
+    if (mode != c->pol.front_mode && mode != 0)   /* (a new start) */
+        c->pol.forget_front();
+    c->pol.set(c->pol.front_mode, mode);
     if (mode != 0)
-        c->want_ring_sorted = false;   /* (a caller that asks for ring-sorted results again pays for them again) */
+        c->pol.set(c->pol.want_ring_sorted, false);   /* (a caller that asks for ring-sorted results again pays for them again) */
     return URF_OK;
 }
 
@@ -614,7 +702,7 @@ extern "C" int urf_enable_kernel_timing(urf_ctx* c, int on)
     if (!c)
         return URF_ERR_INVALID_ARG;
     c->timing = on != 0;
-    c->epoch++;
+    c->pol.epoch++;
     return URF_OK;
 }
 
@@ -689,128 +777,98 @@ static int order_row_after_main(urf_ctx* c, uint32_t row, hipStream_t st)
     return URF_OK;
 }
 
-/* Row-major organised sweeps (urf_front.hpp, k_ring_table's third rule): what the host makes of the device's flags.  h_spec_failed[4]: a scan
- * looked row-major (a sighting) -- once per context the firing-order copies are allocated and the launch sequences hold k_rows_probe and
- * k_transpose from then on; [6]: a scan TOOK the layout.  Everything a captured sequence depends on bumps the epoch.  Never called inside a
- * stream capture (it synchronises). */
-static int rows_state_update(urf_ctx* c, hipStream_t st)
+/* ---- the pipeline ---------------------------------------------------------- */
+/* One call of the pipeline: a call of the public batch entry points (stream == nullptr: row 0 onwards, the context's stream, published
+ * as "the last call"), or one sweep of the callback path on its row and stream (the caller publishes it when it is waited for). */
+struct urf_call {
+    const float *x, *y, *z;
+    const uint32_t* offsets;        /* ragged: [n_scans + 1]; else nullptr */
+    uint32_t n_per_scan, max_len, n_scans;
+    uint8_t* labels;
+    urf_scan_info* info;            /* the scans' summaries are copied there (may be nullptr) */
+    uint32_t row = 0;
+    hipStream_t stream = nullptr;
+    /* the parameters and capture mode a voided sweep was SUBMITTED with (its rerun, urf_classify_pc2_wait); nullptr / -1: the context's */
+    const urf_dev_params* dp = nullptr;
+    int capture = -1;
+    bool general_only = false;      /* no fused kernels (last_row_intact) */
+};
+
+/* k_front_finish's first part runs on a stream of its own (run_pipeline).  Makes the stream and its two events once -- all three or none:
+ * a later call tries again -- and lets the stream wait for `st`; false when it cannot. */
+static bool side_fork(urf_ctx* c, hipStream_t st)
 {
-    if (c->front_mode != 0 && !c->front_rows && !c->rows_oom && c->h_spec_failed[4]) {
-        /* the calls in flight finish first -- what they handed back (such sweeps, possibly all of them) says nothing about the calls to come */
-        URF_HIP(c, hipStreamSynchronize(st));
-        if (scratch_alloc(c, URF_SCR_ROW_MAJOR) == URF_OK) {
-            c->front_rows = true;
-            c->rows_probation = 16;
-            c->front_direct = c->front_off = false;
-            c->h_spec_failed[2] = c->h_spec_failed[3] = 0;
+    if (!c->side_stream) {
+        hipStream_t s = nullptr;
+        hipEvent_t f = nullptr, j = nullptr;
+        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&f, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&j, hipEventDisableTiming) == hipSuccess) {
+            c->side_stream = s;
+            c->ev_fork = f;
+            c->ev_join = j;
         } else {
-            c->rows_oom = true;   /* (such sweeps keep to the general kernels) */
-            c->last_error.clear();
+            if (f)
+                (void)hipEventDestroy(f);
+            if (s)
+                (void)hipStreamDestroy(s);
         }
-        c->epoch++;
     }
-    if (c->front_rows && !c->rows_used && c->h_spec_failed[6]) {
-        c->rows_used = true;
-        c->epoch++;
-    }
-    return URF_OK;
+    return c->side_stream && hipEventRecord(c->ev_fork, st) == hipSuccess && hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) == hipSuccess;
 }
 
-/* ---- the pipeline ---------------------------------------------------------- */
-/* on_stream == nullptr: a call of the public batch entry points (row 0 onwards, the context's stream,
- * published as "the last call"); otherwise one sweep of the callback path on its row and stream (the
- * caller publishes it when it is waited for). */
-static int run_pipeline(urf_ctx* c, const float* d_x, const float* d_y, const float* d_z,
-                        const uint32_t* d_offsets, uint32_t n_per_scan, uint32_t max_len, uint32_t n_scans,
-                        uint8_t* d_labels, urf_scan_info* d_info, uint32_t row = 0, hipStream_t on_stream = nullptr,
-                        urf_kargs* a_out = nullptr, urf_dev_params* dp_out = nullptr, const urf_dev_params* dp_in = nullptr,
-                        int capture_in = -1, bool legacy_only = false)
+/* The launch sequence of one call as the policy plans it (a sweep of the callback path: its arguments and parameters to a_out / dp_out) */
+static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs* a_out = nullptr, urf_dev_params* dp_out = nullptr)
 {
-    /* dp_in / capture_in: the parameters and capture mode a sweep was SUBMITTED with (urf_classify_pc2_wait runs a voided
-     * sweep again: "a sweep in flight keeps its parameters", include/urf.h) */
-    if (!d_x || !d_y || !d_z || !d_labels)
+    if (!call.x || !call.y || !call.z || !call.labels)
         return URF_ERR_INVALID_ARG;
+    const uint32_t n_scans = call.n_scans;
     if (n_scans == 0)
         return URF_OK;
-    if (row + n_scans > c->max_batch || max_len > c->max_points)
+    if (call.row + n_scans > c->max_batch || call.max_len > c->max_points)
         return URF_ERR_CAPACITY;
     URF_HIP(c, hipSetDevice(c->device));
-    hipStream_t st = on_stream ? on_stream : c->stream;
-    if (!on_stream) {   /* (a sweep of the callback path: urf_classify_pc2_async has done both, outside its stream capture) */
+    const bool slot = call.stream != nullptr;
+    hipStream_t st = slot ? call.stream : c->stream;
+    if (!slot) {   /* (a sweep of the callback path: urf_classify_pc2_async has done both, outside its stream capture) */
         int rc = order_after_slots(c);
         if (rc == URF_OK)
-            rc = rows_state_update(c, st);   /* (may allocate the row-major group: before the arguments are taken) */
+            rc = c->pol.fold(c, st);   /* (may allocate the row-major group: before the arguments are taken) */
         if (rc != URF_OK)
             return rc;
     }
-    urf_kargs a = kargs_row(c, row);
-    a.x = d_x;
-    a.y = d_y;
-    a.z = d_z;
+    urf_kargs a = kargs_row(c, call.row);
+    a.x = call.x;
+    a.y = call.y;
+    a.z = call.z;
     a.offsets = nullptr;
-    if (d_offsets) {
+    if (call.offsets) {
         /* the context keeps its own copy: the entry points that look at this call's results later
          * (urf_read_stage, urf_ordered_indices, urf_marker_points) must not depend on the caller
          * keeping d_offsets alive.  Scratch memory is indexed by scan, never by these offsets. */
-        if (d_offsets != c->offsets_copy)   /* (last_row_intact runs the last call again with the copy itself) */
-            URF_HIP(c, hipMemcpyAsync(c->offsets_copy, d_offsets, ((size_t)n_scans + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        if (call.offsets != c->offsets_copy)   /* (last_row_intact runs the last call again with the copy itself) */
+            URF_HIP(c, hipMemcpyAsync(c->offsets_copy, call.offsets, ((size_t)n_scans + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         a.offsets = c->offsets_copy;
     }
-    a.n_per_scan = n_per_scan;
+    a.n_per_scan = call.n_per_scan;
     a.n_scans = n_scans;
-    a.max_len = max_len;
-    a.tiles = (max_len + URF_TILE - 1) / URF_TILE;
+    a.max_len = call.max_len;
+    a.tiles = (call.max_len + URF_TILE - 1) / URF_TILE;
     if (a.tiles == 0)
         a.tiles = 1;
     a.sstride = c->sstride;
-    if (c->speculate && c->h_spec_failed[0]) {   /* an earlier call had to repair a speculative ring table */
-        c->speculate = false;
-        c->epoch++;
-    }
-    if (c->use_hint && c->h_spec_failed[1]) {    /* ... or one that stopped at the previous call's ring count */
-        c->use_hint = false;
-        c->epoch++;
-    }
-    a.table_lookahead = c->speculate ? URF_TABLE_LOOKAHEAD : 0u;
-    a.table_hint = (c->speculate && c->use_hint) ? 1u : 0u;
-    /* A sweep of the callback path is waited for by the host before anybody sees its result: the kernels that
-     * normally find nothing to do -- the two repair kernels behind the speculative ring table, the two for the work
-     * lists of oversized star sectors, 20 of a sweep's 200 microseconds -- are left out, k_index voids a sweep that
-     * needed them, and urf_classify_pc2_wait() runs it again with them. */
-    a.optimistic = on_stream ? ((c->speculate ? URF_OPT_NO_REPAIR : 0u) | (c->slot_lists ? 0u : URF_OPT_NO_LISTS) | (c->slot_nan ? 0u : URF_OPT_NO_NAN) |
-                               (c->slot_ties ? 0u : URF_OPT_NO_TIES)) : 0u;
-    a.capture = (uint32_t)(capture_in >= 0 ? capture_in : c->capture);
-    a.labels = d_labels;
+    a.capture = (uint32_t)(call.capture >= 0 ? call.capture : c->capture);
+    a.labels = call.labels;
     if (a.capture != 1) {
         a.rd2 = nullptr;
         a.caz = nullptr;
     }
-    const urf_dev_params dp = dp_in ? *dp_in : c->dp;
+    const urf_dev_params dp = call.dp ? *call.dp : c->dp;
     const unsigned C = (unsigned)dp.p.channels, K = (unsigned)dp.p.sectors;
     const bool star = dp.p.star_shaped_method != 0;
     const dim3 g_tiles(a.tiles, n_scans), g_scan(n_scans);
-    /* The fused front end (urf_front.hpp) for batches of sweeps in firing order: k_front tries every scan, the legacy kernels
-     * skip the scans it kept.  64 lasers = 64 lanes, the detectors' window of curbPoints == 5 in registers, no stage capture
-     * (its values are the legacy kernels'), not for the single sweeps of the callback path (sixteen waves on the whole device). */
-    if (c->h_spec_failed[2])
-        c->front_direct = true;
-    if (c->h_spec_failed[3] && c->front_mode != 2)
-        c->front_off = true;
-    /* (a context that has sighted row-major sweeps takes the fused kernels at any batch size: the general kernels need 0.64 ms for four
-     * such sweeps, the fused ones 0.26 -- tools/r6_min_scans.py --rows; sweeps in firing order gain from 192 per call on) */
-    const bool front_shape = c->front_mode != 0 && !c->front_off && !legacy_only && !c->want_ring_sorted && a.capture == 0 &&
-                             C == URF_FRONT_LANES && dp.p.curbPoints == 5 && a.tiles <= URF_FRONT_MAX_TILES;
-    const bool small_ok = c->front_rows && (c->rows_used || c->rows_probation > 0);
-    /* (a single sweep of the callback path: only in a context whose sweeps come row-major -- a sweep in firing order is faster through the
-     * general kernels, tools/r6_single_sweep.py) */
-    a.front = (front_shape && (on_stream ? small_ok : (c->front_mode == 2 || small_ok || n_scans >= URF_FRONT_MIN_SCANS))) ? 1u : 0u;
-    if (a.front && !on_stream && c->front_mode != 2 && n_scans < URF_FRONT_MIN_SCANS && !c->rows_used && c->rows_probation)
-        c->rows_probation--;   /* (a sighting that no scan confirms -- a sweep in firing order whose region of interest begins with a single laser -- lapses;
-                                *  the callback path counts its submissions: urf_classify_pc2_async) */
-    a.front_sight = (front_shape && !a.front && !c->front_rows && !c->rows_oom) ? 1u : 0u;
-    a.front_tpb = c->front_tpb ? c->front_tpb : (n_scans >= URF_FRONT_TPB_SCANS ? URF_FRONT_TPB_LARGE : (n_scans >= 16u ? URF_FRONT_TPB_SMALL : 1u));
-    a.front_lists = (a.front && !c->front_direct && !on_stream) ? 1u : 0u;   /* (the callback path's sequence holds the general kernels as grids anyway) */
-    a.front_rows = (a.front && c->front_rows) ? 1u : 0u;   /* (the rows' rule does not depend on the two other speculations: the repair kernels below come with it) */
+    c->pol.plan(a, dp, slot, call.general_only);
+    if (!slot)
+        c->pol.probation_batch(a);
 
     std::vector<hipEvent_t>* ev = nullptr;
     if (c->timing) {
@@ -853,29 +911,12 @@ static int run_pipeline(urf_ctx* c, const float* d_x, const float* d_y, const fl
      * stream, so that the brackets add up to the step. */
     bool side = false, part1 = false;
     const size_t finish_lds = (size_t)a.tiles * 384 + 2 * URF_FINISH_CHUNK * sizeof(urf_u2);
-    if (a.front && !ev && !on_stream) {
-        if (!c->side_stream) {   /* (all three or none: a later call tries again) */
-            hipStream_t s = nullptr;
-            hipEvent_t f = nullptr, j = nullptr;
-            if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&f, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&j, hipEventDisableTiming) == hipSuccess) {
-                c->side_stream = s;
-                c->ev_fork = f;
-                c->ev_join = j;
-            } else {
-                if (f)
-                    (void)hipEventDestroy(f);
-                if (s)
-                    (void)hipStreamDestroy(s);
-            }
-        }
-        if (c->side_stream && hipEventRecord(c->ev_fork, st) == hipSuccess && hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) == hipSuccess) {
-            hipLaunchKernelGGL(k_front_finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, c->side_stream, a, dp, 1u);
-            part1 = true;
-            side = hipEventRecord(c->ev_join, c->side_stream) == hipSuccess;
-            if (!side)   /* (cannot be joined by an event: wait for it here) */
-                (void)hipStreamSynchronize(c->side_stream);
-        }
+    if (a.front && !ev && !slot && side_fork(c, st)) {
+        hipLaunchKernelGGL(k_front_finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, c->side_stream, a, dp, 1u);
+        part1 = true;
+        side = hipEventRecord(c->ev_join, c->side_stream) == hipSuccess;
+        if (!side)   /* (cannot be joined by an event: wait for it here) */
+            (void)hipStreamSynchronize(c->side_stream);
     }
     hipLaunchKernelGGL(k_index, g_scan, dim3(256), 0, st, a, dp);
     mark();
@@ -940,9 +981,9 @@ static int run_pipeline(urf_ctx* c, const float* d_x, const float* d_y, const fl
         hipLaunchKernelGGL(k_label_front, g_tiles, dim3(URF_LABEL_TILE_THREADS), 0, st, a, dp);
     mark();
     URF_HIP(c, hipGetLastError());
-    if (d_info)
-        URF_HIP(c, hipMemcpyAsync(d_info, a.info, (size_t)n_scans * sizeof(urf_scan_info), hipMemcpyDeviceToDevice, st));
-    if (on_stream) {
+    if (call.info)
+        URF_HIP(c, hipMemcpyAsync(call.info, a.info, (size_t)n_scans * sizeof(urf_scan_info), hipMemcpyDeviceToDevice, st));
+    if (slot) {
         *a_out = a;
         *dp_out = dp;
     } else {
@@ -959,7 +1000,7 @@ extern "C" int urf_classify_batch_soa(urf_ctx* c, const float* d_x, const float*
 {
     if (!c)
         return URF_ERR_INVALID_ARG;
-    const int rc = run_pipeline(c, d_x, d_y, d_z, nullptr, n_per_scan, n_per_scan, n_scans, d_labels, d_info);
+    const int rc = run_pipeline(c, urf_call{ d_x, d_y, d_z, nullptr, n_per_scan, n_per_scan, n_scans, d_labels, d_info });
     if (rc == URF_OK && n_scans)
         c->last_batch = URF_LAST_SOA;
     return rc;
@@ -971,7 +1012,7 @@ extern "C" int urf_classify_batch_soa_ragged(urf_ctx* c, const float* d_x, const
 {
     if (!c || !d_offsets)
         return URF_ERR_INVALID_ARG;
-    const int rc = run_pipeline(c, d_x, d_y, d_z, d_offsets, 0, max_len, n_scans, d_labels, d_info);
+    const int rc = run_pipeline(c, urf_call{ d_x, d_y, d_z, d_offsets, 0, max_len, n_scans, d_labels, d_info });
     if (rc == URF_OK && n_scans)
         c->last_batch = URF_LAST_SOA;
     return rc;
@@ -1011,7 +1052,7 @@ static int classify_batch_pc2(urf_ctx* c, const uint8_t* d_data, const uint32_t*
     if (n_total)
         hipLaunchKernelGGL(k_pc2_to_soa, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, c->stream, d_data,
                            (unsigned long long)n_total, point_step, off_x, off_y, off_z, c->sx.p, c->sy.p, c->sz.p);
-    rc = run_pipeline(c, c->sx.p, c->sy.p, c->sz.p, d_offsets, n_per_scan, max_len, n_scans, d_labels, d_info);
+    rc = run_pipeline(c, urf_call{ c->sx.p, c->sy.p, c->sz.p, d_offsets, n_per_scan, max_len, n_scans, d_labels, d_info });
     if (rc == URF_OK)
         c->last_batch = URF_LAST_PC2;
     return rc;
@@ -1167,13 +1208,11 @@ static int slot_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t n_points, uint3
         hipLaunchKernelGGL(k_pc2_to_soa, dim3((n_points + 255) / 256), dim3(256), 0, st, sl.d_raw.p, (unsigned long long)n_points,
                            point_step, off_x, off_y, off_z, sx, sy, sz);
     }
-    urf_kargs a_run;
-    urf_dev_params dp_run;   /* (dp_in may point at sl.cap_dp) */
-    const int rc = run_pipeline(c, sx, sy, sz, nullptr, n_points, n_points, 1, sl.d_labels.p, nullptr, row, st, &a_run, &dp_run, dp_in, capture_in);
+    /* (dp_in may point at sl.cap_dp: run_pipeline copies it before it writes dp_out, and writes a_out / dp_out only on success) */
+    const int rc = run_pipeline(c, urf_call{ sx, sy, sz, nullptr, n_points, n_points, 1, sl.d_labels.p, nullptr, row, st, dp_in, capture_in },
+                                &sl.cap_a, &sl.cap_dp);
     if (rc != URF_OK)
         return rc;
-    sl.cap_a = a_run;
-    sl.cap_dp = dp_run;
     URF_HIP(c, hipMemcpyAsync(sl.h_labels.p, sl.d_labels.p, n_points, hipMemcpyDeviceToHost, st));
     URF_HIP(c, hipMemcpyAsync(sl.h_info.p, kargs_row(c, row).info, sizeof(urf_scan_info), hipMemcpyDeviceToHost, st));
     return URF_OK;
@@ -1247,26 +1286,14 @@ extern "C" int urf_classify_pc2_async(urf_ctx* c, const uint8_t* data, uint32_t 
         sl.key[0] = 0;   /* the captured sequence reads the other format */
     sl.planes = planes;
     HT(0, ht0);   /* staging + H2D enqueue */
-    /* a sweep that defeated the speculative ring table (k_table_repair raised the host-visible flag) ends
-     * the speculation for replayed sequences as well: the captured ones are rebuilt without it */
-    if (c->speculate && c->h_spec_failed[0]) {
-        c->speculate = false;
-        c->epoch++;
-    }
-    if (c->use_hint && c->h_spec_failed[1]) {
-        c->use_hint = false;
-        c->epoch++;
-    }
-    /* row-major organised sweeps: sighted by the general kernels, then the fused ones in this path's sequence as well (rows_state_update); a
-     * sighting that no sweep confirms lapses after sixteen submissions */
-    rc = rows_state_update(c, st);
+    /* what earlier calls reported, for this sweep and the replayed sequences (outside the stream capture: fold may synchronise) */
+    rc = c->pol.fold(c, st);
     if (rc != URF_OK)
         return rc;
-    if (c->front_rows && !c->rows_used && c->rows_probation && --c->rows_probation == 0)
-        c->epoch++;
+    c->pol.probation_sweep();
     /* the launch sequence of a sweep of this shape is captured once and replayed (one graph launch
      * instead of a dozen kernel launches per callback); anything it depends on bumps the epoch */
-    const uint64_t key[3] = { c->epoch, ((uint64_t)n_points << 32) | point_step,
+    const uint64_t key[3] = { c->pol.epoch,((uint64_t)n_points << 32) | point_step,
                               ((uint64_t)off_x << 42) ^ ((uint64_t)off_y << 21) ^ off_z };
     const bool use_graph = !c->timing && !(c->debug_flags & 8u);
     HT(1, ht0);   /* event record, ordering, stream wait */
@@ -1328,34 +1355,22 @@ extern "C" int urf_classify_pc2_wait(urf_ctx* c, uint32_t ticket, uint8_t* label
     HT_START;
     URF_HIP(c, hipEventSynchronize(sl.ev_done));
     HT(4, ht0);
-    /* the short launch sequence left out something this sweep needed (run_pipeline): once more, with it --
-     * the message is still in the slot's device buffer -- and from now on for every sweep */
-    auto redo = [](int st) {
-        return st == URF_STATUS_REDO_TABLE || st == URF_STATUS_REDO_LISTS || st == URF_STATUS_REDO_NAN || st == URF_STATUS_REDO_HINT ||
-               st == URF_STATUS_REDO_TIES;
-    };
-    for (int tries = 0; tries < 6 && redo(sl.h_info.p->status); tries++) {
-        if (sl.h_info.p->status == URF_STATUS_REDO_TABLE)
-            c->speculate = false;
-        else if (sl.h_info.p->status == URF_STATUS_REDO_HINT)
-            c->use_hint = false;
-        else if (sl.h_info.p->status == URF_STATUS_REDO_LISTS)
-            c->slot_lists = true;
-        else if (sl.h_info.p->status == URF_STATUS_REDO_TIES)
-            c->slot_ties = true;
-        else
-            c->slot_nan = true;
-        c->epoch++;   /* the captured sequences are rebuilt */
+    /* the short launch sequence left out something this sweep needed (urf_policy::plan): once more, with it --
+     * the message is still in the slot's device buffer -- and from now on for every sweep (on_redo) */
+    for (int tries = 0; c->pol.on_redo(sl.h_info.p->status); tries++) {
+        if (tries == 6) {
+            sl.pending = false;
+            return URF_ERR_HIP;   /* (cannot happen: the full sequence raises none) */
+        }
         c->n_rerun++;
-        /* with the parameters and capture mode the sweep was submitted with (urf_set_params may have been called since),
-         * behind whatever the context's stream still does with the row */
-        const urf_dev_params dp_sub = sl.cap_dp;
         /* the rerun is the row's LATEST submission: with fewer rows than sweeps in flight a later sweep shares this row, and
          * what it left there is overwritten now -- its read-backs of the row must answer URF_ERR_BUSY, not this sweep's data */
         sl.gen = ++c->row_gen[slot_row(c, sl)];
+        /* with the parameters and capture mode the sweep was submitted with (urf_set_params may have been called since),
+         * behind whatever the context's stream still does with the row */
         int rc = order_row_after_main(c, slot_row(c, sl), slot_stream(c, sl));
         if (rc == URF_OK)
-            rc = slot_launch(c, sl, sl.n_points, sl.point_step, sl.off_x, sl.off_y, sl.off_z, &dp_sub, (int)sl.cap_a.capture);
+            rc = slot_launch(c, sl, sl.n_points, sl.point_step, sl.off_x, sl.off_y, sl.off_z, &sl.cap_dp, (int)sl.cap_a.capture);
         if (rc == URF_OK && hipStreamSynchronize(slot_stream(c, sl)) != hipSuccess) {
             c->last_error = "hipStreamSynchronize (rerun of a voided sweep)";
             rc = URF_ERR_HIP;
@@ -1364,10 +1379,6 @@ extern "C" int urf_classify_pc2_wait(urf_ctx* c, uint32_t ticket, uint8_t* label
             sl.pending = false;   /* the slot must not stay busy for ever */
             return rc;
         }
-    }
-    if (redo(sl.h_info.p->status)) {
-        sl.pending = false;
-        return URF_ERR_HIP;   /* (cannot happen: the full sequence raises neither) */
     }
     /* only now is the sweep "the last call": urf_read_stage / urf_marker_points / urf_ordered_indices look at
      * its scratch row, which stays untouched until the slot (or a batch call) is used again */
@@ -1432,30 +1443,17 @@ static int last_row_intact(urf_ctx* c)
                         "the number of sweeps in flight, or read its intermediate results before submitting on its row again)";
         return URF_ERR_BUSY;
     }
-    if (c->last_is_slot && c->last_a.front) {
-        /* ... and so did the sweep of the callback path that was waited for last (a context whose sweeps come row-major): once more on its
-         * row through the general kernels -- the message is still in the slot's device buffer, the row has not been resubmitted (checked
-         * above) --, as a batch call of one scan with every repair kernel in the sequence; the context stays with the general kernels */
-        c->want_ring_sorted = true;
-        c->epoch++;   /* (the captured sequences are rebuilt without the fused kernels) */
+    if (c->last_a.front) {
+        /* the last call went through the fused front end (urf_front.hpp), which keeps no ring-sorted copies: once more on its row through
+         * the general kernels, as a batch call with every repair kernel in the sequence (same inputs -- a batch caller's arrays must still
+         * be alive, a sweep of the callback path is still in its slot's device buffer and its row has not been resubmitted (checked
+         * above) --, same parameters, same labels), and the context stays with them: a caller that reads ring-sorted results pays for
+         * them once, not per call */
+        c->pol.set(c->pol.want_ring_sorted, true);
         const urf_kargs a = c->last_a;
         const urf_dev_params dp = c->last_dp;
-        const int rc = run_pipeline(c, a.x, a.y, a.z, nullptr, a.n_per_scan, a.max_len, 1, a.labels, nullptr, c->last_row, nullptr, nullptr, nullptr, &dp,
-                                    (int)a.capture, true);
-        if (rc != URF_OK)
-            return rc;
-        c->last_is_slot = false;   /* (what the read-backs look at now is that call's) */
-        return URF_OK;
-    }
-    if (!c->last_is_slot && c->last_a.front) {
-        /* the last batch call went through the fused front end (urf_front.hpp), which keeps no ring-sorted copies: once more through
-         * the legacy kernels (same inputs -- the caller's arrays must still be alive --, same parameters, same labels), and the
-         * context stays with them: a caller that reads ring-sorted results pays for them once, not per call */
-        c->want_ring_sorted = true;
-        const urf_kargs a = c->last_a;
-        const urf_dev_params dp = c->last_dp;
-        return run_pipeline(c, a.x, a.y, a.z, a.offsets, a.n_per_scan, a.max_len, a.n_scans, a.labels, nullptr, 0, nullptr, nullptr, nullptr, &dp,
-                            (int)a.capture, true);
+        return run_pipeline(c, urf_call{ a.x, a.y, a.z, a.offsets, a.n_per_scan, a.max_len, a.n_scans, a.labels, nullptr,
+                                         c->last_is_slot ? c->last_row : 0u, nullptr, &dp, (int)a.capture, true });
     }
     return URF_OK;
 }
@@ -1886,7 +1884,7 @@ extern "C" int urf_set_debug_flags(urf_ctx* c, uint32_t flags)
         return URF_ERR_INVALID_ARG;
     c->debug_flags = flags;
     c->dp.exp_flags = flags;
-    c->epoch++;
+    c->pol.epoch++;
     return URF_OK;
 }
 

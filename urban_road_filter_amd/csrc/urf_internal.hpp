@@ -61,6 +61,17 @@
 #define URF_STATUS_REDO_NAN 0x7f000003
 #define URF_STATUS_REDO_HINT 0x7f000004   /* the table was incomplete because the walk stopped at the previous call's ring count */
 #define URF_STATUS_REDO_TIES 0x7f000005   /* a star sector holds equal planar ranges where the walk looks: needs k_star_ties */
+/* The host-mapped flag words (urf_kargs::flags): the kernels set a word to 1, the host's launch policy reads it before a call's
+ * launches (urf_api.hip: urf_policy::fold) and clears the two front-end words when it forgets what they said (forget_front). */
+enum urf_flag {
+    URF_FLAG_LOOKAHEAD_FAILED = 0,       /* k_table_repair: a quiet look-ahead stopped k_ring_table too early (the context stops speculating) */
+    URF_FLAG_HINT_FAILED = 1,            /* ... the ring count of the row's previous call did (the context stops using it) */
+    URF_FLAG_FRONT_HANDED_BACK = 2,      /* k_table_repair (collecting): k_front handed a scan back to the general kernels */
+    URF_FLAG_FRONT_ALL_HANDED_BACK = 3,  /* ... every scan of a call */
+    URF_FLAG_ROWS_SIGHTED = 4,           /* k_ring_table: a scan looked row-major (URF_FRONT_ROWS) to a call without k_rows_probe / k_transpose */
+    URF_FLAG_ROWS_TAKEN = 6,             /* k_ring_table: a scan took the row-major layout */
+    URF_FLAG_WORDS = 8                   /* (words 5 and 7 are not used) */
+};
 /* star_first[] carries flags above the index (a scan holds at most 2^23 points).  Equal planar ranges of a sector are ordered
  * as libstdc++'s std::sort orders them (star_shaped_search.cpp:109), which only k_star_ties knows how to do; the sort kernels
  * order them by position and say what they saw:
@@ -233,7 +244,7 @@ struct urf_kargs {
     uint32_t* table_cause;      /* [S] which rule ended a speculative walk: 1 the quiet look-ahead, 2 the ring-count hint, 3 the rows' first points */
     uint32_t* ring_hint;        /* [1] per scratch row: the largest n_rings of the row's previous call (k_ring_table reads it, k_split
                                  * zeroes it, k_index collects the new one) */
-    uint32_t* spec_failed;      /* host-mapped flags: [0] a look-ahead speculation failed, [1] a ring-count hint did */
+    uint32_t* flags;            /* [URF_FLAG_WORDS] host-mapped, indexed by enum urf_flag */
     float*    big_r;            /* sector-major copies of the sectors on the "big" list (sorted in place) */
     float*    big_z;
     uint32_t* big_i;
@@ -269,14 +280,12 @@ struct urf_kargs {
     uint32_t* front_ncand;      /* [S] */
     uint32_t* front_st;         /* [S][URF_FRONT_ST_WORDS] k_front_finish part 1 -> part 2 */
     uint32_t* front_list;       /* [S] the scans whose flag is clear (k_front_collect; star_count[6] = how many): the list-driven legacy kernels' work */
-    uint32_t* front_state;      /* host-mapped: [0] some scan of some call was handed back, [1] every scan of some call was, [2] a scan looked
-                                 * row-major (URF_FRONT_ROWS), [3] the row-major speculation failed on one, [4] a scan took the row-major layout */
     uint32_t  front_lists;      /* this call launches the legacy kernels list-driven (k_split_list, k_ring_list, k_label_list) */
     /* row-major organised sweeps (height = the sensor's 64 lasers, width = firings: point l * F + f): front_ok[s] == URF_FRONT_ROWS,
      * k_transpose writes the firing-order copy the fused kernels read instead of x / y / z, k_label_front stores the labels
      * where the points came from.  Everything in between is indexed by firing * 64 + laser. */
     uint32_t  front_rows;       /* this call's sequence holds k_rows_probe and k_transpose: k_ring_table may choose the layout (else it only reports
-                                 * that it saw such a scan: front_state[2], the next call's sequence holds the kernels) */
+                                 * that it saw such a scan: URF_FLAG_ROWS_SIGHTED, the next call's sequence holds the kernels) */
     uint32_t  front_sight;      /* this call takes the general kernels but k_ring_table still reports a row-major sighting (a batch below mode 1's threshold:
                                  * row-major sweeps gain from the fused kernels at ANY batch size, tools/r6_min_scans.py --rows) */
     float*    rows_v;           /* [S][64] k_rows_probe: the vertical angles of the rows' first region-of-interest points, in row order (the table's leaders) */

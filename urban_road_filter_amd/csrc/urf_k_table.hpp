@@ -359,7 +359,7 @@ __device__ void urf_ring_table_scan(const urf_kargs& a, const urf_dev_params& dp
             if (tid == 0) {
                 sh_nL = nr - 1u;
                 a.front_ok[s] = URF_FRONT_ROWS;
-                a.front_state[4] = 1u;   /* host-visible: this context's sweeps DO come row-major (urf_api.hip: the fused kernels at any batch size) */
+                a.flags[URF_FLAG_ROWS_TAKEN] = 1u;   /* host-visible: this context's sweeps DO come row-major (urf_api.hip: the fused kernels at any batch size) */
             }
             rows = true;
             upto = 0;
@@ -493,7 +493,7 @@ __device__ void urf_ring_table_scan(const urf_kargs& a, const urf_dev_params& dp
         const unsigned nl = T.first_nl;
         if (nl != 0u && nl * (len >> 6) <= 63u + (len >> 6)) {   /* nl <= ceil(64 / F) */
             if (tid == 0)
-                a.front_state[2] = 1u;   /* host-visible: the next call's sequence holds k_rows_probe and k_transpose */
+                a.flags[URF_FLAG_ROWS_SIGHTED] = 1u;   /* host-visible: the next call's sequence holds k_rows_probe and k_transpose */
             cause |= 4u;   /* (a row-major sweep defeats the look-ahead wherever its region of interest drops a few rows in succession:
                             * such a failure must not switch ALL speculation off, this rule included -- k_table_repair) */
         }
@@ -597,9 +597,9 @@ __global__ __launch_bounds__(URF_TABLE_THREADS) void k_table_repair(urf_kargs a,
         a.front_ok[s] = 0u;
         const unsigned e = atomicAdd(&a.star_count[6], 1u);
         a.front_list[e] = s;
-        a.front_state[0] = 1u;
+        a.flags[URF_FLAG_FRONT_HANDED_BACK] = 1u;
         if (e + 1u == a.n_scans)
-            a.front_state[1] = 1u;
+            a.flags[URF_FLAG_FRONT_ALL_HANDED_BACK] = 1u;
     }
     if (!redo)
         return;
@@ -610,10 +610,10 @@ __global__ __launch_bounds__(URF_TABLE_THREADS) void k_table_repair(urf_kargs a,
     if (threadIdx.x == 0) {
         if (!collect)   /* (a collected scan is split by k_split_list) */
             a.redo_list[atomicAdd(&a.star_count[2], 1u)] = s;
-        if (cause == 3u)
-            a.front_state[3] = 1u;   /* (the rows' rule: counted, not switched off -- a failure costs that scan the long walk) */
-        else if (!(cause & 4u))     /* (4: a scan that looked row-major to a call whose sequence lacked the kernels for it) */
-            a.spec_failed[cause == 2u ? 1 : 0] = 1u;   /* host-visible: the context stops using the rule that failed */
+        /* host-visible: the context stops using the rule that failed -- not the rows' rule (3: a failure costs that scan the long walk),
+         * nor for a scan that looked row-major to a call whose sequence lacked the kernels for it (4) */
+        if (cause != 3u && !(cause & 4u))
+            a.flags[cause == 2u ? URF_FLAG_HINT_FAILED : URF_FLAG_LOOKAHEAD_FAILED] = 1u;
     }
 }
 
