@@ -66,7 +66,9 @@ extern "C" {
  * urf_callback_path_preset.
  * Additions under 5, additive (no existing entry point, struct or value changed): urf_classify_batch_pc2_ragged (ragged
  * PointCloud2 batches), urf_clouds_batch_soa / urf_clouds_batch_pc2 with struct urf_point_xyzi, URF_ORDER_INPUT and
- * URF_ORDER_REFERENCE (the four published clouds of a batch as device-resident records).
+ * URF_ORDER_REFERENCE (the four published clouds of a batch as device-resident records); urf_marker_strips /
+ * urf_marker_strips_batch with struct urf_marker_strip, URF_MARKER_MAX_STRIPS, URF_MARKER_MAX_STRIP_POINTS (the line strips of
+ * road_marker: one sweep on the host, a batch of sweeps on the device).
  * WHICH std::sort (4 above): the one of libstdc++ as shipped with GCC 5 .. 13 (bits/stl_algo.h: __sort = __introsort_loop with
  * _S_threshold 16, __move_median_to_first on (first + 1, mid, last - 1), __unguarded_partition, depth limit 2 * floor(log2 n),
  * __partial_sort as the fallback, then __final_insertion_sort); tests/test_stdsort.py pins the restatement against the std::sort
@@ -382,7 +384,7 @@ int urf_ordered_indices_batch(urf_ctx* ctx, uint32_t* d_road, uint32_t* d_curb, 
  * classify call this returns the marker points of scan `scan`: pts[4*k + 0..3] = x, y, z, red
  * (host buffer with room for 361 points), *count = their number (the reference's cM).
  * The line strips the reference builds from them (colour grouping, Douglas-Peucker
- * simplification, ghost deletion, :369-602) are host code: urf::Detector::road_marker().
+ * simplification, ghost deletion, :369-602): urf_marker_strips* below, urf::Detector::road_marker().
  * Synchronous; costs one extra per-ring sort. */
 int urf_marker_points(urf_ctx* ctx, uint32_t scan, float* pts, uint32_t* count);
 /* Every scan of the last classify call at once, results on the DEVICE (asynchronous): the marker
@@ -407,6 +409,55 @@ int urf_default_marker_params(urf_marker_params* p);
  * the points of the simplified line.  Boost.Geometry itself is not in the reference checkout:
  * the behaviour is pinned by the worked example of its documentation (tests/test_simplify_kat.py). */
 int urf_simplify_line(const float* xy, uint32_t n, float max_distance, uint8_t* keep);
+
+/* ---- road_marker: the line strips ------------------------------------------------
+ * lidar_segmentation.cpp:369-602: what the reference publishes as "road_marker" for a sweep with more than two marker
+ * points -- the colour fix-ups (:381-415), one LINE_STRIP marker per run of equal colour (green = free, red = a non-road
+ * point ended the degree's beam; the segment that joins two runs is red, so joint points appear twice), each optionally
+ * replaced by its Douglas-Peucker outline at height poly_z_manual (simple_poly_allow), every z optionally replaced by the
+ * sweep's running-mean height (poly_z_avg_allow), and DELETE markers for the strips of the previous publishing sweep that this
+ * one no longer has (:591-598).  One record per marker and a packed point array; all values float: every coordinate the
+ * reference stores in its double geometry_msgs::Point is a float widened.
+ * STATE between sweeps: the ghost count = the id of the last ADD marker of the latest sweep that published (the reference's
+ * `ghostcount`), nothing else (DESIGN.md section 4 derives why the reference's member linestring never carries points over).
+ * A sweep with count <= 2 publishes nothing and leaves it alone.  A ghost count is at most URF_MARKER_MAX_STRIPS - 1 (the id
+ * of the last of URF_MARKER_MAX_STRIPS strips); incoming values outside [0, URF_MARKER_MAX_STRIPS - 1] are clamped to that
+ * range -- the largest value a sweep can leave, and the largest for which ADD + DELETE markers fit URF_MARKER_MAX_STRIPS records.
+ * BOUNDS: after the fix-ups every run of equal colour holds at least two of the at most 361 marker points, so a sweep has at
+ * most 180 strips and 361 + 179 points (each of the 179 joints once more), both reached by 361 points in runs of 2, 2, ..., 3;
+ * DELETE markers only fill up to the previous sweep's strip count. */
+typedef struct urf_marker_strip {
+    int32_t  id;                    /* Marker::id; DELETE markers carry the reference's ids (last ADD id + 1 ...) */
+    int32_t  action;                /* URF_MARKER_ADD or URF_MARKER_DELETE */
+    float    r, g, b, a;            /* a DELETE marker keeps the last strip's colour, as in the reference */
+    uint32_t first_point, n_points; /* into the sweep's xyz; a DELETE marker has 0 points */
+} urf_marker_strip;                 /* 32 bytes */
+#define URF_MARKER_ADD              0
+#define URF_MARKER_DELETE           2
+#define URF_MARKER_MAX_POINTS       361   /* marker points per sweep (urf_marker_points) */
+#define URF_MARKER_MAX_STRIPS       180   /* markers (ADD + DELETE) per sweep */
+#define URF_MARKER_MAX_STRIP_POINTS 540   /* strip points per sweep */
+/* One sweep on the host (no context, no device): pts = count x {x, y, z, red} as urf_marker_points returns them (count at
+ * most 361, red exactly 0 or 1, else URF_ERR_INVALID_ARG), *ghostcount in / out (see STATE).  *published = 0 / 1 (0: no
+ * MarkerArray for this sweep, n_strips = n_points = 0, *ghostcount untouched), strips with room for URF_MARKER_MAX_STRIPS
+ * records, xyz for 3 * URF_MARKER_MAX_STRIP_POINTS floats.  urf::MarkerBuilder runs the same code. */
+int urf_marker_strips(const float* pts, uint32_t count, const urf_marker_params* mp, int32_t* ghostcount, int32_t* published,
+                      urf_marker_strip* strips, uint32_t* n_strips, float* xyz, uint32_t* n_points);
+/* A batch on the device, asynchronous on the context's stream.  A pure function of its arguments (the context lends its
+ * stream and one word of scratch): d_pts / d_counts are laid out as urf_marker_points_batch writes them (scan s: 361 * 4
+ * floats at d_pts + s * 361 * 4, its count in d_counts[s]; counts above 361 are read as 361), so the two calls chain without
+ * the host.  Scan s writes its markers at d_strips + s * URF_MARKER_MAX_STRIPS, its points at
+ * d_xyz + 3 * s * URF_MARKER_MAX_STRIP_POINTS, and d_n[3*s .. 3*s+2] = published (0 / 1), markers, points (0, 0, 0 for a scan
+ * with count <= 2); bytes of the fixed-stride outputs beyond a scan's counts are unspecified.  Records equal
+ * urf_marker_strips' bit for bit.
+ * sequence = 1: the scans are consecutive sweeps of one sensor.  Scan 0 starts from *d_ghost (device int32_t; NULL: 0 and
+ * nothing is written back), every scan from the nearest earlier scan of the call that publishes, and the value the last
+ * publishing scan leaves (the incoming one, unclamped, if none publishes: urf_marker_strips leaves it alone too) is written to *d_ghost, so consecutive calls chain on the
+ * device.  sequence = 0: independent scans, each starts from 0 (no DELETE markers); d_ghost is ignored.
+ * n_scans above the context's max_batch: URF_ERR_CAPACITY; n_scans = 0 is a no-op.  A red value other than 0 is read as 1. */
+int urf_marker_strips_batch(urf_ctx* ctx, const urf_marker_params* mp, const float* d_pts, const uint32_t* d_counts,
+                            uint32_t n_scans, int sequence, int32_t* d_ghost, urf_marker_strip* d_strips, float* d_xyz,
+                            uint32_t* d_n);
 
 /* ---- stage-wise inspection (parity tests) ----------------------------------
  * After a classify call, copies one intermediate array of scan `scan` to host

@@ -7,6 +7,9 @@ package is plumbing for tests and the benchmark: a ctypes binding of that ABI.
 from .api import (  # noqa: F401
     Context,
     MarkerParams,
+    MarkerStrip,
+    marker_strips,
+    MARKER_ADD, MARKER_DELETE, MARKER_MAX_POINTS, MARKER_MAX_STRIPS, MARKER_MAX_STRIP_POINTS, MARKER_STRIP_DTYPE,
     ParamDesc,
     Params,
     PointXYZI,

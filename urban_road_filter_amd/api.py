@@ -80,6 +80,18 @@ class MarkerParams(C.Structure):
                 ("poly_z_manual", C.c_float), ("poly_z_avg_allow", C.c_int32)]
 
 
+class MarkerStrip(C.Structure):
+    """struct urf_marker_strip: one marker of the road_marker MarkerArray (32 bytes); action 0 ADD, 2 DELETE."""
+    _fields_ = [("id", C.c_int32), ("action", C.c_int32), ("r", C.c_float), ("g", C.c_float), ("b", C.c_float), ("a", C.c_float),
+                ("first_point", C.c_uint32), ("n_points", C.c_uint32)]
+
+
+MARKER_ADD, MARKER_DELETE = 0, 2
+MARKER_MAX_POINTS, MARKER_MAX_STRIPS, MARKER_MAX_STRIP_POINTS = 361, 180, 540   # include/urf.h
+MARKER_STRIP_DTYPE = np.dtype([("id", "<i4"), ("action", "<i4"), ("r", "<f4"), ("g", "<f4"), ("b", "<f4"), ("a", "<f4"),
+                               ("first_point", "<u4"), ("n_points", "<u4")])   # the same record for numpy / torch byte views
+
+
 class ParamDesc(C.Structure):
     """struct urf_param_desc: one row of the reference's dynamic_reconfigure interface."""
     _fields_ = [("cfg_name", C.c_char_p), ("field", C.c_char_p), ("where", C.c_int32), ("offset", C.c_uint32),
@@ -146,6 +158,9 @@ def lib(hooks=False):
         "urf_read_stage": [vp, C.c_int, C.c_uint32, vp, C.c_size_t],
         "urf_ordered_indices": [vp, C.c_uint32, vp, vp, vp, vp],
         "urf_marker_points": [vp, C.c_uint32, vp, vp],
+        "urf_marker_strips": [fp, C.c_uint32, C.POINTER(MarkerParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.POINTER(C.c_uint32),
+                              fp, C.POINTER(C.c_uint32)],
+        "urf_marker_strips_batch": [vp, C.POINTER(MarkerParams), fp, u32p, C.c_uint32, C.c_int, vp, vp, fp, u32p],
         "urf_enable_stage_capture": [vp, C.c_int],
         "urf_set_debug_flags": [vp, C.c_uint32],
         "urf_callback_path_state": [vp, C.c_void_p, C.c_void_p],
@@ -202,6 +217,21 @@ def default_marker_params():
     if rc != 0:
         raise UrfError(rc)
     return p
+
+
+def marker_strips(pts, mp, ghost=0):
+    """lidar_segmentation.cpp:369-602 for one sweep on the host (urf_marker_strips, no GPU): pts float32 [k, 4] = x, y, z, red as
+    marker_points returns them, mp a MarkerParams, ghost the count the previous publishing sweep left.  Returns
+    (published, strips, xyz, ghost): strips a MARKER_STRIP_DTYPE array, xyz float32 [n_points, 3], ghost the count to hand on."""
+    pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+    strips = np.zeros(MARKER_MAX_STRIPS, MARKER_STRIP_DTYPE)
+    xyz = np.zeros((MARKER_MAX_STRIP_POINTS, 3), np.float32)
+    g, pub, ns, npts = C.c_int32(ghost), C.c_int32(0), C.c_uint32(0), C.c_uint32(0)
+    rc = lib().urf_marker_strips(pts.ctypes.data, len(pts), C.byref(mp), C.byref(g), C.byref(pub), strips.ctypes.data, C.byref(ns),
+                                 xyz.ctypes.data, C.byref(npts))
+    if rc != 0:
+        raise UrfError(rc, "urf_marker_strips")
+    return bool(pub.value), strips[:ns.value], xyz[:npts.value], g.value
 
 
 def param_table():
@@ -488,6 +518,14 @@ class Context:
 
     def marker_points_batch(self, d_pts, d_counts):
         self._check(self._lib.urf_marker_points_batch(self._h, _ptr(d_pts), _ptr(d_counts)), "urf_marker_points_batch")
+
+    def marker_strips_batch(self, mp, d_pts, d_counts, n_scans, sequence, d_ghost, d_strips, d_xyz, d_n):
+        """road_marker's line strips for n_scans sets of marker points laid out as marker_points_batch writes them, on the
+        device: d_strips [n_scans * MARKER_MAX_STRIPS] records of 32 bytes, d_xyz [n_scans * MARKER_MAX_STRIP_POINTS * 3] float32,
+        d_n [3 * n_scans] uint32 = published, markers, points.  sequence=1: consecutive sweeps, chained through d_ghost
+        (one int32 on the device, read and written; None: starts from 0); sequence=0: independent scans."""
+        self._check(self._lib.urf_marker_strips_batch(self._h, C.byref(mp), _ptr(d_pts), _ptr(d_counts), n_scans, sequence, _ptr(d_ghost),
+                                                      _ptr(d_strips), _ptr(d_xyz), _ptr(d_n)), "urf_marker_strips_batch")
 
     def ordered_indices(self, n_points, scan=0):
         """Input indices of the road / curb / road_probably clouds of scan `scan` in the order the

@@ -325,8 +325,9 @@ bool Detector::filtered(const PointCloud2& msg)
 }
 
 /* ---- BatchDetector ------------------------------------------------------------------------------------- */
-BatchDetector::BatchDetector(int device, uint32_t max_points, uint32_t max_batch) : max_points_(max_points), max_batch_(max_batch)
+BatchDetector::BatchDetector(int device, uint32_t max_points, uint32_t max_batch) : max_points_(max_points), max_batch_(max_batch), device_(device)
 {
+    urf_default_marker_params(&marker_params_);
     int rc = urf_create(&ctx_, device, max_points, max_batch);
     if (rc != URF_OK)
         throw Error(rc, std::string("urf_create: ") + urf_strerror(rc));
@@ -350,7 +351,7 @@ BatchDetector::~BatchDetector()
 {
     if (ctx_)
         urf_destroy(ctx_);
-    for (void* p : { d_data_, d_records_, d_small_ })
+    for (void* p : { d_data_, d_records_, d_small_, d_ghost_, d_marker_ })
         if (p)
             (void)hipFree(p);
     if (stream_)
@@ -370,6 +371,55 @@ urf_params BatchDetector::params() const
     urf_params p;
     check(urf_get_params(ctx_, &p), "urf_get_params");
     return p;
+}
+
+void BatchDetector::enableRoadMarker(bool on, const std::string& fixed_frame)
+{
+    fixed_frame_ = fixed_frame;
+    if (on && !d_ghost_ && (hipSetDevice(device_) != hipSuccess || hipMalloc(&d_ghost_, sizeof(int32_t)) != hipSuccess)) {
+        d_ghost_ = nullptr;
+        throw Error(URF_ERR_OOM, "BatchDetector: hipMalloc failed");
+    }
+    if (on && !marker_on_)
+        resetRoadMarker();
+    marker_on_ = on;
+}
+
+void BatchDetector::resetRoadMarker()
+{
+    if (d_ghost_ && (hipMemsetAsync(d_ghost_, 0, sizeof(int32_t), (hipStream_t)stream_) != hipSuccess))
+        throw Error(URF_ERR_HIP, "BatchDetector: hipMemsetAsync failed");
+}
+
+/* The MarkerArrays of the S messages just classified (the context's last call): marker points and strips on the device, chained
+ * through d_ghost_, one copy back of the counts, records and strip points. */
+void BatchDetector::buildMarkers(size_t S)
+{
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_pts = al(S * URF_MARKER_MAX_POINTS * 4 * sizeof(float)), b_cnt = al(S * sizeof(uint32_t)), b_n = al(3 * S * sizeof(uint32_t)),
+                 b_strips = al(S * URF_MARKER_MAX_STRIPS * sizeof(urf_marker_strip)), b_xyz = al(3 * S * URF_MARKER_MAX_STRIP_POINTS * sizeof(float));
+    uint8_t* base = (uint8_t*)grow(d_marker_, d_marker_cap_, b_pts + b_cnt + b_n + b_strips + b_xyz);
+    float* d_pts = (float*)base;
+    uint32_t* d_cnt = (uint32_t*)(base + b_pts);
+    uint8_t* d_out = base + b_pts + b_cnt;
+    check(urf_marker_points_batch(ctx_, d_pts, d_cnt), "urf_marker_points_batch");
+    check(urf_marker_strips_batch(ctx_, &marker_params_, d_pts, d_cnt, (uint32_t)S, 1, (int32_t*)d_ghost_, (urf_marker_strip*)(d_out + b_n),
+                                  (float*)(d_out + b_n + b_strips), (uint32_t*)d_out),
+          "urf_marker_strips_batch");
+    h_marker_.resize(b_n + b_strips + b_xyz);
+    hipStream_t st = (hipStream_t)stream_;
+    if (hipMemcpyAsync(h_marker_.data(), d_out, h_marker_.size(), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        throw Error(URF_ERR_HIP, "BatchDetector: read-back failed");
+    const uint32_t* n = (const uint32_t*)h_marker_.data();
+    const urf_marker_strip* strips = (const urf_marker_strip*)(h_marker_.data() + b_n);
+    const float* xyz = (const float*)(h_marker_.data() + b_n + b_strips);
+    for (size_t i = 0; i < S; i++) {
+        if (n[3 * i + 1] > URF_MARKER_MAX_STRIPS || n[3 * i + 2] > URF_MARKER_MAX_STRIP_POINTS)
+            throw Error(URF_ERR_HIP, "BatchDetector: marker counts out of range");
+        marker_published_[i] = n[3 * i] != 0;
+        if (marker_published_[i])
+            toMarkerArray(strips + i * URF_MARKER_MAX_STRIPS, n[3 * i + 1], xyz + 3 * i * URF_MARKER_MAX_STRIP_POINTS, fixed_frame_, markers_[i]);
+    }
 }
 
 void* BatchDetector::grow(void*& p, size_t& cap, size_t bytes)
@@ -394,6 +444,8 @@ size_t BatchDetector::filtered(const std::vector<PointCloud2>& msgs)
     const size_t S = msgs.size();
     infos_.assign(S, urf_scan_info{});
     clouds_.resize(4 * S);
+    markers_.resize(S);
+    marker_published_.assign(S, 0);   /* (messages that publish nothing leave the ghost count alone: nothing to do for a batch of them) */
     for (size_t i = 0; i < S; i++)
         for (int k = 0; k < 4; k++) {
             clouds_[4 * i + k].header = msgs[i].header;   /* lidar_segmentation.cpp:612-615 */
@@ -473,6 +525,8 @@ size_t BatchDetector::filtered(const std::vector<PointCloud2>& msgs)
     if (n_rec && (hipMemcpyAsync(h_records_.data(), d_rec, n_rec * sizeof(urf_point_xyzi), hipMemcpyDeviceToHost, st) != hipSuccess ||
                   hipStreamSynchronize(st) != hipSuccess))
         throw Error(URF_ERR_HIP, "BatchDetector: read-back failed");
+    if (marker_on_)
+        buildMarkers(S);
     size_t n_pub = 0;
     for (size_t i = 0; i < S; i++) {
         n_pub += infos_[i].status == URF_OK;

@@ -83,11 +83,6 @@ struct PointCloud2 {
     bool is_dense = false;
 };
 
-struct Error : std::runtime_error {
-    int code;
-    Error(int c, const std::string& what) : std::runtime_error(what), code(c) {}
-};
-
 class Detector {
 public:
     explicit Detector(int device = 0, uint32_t max_points = 1u << 20);
@@ -185,7 +180,12 @@ private:
  * x / y / z / intensity bit for bit with pcl::PointXYZI's w = 1 and zero padding (what pcl::fromROSMsg leaves; Detector
  * copies a pcl::PointXYZI-layout message's padding bytes as they are, which a message from pcl::toROSMsg holds the same way).
  * One context of max_batch scans of up to max_points points: a call with more messages, or a longer one, throws
- * Error(URF_ERR_CAPACITY).  road_marker stays with Detector (its ghost deletion runs from sweep to sweep). */
+ * Error(URF_ERR_CAPACITY).
+ * road_marker (enableRoadMarker): the messages of one filtered() call are consecutive sweeps of one sensor, and the ghost count
+ * -- all the reference keeps from sweep to sweep -- stays in a device word between calls, so a drive cut into batches of any
+ * sizes gives the MarkerArrays Detector gives for the same messages one by one.  Marker points and line strips are built on the
+ * device (urf_marker_points_batch -> urf_marker_strips_batch) and come back in one copy; with the marker off, filtered()
+ * launches nothing for it. */
 class BatchDetector {
 public:
     BatchDetector(int device = 0, uint32_t max_points = 1u << 20, uint32_t max_batch = 64);
@@ -196,6 +196,15 @@ public:
     void setParams(const urf_params& p);
     urf_params params() const;
     void setReferenceOrder(bool on) { reference_order_ = on; }
+
+    /* As Detector's: also build "road_marker" for every message (off by default; the polygon parameters start from
+     * urf_default_marker_params, as Detector's do).  Switching it on starts a new drive. */
+    void enableRoadMarker(bool on, const std::string& fixed_frame = "left_os1/os1_lidar");
+    void setMarkerParams(const urf_marker_params& p) { marker_params_ = p; }
+    /* forget the previous sweep's strips (a new drive): the next publishing message emits no DELETE markers */
+    void resetRoadMarker();
+    /* nullptr when the reference would not publish a MarkerArray for message i of the last filtered() call */
+    const MarkerArray* road_marker(size_t i) const { return marker_published_.at(i) ? &markers_[i] : nullptr; }
 
     /* Classifies every message; returns how many of them publish (the others: < 30 ROI points, or empty). */
     size_t filtered(const std::vector<PointCloud2>& msgs);
@@ -226,6 +235,18 @@ private:
     std::vector<PointXYZI> h_records_;
     std::vector<urf_scan_info> infos_;
     std::vector<PointCloud> clouds_;   /* 4 per message: road, curb, roi, road_probably */
+    /* road_marker */
+    void buildMarkers(size_t S);
+    int device_ = 0;
+    bool marker_on_ = false;
+    std::string fixed_frame_;
+    urf_marker_params marker_params_;
+    void* d_ghost_ = nullptr;    /* int32_t: the ghost count, from call to call */
+    void* d_marker_ = nullptr;   /* marker points and counts, then (one read-back) d_n, strips, strip points */
+    size_t d_marker_cap_ = 0;
+    std::vector<uint8_t> h_marker_;
+    std::vector<MarkerArray> markers_;
+    std::vector<char> marker_published_;
 };
 
 }   // namespace urf

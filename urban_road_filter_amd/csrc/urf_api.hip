@@ -246,6 +246,7 @@ struct urf_ctx {
     lazy_buf<uint32_t> mk_pos;
     lazy_buf<uint8_t> mk_red;       /* ... and one flag per ring and scan behind the cells (k_marker_ring_literal) */
     lazy_buf<float> mk_out;         /* single-scan entry point: 361 x 4 floats + 1 count */
+    lazy_buf<int32_t> mk_ghost;     /* urf_marker_strips_batch: the incoming ghost count (the call's last scan overwrites the caller's word) */
     uint32_t* compact_cnt = nullptr;   /* [max_batch][max_tiles][4] */
     /* the published clouds of a batch (urf_clouds_batch_*): per (scan, tile) counts and bases, and the ordered lists of the
      * reference order: 3 x scans x stride entries + 3 counts per scan */
@@ -1728,6 +1729,32 @@ extern "C" int urf_marker_points(urf_ctx* c, uint32_t scan, float* pts, uint32_t
         return URF_ERR_HIP;
     std::memcpy(pts, h.data(), (size_t)n * 4 * sizeof(float));
     *count = n;
+    return URF_OK;
+}
+
+/* road_marker's line strips for n_scans sets of marker points (include/urf.h).  Reads nothing of the context but its stream:
+ * no scratch row, nothing of the last classify call. */
+extern "C" int urf_marker_strips_batch(urf_ctx* c, const urf_marker_params* mp, const float* d_pts, const uint32_t* d_counts, uint32_t n_scans,
+                                       int sequence, int32_t* d_ghost, urf_marker_strip* d_strips, float* d_xyz, uint32_t* d_n)
+{
+    if (!c || !mp || mp->size != sizeof(urf_marker_params) || !d_pts || !d_counts || !d_strips || !d_xyz || !d_n)
+        return URF_ERR_INVALID_ARG;
+    if (n_scans > c->max_batch)
+        return URF_ERR_CAPACITY;
+    if (n_scans == 0)
+        return URF_OK;
+    URF_HIP(c, hipSetDevice(c->device));
+    const int32_t* ghost_in = nullptr;
+    if (sequence && d_ghost) {   /* a copy: scan 0's wave may read it after the last scan's wave has written the new value */
+        int rc = grow(c, c->mk_ghost, 1);
+        if (rc != URF_OK)
+            return rc;
+        URF_HIP(c, hipMemcpyAsync(c->mk_ghost.p, d_ghost, sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+        ghost_in = c->mk_ghost.p;
+    }
+    hipLaunchKernelGGL(k_marker_strips, dim3(n_scans), dim3(URF_WAVE), 0, c->stream, d_pts, d_counts, n_scans, sequence ? 1 : 0, *mp, ghost_in,
+                       sequence ? d_ghost : nullptr, d_strips, d_xyz, d_n);
+    URF_HIP(c, hipGetLastError());
     return URF_OK;
 }
 
