@@ -132,7 +132,8 @@ typedef struct urf_params {
     float    kdist_param;        /* cfg:66 */
     int32_t  starbeam_filter;    /* cfg:69  bool */
     int32_t  dmin_param;         /* cfg:72 */
-    int32_t  channels;           /* lidar_segmentation.cpp:4   (64), 1..128 */
+    int32_t  channels;           /* lidar_segmentation.cpp:4   (64), 1..128: the ring table's capacity -- set it to the sensor's laser count; 16, 32 and 64
+                                  * also state the points per firing to the fused front end (urf_set_front_mode) */
     int32_t  sectors;            /* star_shaped_search.cpp:8   rep = 360 */
     float    beam_width;         /* star_shaped_search.cpp:9   width = 0.2 */
 } urf_params;
@@ -492,12 +493,17 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
 
 /* ---- the fused front end for batches of sweeps in firing order (round 6) -------
  * A batch call (urf_classify_batch_*) whose scans arrive as a spinning LiDAR's driver delivers them -- firing after
- * firing, the 64 lasers of a firing in one fixed order (any order), returns missing where there were none -- is classified
+ * firing, the `channels` (64, 32 or 16) lasers of a firing in one fixed order (any order): point f * channels + l is laser slot l of
+ * firing f, returns missing where there were none -- is classified
  * by a front end that keeps no ring-sorted copy of the sweep (urban_road_filter_amd/csrc/urf_front.hpp: one lane per
  * laser, the detectors' windows of lidar_segmentation.cpp:280-283 / x_zero_method.cpp:30-67 / z_zero_method.cpp:21-72
  * in registers).  Decided per scan on the device; a scan without that shape takes the general kernels in the same
- * call; labels and summaries are identical either way.  Applies with channels == 64, curbPoints == 5, no stage
- * capture, at most 128 x 2048 points per scan.  mode 0: never; 1 (default): batch calls of at least 192 scans (below that the general kernels are faster: a sweep's fused kernels are
+ * call; labels and summaries are identical either way.  Applies with channels == 64, 32 or 16 (the caller states the sensor's
+ * laser count through `channels`, as the reference's user does in lidar_segmentation.cpp:4; a 32-laser sweep classified with channels
+ * == 64 is handed back to the general kernels), curbPoints == 5, no stage capture, at most 128 x 2048 points per scan.  Row-major
+ * organised clouds (below) have `channels` rows: point l * W + f.  mode 0: never; 1 (default): batch calls of at least 192 scans with channels == 64; with channels == 16 or 32 mode 1 never takes the fused
+ * kernels -- no batch size, no row-major sighting, not on the callback path: they are opt-in through mode 2 until their crossover has been
+ * measured (tools/front_lasers_bench.py) -- (below that the general kernels are faster: a sweep's fused kernels are
  * a few long dependent chains, which need many sweeps side by side to fill the device; a context whose sweeps have turned out to be
  * row-major takes the fused kernels at any batch size -- the general kernels are 2.3 x slower on that layout even for four sweeps --
  * and on the callback path: urf_classify_pc2(_async) of a row-major sweep, from the context's second or third such sweep on); 2: every

@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""tools/front_lasers_bench.py -- the fused front end on sweeps of 16 / 32 / 64 lasers per firing, measured on one MI355X.
+Prints ONE JSON line.
+
+    timeout 900 python tools/front_lasers_bench.py [--scans 1024] [--steps 20] [--warmup 3] [--lasers 16,32,64] [--no-sweep]
+
+For L in --lasers and storage order in {firing, rows}: --scans resident L x 2048 sweeps from urf_synth_cloud(L, 2048, scene 1 and 3
+alternating, seed), params.channels = L.  First a parity gate: the labels of a few sampled scans against oracle B (tests/oracles.py).
+Then urf_set_front_mode 0 and 2, warm-up, --steps calls between device events: median ms per call, scans/s, urf_front_scans.
+"sweep": mode 0 / 1 / 2 over batch sizes 32 .. 1024 of the firing-order sweeps, the numbers mode 1's threshold per laser count
+(urf_front.hpp: urf_front_min_scans) is set from.  Uses only entry points every build since the fused front end has."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+COLS = 2048
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scans", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--lasers", default="16,32,64")
+    ap.add_argument("--distinct", type=int, default=32, help="distinct sweeps the batch is built from")
+    ap.add_argument("--no-sweep", action="store_true")
+    args = ap.parse_args()
+    import torch
+    import urban_road_filter_amd as u
+    import oracles as O
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: nothing is measured here")
+    dev = torch.device("cuda:0")
+    out = {"metric": "front_lasers", "device": torch.cuda.get_device_name(0), "scans": args.scans, "cols": COLS,
+           "timing": "device events, median ms per call after warm-up", "results": [], "sweep": []}
+    t0 = time.time()
+    st = torch.cuda.Stream()
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(args.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return float(np.median(ts))
+
+    with torch.cuda.stream(st):
+        for L in [int(v) for v in args.lasers.split(",")]:
+            n = L * COLS
+            p = u.default_params().wide_roi()
+            p.channels = L
+            base = [u.synth_cloud(L, COLS, 1 + (s % 2) * 2, 100 + s) for s in range(min(args.distinct, args.scans))]
+            for order in ("firing", "rows"):
+                src = base if order == "firing" else [tuple(np.ascontiguousarray(a.reshape(-1, L).T.reshape(-1)) for a in c) for c in base]
+                one = [torch.from_numpy(np.concatenate([c[k] for c in src])).to(dev) for k in range(3)]
+                reps = (args.scans + len(src) - 1) // len(src)
+                dx, dy, dz = (t.repeat(reps)[:args.scans * n].contiguous() for t in one)
+                labels = torch.empty(args.scans * n, dtype=torch.uint8, device=dev)
+                with u.Context(n, args.scans, params=p) as ctx:
+                    ctx.set_stream(st.cuda_stream)
+                    # parity gate: both modes, a few sampled scans
+                    want = {k: O.run_b(*src[k % len(src)], p)[0] for k in (0, 1, args.scans - 1)}
+                    for mode in (0, 2, 2):
+                        ctx.set_front_mode(mode)
+                        ctx.classify_batch_soa(dx, dy, dz, n, args.scans, labels, None)
+                        torch.cuda.synchronize()
+                        got = labels.cpu().numpy().reshape(args.scans, n)
+                        for k, lb in want.items():
+                            if not np.array_equal(got[k], lb):
+                                raise SystemExit("parity gate: L %d %s mode %d scan %d differs from oracle B" % (L, order, mode, k))
+                    row = {"lasers": L, "order": order}
+                    for mode in (0, 2):
+                        ctx.set_front_mode(mode)
+                        ms = timed(lambda: ctx.classify_batch_soa(dx, dy, dz, n, args.scans, labels, None))
+                        row["mode%d_ms" % mode] = ms
+                        row["mode%d_scans_per_s" % mode] = args.scans / ms * 1e3
+                        row["mode%d_front_scans" % mode] = int(ctx.front_scans())
+                    out["results"].append(row)
+                    if order == "firing" and not args.no_sweep:
+                        for S in (32, 64, 128, 192, 256, 384, 512, 768, 1024):
+                            if S > args.scans:
+                                break
+                            r = {"lasers": L, "scans": S}
+                            for mode in (0, 1, 2):
+                                ctx.set_front_mode(mode)
+                                r["mode%d_ms" % mode] = timed(lambda: ctx.classify_batch_soa(dx, dy, dz, n, S, labels, None))
+                                r["mode%d_front_scans" % mode] = int(ctx.front_scans())
+                            out["sweep"].append(r)
+    out["wall_s"] = time.time() - t0
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -382,7 +382,8 @@ class Context:
         return n.value
 
     def set_front_mode(self, mode):
-        """The fused front end for batches of organised sweeps (include/urf.h): 0 never; 1 (default) batch calls of at least 192 scans
+        """The fused front end for batches of organised sweeps of 64, 32 or 16 lasers per firing (params.channels states the laser
+        count; include/urf.h): 0 never; 1 (default) batch calls of at least 192 scans of 64 lasers (16 / 32 lasers: never in mode 1, in either layout or on the callback path; opt in with mode 2)
         -- a context whose sweeps have turned out to be row-major takes it at any batch size, and on the callback path; 2 every batch
         call it applies to."""
         self._check(self._lib.urf_set_front_mode(self._h, int(mode)), "urf_set_front_mode")

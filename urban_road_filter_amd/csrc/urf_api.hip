@@ -164,15 +164,19 @@ struct __attribute__((visibility("hidden"))) urf_policy {
          * sweep's 200 microseconds -- are left out, k_index voids a sweep that needed them, and urf_classify_pc2_wait() runs it again. */
         a.optimistic = slot ? ((speculate ? URF_OPT_NO_REPAIR : 0u) | (slot_lists ? 0u : URF_OPT_NO_LISTS) | (slot_nan ? 0u : URF_OPT_NO_NAN) |
                                (slot_ties ? 0u : URF_OPT_NO_TIES)) : 0u;
-        /* The fused front end: 64 lasers = 64 lanes, the detectors' window of curbPoints == 5 in registers, no stage capture (its values
-         * are the general kernels').  Row-major sweeps gain from it at any batch size (the general kernels need 0.64 ms for four such
+        /* The fused front end: a firing of 64, 32 or 16 lasers (params.channels) = the first lanes of a wave, the detectors' window of
+         * curbPoints == 5 in registers, no stage capture (its values are the general kernels').  Row-major sweeps gain from it at any batch size (the general kernels need 0.64 ms for four such
          * sweeps, the fused ones 0.26, tools/r6_min_scans.py --rows), sweeps in firing order only from 192 per call on, and not as single
          * sweeps of the callback path (tools/r6_single_sweep.py). */
+        const unsigned L = (unsigned)dp.p.channels;
+        const bool lasers = L == 64u || L == 32u || L == 16u;
+        a.front_lsh = L == 16u ? 4u : (L == 32u ? 5u : 6u);
         const bool shape = front_mode != 0 && !front_off && !general_only && !want_ring_sorted && a.capture == 0 &&
-                           (unsigned)dp.p.channels == URF_FRONT_LANES && dp.p.curbPoints == 5 && a.tiles <= URF_FRONT_MAX_TILES;
-        const bool small_ok = front_rows && (rows_used || rows_probation > 0);
-        a.front = (shape && (slot ? small_ok : (front_mode == 2 || small_ok || a.n_scans >= URF_FRONT_MIN_SCANS))) ? 1u : 0u;
-        a.front_sight = (shape && !a.front && !front_rows && !rows_oom) ? 1u : 0u;
+                           lasers && dp.p.curbPoints == 5 && a.tiles <= URF_FRONT_MAX_TILES;
+        /* (16 / 32 lasers: nothing below mode 2 until their crossover has been measured -- no batch size, no row-major sighting, no callback path) */
+        const bool small_ok = front_rows && (rows_used || rows_probation > 0) && (L == 64u || front_mode == 2);
+        a.front = (shape && (slot ? small_ok : (front_mode == 2 || small_ok || a.n_scans >= (L == 64u ? URF_FRONT_MIN_SCANS : (L == 32u ? URF_FRONT_MIN_SCANS_32 : URF_FRONT_MIN_SCANS_16))))) ? 1u : 0u;
+        a.front_sight = (shape && !a.front && !front_rows && !rows_oom && (L == 64u || front_mode == 2)) ? 1u : 0u;
         a.front_tpb = front_tpb ? front_tpb : (a.n_scans >= URF_FRONT_TPB_SCANS ? URF_FRONT_TPB_LARGE : (a.n_scans >= 16u ? URF_FRONT_TPB_SMALL : 1u));
         a.front_lists = (a.front && !front_direct && !slot) ? 1u : 0u;   /* (the callback path's sequence holds the general kernels as grids anyway) */
         a.front_rows = (a.front && front_rows) ? 1u : 0u;   /* (independent of the two other speculations: the repair kernels come with it) */
@@ -893,8 +897,15 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs* a_out = nul
     mark();
     if (a.front_rows)
         hipLaunchKernelGGL(k_transpose, g_tiles, dim3(256), 0, st, a);
-    if (a.front)
-        hipLaunchKernelGGL(k_front, dim3((a.tiles + a.front_tpb - 1) / a.front_tpb, n_scans), dim3(64), 0, st, a, dp);
+    if (a.front) {   /* (a tile is URF_TILE points, whatever the laser count: URF_TILE / L firings) */
+        const dim3 g_front((a.tiles + a.front_tpb - 1) / a.front_tpb, n_scans);
+        if (a.front_lsh == 6u)
+            hipLaunchKernelGGL(k_front, g_front, dim3(64), 0, st, a, dp);
+        else if (a.front_lsh == 5u)
+            hipLaunchKernelGGL(k_front32, g_front, dim3(64), 0, st, a, dp);
+        else
+            hipLaunchKernelGGL(k_front16, g_front, dim3(64), 0, st, a, dp);
+    }
     if (a.front_lists) {   /* what k_front handed back (normally nothing) */
         hipLaunchKernelGGL(k_table_repair, g_scan, dim3(URF_TABLE_THREADS), 0, st, a, dp, 1u);
         hipLaunchKernelGGL(k_split_list, dim3(c->n_cus * 2), dim3(URF_TILE_THREADS), urf_split_lds_bytes(C, K, star), st, a, dp);

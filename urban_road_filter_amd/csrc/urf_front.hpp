@@ -49,6 +49,8 @@
 #define URF_FRONT_MIN_SCANS 192u  /* below (mode 1): the general kernels.  A block of k_front is ONE wave marching 80-144 dependent steps, k_front_finish one
                                    * workgroup per scan: with few scans the device is empty and the chains are the time (tools/r6_min_scans.py, general / fused ms per call:
                                    * 32 sweeps 0.21 / 0.25-0.33, 64: 0.31 / 0.32-0.40, 128: 0.45 / 0.44-0.50, 256: 0.73 / 0.66-0.70, 1024: 2.44 / 2.1) */
+#define URF_FRONT_MIN_SCANS_32 0xffffffffu   /* 32 / 16 lasers per firing, mode 1: never (mode 2 only) */
+#define URF_FRONT_MIN_SCANS_16 0xffffffffu
 #define URF_FRONT_TPB_SMALL 2u    /* tiles per block of k_front for batches below URF_FRONT_TPB_SCANS scans (more, shorter chains), ... */
 #define URF_FRONT_TPB_LARGE 4u    /* ... and from there on (less halo): 256 sweeps 0.663 / 0.703 ms at 2 / 4, 1024 sweeps 0.829 / 0.820 */
 #define URF_FRONT_TPB_SCANS 512u
@@ -105,45 +107,47 @@ __device__ __forceinline__ void urf_front_src(const urf_kargs& a, unsigned s, un
     gz = (rows ? (const float*)a.tz : a.z) + o;
 }
 
-/* Row-major organised sweep -> firing order: tx[f * 64 + l] = x[l * F + f].  Grid (tiles, scans) x 256 threads, a tile = 32 firings:
- * 64 rows x 128 bytes in (a cache line per row), LDS, 8 KB out in one stretch; 24 B/point, HBM-bound. */
+/* Row-major organised sweep of L = 1 << front_lsh rows -> firing order: tx[f * L + l] = x[l * F + f].  Grid (tiles, scans) x 256 threads, a tile =
+ * URF_TILE / L firings: L rows x 128 / 256 / 512 bytes in, LDS, 8 KB out in one stretch; 24 B/point, HBM-bound. */
 __global__ __launch_bounds__(256) void k_transpose(urf_kargs a)
 {
-    __shared__ float T[3][64][33];
+    __shared__ float T[3][64 * 33];   /* [row][W + 1], W = URF_TILE / L columns: 64 x 33, 32 x 65, 16 x 129 */
     const unsigned s = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
+    const unsigned lsh = a.front_lsh, L = 1u << lsh, wsh = 11u - lsh, W = 1u << wsh, RS = W + 1u;
+    static_assert(URF_TILE == 2048u, "a tile's columns: 1 << (11 - lsh)");
     if (a.front_ok[s] != URF_FRONT_ROWS)
         return;
     unsigned off, len;
     urf_scan_range(a, s, off, len);
-    const unsigned F = len >> 6, f0 = t * URF_FRONT_STEPS;
+    const unsigned F = len >> lsh, f0 = t * W;
     if (f0 >= F)
         return;
-    const unsigned c = tid & 31u, r8 = tid >> 5;
+    const unsigned c = tid & (W - 1u), r8 = tid >> wsh, RP = 256u >> wsh;   /* RP rows per pass, eight passes: L rows */
     const bool in = f0 + c < F;
     float vx[8], vy[8], vz[8];
 #pragma unroll
     for (unsigned j = 0; j < 8; j++) {
-        const size_t i = (size_t)off + (size_t)(j * 8u + r8) * F + f0 + (in ? c : 0u);
+        const size_t i = (size_t)off + (size_t)(j * RP + r8) * F + f0 + (in ? c : 0u);
         vx[j] = a.x[i];
         vy[j] = a.y[i];
         vz[j] = a.z[i];
     }
 #pragma unroll
     for (unsigned j = 0; j < 8; j++) {
-        T[0][j * 8u + r8][c] = vx[j];
-        T[1][j * 8u + r8][c] = vy[j];
-        T[2][j * 8u + r8][c] = vz[j];
+        T[0][(j * RP + r8) * RS + c] = vx[j];
+        T[1][(j * RP + r8) * RS + c] = vy[j];
+        T[2][(j * RP + r8) * RS + c] = vz[j];
     }
     __syncthreads();
-    const size_t ob = (size_t)urf_sbase(a, s) + (size_t)f0 * 64u;
-    const unsigned nf = F - f0 < URF_FRONT_STEPS ? F - f0 : URF_FRONT_STEPS;
+    const size_t ob = (size_t)urf_sbase(a, s) + (size_t)f0 * L;
+    const unsigned nf = F - f0 < W ? F - f0 : W;
 #pragma unroll
     for (unsigned j = 0; j < 8; j++) {
-        const unsigned v = j * 256u + tid, f = v >> 6, l = v & 63u;
+        const unsigned v = j * 256u + tid, f = v >> lsh, l = v & (L - 1u);
         if (f < nf) {
-            a.tx[ob + v] = T[0][l][f];
-            a.ty[ob + v] = T[1][l][f];
-            a.tz[ob + v] = T[2][l][f];
+            a.tx[ob + v] = T[0][l * RS + f];
+            a.ty[ob + v] = T[1][l * RS + f];
+            a.tz[ob + v] = T[2][l * RS + f];
         }
     }
 }
@@ -203,7 +207,12 @@ __device__ __forceinline__ void urf_front_push(urf_u2* cbuf, unsigned& ncb, bool
     ncb += (unsigned)__popcll(m);
 }
 
-template <bool STAR, bool BEAM>
+/* L = the lasers of a firing (params.channels: 64, 32, 16).  Point f * L + l is laser slot l of firing f: everything the march leaves behind
+ * -- records, region-of-interest bits, the sector-sorted copies and their slots, candidate indices -- is indexed by the point's place in
+ * the input, a tile is URF_TILE points = URF_TILE / L firings, and k_index and the star-shaped search read a scan of any L alike.  Only
+ * the presence words count in firings: word (f >> 5) * L + l.  For L < 64 the lanes from L on are idle (no point, never in the region of
+ * interest): one march per wave, the chain of a block URF_TILE / L steps per tile. */
+template <bool STAR, bool BEAM, unsigned L>
 __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
 {
     const unsigned s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
@@ -216,16 +225,18 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
     const unsigned ok = a.front_ok[s];
     if (ok == 0u)
         return;
-    constexpr unsigned C = URF_FRONT_LANES;
+    constexpr unsigned C = L;                     /* table entries per scan: params.channels */
+    constexpr unsigned STEPS = URF_TILE / L;      /* firings per tile */
+    static_assert(L == 64u || L == 32u || L == 16u, "a firing fills the wave, half of it or a quarter");
     const unsigned K = (unsigned)dp.p.sectors;
-    const unsigned nf = (len + 63u) >> 6;                                   /* firings of the scan */
-    const unsigned F0 = t_first * URF_FRONT_STEPS;
-    const unsigned F1 = F0 + TPB * URF_FRONT_STEPS < nf ? F0 + TPB * URF_FRONT_STEPS : nf;
+    const unsigned nf = (len + L - 1u) / L;                                 /* firings of the scan */
+    const unsigned F0 = t_first * STEPS;
+    const unsigned F1 = F0 + TPB * STEPS < nf ? F0 + TPB * STEPS : nf;
     const unsigned Fs = F0 > URF_FRONT_HPRE ? F0 - URF_FRONT_HPRE : 0u;
     const unsigned Fe = F1 + URF_FRONT_HPOST < nf ? F1 + URF_FRONT_HPOST : nf;
     const bool from_start = Fs == 0u;   /* the window count IS the ring position + 1 */
     const bool to_end = Fe == nf;       /* no point of the scan lies behind the march */
-    static_assert(URF_FRONT_HPRE % 4u == 0u && URF_FRONT_STEPS % 4u == 0u, "the march runs in groups of four firings");
+    static_assert(URF_FRONT_HPRE % 4u == 0u && STEPS % 4u == 0u, "the march runs in groups of four firings");
     const unsigned sb = urf_sbase(a, s);
     const float *gx, *gy, *gz;
     urf_front_src(a, s, off, ok, gx, gy, gz);
@@ -257,16 +268,23 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
     /* per tile (wave-uniform) */
     unsigned troi = 0, tstar = 0;
     int stepkey_v = (int)URF_SEC_NONE, stepcnt_v = 0;   /* lane j: sector / participating points of step j of the tile */
+    int stepkey_w = (int)URF_SEC_NONE, stepcnt_w = 0;   /* (L = 16, 128 steps per tile) ... of step 64 + j */
 
     /* one firing.  PH 0: the halo in front of the block (windows fill), 1: the block, 2: the halo behind it (windows complete) */
     auto step = [&](auto ph, const unsigned f, const float x, const float y, const float z) {
         constexpr unsigned PH = decltype(ph)::value;
-        const unsigned stp = f % URF_FRONT_STEPS;
-        const unsigned i = f * 64u + lane;
-        const bool roi = i < len && urf_in_roi(dp.p, x, y, z);
+        const unsigned stp = f % STEPS;
+        const unsigned i = f * L + lane;
+        const bool roi = (L == 64u || lane < L) && i < len && urf_in_roi(dp.p, x, y, z);
         const unsigned long long roim = __ballot(roi);
-        if (PH == 1u && lane == 0u)
-            a.roi_bits[((size_t)s * a.tiles + f / URF_FRONT_STEPS) * URF_FRONT_STEPS + stp] = roim;
+        if (PH == 1u && lane == 0u) {   /* bit i of the scan's words: input point i */
+            if (L == 64u)
+                a.roi_bits[((size_t)s * a.tiles + f / STEPS) * STEPS + stp] = roim;
+            else if (L == 32u)
+                ((uint32_t*)(a.roi_bits + (size_t)s * a.tiles * (URF_TILE / 64u)))[f] = (uint32_t)roim;
+            else
+                ((uint16_t*)(a.roi_bits + (size_t)s * a.tiles * (URF_TILE / 64u)))[f] = (uint16_t)roim;
+        }
         if (roim == 0ull)
             return;   /* (uniform) nothing of this firing lies in the region of interest */
         const float rho2 = x * x + y * y;
@@ -302,7 +320,7 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
             /* the record, input order: ring | azimuth code (URF_REC_*; detector hits are OR-ed in by k_front_finish) */
             const unsigned azc_v = urf_az_code(urf_fast_azimuth_of(fi));   /* (unconditionally, then a select: a branch around eight instructions costs more) */
             const unsigned azc = urf_fast_az_ok(x, y) ? azc_v : URF_REC_AZ_UNKNOWN;
-            __builtin_amdgcn_raw_buffer_store_b32((azc << URF_REC_AZ_SHIFT) | (on ? E : URF_FRONT_RING_NONE), brec, i * 4u, 0, URF_FRONT_NT);
+            __builtin_amdgcn_raw_buffer_store_b32((azc << URF_REC_AZ_SHIFT) | (on ? E : URF_FRONT_RING_NONE), brec, (L == 64u || lane < L) ? i * 4u : URF_OOB, 0, URF_FRONT_NT);
             if (STAR) {
                 /* star-shaped search: the firing's participants share one sector */
                 unsigned sk = (unsigned)fs;
@@ -314,15 +332,20 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
                 const unsigned src = psm ? (unsigned)__ffsll((long long)psm) - 1u : 0u;
                 const unsigned f0 = psm ? (unsigned)__builtin_amdgcn_readlane((int)sk, (int)src) : URF_SEC_NONE;
                 failed_m |= psm & __builtin_amdgcn_ballot_w64(sk != f0);
-                const unsigned so = (f / URF_FRONT_STEPS) * URF_TILE + tstar + urf_popc_below(psm);
+                const unsigned so = (f / STEPS) * URF_TILE + tstar + urf_popc_below(psm);
                 const unsigned o4 = ons ? so * 4u : URF_OOB;
                 const float pr = urf_sqrt_rn_normal(rho2);   /* star_shaped_search.cpp:164: sqrtf(x * x + y * y) */
                 failed_m |= psm & ~(__builtin_amdgcn_ballot_w64(rho2 >= 0x1p-90f) & __builtin_amdgcn_ballot_w64(rho2 <= 0x1p126f));   /* (outside the shortcut's interval: the legacy kernels) */
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pr), bsr, o4, 0, URF_FRONT_NT);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(z), bsz, o4, 0, URF_FRONT_NT);
-                __builtin_amdgcn_raw_buffer_store_b16((short)((stp * 64u + lane) | (on ? 0u : URF_SLOT_OFF)), bss, ons ? so * 2u : URF_OOB, 0, URF_FRONT_NT);
-                stepkey_v = lane == stp ? (int)f0 : stepkey_v;
-                stepcnt_v = lane == stp ? (int)__popcll(psm) : stepcnt_v;
+                __builtin_amdgcn_raw_buffer_store_b16((short)((stp * L + lane) | (on ? 0u : URF_SLOT_OFF)), bss, ons ? so * 2u : URF_OOB, 0, URF_FRONT_NT);
+                if (STEPS <= 64u || stp < 64u) {   /* (uniform) */
+                    stepkey_v = lane == stp ? (int)f0 : stepkey_v;
+                    stepcnt_v = lane == stp ? (int)__popcll(psm) : stepcnt_v;
+                } else {
+                    stepkey_w = lane == stp - 64u ? (int)f0 : stepkey_w;
+                    stepcnt_w = lane == stp - 64u ? (int)__popcll(psm) : stepcnt_w;
+                }
                 tstar += (unsigned)__popcll(psm);
             }
             troi += (unsigned)__popcll(roim);
@@ -332,7 +355,7 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
             if (PH == 1u) {
                 const double s2 = (double)x * (double)x + (double)y * (double)y;
                 maxs = s2 > maxs ? s2 : maxs;
-                pw |= 1u << stp;
+                pw |= 1u << (f & 31u);
             }
             econf = true;
             w0 = w1; w1 = w2; w2 = w3; w3 = w4; w4 = w5; w5 = w6; w6 = w7; w7 = w8; w8 = w9; w9 = w10;
@@ -384,19 +407,75 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
                 ex = p_in && !full;
         }
         if (__ballot(zz | xz | ez | ex) != 0ull) {   /* (uniform) */
-            urf_front_push(cbuf, ncb, zz | ez, ((fwA & 0xffffu) + Fs) * 64u + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
-            urf_front_push(cbuf, ncb, xz | ex, ((fwB & 0xffffu) + Fs) * 64u + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
+            urf_front_push(cbuf, ncb, zz | ez, ((fwA & 0xffffu) + Fs) * L + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
+            urf_front_push(cbuf, ncb, xz | ex, ((fwB & 0xffffu) + Fs) * L + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
             if (ncb > URF_FRONT_CBUF - 128u)
                 urf_front_flush(a, s, cbuf, ncb, overflow);
         }
     };
+    /* the presence words of 32 firings (L = 64: the tile's, tile_end) */
+    auto pres_end = [&](const unsigned pt) {
+        if (lane < L)
+            a.front_pres[(size_t)s * a.tiles * 64u + (size_t)pt * L + lane] = pw;
+        pw = 0;
+    };
     auto tile_end = [&](const unsigned t) {
         const size_t row = (size_t)s * a.tiles + t;
-        a.front_pres[row * 64u + lane] = pw;
-        pw = 0;
+        if (L == 64u) {
+            a.front_pres[row * 64u + lane] = pw;
+            pw = 0;
+        }
         if (lane == 0)
             a.tile_roi[row] = troi;
-        if (STAR) {
+        if (STAR && STEPS > 32u) {
+            /* the same construction as below over 64 or 128 steps: a register per 64 of them, the running values carried from one to the
+             * next.  (The 32-step form below is kept word for word for the 64-laser kernel: its code and its register budget are what
+             * tests/test_kernel_resources.py and the benchmark pin.) */
+            constexpr unsigned NH = STEPS > 64u ? 2u : 1u;
+            unsigned fk[NH], sbase_h[NH];
+            unsigned carry = 0, total = 0;
+#pragma unroll
+            for (unsigned h = 0; h < NH; h++) {
+                const unsigned key = (unsigned)(h ? stepkey_w : stepkey_v), sc = (unsigned)(h ? stepcnt_w : stepcnt_v);
+                const unsigned k1 = key != URF_SEC_NONE ? key + 1u : 0u;
+                unsigned m = urf_wave_scan_max(k1);
+                m = m > carry ? m : carry;
+                unsigned exc = (unsigned)__shfl_up((int)m, 1);
+                exc = lane == 0 ? carry : exc;
+                if (__ballot(k1 != 0u && k1 < exc) != 0ull)
+                    failed = true;   /* (uniform) the sectors fall inside the tile */
+                fk[h] = m;
+                carry = (unsigned)__builtin_amdgcn_readlane((int)m, 63);
+                const unsigned sinc = urf_wave_scan_add(sc) + total;
+                sbase_h[h] = sinc - sc;
+                total = (unsigned)__builtin_amdgcn_readlane((int)sinc, 63);
+            }
+            for (unsigned k0 = 0; k0 <= K; k0 += 64u) {
+                const unsigned k = k0 + lane;
+                unsigned cnt = 0;   /* number of steps whose filled-in key + 1 is < k + 1 (the keys do not fall: a count per register adds up) */
+#pragma unroll
+                for (unsigned h = 0; h < NH; h++) {
+                    unsigned lo = 0;
+#pragma unroll
+                    for (unsigned st = 32u; st > 0; st >>= 1) {
+                        const unsigned v = (unsigned)__shfl((int)fk[h], (int)(lo + st - 1u));
+                        lo += v < k + 1u ? st : 0u;
+                    }
+                    const unsigned v = (unsigned)__shfl((int)fk[h], (int)lo);
+                    lo += (lo == 63u && v < k + 1u) ? 1u : 0u;
+                    cnt += lo;
+                }
+                unsigned so = total;
+#pragma unroll
+                for (unsigned h = 0; h < NH; h++) {
+                    const unsigned v = (unsigned)__shfl((int)sbase_h[h], (int)(cnt & 63u));
+                    so = (cnt >> 6) == h ? v : so;
+                }
+                if (k <= K)
+                    a.tsoff[row * (K + 1) + k] = (uint16_t)so;
+            }
+        }
+        if (STAR && STEPS == 32u) {
             /* sector k starts with the first step whose sector is >= k (urf_split_holey's construction: the steps' keys
              * with the empty steps filled in from the left must not fall; bisection over the 32 of them) */
             const unsigned k1 = (lane < URF_FRONT_STEPS && (unsigned)stepkey_v != URF_SEC_NONE) ? (unsigned)stepkey_v + 1u : 0u;
@@ -429,13 +508,16 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
         tstar = 0;
         stepkey_v = (int)URF_SEC_NONE;
         stepcnt_v = 0;
+        stepkey_w = (int)URF_SEC_NONE;
+        stepcnt_w = 0;
     };
 
     /* The points arrive four firings ahead, in four register sets that are refilled as soon as they have been used: no
      * copies between sets (a copy waits for its source), every wait is for a load issued three firings ago. */
     float px[4], py[4], pz[4];
     auto ld = [&](const unsigned j, const unsigned f) {
-        const unsigned i = f * 64u + lane, o = i < len ? i : len - 1u;   /* (a lane behind the scan's end: some point of the scan, never looked at) */
+        /* (a lane behind the scan's end, a lane without a laser: one point of the scan for all of them, never looked at) */
+        const unsigned i = f * L + lane, o = ((L == 64u || lane < L) && i < len) ? i : len - 1u;
         px[j] = gx[o];
         py[j] = gy[o];
         pz[j] = gz[o];
@@ -457,8 +539,10 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
                 step(std::integral_constant<unsigned, 1u>{}, f + j, px[j], py[j], pz[j]);
             ld(j, f + j + 4u);
         }
-        if (((f + 4u) % URF_FRONT_STEPS) == 0u || f + 4u >= F1) {   /* (uniform) the tile is complete */
-            tile_end(f / URF_FRONT_STEPS);
+        if (L != 64u && (((f + 4u) & 31u) == 0u || f + 4u >= F1))   /* (uniform) */
+            pres_end(f >> 5);
+        if (((f + 4u) % STEPS) == 0u || f + 4u >= F1) {   /* (uniform) the tile is complete */
+            tile_end(f / STEPS);
             if (failed_m != 0ull || __ballot(failed | overflow) != 0ull) {   /* (uniform) */
                 a.front_ok[s] = 0u;
                 if (ok == URF_FRONT_ROWS)
@@ -485,7 +569,7 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
             const unsigned what = (use_z ? URF_FC_EDGE_Z : 0u) | ((use_x && e >= 2u) ? URF_FC_EDGE_X : 0u);
             if (ncb > URF_FRONT_CBUF - 64u)
                 urf_front_flush(a, s, cbuf, ncb, overflow);
-            urf_front_push(cbuf, ncb, in && what != 0u, (fr[e] + Fs) * 64u + lane, what);
+            urf_front_push(cbuf, ncb, in && what != 0u, (fr[e] + Fs) * L + lane, what);
         }
     }
     urf_front_flush(a, s, cbuf, ncb, overflow);
@@ -503,16 +587,26 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
     }
 }
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT_WAVES, URF_FRONT_WAVES))) void k_front(urf_kargs a, urf_dev_params dp)
+template <unsigned L>
+__device__ __forceinline__ void urf_front_kernel(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
 {
-    __shared__ urf_u2 cbuf[URF_FRONT_CBUF];
     if (!dp.p.star_shaped_method)
-        urf_front_body<false, false>(a, dp, cbuf);
+        urf_front_body<false, false, L>(a, dp, cbuf);
     else if (!dp.p.starbeam_filter)
-        urf_front_body<true, false>(a, dp, cbuf);
+        urf_front_body<true, false, L>(a, dp, cbuf);
     else
-        urf_front_body<true, true>(a, dp, cbuf);
+        urf_front_body<true, true, L>(a, dp, cbuf);
 }
+/* one kernel per laser count, each under a name of its own (tools/kernel_resources.py lists kernels by their base identifier) */
+#define URF_FRONT_KERNEL(name, L)                                                                                                             \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT_WAVES, URF_FRONT_WAVES))) void name(urf_kargs a, urf_dev_params dp) \
+    {                                                                                                                                         \
+        __shared__ urf_u2 cbuf[URF_FRONT_CBUF];                                                                                               \
+        urf_front_kernel<L>(a, dp, cbuf);                                                                                                     \
+    }
+URF_FRONT_KERNEL(k_front, 64u)
+URF_FRONT_KERNEL(k_front32, 32u)
+URF_FRONT_KERNEL(k_front16, 16u)
 
 /* ------------------------------------------------------------------------- */
 /* k_front_finish                                                              */
@@ -534,27 +628,28 @@ struct urf_finish_shared {
 };
 
 /* firing of the ring point in front of / behind firing f in lane l; 0xffffffff: none */
-__device__ __forceinline__ unsigned urf_front_prev(const unsigned* P, unsigned l, unsigned f)
+/* (P: word (f >> 5) * L + l, L = 1 << lsh lasers per firing) */
+__device__ __forceinline__ unsigned urf_front_prev(const unsigned* P, unsigned lsh, unsigned l, unsigned f)
 {
     unsigned t = f >> 5;
-    unsigned w = P[t * 64u + l] & ((1u << (f & 31u)) - 1u);
+    unsigned w = P[(t << lsh) + l] & ((1u << (f & 31u)) - 1u);
     while (w == 0u) {
         if (t == 0u)
             return 0xffffffffu;
         t--;
-        w = P[t * 64u + l];
+        w = P[(t << lsh) + l];
     }
     return t * 32u + 31u - (unsigned)__clz((int)w);
 }
-__device__ __forceinline__ unsigned urf_front_next(const unsigned* P, unsigned ntiles, unsigned l, unsigned f)
+__device__ __forceinline__ unsigned urf_front_next(const unsigned* P, unsigned lsh, unsigned ntiles, unsigned l, unsigned f)
 {
     unsigned t = f >> 5;
-    unsigned w = (f & 31u) == 31u ? 0u : P[t * 64u + l] & ~((2u << (f & 31u)) - 1u);
+    unsigned w = (f & 31u) == 31u ? 0u : P[(t << lsh) + l] & ~((2u << (f & 31u)) - 1u);
     while (w == 0u) {
         t++;
         if (t >= ntiles)
             return 0xffffffffu;
-        w = P[t * 64u + l];
+        w = P[(t << lsh) + l];
     }
     return t * 32u + (unsigned)__ffs((int)w) - 1u;
 }
@@ -574,6 +669,9 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
     unsigned off, len;
     urf_scan_range(a, s, off, len);
     const unsigned ntiles = (len + URF_TILE - 1) / URF_TILE;
+    /* L lasers per firing: candidate index = firing * L + laser slot (its place in the input), presence words per 32 firings and slot */
+    const unsigned lsh = a.front_lsh, L = 1u << lsh, lm = L - 1u;
+    const unsigned npt = (((len + lm) >> lsh) + 31u) >> 5;   /* (L = 64: ntiles; always npt * L <= ntiles * 64) */
     const unsigned C = (unsigned)dp.p.channels, K = (unsigned)dp.p.sectors;
     const urf_scan_info in = a.info[s];
     if (in.status != URF_OK)
@@ -596,7 +694,7 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
     const urf_u2* const cand = a.front_cand + (size_t)s * a.front_cand_cap;
     const unsigned nc_raw = a.front_ncand[s];
     const unsigned nc = nc_raw < a.front_cand_cap ? nc_raw : a.front_cand_cap;
-    for (unsigned k = tid; k < ntiles * 64u; k += URF_FINISH_THREADS)
+    for (unsigned k = tid; k < npt * L; k += URF_FINISH_THREADS)
         P[k] = a.front_pres[(size_t)s * a.tiles * 64u + k];
     if (tid < URF_FRONT_LANES)
         S.ncurb[tid] = 0;
@@ -615,10 +713,11 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
     {
         constexpr unsigned NP = URF_FINISH_THREADS / 64u;
         const unsigned l = tid & 63u, prt = tid >> 6;
-        const unsigned tq = (ntiles + NP - 1u) / NP, ta = prt * tq < ntiles ? prt * tq : ntiles, tb = ta + tq < ntiles ? ta + tq : ntiles;
+        const unsigned nt = l < L ? npt : 0u;   /* (the lanes from L on hold no laser) */
+        const unsigned tq = (nt + NP - 1u) / NP, ta = prt * tq < nt ? prt * tq : nt, tb = ta + tq < nt ? ta + tq : nt;
         unsigned run = 0;
         for (unsigned t = ta; t < tb; t++)
-            run += (unsigned)__popc(P[t * 64u + l]);
+            run += (unsigned)__popc(P[(t << lsh) + l]);
         S.qsum[prt][l] = run;
         __syncthreads();
         unsigned add = 0, all = 0;
@@ -627,8 +726,8 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
             all += S.qsum[p][l];
         }
         for (unsigned t = ta; t < tb; t++) {
-            B[t * 64u + l] = (uint16_t)add;
-            add += (unsigned)__popc(P[t * 64u + l]);
+            B[(t << lsh) + l] = (uint16_t)add;
+            add += (unsigned)__popc(P[(t << lsh) + l]);
         }
         if (prt == 0)
             S.n[l] = all;
@@ -695,17 +794,17 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
         if (dp.p.x_zero_method)
             for (unsigned e = tid; e < nx; e += URF_FINISH_THREADS) {
                 const urf_u2 cd = chunk[e];
-                const unsigned idx = cd.x, l = idx & 63u, f = idx >> 6;
+                const unsigned idx = cd.x, l = idx & lm, f = idx >> lsh;
                 const unsigned n = S.n[l];
-                const unsigned p = (unsigned)B[(f >> 5) * 64u + l] + (unsigned)__popc(P[(f >> 5) * 64u + l] & ((1u << (f & 31u)) - 1u));
+                const unsigned p = (unsigned)B[((f >> 5) << lsh) + l] + (unsigned)__popc(P[((f >> 5) << lsh) + l] & ((1u << (f & 31u)) - 1u));
                 if (!(p >= 7u && p + 3u < n))
                     continue;
-                unsigned fj = urf_front_prev(P, l, f);
-                fj = urf_front_prev(P, l, fj);
-                unsigned f3 = urf_front_next(P, ntiles, l, f);
-                f3 = urf_front_next(P, ntiles, l, f3);
-                f3 = urf_front_next(P, ntiles, l, f3);
-                const unsigned ij = fj * 64u + l, i3 = f3 * 64u + l;
+                unsigned fj = urf_front_prev(P, lsh, l, f);
+                fj = urf_front_prev(P, lsh, l, fj);
+                unsigned f3 = urf_front_next(P, lsh, npt, l, f);
+                f3 = urf_front_next(P, lsh, npt, l, f3);
+                f3 = urf_front_next(P, lsh, npt, l, f3);
+                const unsigned ij = (fj << lsh) + l, i3 = (f3 << lsh) + l;
                 const float pz = gz[idx], xj = gx[ij], yj = gy[ij], zj = gz[ij], x3 = gx[i3], y3 = gy[i3], z3 = gz[i3];
                 const float nyj = a.newY[p - 2u], ny2 = a.newY[p], ny3 = a.newY[p + 3u];
                 bool heights = true;
@@ -719,9 +818,9 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
         if (dp.p.z_zero_method)
             for (unsigned e = tid; e < nz; e += URF_FINISH_THREADS) {
                 const urf_u2 cd = chunk[2u * CH - 1u - e];
-                const unsigned idx = cd.x, l = idx & 63u, f = idx >> 6;
+                const unsigned idx = cd.x, l = idx & lm, f = idx >> lsh;
                 const unsigned n = S.n[l];
-                const unsigned p = (unsigned)B[(f >> 5) * 64u + l] + (unsigned)__popc(P[(f >> 5) * 64u + l] & ((1u << (f & 31u)) - 1u));
+                const unsigned p = (unsigned)B[((f >> 5) << lsh) + l] + (unsigned)__popc(P[((f >> 5) << lsh) + l] & ((1u << (f & 31u)) - 1u));
                 if (!(p >= 5u && p + 5u < n))
                     continue;
                 unsigned im[5], ip[5];
@@ -729,14 +828,14 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
                     unsigned g = f;
 #pragma unroll
                     for (unsigned k = 0; k < 5; k++) {
-                        g = urf_front_prev(P, l, g);
-                        im[k] = g * 64u + l;
+                        g = urf_front_prev(P, lsh, l, g);
+                        im[k] = (g << lsh) + l;
                     }
                     g = f;
 #pragma unroll
                     for (unsigned k = 0; k < 5; k++) {
-                        g = urf_front_next(P, ntiles, l, g);
-                        ip[k] = g * 64u + l;
+                        g = urf_front_next(P, lsh, npt, l, g);
+                        ip[k] = (g << lsh) + l;
                     }
                 }
                 const bool needz = (cd.y & URF_FC_EDGE_Z) != 0u;   /* (the march has not looked at the heights) */
@@ -810,7 +909,7 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
     const unsigned n_pend = S.n_pend < a.front_cand_cap ? S.n_pend : a.front_cand_cap;
     for (unsigned e = m_from + tid; e < n_pend; e += URF_FINISH_THREADS) {
         const urf_u2 pd = pend[e];
-        const unsigned idx = pd.x, r = S.ring[idx & 63u];
+        const unsigned idx = pd.x, r = S.ring[idx & lm];
         const float px = gx[idx], py = gy[idx];
         const unsigned old = atomicOr(&a.rec[sb + idx], pd.y << URF_REC_FLAG_SHIFT);
         float d2;
@@ -924,7 +1023,7 @@ __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves
 {
     __shared__ unsigned cnt_road, cnt_curb, n_unsure;
     __shared__ unsigned un_idx[URF_LABEL_UNSURE], un_ring[URF_LABEL_UNSURE];
-    __shared__ __attribute__((aligned(8))) uint8_t lab_t[64][40];   /* (row-major scans) [laser][firing of the tile] */
+    __shared__ __attribute__((aligned(8))) uint8_t lab_t[64 * 40];   /* (row-major scans) [laser][firings of the tile + 8]: 64 x 40, 32 x 72, 16 x 136 */
     unsigned s = blockIdx.y, t = blockIdx.x;
     {   /* the tiles of one scan on one XCD (k_label: the scan's window table is fetched by one L2) */
         const unsigned T = gridDim.x, lin = blockIdx.y * T + blockIdx.x;
@@ -944,7 +1043,8 @@ __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves
     if (tbase >= len)
         return;
     const bool rows = ok == URF_FRONT_ROWS;   /* (uniform) the labels go where the points came from: row l, column f */
-    const unsigned F = len >> 6;
+    const unsigned lsh = a.front_lsh, wsh = 11u - lsh;   /* L = 1 << lsh lasers per firing, 1 << wsh firings per tile */
+    const unsigned F = len >> lsh;
     const float *gx, *gy, *gz;
     urf_front_src(a, s, off, ok, gx, gy, gz);
     const unsigned C = (unsigned)dp.p.channels;
@@ -958,16 +1058,17 @@ __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves
     const unsigned bits = ((const uint8_t*)(a.roi_bits + row * URF_FRONT_STEPS))[tid] & in_scan;
     uint8_t* const out = a.labels + off + i0;
     const bool whole = tbase + URF_TILE <= len && ((uintptr_t)(a.labels + off + tbase) & 7u) == 0;   /* (uniform) */
-    /* row-major: the tile's 32 firings x 64 lasers through LDS, then 8 columns of a row per thread (32 bytes per row and tile) */
+    /* row-major: the tile's firings x lasers through LDS, then 8 columns of a row per thread */
     auto store_rows = [&](const unsigned (&lb)[8]) {
-        const unsigned stp = tid >> 3, l0 = (tid & 7u) * 8u;
+        const unsigned RS = (1u << wsh) + 8u;
+        const unsigned stp = (tid * 8u) >> lsh, l0 = (tid * 8u) & ((1u << lsh) - 1u);
 #pragma unroll
         for (unsigned e = 0; e < 8; e++)
-            lab_t[l0 + e][stp] = (uint8_t)lb[e];
+            lab_t[(l0 + e) * RS + stp] = (uint8_t)lb[e];
         __syncthreads();
-        const unsigned l = tid >> 2, c0 = (tid & 3u) * 8u, f0 = t * URF_FRONT_STEPS + c0;
+        const unsigned l = tid >> (wsh - 3u), c0 = (tid & ((1u << (wsh - 3u)) - 1u)) * 8u, f0 = (t << wsh) + c0;
         uint8_t* const o = a.labels + off + (size_t)l * F + f0;
-        const uint8_t* const src = &lab_t[l][c0];
+        const uint8_t* const src = &lab_t[l * RS + c0];
         if (f0 + 8u <= F && ((uintptr_t)o & 7u) == 0) {
             *(uint2*)o = *(const uint2*)src;
         } else {
@@ -1080,7 +1181,7 @@ __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves
         float d2;
         const float az = urf_azimuth(gx[i], gy[i], &d2);
         if (urf_road_test(win + c * URF_DEG_CELLS, az, 0.0f, dummy)) {
-            a.labels[off + (rows ? (size_t)(i & 63u) * F + (i >> 6) : (size_t)i)] = URF_FLAG_ROI | URF_FLAG_RING | (c == 10 ? URF_FLAG_RING10 : 0) | URF_LABEL_ROAD;
+            a.labels[off + (rows ? (size_t)(i & ((1u << lsh) - 1u)) * F + (i >> lsh) : (size_t)i)] = URF_FLAG_ROI | URF_FLAG_RING | (c == 10 ? URF_FLAG_RING10 : 0) | URF_LABEL_ROAD;
             my_road++;
         }
     }

@@ -271,7 +271,8 @@ struct urf_kargs {
     /* the fused front end (urf_front.hpp): scans that arrive firing by firing skip k_split / k_ring / k_label */
     uint32_t* front_ok;         /* [S] 1: the scan has the shape so far (k_ring_table sets it, k_front / k_table_repair clear it); the legacy
                                  * kernels skip a scan whose flag is set, the fused ones a scan whose flag is clear */
-    uint32_t* front_pres;       /* [S][tiles][64] bit j of word (t, l): lane l of firing j of tile t is a ring point */
+    uint32_t* front_pres;       /* [S][tiles * 64] word (f >> 5) * L + l, bit f & 31: laser slot l of firing f is a ring point (L = 1 << front_lsh lasers per
+                                 * firing; for L = 64 that is [S][tiles][64]: a word per tile and lane) */
     unsigned long long* front_maxs; /* [S][tiles][64] per block and lane the largest x*x + y*y of its ring points (binary64 bits) */
     uint32_t* front_lane_ring;  /* [S][64] the ring of lane l (0xffffffff: none yet) */
     uint32_t* front_ring_lane;  /* [S][channels] the lane of ring r */
@@ -280,10 +281,12 @@ struct urf_kargs {
     uint32_t* front_ncand;      /* [S] */
     uint32_t* front_st;         /* [S][URF_FRONT_ST_WORDS] k_front_finish part 1 -> part 2 */
     uint32_t* front_list;       /* [S] the scans whose flag is clear (k_front_collect; star_count[6] = how many): the list-driven legacy kernels' work */
+    uint32_t  front_lsh;        /* log2 of the lasers per firing the fused kernels march with (4, 5, 6: params.channels = 16, 32, 64); point f * L + l is
+                                 * laser slot l of firing f, a tile holds URF_TILE / L firings */
     uint32_t  front_lists;      /* this call launches the legacy kernels list-driven (k_split_list, k_ring_list, k_label_list) */
-    /* row-major organised sweeps (height = the sensor's 64 lasers, width = firings: point l * F + f): front_ok[s] == URF_FRONT_ROWS,
+    /* row-major organised sweeps (height = the sensor's L = 1 << front_lsh lasers, width = firings: point l * F + f): front_ok[s] == URF_FRONT_ROWS,
      * k_transpose writes the firing-order copy the fused kernels read instead of x / y / z, k_label_front stores the labels
-     * where the points came from.  Everything in between is indexed by firing * 64 + laser. */
+     * where the points came from.  Everything in between is indexed by firing * L + laser. */
     uint32_t  front_rows;       /* this call's sequence holds k_rows_probe and k_transpose: k_ring_table may choose the layout (else it only reports
                                  * that it saw such a scan: URF_FLAG_ROWS_SIGHTED, the next call's sequence holds the kernels) */
     uint32_t  front_sight;      /* this call takes the general kernels but k_ring_table still reports a row-major sighting (a batch below mode 1's threshold:

@@ -1321,7 +1321,7 @@ __device__ __forceinline__ void urf_tie_sector_body(const urf_kargs& a, const ur
         for (unsigned i = lane; i < n; i += 64) {
             const unsigned adr = P[i];
             const unsigned sl = (unsigned)a.sslot[sb + adr] & (URF_TILE - 1u);
-            LP[i] = ((sl & 63u) << 16) | ((adr / URF_TILE) * (URF_TILE / 64u) + (sl >> 6));
+            LP[i] = ((sl & ((1u << a.front_lsh) - 1u)) << 16) | ((adr / URF_TILE) * (URF_TILE >> a.front_lsh) + (sl >> a.front_lsh));   /* (laser, firing): L = 1 << front_lsh lasers per firing */
         }
         MEM::sync();
         for (unsigned i = lane; i < n; i += 64) {

@@ -130,12 +130,13 @@ __global__ __launch_bounds__(256) void k_rows_probe(urf_kargs a, urf_dev_params 
     const unsigned s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned off, len;
     urf_scan_range(a, s, off, len);
-    if (len < 128u || (len & 63u) != 0u) {
+    const unsigned lsh = a.front_lsh, L = 1u << lsh;   /* the rows of the cloud: params.channels (64, 32, 16) */
+    if (len < 2u * L || (len & (L - 1u)) != 0u) {
         if (tid == 0)
             a.rows_ok[s] = 0u;
         return;
     }
-    const unsigned F = len >> 6;
+    const unsigned F = len >> lsh;
     volatile unsigned* const alive = &sh_alive;
     if (tid == 0)
         sh_alive = 1u;
@@ -144,6 +145,11 @@ __global__ __launch_bounds__(256) void k_rows_probe(urf_kargs a, urf_dev_params 
     const float tol = 2.0f * dp.p.interval * 0.017453292f;
     for (unsigned g = 0; g < 16u && *alive; g += 4u) {
         const unsigned r0 = wave * 16u + g;
+        if (r0 >= L) {   /* (uniform) a sensor with fewer rows: nothing there */
+            if (lane < 4u)
+                rowv[r0 + lane] = -1.0f;
+            continue;
+        }
         unsigned found = 0;   /* bit q: row r0 + q is settled */
         for (unsigned c0 = 0; c0 < F && found != 15u && *alive; c0 += 64u) {
             float px[4], py[4], pz[4];
@@ -349,7 +355,7 @@ __device__ void urf_ring_table_scan(const urf_kargs& a, const urf_dev_params& dp
      * Tried when the walk's first step (64 points: one row's) has shown at most one ring; given up as soon as the 64 points around
      * a row's first one show a second ring (a sweep in firing order whose first firing lies outside the region of interest). */
     bool rows = false;
-    bool rows_try = first_walk && (a.front || a.front_sight) && C == 64u && len >= 128u && (len & 63u) == 0u;   /* (not k_table_repair's walk: that one follows a failure) */
+    bool rows_try = first_walk && (a.front || a.front_sight) && C == (1u << a.front_lsh) && len >= 2u * C && (len & (C - 1u)) == 0u;   /* (C = 64, 32, 16 rows) */   /* (not k_table_repair's walk: that one follows a failure) */
     if (rows_try && a.front_rows) {
         /* k_rows_probe has found the rows' first points and put them through the reference's insertion: rows_ok[s] - 1 leaders, in row order */
         const unsigned nr = a.rows_ok[s];   /* (uniform) */
@@ -491,7 +497,7 @@ __device__ void urf_ring_table_scan(const urf_kargs& a, const urf_dev_params& dp
         /* The first 64-point step that met a ring: a sweep in firing order shows many at once there (wherever its region of interest
          * begins), a row-major one as many as rows of len / 64 points fit into the step.  A sighting: */
         const unsigned nl = T.first_nl;
-        if (nl != 0u && nl * (len >> 6) <= 63u + (len >> 6)) {   /* nl <= ceil(64 / F) */
+        if (nl != 0u && nl * (len >> a.front_lsh) <= 63u + (len >> a.front_lsh)) {   /* nl <= ceil(64 / F), F = len / rows */
             if (tid == 0)
                 a.flags[URF_FLAG_ROWS_SIGHTED] = 1u;   /* host-visible: the next call's sequence holds k_rows_probe and k_transpose */
             cause |= 4u;   /* (a row-major sweep defeats the look-ahead wherever its region of interest drops a few rows in succession:
