@@ -1,7 +1,8 @@
 """tests/fuzz_organised.py's idea for sensors with fewer lasers: a synthetic sweep of L = 16 or 32 rings in firing order
 (urf_synth_cloud, tie-free or sensor-like) with random drop-outs (single points, whole firings, whole rings, azimuth ranges, runs
 inside a ring), points moved off their ring or their sector, a random region of interest and random detector parameters;
-params.channels = L, as a user of such a sensor sets it.  GPU against oracle B (tests/test_gpu_front_lasers.py)."""
+params.channels = L, as a user of such a sensor sets it.  GPU against oracle B (tests/test_gpu_front_lasers.py).
+Holes here are (0, 0, 0) only; other encodings: sensor_models.py."""
 import numpy as np
 
 import urban_road_filter_amd as u

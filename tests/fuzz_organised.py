@@ -2,7 +2,8 @@
 real data and the random unorganised clouds of tests/fuzz.py never produce: a synthetic 64-ring sweep (urf_synth_cloud, tie-free or
 sensor-like) with random drop-outs (single points, whole firings, whole rings, azimuth ranges, runs inside a ring), points moved off
 their ring or their sector, a random region of interest and random detector parameters.  GPU against oracle B (tests/test_gpu_organised.py,
-tools/fuzz_organised_more.py)."""
+tools/fuzz_organised_more.py).
+Holes here are (0, 0, 0) only; other encodings: sensor_models.py."""
 import numpy as np
 
 import urban_road_filter_amd as u
