@@ -10,6 +10,7 @@ import oracles as O
 import urban_road_filter_amd as u
 from hipmem import DevBuf, hip
 from test_gpu_async import records
+from test_gpu_front import ring_major
 from test_gpu_parity import check_against_b
 
 pytestmark = pytest.mark.gpu
@@ -194,6 +195,39 @@ def test_rerun_of_a_voided_sweep_counts_as_the_rows_latest_submission():
             with pytest.raises(u.UrfError) as e:
                 call()
             assert e.value.code == -7
+
+
+def test_rerun_of_a_fused_sweep_stays_the_sweep_it_was():
+    """One scratch row, a row-major 64 x 256 sweep that the callback path runs through the fused front end (sighted by the first
+    call, fused from the second on).  Reading its ring-sorted results runs it again through the general kernels, as a batch call
+    on its row: it is still the sweep that was waited for, so once another sweep has been submitted on the row the read-backs
+    refuse (URF_ERR_BUSY) until that one has been waited for, and then serve it."""
+    L, W = 64, 256
+    n = L * W
+    p = u.default_params().wide_roi()
+    first, second = ring_major(u.synth_cloud(L, W, 1, 7)), ring_major(u.synth_cloud(L, W, 3, 8))
+    wa, wb = O.run_b(*first, p, debug=True), O.run_b(*second, p, debug=True)
+    assert wa[1]["n_road"] > 0 and wb[1]["n_road"] > 0 and not np.array_equal(wa[0], wb[0])
+    with u.Context(n, 1, params=p) as ctx:
+        fused = []
+        for _ in range(3):
+            lab, _ = ctx.classify_xyz(*first)
+            assert np.array_equal(lab, wa[0])
+            fused.append(ctx.front_scans())
+        print("fused per call:", fused)
+        assert fused[2] == 1, fused
+        road, curb, _ = ctx.ordered_indices(n)         # the rerun through the general kernels
+        assert np.array_equal(road, wa[2]["road_order"]) and np.array_equal(curb, wa[2]["curb_order"])
+        t = ctx.classify_pc2_async(records(*second), n, 32, 0, 4, 8)
+        for call in (lambda: ctx.ordered_indices(n), lambda: ctx.marker_points(), lambda: ctx.read_stage(u.STAGE_QUADRANTS, n)):
+            with pytest.raises(u.UrfError) as e:
+                call()
+            assert e.value.code == -7
+        lab = np.empty(n, np.uint8)
+        ctx.classify_pc2_wait(t, lab)
+        assert np.array_equal(lab, wb[0])
+        road, curb, _ = ctx.ordered_indices(n)
+        assert np.array_equal(road, wb[2]["road_order"]) and np.array_equal(curb, wb[2]["curb_order"])
 
 
 def test_classify_batch_pc2_row_major_and_firing_order_take_the_fused_kernels():

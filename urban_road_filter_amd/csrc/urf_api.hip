@@ -100,7 +100,7 @@ struct __attribute__((visibility("hidden"))) urf_policy {
     bool slot_lists = false, slot_nan = false, slot_ties = false;
     /* the fused front end (urf_front.hpp, urf_set_front_mode): 0 never, 1 batches of at least URF_FRONT_MIN_SCANS scans (default), 2 every
      * batch call it applies to.  After a read-back of ring-sorted results the context keeps to the general kernels (want_ring_sorted,
-     * last_row_intact). */
+     * last_call). */
     int front_mode = 1;
     uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
     bool want_ring_sorted = false;
@@ -154,7 +154,7 @@ struct __attribute__((visibility("hidden"))) urf_policy {
         return false;
     }
     /* The launch decisions of one call (a.tiles, a.capture, a.n_scans set): slot, a sweep of the callback path; general_only, no fused
-     * kernels (last_row_intact). */
+     * kernels (last_call). */
     void plan(urf_kargs& a, const urf_dev_params& dp, bool slot, bool general_only) const
     {
         a.table_lookahead = speculate ? URF_TABLE_LOOKAHEAD : 0u;
@@ -181,6 +181,18 @@ struct __attribute__((visibility("hidden"))) urf_policy {
         a.front_lists = (a.front && !front_direct && !slot) ? 1u : 0u;   /* (the callback path's sequence holds the general kernels as grids anyway) */
         a.front_rows = (a.front && front_rows) ? 1u : 0u;   /* (independent of the two other speculations: the repair kernels come with it) */
     }
+};
+
+/* "The last call", for the entry points that take their input from it (urf_read_stage, urf_ordered_indices, urf_marker_points,
+ * urf_clouds_batch_*): publish_last() is the only writer of the whole record, last_call() the readers' way to it. */
+enum urf_last_kind { URF_LAST_NONE, URF_LAST_SOA, URF_LAST_PC2, URF_LAST_SWEEP };   /* no call yet | the batch entry point | a sweep waited for */
+struct urf_last_call {
+    int kind = URF_LAST_NONE;
+    uint32_t scans = 0;
+    urf_kargs a;                    /* the kernel arguments and parameters it ran with */
+    urf_dev_params dp;
+    uint32_t row = 0;               /* the scratch row of a.* (a batch call: 0) */
+    uint64_t gen = 0;               /* a sweep: the row's submission number it was (urf_ctx::row_gen) */
 };
 
 struct urf_ctx {
@@ -234,11 +246,8 @@ struct urf_ctx {
     /* Slots that share a scratch row (max_batch < URF_ASYNC_SLOTS) are serialised on the row's stream, and a later
      * sweep overwrites the row.  Labels and summary of every sweep are safe (each slot has its own result buffers,
      * filled in stream order); what reads the ROW afterwards (urf_read_stage / urf_ordered_indices /
-     * urf_marker_points) checks that the sweep published as "the last call" is still the row's latest submission. */
+     * urf_marker_points) checks that the sweep published as "the last call" is still the row's latest submission (last_call). */
     uint64_t row_gen[URF_ASYNC_SLOTS] = { 0, 0, 0, 0 };   /* submissions on the row so far */
-    bool last_is_slot = false;             /* "the last call" is a sweep of the callback path ... */
-    uint32_t last_row = 0;                 /* ... on this row ... */
-    uint64_t last_gen = 0;                 /* ... which was the row's submission number last_gen */
     uint32_t next_ticket = 0;
     /* sized for the largest number of scans asked for so far: scratch of the index-list and marker-point outputs
      * (sstride entries resp. channels x 361 cells per scan) */
@@ -267,21 +276,13 @@ struct urf_ctx {
     /* k_front_finish's first part runs on a stream of its own next to the star-shaped search (side_fork): all three or none */
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    /* last call, for the entry points that read its intermediate results (urf_read_stage,
-     * urf_ordered_indices, urf_marker_points): the kernel arguments and parameters it ran with */
-    uint32_t last_scans = 0;
-    int last_batch = 0;             /* URF_LAST_*: the batch entry point that made the last call (0: none, or a sweep of the callback path) */
-    urf_kargs last_a;
-    urf_dev_params last_dp;
+    urf_last_call last;
     std::string last_error;
     /* host-side cost of the callback path, phase by phase (only the build with the test hooks fills them:
      * URF_HOST_TIMES=1, printed by its benchmark loop; the context's layout is the same in both builds) */
     double ht[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     bool ht_on = false;
 };
-
-#define URF_LAST_SOA 1
-#define URF_LAST_PC2 2
 
 #define URF_HIP(ctx, call)                                                              \
     do {                                                                                \
@@ -490,7 +491,7 @@ extern "C" int urf_create(urf_ctx** out, int device_id, uint32_t max_points, uin
     }
     urf_default_params(&c->params);
     std::memset(&c->k, 0, sizeof(c->k));
-    std::memset(&c->last_a, 0, sizeof(c->last_a));
+    std::memset(&c->last.a, 0, sizeof(c->last.a));
     urf_kargs& k = c->k;
     k.front_cand_cap = max_points / 8 > 4096 ? max_points / 8 : 4096;
     if ((rc = scratch_alloc(c, URF_SCR_ALWAYS)) != URF_OK || (rc = dev_alloc(c, &c->offsets_copy, (size_t)max_batch + 1)) != URF_OK ||
@@ -691,12 +692,12 @@ extern "C" int urf_front_scans(urf_ctx* c, uint32_t* n_fused)
     if (!c || !n_fused)
         return URF_ERR_INVALID_ARG;
     *n_fused = 0;
-    if (!c->last_a.front || c->last_scans == 0)
+    if (!c->last.a.front)   /* (or no call yet) */
         return URF_OK;
     URF_HIP(c, hipSetDevice(c->device));
     URF_HIP(c, hipStreamSynchronize(c->stream));   /* (a sweep of the callback path has been waited for: its row is at rest) */
-    std::vector<uint32_t> ok(c->last_is_slot ? 1u : c->last_scans);
-    URF_HIP(c, hipMemcpy(ok.data(), c->last_a.front_ok, ok.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> ok(c->last.scans);
+    URF_HIP(c, hipMemcpy(ok.data(), c->last.a.front_ok, ok.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (uint32_t v : ok)
         *n_fused += v ? 1u : 0u;
     return URF_OK;
@@ -783,8 +784,9 @@ static int order_row_after_main(urf_ctx* c, uint32_t row, hipStream_t st)
 }
 
 /* ---- the pipeline ---------------------------------------------------------- */
-/* One call of the pipeline: a call of the public batch entry points (stream == nullptr: row 0 onwards, the context's stream, published
- * as "the last call"), or one sweep of the callback path on its row and stream (the caller publishes it when it is waited for). */
+/* One call of the pipeline: a call of the public batch entry points (stream == nullptr: row 0 onwards, the context's stream), or one
+ * sweep of the callback path on its row and stream.  Either caller publishes it as "the last call" (publish_last): a batch call at once,
+ * a sweep when it is waited for. */
 struct urf_call {
     const float *x, *y, *z;
     const uint32_t* offsets;        /* ragged: [n_scans + 1]; else nullptr */
@@ -796,7 +798,7 @@ struct urf_call {
     /* the parameters and capture mode a voided sweep was SUBMITTED with (its rerun, urf_classify_pc2_wait); nullptr / -1: the context's */
     const urf_dev_params* dp = nullptr;
     int capture = -1;
-    bool general_only = false;      /* no fused kernels (last_row_intact) */
+    bool general_only = false;      /* no fused kernels (last_call) */
 };
 
 /* k_front_finish's first part runs on a stream of its own (run_pipeline).  Makes the stream and its two events once -- all three or none:
@@ -821,8 +823,9 @@ static bool side_fork(urf_ctx* c, hipStream_t st)
     return c->side_stream && hipEventRecord(c->ev_fork, st) == hipSuccess && hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) == hipSuccess;
 }
 
-/* The launch sequence of one call as the policy plans it (a sweep of the callback path: its arguments and parameters to a_out / dp_out) */
-static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs* a_out = nullptr, urf_dev_params* dp_out = nullptr)
+/* The launch sequence of one call as the policy plans it; the arguments and parameters it ran with go to a_out / dp_out, last of all and
+ * only for a call that succeeded and was not empty (call.dp may point at dp_out, the call's values may come from a_out: the two reruns) */
+static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_dev_params& dp_out)
 {
     if (!call.x || !call.y || !call.z || !call.labels)
         return URF_ERR_INVALID_ARG;
@@ -850,7 +853,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs* a_out = nul
         /* the context keeps its own copy: the entry points that look at this call's results later
          * (urf_read_stage, urf_ordered_indices, urf_marker_points) must not depend on the caller
          * keeping d_offsets alive.  Scratch memory is indexed by scan, never by these offsets. */
-        if (call.offsets != c->offsets_copy)   /* (last_row_intact runs the last call again with the copy itself) */
+        if (call.offsets != c->offsets_copy)   /* (last_call runs the last call again with the copy itself) */
             URF_HIP(c, hipMemcpyAsync(c->offsets_copy, call.offsets, ((size_t)n_scans + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         a.offsets = c->offsets_copy;
     }
@@ -995,16 +998,25 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs* a_out = nul
     URF_HIP(c, hipGetLastError());
     if (call.info)
         URF_HIP(c, hipMemcpyAsync(call.info, a.info, (size_t)n_scans * sizeof(urf_scan_info), hipMemcpyDeviceToDevice, st));
-    if (slot) {
-        *a_out = a;
-        *dp_out = dp;
-    } else {
-        c->last_scans = n_scans;
-        c->last_a = a;
-        c->last_dp = dp;
-        c->last_is_slot = false;
-    }
+    a_out = a;
+    dp_out = dp;
     return URF_OK;
+}
+
+static void publish_last(urf_ctx* c, int kind, uint32_t scans, const urf_kargs& a, const urf_dev_params& dp, uint32_t row = 0, uint64_t gen = 0)
+{
+    c->last = urf_last_call{ kind, scans, a, dp, row, gen };
+}
+
+/* a call of the public batch entry points: published after a successful call that was not empty (an empty one leaves the last call as it was) */
+static int classify_batch(urf_ctx* c, int kind, const urf_call& call)
+{
+    urf_kargs a;
+    urf_dev_params dp;
+    const int rc = run_pipeline(c, call, a, dp);
+    if (rc == URF_OK && call.n_scans)
+        publish_last(c, kind, call.n_scans, a, dp);
+    return rc;
 }
 
 extern "C" int urf_classify_batch_soa(urf_ctx* c, const float* d_x, const float* d_y, const float* d_z,
@@ -1012,10 +1024,7 @@ extern "C" int urf_classify_batch_soa(urf_ctx* c, const float* d_x, const float*
 {
     if (!c)
         return URF_ERR_INVALID_ARG;
-    const int rc = run_pipeline(c, urf_call{ d_x, d_y, d_z, nullptr, n_per_scan, n_per_scan, n_scans, d_labels, d_info });
-    if (rc == URF_OK && n_scans)
-        c->last_batch = URF_LAST_SOA;
-    return rc;
+    return classify_batch(c, URF_LAST_SOA, urf_call{ d_x, d_y, d_z, nullptr, n_per_scan, n_per_scan, n_scans, d_labels, d_info });
 }
 
 extern "C" int urf_classify_batch_soa_ragged(urf_ctx* c, const float* d_x, const float* d_y, const float* d_z,
@@ -1024,10 +1033,7 @@ extern "C" int urf_classify_batch_soa_ragged(urf_ctx* c, const float* d_x, const
 {
     if (!c || !d_offsets)
         return URF_ERR_INVALID_ARG;
-    const int rc = run_pipeline(c, urf_call{ d_x, d_y, d_z, d_offsets, 0, max_len, n_scans, d_labels, d_info });
-    if (rc == URF_OK && n_scans)
-        c->last_batch = URF_LAST_SOA;
-    return rc;
+    return classify_batch(c, URF_LAST_SOA, urf_call{ d_x, d_y, d_z, d_offsets, 0, max_len, n_scans, d_labels, d_info });
 }
 
 static int ensure_soa_staging(urf_ctx* c)
@@ -1064,10 +1070,7 @@ static int classify_batch_pc2(urf_ctx* c, const uint8_t* d_data, const uint32_t*
     if (n_total)
         hipLaunchKernelGGL(k_pc2_to_soa, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, c->stream, d_data,
                            (unsigned long long)n_total, point_step, off_x, off_y, off_z, c->sx.p, c->sy.p, c->sz.p);
-    rc = run_pipeline(c, urf_call{ c->sx.p, c->sy.p, c->sz.p, d_offsets, n_per_scan, max_len, n_scans, d_labels, d_info });
-    if (rc == URF_OK)
-        c->last_batch = URF_LAST_PC2;
-    return rc;
+    return classify_batch(c, URF_LAST_PC2, urf_call{ c->sx.p, c->sy.p, c->sz.p, d_offsets, n_per_scan, max_len, n_scans, d_labels, d_info });
 }
 
 extern "C" int urf_classify_batch_pc2(urf_ctx* c, const uint8_t* d_data, uint32_t n_per_scan, uint32_t n_scans,
@@ -1220,9 +1223,8 @@ static int slot_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t n_points, uint3
         hipLaunchKernelGGL(k_pc2_to_soa, dim3((n_points + 255) / 256), dim3(256), 0, st, sl.d_raw.p, (unsigned long long)n_points,
                            point_step, off_x, off_y, off_z, sx, sy, sz);
     }
-    /* (dp_in may point at sl.cap_dp: run_pipeline copies it before it writes dp_out, and writes a_out / dp_out only on success) */
     const int rc = run_pipeline(c, urf_call{ sx, sy, sz, nullptr, n_points, n_points, 1, sl.d_labels.p, nullptr, row, st, dp_in, capture_in },
-                                &sl.cap_a, &sl.cap_dp);
+                                sl.cap_a, sl.cap_dp);
     if (rc != URF_OK)
         return rc;
     URF_HIP(c, hipMemcpyAsync(sl.h_labels.p, sl.d_labels.p, n_points, hipMemcpyDeviceToHost, st));
@@ -1392,15 +1394,8 @@ extern "C" int urf_classify_pc2_wait(urf_ctx* c, uint32_t ticket, uint8_t* label
             return rc;
         }
     }
-    /* only now is the sweep "the last call": urf_read_stage / urf_marker_points / urf_ordered_indices look at
-     * its scratch row, which stays untouched until the slot (or a batch call) is used again */
-    c->last_scans = 1;
-    c->last_a = sl.cap_a;
-    c->last_dp = sl.cap_dp;
-    c->last_is_slot = true;
-    c->last_batch = 0;
-    c->last_row = slot_row(c, sl);
-    c->last_gen = sl.gen;
+    /* only now is the sweep "the last call": its scratch row stays untouched until the row (or a batch call) is used again */
+    publish_last(c, URF_LAST_SWEEP, 1, sl.cap_a, sl.cap_dp, slot_row(c, sl), sl.gen);
     if (labels_out)
         std::memcpy(labels_out, sl.h_labels.p, sl.n_points);
     if (info)
@@ -1445,29 +1440,45 @@ extern "C" int urf_classify_pc2(urf_ctx* c, const uint8_t* data, uint32_t n_poin
     return urf_classify_pc2_wait(c, ticket, labels_out, info);
 }
 
-/* urf_read_stage / urf_ordered_indices / urf_marker_points read the scratch ROW of the last call.  For a sweep of the
- * callback path that row is only intact while no later sweep has been submitted on it (slots that share a row:
- * max_batch < URF_MAX_IN_FLIGHT and more sweeps in flight than rows). */
-static int last_row_intact(urf_ctx* c)
+/* Step 1 of last_call(), on its own for the entry points that check sizes of theirs against the call before any HIP call: a last call
+ * exists, holds `scan` (a batch read-out: 0) and is of `kind` where that matters (urf_clouds_batch_*).  nullptr: URF_ERR_INVALID_ARG. */
+static const urf_last_call* last_valid(urf_ctx* c, uint32_t scan = 0, int kind = URF_LAST_NONE)
 {
-    if (c->last_is_slot && c->row_gen[c->last_row] != c->last_gen) {
+    const urf_last_call& l = c->last;
+    if (kind != URF_LAST_NONE && l.kind != kind) {
+        c->last_error = l.kind == URF_LAST_SOA || l.kind == URF_LAST_PC2 ? "the last batch call was of the other kind (SoA / PointCloud2)"
+                                                                         : "the last classify call was no batch call (urf_classify_batch_*)";
+        return nullptr;
+    }
+    return scan < l.scans && l.a.labels ? &l : nullptr;   /* (no call yet: no scans) */
+}
+
+/* The readers' way to the last call and its scratch ROW: valid, on the context's device, the row intact and ring-sorted, the context's
+ * stream behind the sweeps in flight.  A sweep's row is only intact while no later sweep has been submitted on it (slots that share a
+ * row: max_batch < URF_MAX_IN_FLIGHT and more sweeps in flight than rows). */
+static int last_call(urf_ctx* c, uint32_t scan, const urf_last_call*& out)
+{
+    urf_last_call& l = c->last;
+    if (!(out = last_valid(c, scan)))
+        return URF_ERR_INVALID_ARG;
+    URF_HIP(c, hipSetDevice(c->device));
+    if (l.kind == URF_LAST_SWEEP && c->row_gen[l.row] != l.gen) {
         c->last_error = "the scratch row of the sweep waited for last has been resubmitted (create the context with max_batch >= "
                         "the number of sweeps in flight, or read its intermediate results before submitting on its row again)";
         return URF_ERR_BUSY;
     }
-    if (c->last_a.front) {
+    int rc = URF_OK;
+    if (l.a.front) {
         /* the last call went through the fused front end (urf_front.hpp), which keeps no ring-sorted copies: once more on its row through
          * the general kernels, as a batch call with every repair kernel in the sequence (same inputs -- a batch caller's arrays must still
          * be alive, a sweep of the callback path is still in its slot's device buffer and its row has not been resubmitted (checked
          * above) --, same parameters, same labels), and the context stays with them: a caller that reads ring-sorted results pays for
-         * them once, not per call */
+         * them once, not per call.  Only the record's arguments and parameters change: a sweep stays the sweep it was. */
         c->pol.set(c->pol.want_ring_sorted, true);
-        const urf_kargs a = c->last_a;
-        const urf_dev_params dp = c->last_dp;
-        return run_pipeline(c, urf_call{ a.x, a.y, a.z, a.offsets, a.n_per_scan, a.max_len, a.n_scans, a.labels, nullptr,
-                                         c->last_is_slot ? c->last_row : 0u, nullptr, &dp, (int)a.capture, true });
+        rc = run_pipeline(c, urf_call{ l.a.x, l.a.y, l.a.z, l.a.offsets, l.a.n_per_scan, l.a.max_len, l.a.n_scans, l.a.labels, nullptr, l.row,
+                                       nullptr, &l.dp, (int)l.a.capture, true }, l.a, l.dp);
     }
-    return URF_OK;
+    return rc != URF_OK ? rc : order_after_slots(c);
 }
 
 /* ---- index-set and marker outputs: every scan of a batch in one launch sequence ------------- */
@@ -1512,19 +1523,15 @@ static int ensure_order_scratch(urf_ctx* c, uint32_t n_scans)
     return grow(c, c->ord_cls, (size_t)n_scans * URF_MAX_CHANNELS * 2, c->stream);
 }
 
-/* scans [s0, s0 + n) of the last classify call, lists of `stride` entries per scan on the device */
-static int launch_ordered(urf_ctx* c, uint32_t s0, uint32_t n, uint32_t* d_road, uint32_t* d_curb, uint32_t* d_r10,
+/* scans [s0, s0 + n) of the last classify call (l: from last_call), lists of `stride` entries per scan on the device */
+static int launch_ordered(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t n, uint32_t* d_road, uint32_t* d_curb, uint32_t* d_r10,
                           uint32_t stride, uint32_t* d_counts)
 {
-    int rc = last_row_intact(c);
-    if (rc == URF_OK)
-        rc = order_after_slots(c);
-    if (rc == URF_OK)
-        rc = ensure_order_scratch(c, n);
+    const int rc = ensure_order_scratch(c, n);
     if (rc != URF_OK)
         return rc;
-    const urf_kargs a = c->last_a;   /* the call's own arguments and parameters, whatever was set since */
-    const urf_dev_params dp = c->last_dp;
+    const urf_kargs& a = l.a;   /* the call's own arguments and parameters, whatever was set since */
+    const urf_dev_params& dp = l.dp;
     hipLaunchKernelGGL(k_ring_order, dim3((unsigned)dp.p.channels, n), dim3(256), (2 * (size_t)a.tiles + 1) * sizeof(unsigned), c->stream, a, dp,
                        s0, c->ord_keys.p, c->ord_pos.p, c->ord_cls.p);
     hipLaunchKernelGGL(k_ordered_lists, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, c->ord_pos.p, c->ord_cls.p, d_road,
@@ -1536,29 +1543,29 @@ static int launch_ordered(urf_ctx* c, uint32_t s0, uint32_t n, uint32_t* d_road,
 extern "C" int urf_ordered_indices_batch(urf_ctx* c, uint32_t* d_road, uint32_t* d_curb, uint32_t* d_ring10, uint32_t stride,
                                          uint32_t* d_counts)
 {
-    if (!c || !d_counts || c->last_scans == 0 || !c->last_a.labels || stride < c->last_a.max_len)
+    const urf_last_call* l = c ? last_valid(c) : nullptr;
+    if (!l || !d_counts || stride < l->a.max_len)
         return URF_ERR_INVALID_ARG;
-    URF_HIP(c, hipSetDevice(c->device));
-    return launch_ordered(c, 0, c->last_scans, d_road, d_curb, d_ring10, stride, d_counts);
+    const int rc = last_call(c, 0, l);
+    return rc != URF_OK ? rc : launch_ordered(c, *l, 0, l->scans, d_road, d_curb, d_ring10, stride, d_counts);
 }
 
 extern "C" int urf_ordered_indices(urf_ctx* c, uint32_t scan, uint32_t* road, uint32_t* curb, uint32_t* ring10,
                                    uint32_t* counts)
 {
-    if (!c || !counts || scan >= c->last_scans || !c->last_a.labels)
+    if (!c || !counts)
         return URF_ERR_INVALID_ARG;
-    URF_HIP(c, hipSetDevice(c->device));
     const size_t mp = c->sstride;
-    const int grc = grow(c, c->ord_lists, mp * 3 + 4);
-    if (grc != URF_OK)
-        return grc;
+    const urf_last_call* l;
+    int rc;
+    if ((rc = last_call(c, scan, l)) != URF_OK || (rc = grow(c, c->ord_lists, mp * 3 + 4)) != URF_OK)
+        return rc;
     uint32_t* d_road = c->ord_lists.p;
     uint32_t* d_curb = d_road + mp;
     uint32_t* d_r10 = d_curb + mp;
     uint32_t* d_cnt = d_r10 + mp;
     hipStream_t st = c->stream;
-    const int rc = launch_ordered(c, scan, 1, d_road, d_curb, d_r10, (uint32_t)mp, d_cnt);
-    if (rc != URF_OK)
+    if ((rc = launch_ordered(c, *l, scan, 1, d_road, d_curb, d_r10, (uint32_t)mp, d_cnt)) != URF_OK)
         return rc;
     uint32_t h[3] = { 0, 0, 0 };
     URF_HIP(c, hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -1590,14 +1597,10 @@ static int ensure_clouds_scratch(urf_ctx* c, uint32_t n_scans, uint32_t stride, 
 static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, urf_point_xyzi* d_records, uint64_t capacity,
                         uint32_t* d_counts, uint64_t* d_offsets)
 {
-    if (!d_counts || !d_offsets || (order != URF_ORDER_INPUT && order != URF_ORDER_REFERENCE))
+    const urf_last_call* l;
+    if (!d_counts || !d_offsets || (order != URF_ORDER_INPUT && order != URF_ORDER_REFERENCE) || !(l = last_valid(c, 0, kind)))
         return URF_ERR_INVALID_ARG;
-    if (c->last_is_slot || c->last_batch != kind || c->last_scans == 0 || !c->last_a.labels) {
-        c->last_error = c->last_batch == 0 ? "the last classify call was no batch call (urf_classify_batch_*)"
-                                           : "the last batch call was of the other kind (SoA / PointCloud2)";
-        return URF_ERR_INVALID_ARG;
-    }
-    const uint32_t S = c->last_scans, max_len = c->last_a.max_len, stride = max_len ? max_len : 1u;
+    const uint32_t S = l->scans, max_len = l->a.max_len, stride = max_len ? max_len : 1u;
     if (d_records && capacity < 3ull * S * max_len)
         return URF_ERR_CAPACITY;
     URF_HIP(c, hipSetDevice(c->device));
@@ -1606,14 +1609,15 @@ static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, ur
     if (rc != URF_OK)
         return rc;
     if (ref) {   /* urf_ordered_indices_batch's kernels (after a fused call: the documented rerun through the general kernels) */
-        uint32_t* const l = c->cl_lists.p;
-        rc = launch_ordered(c, 0, S, l, l + (size_t)S * stride, l + 2 * (size_t)S * stride, stride, l + 3 * (size_t)S * stride);
+        uint32_t* const o = c->cl_lists.p;
+        if ((rc = last_call(c, 0, l)) == URF_OK)
+            rc = launch_ordered(c, *l, 0, S, o, o + (size_t)S * stride, o + 2 * (size_t)S * stride, stride, o + 3 * (size_t)S * stride);
     } else {
-        rc = order_after_slots(c);   /* cl_tiles is the context's */
+        rc = order_after_slots(c);   /* cl_tiles is the context's; the input order needs nothing ring-sorted of the row */
     }
     if (rc != URF_OK)
         return rc;
-    const urf_kargs& a = c->last_a;   /* (after a rerun: the same labels, inputs and offsets) */
+    const urf_kargs& a = l->a;   /* (after a rerun: the same labels, inputs and offsets) */
     src.labels = a.labels;
     src.offsets = a.offsets;
     src.info = a.info;
@@ -1660,9 +1664,9 @@ extern "C" int urf_clouds_batch_soa(urf_ctx* c, const float* d_intensity, int or
         return URF_ERR_INVALID_ARG;
     urf_clouds_args src{};
     src.src = URF_SRC_SOA;
-    src.x = (const unsigned*)c->last_a.x;
-    src.y = (const unsigned*)c->last_a.y;
-    src.z = (const unsigned*)c->last_a.z;
+    src.x = (const unsigned*)c->last.a.x;
+    src.y = (const unsigned*)c->last.a.y;
+    src.z = (const unsigned*)c->last.a.z;
     src.in = (const unsigned*)d_intensity;
     src.oi = -1;
     return clouds_batch(c, URF_LAST_SOA, src, order, d_records, capacity, d_counts, d_offsets);
@@ -1692,15 +1696,15 @@ extern "C" int urf_clouds_batch_pc2(urf_ctx* c, const uint8_t* d_data, uint32_t 
     return clouds_batch(c, URF_LAST_PC2, src, order, d_records, capacity, d_counts, d_offsets);
 }
 
-static int launch_markers(urf_ctx* c, uint32_t s0, uint32_t n, float* d_pts, uint32_t* d_counts)
+static int launch_markers(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t n, float* d_pts, uint32_t* d_counts)
 {
     const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;
     int rc;
-    if ((rc = last_row_intact(c)) != URF_OK || (rc = order_after_slots(c)) != URF_OK || (rc = grow(c, c->mk_d, n * cells, c->stream)) != URF_OK ||
-        (rc = grow(c, c->mk_pos, n * cells, c->stream)) != URF_OK || (rc = grow(c, c->mk_red, n * (cells + URF_MAX_CHANNELS), c->stream)) != URF_OK)
+    if ((rc = grow(c, c->mk_d, n * cells, c->stream)) != URF_OK || (rc = grow(c, c->mk_pos, n * cells, c->stream)) != URF_OK ||
+        (rc = grow(c, c->mk_red, n * (cells + URF_MAX_CHANNELS), c->stream)) != URF_OK)
         return rc;
-    const urf_kargs a = c->last_a;
-    const urf_dev_params dp = c->last_dp;
+    const urf_kargs& a = l.a;
+    const urf_dev_params& dp = l.dp;
     uint8_t* const mk_lit = c->mk_red.p + n * cells;
     hipLaunchKernelGGL(k_marker_ring, dim3((unsigned)dp.p.channels, n), dim3(256), (2 * (size_t)a.tiles + 1) * sizeof(unsigned), c->stream, a, dp, s0,
                        c->mk_d.p, c->mk_pos.p, c->mk_red.p, mk_lit);
@@ -1713,23 +1717,24 @@ static int launch_markers(urf_ctx* c, uint32_t s0, uint32_t n, float* d_pts, uin
 
 extern "C" int urf_marker_points_batch(urf_ctx* c, float* d_pts, uint32_t* d_counts)
 {
-    if (!c || !d_pts || !d_counts || c->last_scans == 0 || !c->last_a.labels)
+    if (!c || !d_pts || !d_counts)
         return URF_ERR_INVALID_ARG;
-    URF_HIP(c, hipSetDevice(c->device));
-    return launch_markers(c, 0, c->last_scans, d_pts, d_counts);
+    const urf_last_call* l;
+    const int rc = last_call(c, 0, l);
+    return rc != URF_OK ? rc : launch_markers(c, *l, 0, l->scans, d_pts, d_counts);
 }
 
 extern "C" int urf_marker_points(urf_ctx* c, uint32_t scan, float* pts, uint32_t* count)
 {
-    if (!c || !pts || !count || scan >= c->last_scans || !c->last_a.labels)
+    if (!c || !pts || !count)
         return URF_ERR_INVALID_ARG;
-    URF_HIP(c, hipSetDevice(c->device));
-    int rc = grow(c, c->mk_out, URF_DEG_CELLS * 4 + 4);
-    if (rc != URF_OK)
+    const urf_last_call* l;
+    int rc;
+    if ((rc = last_call(c, scan, l)) != URF_OK || (rc = grow(c, c->mk_out, URF_DEG_CELLS * 4 + 4)) != URF_OK)
         return rc;
     hipStream_t st = c->stream;
     unsigned* d_cnt = (unsigned*)(c->mk_out.p + URF_DEG_CELLS * 4);
-    if ((rc = launch_markers(c, scan, 1, c->mk_out.p, d_cnt)) != URF_OK)
+    if ((rc = launch_markers(c, *l, scan, 1, c->mk_out.p, d_cnt)) != URF_OK)
         return rc;
     std::vector<float> h(URF_DEG_CELLS * 4 + 4);
     URF_HIP(c, hipMemcpyAsync(h.data(), c->mk_out.p, h.size() * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -1782,10 +1787,10 @@ static int fetch(urf_ctx* c, std::vector<T>& dst, const T* src, size_t count)
 /* The ring-sorted slots of scan `scan` that hold a point (index relative to the scan's scratch
  * base) and the input index of each, rebuilt on the host from k_split's per-tile tables: tile t
  * fills its first troff[t][C] slots. */
-static int ring_slot_sources(urf_ctx* c, uint32_t scan, uint32_t len, std::vector<uint32_t>& slot, std::vector<uint32_t>& src)
+static int ring_slot_sources(urf_ctx* c, const urf_last_call& l, uint32_t scan, uint32_t len, std::vector<uint32_t>& slot, std::vector<uint32_t>& src)
 {
-    const urf_kargs& k = c->last_a;
-    const unsigned C = (unsigned)c->last_dp.p.channels;
+    const urf_kargs& k = l.a;
+    const unsigned C = (unsigned)l.dp.p.channels;
     const unsigned ntiles = (len + URF_TILE - 1) / URF_TILE;
     std::vector<uint16_t> troff;
     std::vector<uint32_t> rec;
@@ -1804,19 +1809,14 @@ static int ring_slot_sources(urf_ctx* c, uint32_t scan, uint32_t len, std::vecto
 
 extern "C" int urf_read_stage(urf_ctx* c, urf_stage what, uint32_t scan, void* host_dst, size_t bytes)
 {
-    if (!c || !host_dst || scan >= c->last_scans)
+    if (!c || !host_dst)
         return URF_ERR_INVALID_ARG;
-    URF_HIP(c, hipSetDevice(c->device));
-    {
-        const int irc = last_row_intact(c);
-        if (irc != URF_OK)
-            return irc;
-        const int orc = order_after_slots(c);   /* (sweeps still in flight on other rows' streams) */
-        if (orc != URF_OK)
-            return orc;
-    }
+    const urf_last_call* l;
+    int rc = last_call(c, scan, l);
+    if (rc != URF_OK)
+        return rc;
     URF_HIP(c, hipStreamSynchronize(c->stream));
-    const urf_kargs& k = c->last_a;   /* the arguments and parameters of the call whose results are read */
+    const urf_kargs& k = l->a;   /* the arguments and parameters of the call whose results are read */
     uint32_t len;
     if (k.offsets) {
         uint32_t o2[2];
@@ -1827,11 +1827,10 @@ extern "C" int urf_read_stage(urf_ctx* c, urf_stage what, uint32_t scan, void* h
     } else {
         len = k.n_per_scan;
     }
-    const unsigned C = (unsigned)c->last_dp.p.channels;
+    const unsigned C = (unsigned)l->dp.p.channels;
     const size_t sb = (size_t)scan * k.sstride;
     urf_scan_info in;
     URF_HIP(c, hipMemcpy(&in, k.info + scan, sizeof(in), hipMemcpyDeviceToHost));
-    int rc;
     switch (what) {
     case URF_STAGE_VALPHA:
         if (k.capture != 1) return URF_ERR_INVALID_ARG;
@@ -1867,7 +1866,7 @@ extern "C" int urf_read_stage(urf_ctx* c, urf_stage what, uint32_t scan, void* h
         std::memset(host_dst, 0, len * esz);
         if (in.status != URF_OK) return URF_OK;
         std::vector<uint32_t> slot, src;
-        if ((rc = ring_slot_sources(c, scan, len, slot, src)) != URF_OK) return rc;
+        if ((rc = ring_slot_sources(c, *l, scan, len, slot, src)) != URF_OK) return rc;
         const size_t span = (size_t)((len + URF_TILE - 1) / URF_TILE) * URF_TILE;
         if (what == URF_STAGE_DETECT) {
             std::vector<uint32_t> rec;   /* the detector hits of a slot's record */
