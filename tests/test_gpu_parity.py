@@ -183,14 +183,15 @@ def test_ragged_batch_inside_a_larger_buffer(ctx_big):
             assert (L[offs[k] + n:offs[k + 1]] == 0xEE).all()
 
 
-def check_against_b(labels, infos, scans, p):
+def check_against_b(labels, infos, scans, p, n_nan=None):
+    """(n_nan: scan -> its ring points with x == y == 0, whose azimuth is NaN; none anywhere else)"""
     for k, (x, y, z) in enumerate(scans):
         lb, ib, _ = O.run_b(x, y, z, p)
         assert np.array_equal(labels[k], lb), "scan %d" % k
         keys = ("status", "n_roi", "n_rings", "n_ring_pts", "n_road", "n_curb", "n_ring10")
         got = dict(zip(keys, infos[k][:7]))
         assert got == {f: ib[f] for f in keys}, "scan %d" % k
-        assert infos[k][7] == 0, "scan %d: NaN azimuths counted on a sweep without x == y == 0 points" % k
+        assert infos[k][7] == (n_nan or {}).get(k, 0), "scan %d: NaN azimuths counted" % k
 
 
 def test_uniform_batch_of_distinct_scans():
@@ -229,6 +230,67 @@ def test_ragged_batch_with_empty_tiny_and_partial_scans():
         labels, infos = run_batch(ctx, scans, p, ragged=True)
         check_against_b(labels, infos, scans, p)
         assert infos[1][0] == 1 and infos[3][0] == 1 and not labels[3].any()   # URF_TOO_FEW_POINTS, nothing published
+
+
+def test_two_calls_fill_every_work_list():
+    """Six scans that put an entry on each of the eight device work lists (enum urf_list), as one ragged batch on two new contexts,
+    every scan of both calls against oracle B: a list read with another list's length, or an entry appended to the wrong list,
+    leaves a scan's work undone.  64 channels, curbPoints 5, star search on.
+      0  an organised 64-laser sweep with quantised ranges: URF_LIST_TIE, URF_LIST_TIE_POST
+      1  the same sweep shuffled: sectors of many short runs (URF_LIST_STAR_RUNS) -- and, for the rest of its sectors, scattered
+         ones of fewer than 385 points (URF_LIST_STAR_MID)
+      2  late_ring_cloud: the speculative ring table is incomplete
+      3  axis points among the rings of a short sweep (URF_LIST_NAN): half_laser_axis_cloud
+      4  crowded_cloud with a sector of 385..2048 points (URF_LIST_STAR_MID)
+      5  ... of more than 2048 points (URF_LIST_STAR_BIG)
+    Front mode 2: the fused and the general kernels in one call.  Scan 0 takes the fused front end (at least one scan does: asserted), the others are
+    handed back: URF_LIST_FRONT, which the list-driven k_split_list, k_ring_list and k_label_list walk.  URF_LIST_REDO stays EMPTY
+    in this call: k_front marches scan 2 as well and raises table_redo itself at the late ring's points, so the collecting
+    k_table_repair rebuilds the table and lists the scan on URF_LIST_FRONT only.  Seven lists.
+    Front mode 0: no k_front; k_split meets the late ring behind the speculative table's look-ahead, k_table_repair lists the
+    scan on URF_LIST_REDO and k_split_repair splits it again (what test_speculative_ring_table_is_repaired rests on, too); the
+    other lists except URF_LIST_FRONT fill as in the first call, from the full-grid kernels' output.
+    Asserted on the CPU before the calls: the two crowded sectors' populations, a ring point on the axis, a tie of two heights
+    inside a sector, a sector of the shuffled sweep that meets k_index's rule for URF_LIST_STAR_RUNS, the ninth ring.  That the
+    tie lies where the walk looks and that the walk stops at a twin rest on the sweep generator, which
+    tests/test_gpu_sensor_models.py uses for that purpose."""
+    import sensor_models as SM
+    from test_gpu_front import shuffled
+    p = SM.params_for("ideal64")
+    assert p.channels == 64 and p.curbPoints == 5 and p.star_shaped_method
+    sweep = SM.sweep("ideal64", firings=1024, world=1, seed=41, noise=True)
+    scans = [sweep, shuffled(sweep, 4), late_ring_cloud(), half_laser_axis_cloud(1, 3),
+             crowded_cloud(1500), crowded_cloud(6000)]
+    assert all(len(s[0]) <= 70000 for s in scans)
+    dbg = [O.run_b(x, y, z, p, debug=True) for x, y, z in scans]
+    sectors = [st["sector"].astype(np.int64) for _, _, st in dbg]
+
+    def populations(k, per_tile=False):
+        sec, n = sectors[k], len(sectors[k])
+        tile = np.arange(n) // 2048 if per_tile else np.zeros(n, np.int64)
+        cnt = np.zeros((p.sectors, tile.max() + 1), np.int64)
+        np.add.at(cnt, (sec[sec >= 0], tile[sec >= 0]), 1)
+        return cnt
+    assert 385 <= populations(4).max() <= 2048 and populations(5).max() > 2048
+    x, y, z = scans[3]
+    n_axis = int(((x == 0) & (y == 0) & (dbg[3][2]["ring"] >= 0)).sum())   # (on a ring: inside the region of interest)
+    assert n_axis > 0
+    x, y, z = scans[0]
+    star = sectors[0] >= 0
+    r = np.sqrt(x * x + y * y)[star]
+    o = np.lexsort((r, sectors[0][star]))
+    sk, rk, zk = sectors[0][star][o], r[o], z[star][o]
+    assert ((sk[1:] == sk[:-1]) & (rk[1:] == rk[:-1]) & (zk[1:] != zk[:-1])).any()
+    cnt = populations(1, per_tile=True)   # (k_index: more than two runs, at most 64 tiles, at most six points per run)
+    assert cnt.shape[1] <= 64 and (((cnt > 0).sum(1) > 2) & (cnt.max(1) <= 6) & (cnt.sum(1) >= 2)).any()
+    assert dbg[2][1]["n_rings"] == 9
+
+    for mode in (2, 0):   # (a new context each: its first call speculates on the ring table and walks URF_LIST_FRONT)
+        with u.Context(max(len(s[0]) for s in scans), len(scans)) as ctx:
+            ctx.set_front_mode(mode)
+            labels, infos = run_batch(ctx, scans, p, ragged=True)
+            check_against_b(labels, infos, scans, p, n_nan={3: n_axis})
+            assert 1 <= ctx.front_scans() < len(scans) if mode else ctx.front_scans() == 0
 
 
 def test_pointcloud2_layouts(ctx_big):
@@ -586,6 +648,14 @@ def nan_ring_cloud(seed, n_axis, n_near):
     rng = np.random.default_rng(seed)
     base = tuple(a[:16384].copy() for a in O.cfg_cloud("narrow" if seed % 2 else "cfg2", 400 + seed))
     return axis_points(base, rng, n_axis, near=n_near)
+
+
+def half_laser_axis_cloud(seed, n_axis):
+    """nan_ring_cloud's base fills all 64 entries of a 64-channel ring table at the default interval, which leaves its axis points
+    on no ring; this one keeps every second laser of that base, so that the axis points get a table entry of their own."""
+    from fuzz import axis_points
+    base = tuple(np.ascontiguousarray(a[:16384].reshape(-1, 64)[:, ::2]).reshape(-1) for a in O.cfg_cloud("cfg2", 400 + seed))
+    return axis_points(base, np.random.default_rng(seed), n_axis)
 
 
 @pytest.mark.parametrize("seed", range(16))

@@ -49,10 +49,10 @@ struct lazy_buf {
 
 /* Every scratch array of urf_kargs, declared once with its elements per row: X(field, elements).  A row is one scan's slice of
  * each array -- scan r of a batch call, or the sweep of the callback path that runs on row r -- and starts r * elements into it
- * (kargs_row).  Most arrays have max_batch rows; the two per-call counters (SLOTS) have URF_ASYNC_SLOTS, one per sweep in flight,
- * whatever max_batch is.  urf_create allocates SCANS and SLOTS; CAPTURE comes with the first urf_enable_stage_capture, ROW_MAJOR
- * (the firing-order copies of row-major organised sweeps) once such a sweep has been sighted (rows_state_update).  sstride,
- * max_tiles and front_cand_cap are the context's (scratch_walk). */
+ * (kargs_row).  Most arrays have max_batch rows; the two per-call counters (SLOTS: the URF_LIST_COUNT work-list lengths and the
+ * ring-count hint) have URF_ASYNC_SLOTS, one per sweep in flight, whatever max_batch is.  urf_create allocates SCANS and SLOTS;
+ * CAPTURE comes with the first urf_enable_stage_capture, ROW_MAJOR (the firing-order copies of row-major organised sweeps) once
+ * such a sweep has been sighted (rows_state_update).  sstride, max_tiles and front_cand_cap are the context's (scratch_walk). */
 #define URF_SCRATCH_SCANS(X)                                                                                                     \
     X(rx, sstride) X(ry, sstride) X(rz, sstride) X(rec, sstride)                                                                 \
     X(sr, sstride) X(sz, sstride) X(sslot, sstride) X(ssrt16, sstride) X(ssrt, sstride) X(wsg, sstride)                          \
@@ -76,7 +76,7 @@ struct lazy_buf {
     X(front_ok, 1) X(front_pres, max_tiles * 64) X(front_maxs, max_tiles * 64) X(front_lane_ring, 64)                            \
     X(front_ring_lane, URF_MAX_CHANNELS) X(front_cand, front_cand_cap) X(front_all, front_cand_cap) X(front_ncand, 1)             \
     X(front_list, 1) X(front_st, URF_FRONT_ST_WORDS)
-#define URF_SCRATCH_SLOTS(X) X(star_count, 8) X(ring_hint, 1)
+#define URF_SCRATCH_SLOTS(X) X(list_len, URF_LIST_COUNT) X(ring_hint, 1)
 #define URF_SCRATCH_CAPTURE(X) X(valpha, sstride) X(seckey, sstride) X(ringkey, sstride) X(rd2, sstride) X(caz, sstride)
 #define URF_SCRATCH_ROW_MAJOR(X) X(tx, sstride) X(ty, sstride) X(tz, sstride) X(rows_v, 64) X(rows_ok, 1)
 enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR };

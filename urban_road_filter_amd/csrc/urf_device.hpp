@@ -69,6 +69,57 @@ __device__ __forceinline__ bool urf_is_leader(unsigned long long m)
     return (unsigned)__ffsll((long long)m) - 1u == urf_lane();
 }
 
+/* The device work lists (enum urf_list).  The selector is a compile-time constant everywhere and picks both the array and
+ * its length, so no site can pair a list with another list's counter. */
+template <urf_list L>
+__device__ __forceinline__ uint32_t* urf_list_entries(const urf_kargs& a)
+{
+    static_assert(L < URF_LIST_COUNT, "not a work list");
+    switch (L) {
+    case URF_LIST_STAR_MID: return a.star_list_mid;
+    case URF_LIST_STAR_BIG: return a.star_list_big;
+    case URF_LIST_REDO: return a.redo_list;
+    case URF_LIST_NAN: return a.nan_list;
+    case URF_LIST_TIE: return a.tie_list;
+    case URF_LIST_TIE_POST: return a.tie_post;
+    case URF_LIST_FRONT: return a.front_list;
+    case URF_LIST_STAR_RUNS: return a.star_list_runs;
+    case URF_LIST_COUNT: break;
+    }
+    return nullptr;
+}
+template <urf_list L>
+__device__ __forceinline__ unsigned urf_list_len(const urf_kargs& a)   /* (uniform) */
+{
+    return a.list_len[L];
+}
+/* one thread appends one entry; returns its place in the list */
+template <urf_list L>
+__device__ __forceinline__ unsigned urf_list_push(const urf_kargs& a, unsigned entry)
+{
+    const unsigned e = atomicAdd(&a.list_len[L], 1u);
+    urf_list_entries<L>(a)[e] = entry;
+    return e;
+}
+/* the lanes of `m` (= __ballot(on), every lane of the wave active) append their entries in lane order: one atomic per wave */
+template <urf_list L>
+__device__ __forceinline__ void urf_list_push_wave(const urf_kargs& a, unsigned long long m, bool on, unsigned entry)
+{
+    unsigned p = 0;
+    if (m && urf_lane() == 0)
+        p = atomicAdd(&a.list_len[L], (unsigned)__popcll(m));
+    p = __shfl(p, 0);
+    if (on)
+        urf_list_entries<L>(a)[p + urf_popc_below(m)] = entry;
+}
+/* Work item w < urf_list_len * per_entry of a persistent consumer over list x per_entry sub-items (tiles, rings) */
+struct urf_list_item { unsigned entry, sub; };
+template <urf_list L>
+__device__ __forceinline__ urf_list_item urf_list_item_at(const urf_kargs& a, unsigned w, unsigned per_entry)
+{
+    return urf_list_item{ urf_list_entries<L>(a)[w / per_entry], w % per_entry };
+}
+
 /* Wave-wide minimum / maximum of an unsigned value, result in every lane.  DPP row shifts and the
  * gfx9 row broadcasts (the cross-lane data path of the VALU) instead of six ds_bpermute round trips
  * through the LDS crossbar: lanes without a source keep the identity passed as `old`. */

@@ -72,6 +72,21 @@ enum urf_flag {
     URF_FLAG_ROWS_TAKEN = 6,             /* k_ring_table: a scan took the row-major layout */
     URF_FLAG_WORDS = 8                   /* (words 5 and 7 are not used) */
 };
+/* The device work lists (urf_kargs::list_len, indexed by enum urf_list): a producer kernel appends an entry with an atomic, a normally
+ * idle consumer walks the list with persistent workgroups; k_ring_table, the first kernel of a call, zeroes the lengths.  All access
+ * goes through urf_device.hpp's urf_list_* helpers, which pair a list with its length.  An entry is a scan index, scan * sectors +
+ * sector, or scan * channels + ring. */
+enum urf_list {
+    URF_LIST_STAR_MID = 0,    /* star_list_mid: scan * sectors + sector, 385..2048 points or more than two runs; k_index -> k_star_sort_mid */
+    URF_LIST_STAR_BIG = 1,    /* star_list_big: scan * sectors + sector, more than 2048 points; k_index -> k_star_sort_big */
+    URF_LIST_REDO = 2,        /* redo_list: scan whose speculative ring table was incomplete; k_table_repair (not collecting) -> k_split_repair */
+    URF_LIST_NAN = 3,         /* nan_list: scan * channels + ring of a ring whose nan_mask bit was newly set; k_split's tile body -> k_nan_rings */
+    URF_LIST_TIE = 4,         /* tie_list: scan * sectors + sector that carries URF_TIE_FLAG; sort kernels (urf_tie_found) -> k_star_ties, first pass */
+    URF_LIST_TIE_POST = 5,    /* tie_post: scan * sectors + sector that carries URF_TIE_POST; walk kernels (urf_walk_twins) -> k_star_ties, second pass */
+    URF_LIST_FRONT = 6,       /* front_list: scan whose front_ok is clear; k_table_repair (collecting) -> k_split_list, k_ring_list, k_label_list */
+    URF_LIST_STAR_RUNS = 7,   /* star_list_runs: scan * sectors + sector of many short runs (URF_RUNS_FLAG); k_index -> k_star_sort_runs */
+    URF_LIST_COUNT = 8
+};
 /* star_first[] carries flags above the index (a scan holds at most 2^23 points).  Equal planar ranges of a sector are ordered
  * as libstdc++'s std::sort orders them (star_shaped_search.cpp:109), which only k_star_ties knows how to do; the sort kernels
  * order them by position and say what they saw:
@@ -231,16 +246,15 @@ struct urf_kargs {
     uint32_t* sec_off;          /* [S][sectors+1] */
     int32_t*  star_hit;         /* [S][sectors] ring-major position of the sector's curb point; -1 = none or on no ring */
     uint32_t* star_first;       /* [S][sectors] last sorted index the walk may visit */
-    uint32_t* star_list_mid;    /* [S*sectors] work list: scan*sectors+sector of sectors with 385..2048 points */
-    uint32_t* star_list_big;    /* [S*sectors] ... with more than 2048 points */
-    uint32_t* star_list_runs;   /* [S*sectors] ... of many short runs (URF_RUNS_FLAG; star_count[7]) */
-    uint32_t* tie_list;         /* [S*sectors] scan*sectors+sector of the sectors that carry URF_TIE_FLAG (sort kernels -> k_star_ties, first pass) */
-    uint32_t* tie_post;         /* [S*sectors] ... URF_TIE_POST (walk kernels -> second pass) */
-    uint32_t* star_count;       /* [8] lengths of the two lists, [2] = length of redo_list, [3] = length of nan_list, [4] = length of
-                                 * tie_list, [5] = of tie_post, [6] = of front_list (zeroed per call) */
+    uint32_t* star_list_mid;    /* [S*sectors] the work lists (enum urf_list) ... */
+    uint32_t* star_list_big;    /* [S*sectors] */
+    uint32_t* star_list_runs;   /* [S*sectors] */
+    uint32_t* tie_list;         /* [S*sectors] */
+    uint32_t* tie_post;         /* [S*sectors] */
+    uint32_t* list_len;         /* [URF_LIST_COUNT] ... and their lengths in this call */
     uint32_t* table_upto;       /* [S] first point a speculative k_ring_table did not look at (0xffffffff: none) */
     uint32_t* table_redo;       /* [S] k_split: the speculative table of the scan is incomplete */
-    uint32_t* redo_list;        /* [S] such scans (k_table_repair) */
+    uint32_t* redo_list;        /* [S] URF_LIST_REDO */
     uint32_t* table_cause;      /* [S] which rule ended a speculative walk: 1 the quiet look-ahead, 2 the ring-count hint, 3 the rows' first points */
     uint32_t* ring_hint;        /* [1] per scratch row: the largest n_rings of the row's previous call (k_ring_table reads it, k_split
                                  * zeroes it, k_index collects the new one) */
@@ -251,7 +265,7 @@ struct urf_kargs {
     /* rings that hold a point with x == y == 0, whose azimuth is NaN (normally none): the reference's per-ring quicksort
      * parks such a point at an input-order-dependent place and its beam scans stop there -- k_nan_rings reproduces both */
     uint32_t* nan_mask;         /* [S][4] bit c: ring c of the scan holds such a point (k_split's exact pass; zeroed by k_ring_table) */
-    uint32_t* nan_list;         /* [2 * S * channels] scan * channels + ring of the rings whose bit was newly set (k_split -> k_nan_rings) */
+    uint32_t* nan_list;         /* [2 * S * channels] URF_LIST_NAN */
     urf_vis*  vis;              /* [S][channels] what of ring c the beam scans see (k_ring: everything; k_nan_rings; -> k_beams) */
     float*    maxdist;          /* [S][channels] */
     float*    quad;             /* [S][4] */
@@ -280,7 +294,7 @@ struct urf_kargs {
     urf_u2*   front_all;        /* [S][front_cand_cap] (azimuth bits, ring) of every curb point (k_front_finish: rings whose list overflowed) */
     uint32_t* front_ncand;      /* [S] */
     uint32_t* front_st;         /* [S][URF_FRONT_ST_WORDS] k_front_finish part 1 -> part 2 */
-    uint32_t* front_list;       /* [S] the scans whose flag is clear (k_front_collect; star_count[6] = how many): the list-driven legacy kernels' work */
+    uint32_t* front_list;       /* [S] URF_LIST_FRONT */
     uint32_t  front_lsh;        /* log2 of the lasers per firing the fused kernels march with (4, 5, 6: params.channels = 16, 32, 64); point f * L + l is
                                  * laser slot l of firing f, a tile holds URF_TILE / L firings */
     uint32_t  front_lists;      /* this call launches the legacy kernels list-driven (k_split_list, k_ring_list, k_label_list) */

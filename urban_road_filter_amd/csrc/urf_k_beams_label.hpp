@@ -625,9 +625,10 @@ __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves
 /* the scans the fused front end handed back (k_ring_list): persistent workgroups over list x tiles */
 __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) void k_label_list(urf_kargs a, urf_dev_params dp)
 {
-    const unsigned n = a.star_count[6];
+    const unsigned n = urf_list_len<URF_LIST_FRONT>(a);
     for (unsigned w = blockIdx.x; w < n * a.tiles; w += gridDim.x) {
-        urf_label_tile(a, dp, a.front_list[w / a.tiles], w % a.tiles);
+        const urf_list_item it = urf_list_item_at<URF_LIST_FRONT>(a, w, a.tiles);
+        urf_label_tile(a, dp, it.entry, it.sub);
         __syncthreads();   /* the LDS is reused by the next tile */
     }
 }

@@ -810,13 +810,13 @@ __global__ __launch_bounds__(URF_RING_THREADS) __attribute__((amdgpu_waves_per_e
  * that look at a flag and leave. */
 __global__ __launch_bounds__(URF_RING_THREADS) void k_ring_list(urf_kargs a, urf_dev_params dp)
 {
-    const unsigned n = a.star_count[6], C = (unsigned)dp.p.channels;
+    const unsigned n = urf_list_len<URF_LIST_FRONT>(a), C = (unsigned)dp.p.channels;
     for (unsigned w = blockIdx.x; w < n * C; w += gridDim.x) {
-        const unsigned s = a.front_list[w / C], c = w % C;
+        const urf_list_item it = urf_list_item_at<URF_LIST_FRONT>(a, w, C);
         if (dp.p.curbPoints == 5)
-            urf_ring_body<true>(a, dp, c, s);
+            urf_ring_body<true>(a, dp, it.sub, it.entry);
         else
-            urf_ring_body<false>(a, dp, c, s);
+            urf_ring_body<false>(a, dp, it.sub, it.entry);
         __syncthreads();   /* the LDS is reused by the next ring */
     }
 }
@@ -926,12 +926,12 @@ __global__ __launch_bounds__(256) void k_nan_rings(urf_kargs a, urf_dev_params d
     extern __shared__ __attribute__((aligned(16))) unsigned long long sh_pairs[];
     __shared__ int stk[2 * 64];
     __shared__ unsigned n_nan, first_nan, last_nan, claimed;
-    const unsigned n_list = a.star_count[3];
+    const unsigned n_list = urf_list_len<URF_LIST_NAN>(a);
     if (n_list == 0)
         return;
     const unsigned tid = threadIdx.x, C = (unsigned)dp.p.channels;
     for (unsigned w = blockIdx.x; w < n_list; w += gridDim.x) {
-        const unsigned ent = a.nan_list[w], s = ent / C, c = ent % C;
+        const unsigned ent = urf_list_entries<URF_LIST_NAN>(a)[w], s = ent / C, c = ent % C;
         const urf_scan_info in = a.info[s];
         if (in.status != URF_OK || c >= in.n_rings)
             continue;   /* (uniform) */

@@ -503,7 +503,7 @@ __device__ __forceinline__ void urf_split_tile(const urf_kargs& a, const urf_dev
             const unsigned bit = 1u << (ek.ring & 31u);
             const unsigned old = atomicOr(&a.nan_mask[(size_t)s * 4 + (ek.ring >> 5)], bit);
             if (!(old & bit))
-                a.nan_list[atomicAdd(&a.star_count[3], 1u)] = s * C + ek.ring;
+                urf_list_push<URF_LIST_NAN>(a, s * C + ek.ring);
         }
         keyr[li] = (uint8_t)ek.ring;
         keys[li] = (uint16_t)sk;
@@ -801,11 +801,12 @@ __global__ __launch_bounds__(URF_TILE_THREADS) __attribute__((amdgpu_waves_per_e
 __global__ __launch_bounds__(URF_TILE_THREADS) __attribute__((amdgpu_waves_per_eu(URF_SPLIT_WAVES_PER_EU, URF_SPLIT_WAVES_PER_EU))) void k_split_repair(urf_kargs a, urf_dev_params dp)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char sh_split[];
-    const unsigned n = a.star_count[2];
+    const unsigned n = urf_list_len<URF_LIST_REDO>(a);
     for (unsigned w = blockIdx.x; w < n * a.tiles; w += gridDim.x) {
         unsigned tid_i = threadIdx.x;   /* opaque per iteration: nothing thread-derived is hoisted out of the loop (and spilled) */
         asm volatile("" : "+v"(tid_i));
-        urf_split_tile(a, dp, a.redo_list[w / a.tiles], w % a.tiles, sh_split, tid_i);
+        const urf_list_item it = urf_list_item_at<URF_LIST_REDO>(a, w, a.tiles);
+        urf_split_tile(a, dp, it.entry, it.sub, sh_split, tid_i);
         __syncthreads();   /* the LDS carve is reused by the next tile */
     }
 }
@@ -817,11 +818,12 @@ __global__ __launch_bounds__(URF_TILE_THREADS) __attribute__((amdgpu_waves_per_e
     extern __shared__ __attribute__((aligned(16))) unsigned char sh_split[];
     if (blockIdx.x == 0 && threadIdx.x == 0)
         *a.ring_hint = 0;   /* (k_split's duty) */
-    const unsigned n = a.star_count[6];
+    const unsigned n = urf_list_len<URF_LIST_FRONT>(a);
     for (unsigned w = blockIdx.x; w < n * a.tiles; w += gridDim.x) {
         unsigned tid_i = threadIdx.x;
         asm volatile("" : "+v"(tid_i));
-        urf_split_tile(a, dp, a.front_list[w / a.tiles], w % a.tiles, sh_split, tid_i);
+        const urf_list_item it = urf_list_item_at<URF_LIST_FRONT>(a, w, a.tiles);
+        urf_split_tile(a, dp, it.entry, it.sub, sh_split, tid_i);
         __syncthreads();
     }
 }
@@ -1092,26 +1094,11 @@ __device__ __forceinline__ void urf_index_body(const urf_kargs& a, const urf_dev
         const bool runs = (nr & URF_RUNS_FLAG) != 0u && c >= 2 && c <= URF_STAR_SMALL_CAP;
         const bool mid = (c > URF_STAR_SMALL_CAP || (nr > 2 && c >= 2 && !runs)) && c <= URF_STAR_MID_CAP_, big = c > URF_STAR_MID_CAP_;
         const unsigned long long bm = __ballot(mid), bb = __ballot(big), br = __ballot(runs);
-        unsigned pm = 0, pb = 0, pr = 0;
         if ((a.optimistic & URF_OPT_NO_LISTS) && (bm | bb | br) && urf_lane() == 0)
             a.info[s].status = URF_STATUS_REDO_LISTS;   /* nobody sorts the lists in this launch sequence (every writer writes the same value) */
-        if (urf_lane() == 0) {
-            if (bm)
-                pm = atomicAdd(&a.star_count[0], (unsigned)__popcll(bm));
-            if (bb)
-                pb = atomicAdd(&a.star_count[1], (unsigned)__popcll(bb));
-            if (br)
-                pr = atomicAdd(&a.star_count[7], (unsigned)__popcll(br));
-        }
-        pm = __shfl(pm, 0);
-        pb = __shfl(pb, 0);
-        pr = __shfl(pr, 0);
-        if (runs)
-            a.star_list_runs[pr + urf_popc_below(br)] = s * K + k;
-        if (mid)
-            a.star_list_mid[pm + urf_popc_below(bm)] = s * K + k;
-        if (big)
-            a.star_list_big[pb + urf_popc_below(bb)] = s * K + k;
+        urf_list_push_wave<URF_LIST_STAR_MID>(a, bm, mid, s * K + k);
+        urf_list_push_wave<URF_LIST_STAR_BIG>(a, bb, big, s * K + k);
+        urf_list_push_wave<URF_LIST_STAR_RUNS>(a, br, runs, s * K + k);
     }
 }
 

@@ -419,7 +419,7 @@ __device__ __forceinline__ bool urf_star_sort_sector(const urf_kargs& a, const u
  * writes the same value) */
 __device__ __forceinline__ void urf_tie_found(const urf_kargs& a, unsigned s, unsigned sk)
 {
-    a.tie_list[atomicAdd(&a.star_count[4], 1u)] = sk;   /* (one sector in a hundred of a sensor's sweep; none of a benchmark cloud) */
+    urf_list_push<URF_LIST_TIE>(a, sk);   /* (one sector in a hundred of a sensor's sweep; none of a benchmark cloud) */
     if (a.optimistic & URF_OPT_NO_TIES)
         a.info[s].status = URF_STATUS_REDO_TIES;
 }
@@ -474,10 +474,10 @@ __global__ __launch_bounds__(URF_STAR_THREADS) __attribute__((amdgpu_waves_per_e
     __shared__ unsigned long long A[8 * 64];
     __shared__ unsigned cnt[NB + 1];
     __shared__ unsigned sh_first;
-    const unsigned count = a.star_count[7], lane = threadIdx.x;
+    const unsigned count = urf_list_len<URF_LIST_STAR_RUNS>(a), lane = threadIdx.x;
     const unsigned K = (unsigned)dp.p.sectors;
     for (unsigned w = blockIdx.x; w < count; w += gridDim.x) {
-        const unsigned sk = a.star_list_runs[w], s = sk / K, k = sk % K;
+        const unsigned sk = urf_list_entries<URF_LIST_STAR_RUNS>(a)[w], s = sk / K, k = sk % K;
         if (a.info[s].status != URF_OK)
             continue;
         unsigned off, len;
@@ -715,14 +715,14 @@ __global__ __launch_bounds__(URF_STAR_MID_THREADS) __attribute__((amdgpu_waves_p
     __shared__ urf_sort_shared ssh;
     __shared__ unsigned sh_first, sh_nruns, sh_tie;
     const unsigned K = (unsigned)dp.p.sectors;
-    const unsigned count = a.star_count[0];
+    const unsigned count = urf_list_len<URF_LIST_STAR_MID>(a);
     const unsigned tid = threadIdx.x;
     URF_PHASE_ACC_DECL;
     /* The description of a sector (list entry -> size, place, first two runs: two dependent round
      * trips) is fetched one iteration ahead, into scalar registers: at the top of an iteration it
      * has long arrived.  (Fetched on the spot, with the run list built from the per-tile tables by
      * one wave, this cost 7 000 of the 32 000 cycles a sector took.) */
-    auto list_entry = [&](unsigned w) -> unsigned { return w < count ? a.star_list_mid[w] : 0u; };
+    auto list_entry = [&](unsigned w) -> unsigned { return w < count ? urf_list_entries<URF_LIST_STAR_MID>(a)[w] : 0u; };
     auto rfl = [](unsigned v) -> unsigned { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); };
     /* (r5) The list entry is fetched TWO iterations ahead and the description one, and both are taken into scalar registers
      * in front of the tail's stores: loads and stores share one in-order counter on this chip, so a load still pending when
@@ -900,10 +900,10 @@ __global__ __launch_bounds__(256) void k_star_sort_big(urf_kargs a, urf_dev_para
     __shared__ unsigned P[URF_MAX_TILES + 1];   /* the sector's points in the tiles before t */
     __shared__ uint16_t ST[URF_MAX_TILES];      /* first slot of its run in tile t */
     const unsigned K = (unsigned)dp.p.sectors;
-    const unsigned count = a.star_count[1];
+    const unsigned count = urf_list_len<URF_LIST_STAR_BIG>(a);
     const float slope_param = dp.slope_param, kdist = dp.p.kdist_param;
     for (unsigned w = blockIdx.x; w < count; w += gridDim.x) {
-        const unsigned sk = a.star_list_big[w];
+        const unsigned sk = urf_list_entries<URF_LIST_STAR_BIG>(a)[w];
         const unsigned s = sk / K, k = sk % K;
         unsigned off, len;
         urf_scan_range(a, s, off, len);
@@ -1426,9 +1426,10 @@ __global__ __launch_bounds__(64) void k_star_ties(urf_kargs a, urf_dev_params dp
 {
     __shared__ unsigned W[4 * CAP];   /* R, P, LP, RP */
     __shared__ int stk[3 * 64];
-    const unsigned count = a.star_count[POST ? 5 : 4];   /* (uniform; 0 for every tie-free sweep: the kernel returns at once) */
+    constexpr urf_list LIST = POST ? URF_LIST_TIE_POST : URF_LIST_TIE;
+    const unsigned count = urf_list_len<LIST>(a);   /* (uniform; 0 for every tie-free sweep: the kernel returns at once) */
     const unsigned K = (unsigned)dp.p.sectors;
-    const uint32_t* const list = POST ? a.tie_post : a.tie_list;
+    const uint32_t* const list = urf_list_entries<LIST>(a);
     for (unsigned w = blockIdx.x; w < count; w += gridDim.x) {
         {
             const unsigned sk = list[w];
@@ -1731,7 +1732,7 @@ __device__ __forceinline__ void urf_walk_twins(const urf_kargs& a, unsigned s, u
     if (!twin)
         return;
     a.star_first[(size_t)s * K + k] = URF_TIE_POST | hit_i;
-    a.tie_post[atomicAdd(&a.star_count[5], 1u)] = s * K + k;
+    urf_list_push<URF_LIST_TIE_POST>(a, s * K + k);
     if (a.optimistic & URF_OPT_NO_TIES)
         a.info[s].status = URF_STATUS_REDO_TIES;   /* nobody runs the second pass in this launch sequence: once more, with it */
 }

@@ -573,8 +573,8 @@ __device__ void urf_ring_table_scan(const urf_kargs& a, const urf_dev_params& dp
 __global__ __launch_bounds__(URF_TABLE_THREADS) void k_ring_table(urf_kargs a, urf_dev_params dp)
 {
     __shared__ urf_table_shared T;
-    if (blockIdx.x == 0 && threadIdx.x < 8)
-        a.star_count[threadIdx.x] = 0;   /* the call's work-list lengths (k_table_repair, k_index): first kernel of the sequence */
+    if (blockIdx.x == 0 && threadIdx.x < URF_LIST_COUNT)
+        a.list_len[threadIdx.x] = 0;   /* the call's work-list lengths (k_table_repair, k_index): first kernel of the sequence */
     {   /* the fused front end's per-scan state (urf_front.hpp): every scan is a candidate until k_front finds otherwise */
         const unsigned s = blockIdx.x, tid = threadIdx.x;
         if (tid == 0) {
@@ -601,8 +601,7 @@ __global__ __launch_bounds__(URF_TABLE_THREADS) void k_table_repair(urf_kargs a,
      * found incomplete -- are listed for the list-driven legacy kernels; host-visible: was there one, were they all */
     if (collect && threadIdx.x == 0 && (redo || a.front_ok[s] == 0u)) {
         a.front_ok[s] = 0u;
-        const unsigned e = atomicAdd(&a.star_count[6], 1u);
-        a.front_list[e] = s;
+        const unsigned e = urf_list_push<URF_LIST_FRONT>(a, s);
         a.flags[URF_FLAG_FRONT_HANDED_BACK] = 1u;
         if (e + 1u == a.n_scans)
             a.flags[URF_FLAG_FRONT_ALL_HANDED_BACK] = 1u;
@@ -615,7 +614,7 @@ __global__ __launch_bounds__(URF_TABLE_THREADS) void k_table_repair(urf_kargs a,
     urf_ring_table_scan(a, dp, s, 0, T, false);
     if (threadIdx.x == 0) {
         if (!collect)   /* (a collected scan is split by k_split_list) */
-            a.redo_list[atomicAdd(&a.star_count[2], 1u)] = s;
+            urf_list_push<URF_LIST_REDO>(a, s);
         /* host-visible: the context stops using the rule that failed -- not the rows' rule (3: a failure costs that scan the long walk),
          * nor for a scan that looked row-major to a call whose sequence lacked the kernels for it (4) */
         if (cause != 3u && !(cause & 4u))
