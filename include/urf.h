@@ -507,7 +507,13 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * a few long dependent chains, which need many sweeps side by side to fill the device; a context whose sweeps have turned out to be
  * row-major takes the fused kernels at any batch size -- the general kernels are 2.3 x slower on that layout even for four sweeps --
  * and on the callback path: urf_classify_pc2(_async) of a row-major sweep, from the context's second or third such sweep on); 2: every
- * batch call it applies to.  urf_read_stage / urf_ordered_indices* / urf_marker_points* read ring-sorted intermediate
+ * batch call it applies to; 3: as 2 in everything (batch sizes, row-major sweeps, 16 / 32 lasers), and with channels == 64 additionally
+ * curbPoints 1..8 instead of 5 only: one instance of the march and of its finish per value, the detectors' window of 2 * curbPoints + 1
+ * heights in registers; chosen per call from the parameters in force (with curbPoints == 5 mode 3 launches the very kernels of modes 1
+ * and 2).  curbPoints 9..30, and channels 16 / 32 with curbPoints != 5, keep the general kernels in every mode; modes 1 and 2 keep them
+ * for every curbPoints != 5.  urf_set_params starts the captured per-slot sequences of the callback path afresh, so a row-major
+ * context in mode 3 whose curbPoints changes stays on the fused kernels there, with the instance for the new value.  Mode 3 is opt-in:
+ * its times are in profiles/curb_points_bench.json.  urf_read_stage / urf_ordered_indices* / urf_marker_points* read ring-sorted intermediate
  * results: after a call that took the fused front end they first run that call again through the general kernels
  * (the call's INPUT arrays must then still be alive, like its label buffer), and the context stays with the general
  * kernels afterwards (until urf_set_front_mode is called again with a mode other than 0).  A context that has handed a

@@ -384,8 +384,9 @@ class Context:
     def set_front_mode(self, mode):
         """The fused front end for batches of organised sweeps of 64, 32 or 16 lasers per firing (params.channels states the laser
         count; include/urf.h): 0 never; 1 (default) batch calls of at least 192 scans of 64 lasers (16 / 32 lasers: never in mode 1, in either layout or on the callback path; opt in with mode 2)
-        -- a context whose sweeps have turned out to be row-major takes it at any batch size, and on the callback path; 2 every batch
-        call it applies to."""
+        -- row-major sweeps are the exception to the 192: a context whose sweeps have turned out to be row-major takes it at any batch
+        size, and on the callback path; 2 every batch call it applies to; 3 as 2, and with 64 lasers per firing curb_points 1..8 instead
+        of 5 only (9..30, and 16 / 32 lasers with curb_points != 5, keep the general kernels in every mode)."""
         self._check(self._lib.urf_set_front_mode(self._h, int(mode)), "urf_set_front_mode")
 
     def callback_path_preset(self, sequence_bits):

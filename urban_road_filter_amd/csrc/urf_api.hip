@@ -81,6 +81,43 @@ struct lazy_buf {
 #define URF_SCRATCH_ROW_MAJOR(X) X(tx, sstride) X(ty, sstride) X(tz, sstride) X(rows_v, 64) X(rows_ok, 1)
 enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR };
 
+
+/* curbPoints the fused front end has an instance for: 5 in every mode; with urf_set_front_mode(3) and 64 lasers per firing the values of
+ * URF_FRONT_CP_MASK (urf_front.hpp).  16 / 32 lasers and 9..30 keep the general kernels. */
+static bool front_curb_points_ok(int front_mode, unsigned L, int cp)
+{
+    return cp == 5 || (front_mode == 3 && L == 64u && cp >= 1 && cp <= 8 && ((URF_FRONT_CP_MASK >> cp) & 1u) != 0u);
+}
+/* ... and the instances (64 lasers), chosen per call from the parameters in force: 5 is k_front / k_front_finish in every mode */
+using urf_front_fn = void (*)(urf_kargs, urf_dev_params);
+using urf_front_finish_fn = void (*)(urf_kargs, urf_dev_params, unsigned);
+static urf_front_fn front_kernel(int cp)
+{
+    switch (cp) {
+    case 1: return k_front_cp1;
+    case 2: return k_front_cp2;
+    case 3: return k_front_cp3;
+    case 4: return k_front_cp4;
+    case 6: return k_front_cp6;
+    case 7: return k_front_cp7;
+    case 8: return k_front_cp8;
+    }
+    return k_front;
+}
+static urf_front_finish_fn front_finish_kernel(int cp)
+{
+    switch (cp) {
+    case 1: return k_front_finish_cp1;
+    case 2: return k_front_finish_cp2;
+    case 3: return k_front_finish_cp3;
+    case 4: return k_front_finish_cp4;
+    case 6: return k_front_finish_cp6;
+    case 7: return k_front_finish_cp7;
+    case 8: return k_front_finish_cp8;
+    }
+    return k_front_finish;
+}
+
 /* The launch policy: which kernels a call launches, decided on the host from what the kernels of earlier calls reported through the
  * host-mapped flag words (enum urf_flag).  fold() is the only reader of the words: a batch call runs it in run_pipeline, a sweep of the
  * callback path in urf_classify_pc2_async, before either launches anything.  plan() turns the fields into a call's urf_kargs.  Every
@@ -99,9 +136,10 @@ struct __attribute__((visibility("hidden"))) urf_policy {
      * ones (on_redo) */
     bool slot_lists = false, slot_nan = false, slot_ties = false;
     /* the fused front end (urf_front.hpp, urf_set_front_mode): 0 never, 1 batches of at least URF_FRONT_MIN_SCANS scans (default), 2 every
-     * batch call it applies to.  After a read-back of ring-sorted results the context keeps to the general kernels (want_ring_sorted,
+     * batch call it applies to, 3 as 2 and curbPoints 1..8 at 64 lasers (every_batch(): 2 or 3).  After a read-back of ring-sorted results the context keeps to the general kernels (want_ring_sorted,
      * last_call). */
     int front_mode = 1;
+    bool every_batch() const { return front_mode >= 2; }
     uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
     bool want_ring_sorted = false;
     /* k_front hands a scan without the shape back to the general kernels: launched list-driven until a call has done so
@@ -135,7 +173,7 @@ struct __attribute__((visibility("hidden"))) urf_policy {
      * that count: every submission on the callback path, whichever kernels it takes, but only those batch calls below mode 1's threshold
      * that took the fused kernels on its strength. */
     void probation_sweep() { lapse(front_rows); }
-    void probation_batch(const urf_kargs& a) { lapse(a.front && front_mode != 2 && a.n_scans < URF_FRONT_MIN_SCANS); }
+    void probation_batch(const urf_kargs& a) { lapse(a.front && !every_batch() && a.n_scans < URF_FRONT_MIN_SCANS); }
     void lapse(bool counts)
     {
         if (counts && !rows_used && rows_probation && --rows_probation == 0)
@@ -165,18 +203,18 @@ struct __attribute__((visibility("hidden"))) urf_policy {
         a.optimistic = slot ? ((speculate ? URF_OPT_NO_REPAIR : 0u) | (slot_lists ? 0u : URF_OPT_NO_LISTS) | (slot_nan ? 0u : URF_OPT_NO_NAN) |
                                (slot_ties ? 0u : URF_OPT_NO_TIES)) : 0u;
         /* The fused front end: a firing of 64, 32 or 16 lasers (params.channels) = the first lanes of a wave, the detectors' window of
-         * curbPoints == 5 in registers, no stage capture (its values are the general kernels').  Row-major sweeps gain from it at any batch size (the general kernels need 0.64 ms for four such
+         * curbPoints == 5 (mode 3, 64 lasers: 1..8, URF_FRONT_CP_MASK; the instance is chosen per call, front_kernel()) in registers, no stage capture (its values are the general kernels').  Row-major sweeps gain from it at any batch size (the general kernels need 0.64 ms for four such
          * sweeps, the fused ones 0.26, tools/r6_min_scans.py --rows), sweeps in firing order only from 192 per call on, and not as single
          * sweeps of the callback path (tools/r6_single_sweep.py). */
         const unsigned L = (unsigned)dp.p.channels;
         const bool lasers = L == 64u || L == 32u || L == 16u;
         a.front_lsh = L == 16u ? 4u : (L == 32u ? 5u : 6u);
         const bool shape = front_mode != 0 && !front_off && !general_only && !want_ring_sorted && a.capture == 0 &&
-                           lasers && dp.p.curbPoints == 5 && a.tiles <= URF_FRONT_MAX_TILES;
+                           lasers && front_curb_points_ok(front_mode, L, dp.p.curbPoints) && a.tiles <= URF_FRONT_MAX_TILES;
         /* (16 / 32 lasers: nothing below mode 2 until their crossover has been measured -- no batch size, no row-major sighting, no callback path) */
-        const bool small_ok = front_rows && (rows_used || rows_probation > 0) && (L == 64u || front_mode == 2);
-        a.front = (shape && (slot ? small_ok : (front_mode == 2 || small_ok || a.n_scans >= (L == 64u ? URF_FRONT_MIN_SCANS : (L == 32u ? URF_FRONT_MIN_SCANS_32 : URF_FRONT_MIN_SCANS_16))))) ? 1u : 0u;
-        a.front_sight = (shape && !a.front && !front_rows && !rows_oom && (L == 64u || front_mode == 2)) ? 1u : 0u;
+        const bool small_ok = front_rows && (rows_used || rows_probation > 0) && (L == 64u || every_batch());
+        a.front = (shape && (slot ? small_ok : (every_batch() || small_ok || a.n_scans >= (L == 64u ? URF_FRONT_MIN_SCANS : (L == 32u ? URF_FRONT_MIN_SCANS_32 : URF_FRONT_MIN_SCANS_16))))) ? 1u : 0u;
+        a.front_sight = (shape && !a.front && !front_rows && !rows_oom && (L == 64u || every_batch())) ? 1u : 0u;
         a.front_tpb = front_tpb ? front_tpb : (a.n_scans >= URF_FRONT_TPB_SCANS ? URF_FRONT_TPB_LARGE : (a.n_scans >= 16u ? URF_FRONT_TPB_SMALL : 1u));
         a.front_lists = (a.front && !front_direct && !slot) ? 1u : 0u;   /* (the callback path's sequence holds the general kernels as grids anyway) */
         a.front_rows = (a.front && front_rows) ? 1u : 0u;   /* (independent of the two other speculations: the repair kernels come with it) */
@@ -374,7 +412,7 @@ int urf_policy::fold(urf_ctx* c, hipStream_t st)
         set(use_hint, false);
     if (flags[URF_FLAG_FRONT_HANDED_BACK])
         set(front_direct, true);
-    if (flags[URF_FLAG_FRONT_ALL_HANDED_BACK] && front_mode != 2)
+    if (flags[URF_FLAG_FRONT_ALL_HANDED_BACK] && !every_batch())
         set(front_off, true);
     return URF_OK;
 }
@@ -677,7 +715,7 @@ extern "C" double urf_ring_threshold_cot(double angle_deg)
 
 extern "C" int urf_set_front_mode(urf_ctx* c, int mode)
 {
-    if (!c || mode < 0 || mode > 2)
+    if (!c || mode < 0 || mode > 3)
         return URF_ERR_INVALID_ARG;
     if (mode != c->pol.front_mode && mode != 0)   /* (a new start) */
         c->pol.forget_front();
@@ -903,7 +941,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
     if (a.front) {   /* (a tile is URF_TILE points, whatever the laser count: URF_TILE / L firings) */
         const dim3 g_front((a.tiles + a.front_tpb - 1) / a.front_tpb, n_scans);
         if (a.front_lsh == 6u)
-            hipLaunchKernelGGL(k_front, g_front, dim3(64), 0, st, a, dp);
+            hipLaunchKernelGGL(front_kernel(dp.p.curbPoints), g_front, dim3(64), 0, st, a, dp);
         else if (a.front_lsh == 5u)
             hipLaunchKernelGGL(k_front32, g_front, dim3(64), 0, st, a, dp);
         else
@@ -927,7 +965,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
     bool side = false, part1 = false;
     const size_t finish_lds = (size_t)a.tiles * 384 + 2 * URF_FINISH_CHUNK * sizeof(urf_u2);
     if (a.front && !ev && !slot && side_fork(c, st)) {
-        hipLaunchKernelGGL(k_front_finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, c->side_stream, a, dp, 1u);
+        hipLaunchKernelGGL(front_finish_kernel(dp.p.curbPoints), g_scan, dim3(URF_FINISH_THREADS), finish_lds, c->side_stream, a, dp, 1u);
         part1 = true;
         side = hipEventRecord(c->ev_join, c->side_stream) == hipSuccess;
         if (!side)   /* (cannot be joined by an event: wait for it here) */
@@ -980,7 +1018,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
     if (a.front) {
         if (side && hipStreamWaitEvent(st, c->ev_join, 0) != hipSuccess)
             (void)hipStreamSynchronize(c->side_stream);
-        hipLaunchKernelGGL(k_front_finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, st, a, dp, part1 ? 2u : 0u);   /* (2: the star-shaped hits, the hand-over to k_beams) */
+        hipLaunchKernelGGL(front_finish_kernel(dp.p.curbPoints), g_scan, dim3(URF_FINISH_THREADS), finish_lds, st, a, dp, part1 ? 2u : 0u);   /* (2: the star-shaped hits, the hand-over to k_beams) */
     }
     /* the rings that hold a point with a NaN azimuth (k_split listed them: normally none, the kernel returns at once) */
     if (!(a.optimistic & URF_OPT_NO_NAN))

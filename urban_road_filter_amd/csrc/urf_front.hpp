@@ -41,6 +41,9 @@
 #define URF_FRONT_HPP
 
 #define URF_FRONT_HPRE 8u      /* firings in front of a block: 7 fill a window without holes (x_zero's j >= 5 rule) */
+#ifndef URF_FRONT_HPRE_WIDE
+#define URF_FRONT_HPRE_WIDE 12u   /* ... for curbPoints 6..8 (mode 3): the point x_zero marks needs CP + CP / 2 = 9, 10, 12 ring points in front of it */
+#endif
 #ifndef URF_FRONT_HPOST
 #define URF_FRONT_HPOST 8u     /* firings behind it: 5 complete the last centre's window */
 #endif
@@ -54,6 +57,7 @@
 #define URF_FRONT_TPB_SMALL 2u    /* tiles per block of k_front for batches below URF_FRONT_TPB_SCANS scans (more, shorter chains), ... */
 #define URF_FRONT_TPB_LARGE 4u    /* ... and from there on (less halo): 256 sweeps 0.663 / 0.703 ms at 2 / 4, 1024 sweeps 0.829 / 0.820 */
 #define URF_FRONT_TPB_SCANS 512u
+#define URF_FRONT_CP_MASK 0x1feu   /* curbPoints with a fused instance at 64 lasers (bit cp; 5 in every mode, the others with urf_set_front_mode(3)) */
 #define URF_FRONT_MAX_TILES 128u   /* k_front_finish keeps a presence word per (tile, lane) in LDS */
 #define URF_FRONT_RING_NONE 0x7fu  /* ring field of an input-order record */
 /* candidate kinds */
@@ -181,6 +185,36 @@ __device__ __noinline__ unsigned urf_front_open(const float* tab, unsigned nR, f
 
 /* the wave's candidate buffer (LDS; the workgroup IS the wave) and its flush into the scan's list: one atomic per ~150 candidates */
 #define URF_FRONT_CBUF 256u
+/* max(|v[I]|, |v[I + S]|, ..., N operands) as the chain of v_max3_f32 the march has always used (window values are region-of-interest
+ * points' heights, never NaN: |.| modifiers, no quieting): three operands first, two more per instruction, a last single one with v_max_f32.
+ * Every index is a compile-time constant: the window stays in registers. */
+template <unsigned N, int I, int S, unsigned NW>
+__device__ __forceinline__ float urf_front_absmax_more(float t, const float (&v)[NW])
+{
+    if constexpr (N == 0u) {
+        return t;
+    } else if constexpr (N == 1u) {
+        float m;
+        asm("v_max_f32_e64 %0, %1, |%2|" : "=v"(m) : "v"(t), "v"(v[I]));
+        return m;
+    } else {
+        asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(t) : "v"(t), "v"(v[I]), "v"(v[I + S]));
+        return urf_front_absmax_more<N - 2u, I + 2 * S, S>(t, v);
+    }
+}
+template <unsigned N, int I, int S, unsigned NW>
+__device__ __forceinline__ float urf_front_absmax(const float (&v)[NW])
+{
+    static_assert(N >= 2u, "the centre and at least one neighbour");
+    float t;
+    if constexpr (N == 2u) {
+        asm("v_max_f32_e64 %0, |%1|, |%2|" : "=v"(t) : "v"(v[I]), "v"(v[I + S]));
+        return t;
+    } else {
+        asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(t) : "v"(v[I]), "v"(v[I + S]), "v"(v[I + 2 * S]));
+        return urf_front_absmax_more<N - 3u, I + 3 * S, S>(t, v);
+    }
+}
 __device__ __forceinline__ void urf_front_flush(const urf_kargs& a, unsigned s, urf_u2* cbuf, unsigned& ncb, bool& overflow)
 {
     if (ncb == 0u)
@@ -587,26 +621,452 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
     }
 }
 
-template <unsigned L>
+/* The same march for any curbPoints of 1..8 (urf_set_front_mode(ctx, 3), 64 lasers per firing).  The body above stays word for word what it
+ * was -- its code generation is what tests/test_kernel_resources.py and the benchmark pin, and written with CP as a parameter it came out
+ * with four more registers and a spill -- this one is its general form, the constants 5, 3, 6, 4 and 11 as functions of CP.
+ *
+ * CP = params.curbPoints, h = CP / 2.  The lane's window holds its last 2 * CP + 1 ring points, w[2 * CP] the newest: z_zero's centre is
+ * w[CP] (CP points on either side, z_zero_method.cpp:21-50), x_zero's triple (j, j + h, j + CP) is (w[CP], w[CP + h], w[2 * CP]) and the
+ * point it marks the one CP - h back (x_zero_method.cpp:30-34; CP == 1: the triple is (j, j, j + 1)).  Both loops start at j = CP: a
+ * decision needs the FULL window.  The march keeps the firing numbers of the newest CP + 1 points, 16 bits each, the newest in the upper
+ * half of the last register: the point `back` places behind it sits in half 2 * NFW - 1 - back. */
+template <bool STAR, bool BEAM, unsigned L, unsigned CP>
+__device__ __forceinline__ void urf_front_body_cp(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
+{
+    const unsigned s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
+    unsigned off, len;
+    urf_scan_range(a, s, off, len);
+    const unsigned TPB = a.front_tpb;
+    const unsigned t_first = b * TPB;
+    if (t_first * URF_TILE >= len)
+        return;
+    const unsigned ok = a.front_ok[s];
+    if (ok == 0u)
+        return;
+    constexpr unsigned C = L;                     /* table entries per scan: params.channels */
+    constexpr unsigned STEPS = URF_TILE / L;      /* firings per tile */
+    static_assert(L == 64u || L == 32u || L == 16u, "a firing fills the wave, half of it or a quarter");
+    static_assert(CP >= 1u && CP <= 8u && URF_FRONT_HPOST >= CP, "the halo behind a block completes the last centre's window");
+    constexpr unsigned H = CP / 2u, NW = 2u * CP + 1u, NFW = (CP + 2u) / 2u;
+    constexpr unsigned HPRE = CP <= 5u ? URF_FRONT_HPRE : URF_FRONT_HPRE_WIDE;   /* CP + H ring points in front of a block's first marked point */
+    const unsigned K = (unsigned)dp.p.sectors;
+    const unsigned nf = (len + L - 1u) / L;                                 /* firings of the scan */
+    const unsigned F0 = t_first * STEPS;
+    const unsigned F1 = F0 + TPB * STEPS < nf ? F0 + TPB * STEPS : nf;
+    const unsigned Fs = F0 > HPRE ? F0 - HPRE : 0u;
+    const unsigned Fe = F1 + URF_FRONT_HPOST < nf ? F1 + URF_FRONT_HPOST : nf;
+    const bool from_start = Fs == 0u;   /* the window count IS the ring position + 1 */
+    const bool to_end = Fe == nf;       /* no point of the scan lies behind the march */
+    static_assert(HPRE % 4u == 0u && STEPS % 4u == 0u, "the march runs in groups of four firings");
+    const unsigned sb = urf_sbase(a, s);
+    const float *gx, *gy, *gz;
+    urf_front_src(a, s, off, ok, gx, gy, gz);
+    const __amdgpu_buffer_rsrc_t brec = urf_buf(a.rec + sb, len * 4u);
+    const __amdgpu_buffer_rsrc_t bsr = urf_buf(a.sr + sb, a.tiles * URF_TILE * 4u), bsz = urf_buf(a.sz + sb, a.tiles * URF_TILE * 4u);
+    const __amdgpu_buffer_rsrc_t bss = urf_buf(a.sslot + sb, a.tiles * URF_TILE * 2u);
+    const unsigned nR = a.info[s].n_rings;
+    const unsigned upto_v = a.table_upto[s];
+    /* (a row-major scan's table rests on EVERY point lying on its row's entry -- k_ring_table's third rule: a point on none asks for the long walk) */
+    const unsigned upto = ok == URF_FRONT_ROWS ? 0u : (nR < C ? upto_v : 0xffffffffu);
+    const float* const tab = a.angle + (size_t)s * dp.p.channels;
+    const float curbH = dp.p.curbHeight;
+    const bool use_x = dp.p.x_zero_method != 0, use_z = dp.p.z_zero_method != 0;
+
+    unsigned E = lane;        /* the table entry this lane's points are expected on */
+    bool econf = false;       /* ... and a point of this march has confirmed it */
+    urf_front_thr th = urf_front_load_thr(a, s, C, E, nR);
+    bool failed = false, overflow = false;
+    unsigned long long failed_m = 0;   /* ... what the hot path finds wrong, as lane masks (wave-uniform) */
+    unsigned ncb = 0;         /* candidates in the wave's buffer */
+
+    /* the lane's window: w[2 * CP] = its newest ring point, w[0] the one 2 * CP before; firing (relative to Fs) of the CP + 1 newest */
+    float w[NW];
+    unsigned fw[NFW];                      /* (CP == 5: (f6 << 16 | f5), (f8 << 16 | f7), (f10 << 16 | f9)) */
+#pragma unroll
+    for (unsigned k = 0; k < NW; k++)
+        w[k] = 0.f;
+#pragma unroll
+    for (unsigned k = 0; k < NFW; k++)
+        fw[k] = 0u;
+    auto fwat = [&](auto back) -> unsigned {   /* firing of the point `back` places behind the newest */
+        constexpr unsigned SL = 2u * NFW - 1u - decltype(back)::value;
+        return (SL & 1u) ? fw[SL / 2u] >> 16 : fw[SL / 2u] & 0xffffu;
+    };
+    unsigned wc = 0;                       /* points in the window, at most 2 * CP + 1 */
+    unsigned tot = 0, nin = 0;             /* ring points of this lane since the block's first firing / inside the block */
+    double maxs = 0.0;                     /* largest x*x + y*y among the lane's ring points of the block (maxDistance, lidar_segmentation.cpp:271-274) */
+    unsigned pw = 0;                       /* presence bits of the tile at hand */
+    /* per tile (wave-uniform) */
+    unsigned troi = 0, tstar = 0;
+    int stepkey_v = (int)URF_SEC_NONE, stepcnt_v = 0;   /* lane j: sector / participating points of step j of the tile */
+    int stepkey_w = (int)URF_SEC_NONE, stepcnt_w = 0;   /* (L = 16, 128 steps per tile) ... of step 64 + j */
+
+    /* one firing.  PH 0: the halo in front of the block (windows fill), 1: the block, 2: the halo behind it (windows complete) */
+    auto step = [&](auto ph, const unsigned f, const float x, const float y, const float z) {
+        constexpr unsigned PH = decltype(ph)::value;
+        const unsigned stp = f % STEPS;
+        const unsigned i = f * L + lane;
+        const bool roi = (L == 64u || lane < L) && i < len && urf_in_roi(dp.p, x, y, z);
+        const unsigned long long roim = __ballot(roi);
+        if (PH == 1u && lane == 0u) {   /* bit i of the scan's words: input point i */
+            if (L == 64u)
+                a.roi_bits[((size_t)s * a.tiles + f / STEPS) * STEPS + stp] = roim;
+            else if (L == 32u)
+                ((uint32_t*)(a.roi_bits + (size_t)s * a.tiles * (URF_TILE / 64u)))[f] = (uint32_t)roim;
+            else
+                ((uint16_t*)(a.roi_bits + (size_t)s * a.tiles * (URF_TILE / 64u)))[f] = (uint16_t)roim;
+        }
+        if (roim == 0ull)
+            return;   /* (uniform) nothing of this firing lies in the region of interest */
+        const float rho2 = x * x + y * y;
+        const float u = -z * __builtin_amdgcn_rsqf(rho2);   /* urf_fast_cot */
+        const bool fast = (rho2 >= URF_FAST_MIN2) & (rho2 <= URF_FAST_MAX2) & (__builtin_fabsf(u) <= URF_LUT_UMAX) & roi;
+        const bool on_f = fast & (u >= th.y) & (u <= th.z) & (u < th.below);
+        float fi = 0.f;
+        int fs = -1;
+        if (PH == 1u) {
+            fi = urf_fast_polar(x, y);
+            if (STAR)
+                fs = fast ? urf_fast_sector_ranged(fi, dp.Kfi, K, dp.sector_margin) : -1;
+        }
+        bool on = on_f;
+        const bool open = roi && !(on_f && (PH != 1u || !STAR || fs >= 0));
+        /* (r6, vector-issue diet: a ballot of anything but a direct compare costs two vector instructions -- v_cndmask 0 / 1, v_cmp -- to
+         * mask it with exec; a plain divergent branch skips its block when no lane takes it for two SCALAR instructions.  Wave-level
+         * flags (failed, overflow) are OR-ed up as masks, per-lane state that only rare paths read (econf) likewise.) */
+        if (open) {   /* rare: the reference's exact sequence for the lanes that need it */
+            const unsigned r = urf_front_open(tab, nR, dp.p.interval, x, y, z, (PH == 1u && STAR) ? K : 0u, dp.Kfi, E, econf ? 1u : 0u);
+            on = (r & 1u) != 0u;
+            fs = (int)((r >> 1) & 0x7ffu) - 1;
+            if (r & URF_FO_FAIL)
+                failed = true;
+            if (PH == 1u && (r & URF_FO_NONE) && i >= upto)
+                a.table_redo[s] = 1u;   /* the speculative ring table is incomplete (k_table_repair, legacy path) */
+            if (r & URF_FO_ADOPT) {   /* this lane's laser sits on another table entry: learned from its first point */
+                E = (r >> 12) & 0x7fu;
+                th = urf_front_load_thr(a, s, C, E, nR);
+            }
+        }
+        if (PH == 1u) {
+            /* the record, input order: ring | azimuth code (URF_REC_*; detector hits are OR-ed in by k_front_finish) */
+            const unsigned azc_v = urf_az_code(urf_fast_azimuth_of(fi));   /* (unconditionally, then a select: a branch around eight instructions costs more) */
+            const unsigned azc = urf_fast_az_ok(x, y) ? azc_v : URF_REC_AZ_UNKNOWN;
+            __builtin_amdgcn_raw_buffer_store_b32((azc << URF_REC_AZ_SHIFT) | (on ? E : URF_FRONT_RING_NONE), brec, (L == 64u || lane < L) ? i * 4u : URF_OOB, 0, URF_FRONT_NT);
+            if (STAR) {
+                /* star-shaped search: the firing's participants share one sector */
+                unsigned sk = (unsigned)fs;
+                if (BEAM && roi && !urf_in_beam(a.beams[fs < 0 ? 0 : fs], x, y))
+                    sk = URF_SEC_NONE;
+                /* (every lane is active here: the masks of direct compares need no exec) */
+                const unsigned long long psm = roim & __builtin_amdgcn_ballot_w64(sk != URF_SEC_NONE) & __builtin_amdgcn_ballot_w64((int)sk >= 0);
+                const bool ons = roi && sk != URF_SEC_NONE && (int)sk >= 0;
+                const unsigned src = psm ? (unsigned)__ffsll((long long)psm) - 1u : 0u;
+                const unsigned f0 = psm ? (unsigned)__builtin_amdgcn_readlane((int)sk, (int)src) : URF_SEC_NONE;
+                failed_m |= psm & __builtin_amdgcn_ballot_w64(sk != f0);
+                const unsigned so = (f / STEPS) * URF_TILE + tstar + urf_popc_below(psm);
+                const unsigned o4 = ons ? so * 4u : URF_OOB;
+                const float pr = urf_sqrt_rn_normal(rho2);   /* star_shaped_search.cpp:164: sqrtf(x * x + y * y) */
+                failed_m |= psm & ~(__builtin_amdgcn_ballot_w64(rho2 >= 0x1p-90f) & __builtin_amdgcn_ballot_w64(rho2 <= 0x1p126f));   /* (outside the shortcut's interval: the legacy kernels) */
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pr), bsr, o4, 0, URF_FRONT_NT);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(z), bsz, o4, 0, URF_FRONT_NT);
+                __builtin_amdgcn_raw_buffer_store_b16((short)((stp * L + lane) | (on ? 0u : URF_SLOT_OFF)), bss, ons ? so * 2u : URF_OOB, 0, URF_FRONT_NT);
+                if (STEPS <= 64u || stp < 64u) {   /* (uniform) */
+                    stepkey_v = lane == stp ? (int)f0 : stepkey_v;
+                    stepcnt_v = lane == stp ? (int)__popcll(psm) : stepcnt_v;
+                } else {
+                    stepkey_w = lane == stp - 64u ? (int)f0 : stepkey_w;
+                    stepcnt_w = lane == stp - 64u ? (int)__popcll(psm) : stepcnt_w;
+                }
+                tstar += (unsigned)__popcll(psm);
+            }
+            troi += (unsigned)__popcll(roim);
+        }
+        /* the lane's window moves on by its new ring point; what has become decidable is decided */
+        if (on) {
+            if (PH == 1u) {
+                const double s2 = (double)x * (double)x + (double)y * (double)y;
+                maxs = s2 > maxs ? s2 : maxs;
+                pw |= 1u << (f & 31u);
+            }
+            econf = true;
+#pragma unroll
+            for (unsigned k = 0; k + 1u < NW; k++)
+                w[k] = w[k + 1u];
+            w[NW - 1u] = z;
+#pragma unroll
+            for (unsigned k = 0; k + 1u < NFW; k++)
+                fw[k] = __builtin_amdgcn_alignbit(fw[k + 1u], fw[k], 16);
+            fw[NFW - 1u] = __builtin_amdgcn_alignbit(f - Fs, fw[NFW - 1u], 16);
+            wc = wc < NW ? wc + 1u : NW;
+            if (PH >= 1u)
+                tot++;
+            if (PH == 1u)
+                nin++;
+        }
+        if (PH == 0u)
+            return;
+        /* (straight-line: every lane computes, the lanes without a new point are masked out at the end -- branches around the
+         * tests put the four results through registers and selects) */
+        const bool full = wc == NW;
+        /* the centre (CP points back) and the point x_zero marks (CP - h back): are they this block's */
+        const bool c_in = on & (tot >= CP + 1u) & (tot - CP <= nin);
+        const bool p_in = on & (tot >= CP - H + 1u) & (tot - (CP - H) <= nin);
+        /* z_zero_method.cpp:39-40, 48-49, 67-69 */
+        const float a5 = __builtin_fabsf(w[CP]);
+        /* (window values are region-of-interest points' heights, never NaN: v_max3 with |.| modifiers, three instructions per side for
+         * CP == 5 -- the compiler's fmaxf quiets the first two operands of every chain with a v_max x, x each: five) */
+        const float m1 = urf_front_absmax<CP + 1u, 0, 1>(w);               /* the CP older points, then the centre */
+        const float m2 = urf_front_absmax<CP + 1u, (int)(2u * CP), -1>(w);   /* the CP newer points from the newest on, then the centre */
+        const bool hz = ((m1 - a5 >= curbH) | (m2 - a5 >= curbH)) & (__builtin_fabsf(m1 - m2) >= 0.05f);   /* ((double)v >= 0.05 <=> v >= 0.05f: the float above 0.05) */
+        /* x_zero_method.cpp:62-64 for the triple (w[CP], w[CP + h], w[2 CP]) = (j, j + h, j + CP) */
+        const bool hx = ((__builtin_fabsf(w[CP] - w[CP + H]) >= curbH) | (__builtin_fabsf(w[2u * CP] - w[CP + H]) >= curbH)) &
+                        (__builtin_fabsf(w[CP] - w[2u * CP]) >= 0.05f);
+        /* (lane masks combined as masks: `&` on bools mixed with the wave-uniform switches went through 0 / 1 integers in vector
+         * registers -- v_cndmask, v_and, v_cmp per term) */
+        bool zz = false, xz = false, ez = false, ex = false;
+        /* a window that began inside this march (a block border with a hole in the halo, a ring that has just entered the
+         * region of interest): positions unknown here, k_front_finish decides */
+        if (use_z) {   /* (uniform) */
+            zz = c_in && full && hz;
+            if (!from_start)
+                ez = c_in && !full;
+        }
+        if (use_x) {
+            xz = p_in && full && hx;
+            if (!from_start)
+                ex = p_in && !full;
+        }
+        if (__ballot(zz | xz | ez | ex) != 0ull) {   /* (uniform) */
+            urf_front_push(cbuf, ncb, zz | ez, (fwat(std::integral_constant<unsigned, CP>{}) + Fs) * L + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
+            urf_front_push(cbuf, ncb, xz | ex, (fwat(std::integral_constant<unsigned, CP - H>{}) + Fs) * L + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
+            if (ncb > URF_FRONT_CBUF - 128u)
+                urf_front_flush(a, s, cbuf, ncb, overflow);
+        }
+    };
+    /* the presence words of 32 firings (L = 64: the tile's, tile_end) */
+    auto pres_end = [&](const unsigned pt) {
+        if (lane < L)
+            a.front_pres[(size_t)s * a.tiles * 64u + (size_t)pt * L + lane] = pw;
+        pw = 0;
+    };
+    auto tile_end = [&](const unsigned t) {
+        const size_t row = (size_t)s * a.tiles + t;
+        if (L == 64u) {
+            a.front_pres[row * 64u + lane] = pw;
+            pw = 0;
+        }
+        if (lane == 0)
+            a.tile_roi[row] = troi;
+        if (STAR && STEPS > 32u) {
+            /* the same construction as below over 64 or 128 steps: a register per 64 of them, the running values carried from one to the
+             * next.  (The 32-step form below is kept word for word for the 64-laser kernel: its code and its register budget are what
+             * tests/test_kernel_resources.py and the benchmark pin.) */
+            constexpr unsigned NH = STEPS > 64u ? 2u : 1u;
+            unsigned fk[NH], sbase_h[NH];
+            unsigned carry = 0, total = 0;
+#pragma unroll
+            for (unsigned h = 0; h < NH; h++) {
+                const unsigned key = (unsigned)(h ? stepkey_w : stepkey_v), sc = (unsigned)(h ? stepcnt_w : stepcnt_v);
+                const unsigned k1 = key != URF_SEC_NONE ? key + 1u : 0u;
+                unsigned m = urf_wave_scan_max(k1);
+                m = m > carry ? m : carry;
+                unsigned exc = (unsigned)__shfl_up((int)m, 1);
+                exc = lane == 0 ? carry : exc;
+                if (__ballot(k1 != 0u && k1 < exc) != 0ull)
+                    failed = true;   /* (uniform) the sectors fall inside the tile */
+                fk[h] = m;
+                carry = (unsigned)__builtin_amdgcn_readlane((int)m, 63);
+                const unsigned sinc = urf_wave_scan_add(sc) + total;
+                sbase_h[h] = sinc - sc;
+                total = (unsigned)__builtin_amdgcn_readlane((int)sinc, 63);
+            }
+            for (unsigned k0 = 0; k0 <= K; k0 += 64u) {
+                const unsigned k = k0 + lane;
+                unsigned cnt = 0;   /* number of steps whose filled-in key + 1 is < k + 1 (the keys do not fall: a count per register adds up) */
+#pragma unroll
+                for (unsigned h = 0; h < NH; h++) {
+                    unsigned lo = 0;
+#pragma unroll
+                    for (unsigned st = 32u; st > 0; st >>= 1) {
+                        const unsigned v = (unsigned)__shfl((int)fk[h], (int)(lo + st - 1u));
+                        lo += v < k + 1u ? st : 0u;
+                    }
+                    const unsigned v = (unsigned)__shfl((int)fk[h], (int)lo);
+                    lo += (lo == 63u && v < k + 1u) ? 1u : 0u;
+                    cnt += lo;
+                }
+                unsigned so = total;
+#pragma unroll
+                for (unsigned h = 0; h < NH; h++) {
+                    const unsigned v = (unsigned)__shfl((int)sbase_h[h], (int)(cnt & 63u));
+                    so = (cnt >> 6) == h ? v : so;
+                }
+                if (k <= K)
+                    a.tsoff[row * (K + 1) + k] = (uint16_t)so;
+            }
+        }
+        if (STAR && STEPS == 32u) {
+            /* sector k starts with the first step whose sector is >= k (urf_split_holey's construction: the steps' keys
+             * with the empty steps filled in from the left must not fall; bisection over the 32 of them) */
+            const unsigned k1 = (lane < URF_FRONT_STEPS && (unsigned)stepkey_v != URF_SEC_NONE) ? (unsigned)stepkey_v + 1u : 0u;
+            const unsigned fk = urf_wave_scan_max(k1);
+            unsigned exc = (unsigned)__shfl_up((int)fk, 1);
+            exc = lane == 0 ? 0u : exc;
+            if (__ballot(k1 != 0u && k1 < exc) != 0ull)
+                failed = true;   /* (uniform) the sectors fall inside the tile (the sweep's seam, an unorganised cloud) */
+            const unsigned sc = lane < URF_FRONT_STEPS ? (unsigned)stepcnt_v : 0u;
+            const unsigned sinc = urf_wave_scan_add(sc);
+            const unsigned sbase_l = sinc - sc;   /* lane j: participating points of the steps in front of step j; lane 32: all */
+            for (unsigned k0 = 0; k0 <= K; k0 += 64u) {
+                const unsigned k = k0 + lane;
+                unsigned lo = 0;   /* number of steps whose filled-in key + 1 is < k + 1 */
+#pragma unroll
+                for (unsigned st = URF_FRONT_STEPS / 2; st > 0; st >>= 1) {
+                    const unsigned v = (unsigned)__shfl((int)fk, (int)(lo + st - 1u));
+                    lo += v < k + 1u ? st : 0u;
+                }
+                {
+                    const unsigned v = (unsigned)__shfl((int)fk, (int)lo);
+                    lo += (lo == URF_FRONT_STEPS - 1u && v < k + 1u) ? 1u : 0u;
+                }
+                const unsigned so = (unsigned)__shfl((int)sbase_l, (int)lo);   /* (lane 32 holds the tile's total) */
+                if (k <= K)
+                    a.tsoff[row * (K + 1) + k] = (uint16_t)so;
+            }
+        }
+        troi = 0;
+        tstar = 0;
+        stepkey_v = (int)URF_SEC_NONE;
+        stepcnt_v = 0;
+        stepkey_w = (int)URF_SEC_NONE;
+        stepcnt_w = 0;
+    };
+
+    /* The points arrive four firings ahead, in four register sets that are refilled as soon as they have been used: no
+     * copies between sets (a copy waits for its source), every wait is for a load issued three firings ago. */
+    float px[4], py[4], pz[4];
+    auto ld = [&](const unsigned j, const unsigned f) {
+        /* (a lane behind the scan's end, a lane without a laser: one point of the scan for all of them, never looked at) */
+        const unsigned i = f * L + lane, o = ((L == 64u || lane < L) && i < len) ? i : len - 1u;
+        px[j] = gx[o];
+        py[j] = gy[o];
+        pz[j] = gz[o];
+    };
+#pragma unroll
+    for (unsigned j = 0; j < 4; j++)
+        ld(j, Fs + j);
+    for (unsigned f = Fs; f < F0; f += 4) {
+#pragma unroll
+        for (unsigned j = 0; j < 4; j++) {
+            step(std::integral_constant<unsigned, 0u>{}, f + j, px[j], py[j], pz[j]);
+            ld(j, f + j + 4u);
+        }
+    }
+    for (unsigned f = F0; f < F1; f += 4) {
+#pragma unroll
+        for (unsigned j = 0; j < 4; j++) {
+            if (f + j < F1)   /* (uniform: the scan's last tile may end anywhere) */
+                step(std::integral_constant<unsigned, 1u>{}, f + j, px[j], py[j], pz[j]);
+            ld(j, f + j + 4u);
+        }
+        if (L != 64u && (((f + 4u) & 31u) == 0u || f + 4u >= F1))   /* (uniform) */
+            pres_end(f >> 5);
+        if (((f + 4u) % STEPS) == 0u || f + 4u >= F1) {   /* (uniform) the tile is complete */
+            tile_end(f / STEPS);
+            if (failed_m != 0ull || __ballot(failed | overflow) != 0ull) {   /* (uniform) */
+                a.front_ok[s] = 0u;
+                if (ok == URF_FRONT_ROWS)
+                    a.table_redo[s] = 1u;   /* (nobody has checked the rest of the scan against the rows' table) */
+                return;
+            }
+        }
+    }
+    for (unsigned f = F1; f < Fe; f += 4) {
+#pragma unroll
+        for (unsigned j = 0; j < 4; j++) {
+            if (f + j < Fe)
+                step(std::integral_constant<unsigned, 2u>{}, f + j, px[j], py[j], pz[j]);
+            ld(j, f + j + 4u);
+        }
+    }
+    /* the block's last ring points of every lane: their windows reach behind the march */
+    if (!to_end) {
+        /* the CP newest, oldest first: none has been a centre, the CP - h newest have not been x_zero's marked point either */
+        auto tail = [&](auto bk) {
+            constexpr unsigned back = decltype(bk)::value;
+            const bool in = tot > back && tot - back <= nin;
+            const unsigned what = (use_z ? URF_FC_EDGE_Z : 0u) | ((use_x && back < CP - H) ? URF_FC_EDGE_X : 0u);
+            if (ncb > URF_FRONT_CBUF - 64u)
+                urf_front_flush(a, s, cbuf, ncb, overflow);
+            urf_front_push(cbuf, ncb, in && what != 0u, (fwat(bk) + Fs) * L + lane, what);
+        };
+        if constexpr (CP >= 8u) tail(std::integral_constant<unsigned, 7u>{});
+        if constexpr (CP >= 7u) tail(std::integral_constant<unsigned, 6u>{});
+        if constexpr (CP >= 6u) tail(std::integral_constant<unsigned, 5u>{});
+        if constexpr (CP >= 5u) tail(std::integral_constant<unsigned, 4u>{});
+        if constexpr (CP >= 4u) tail(std::integral_constant<unsigned, 3u>{});
+        if constexpr (CP >= 3u) tail(std::integral_constant<unsigned, 2u>{});
+        if constexpr (CP >= 2u) tail(std::integral_constant<unsigned, 1u>{});
+        tail(std::integral_constant<unsigned, 0u>{});
+    }
+    urf_front_flush(a, s, cbuf, ncb, overflow);
+    a.front_maxs[((size_t)s * a.tiles + b) * 64u + lane] = (unsigned long long)__double_as_longlong(maxs);
+    /* one lane, one ring -- over the whole scan: the blocks agree through the scan's two tables */
+    if (econf) {
+        const unsigned o1 = atomicCAS(&a.front_lane_ring[(size_t)s * 64u + lane], 0xffffffffu, E);
+        const unsigned o2 = atomicCAS(&a.front_ring_lane[(size_t)s * C + E], 0xffffffffu, lane);
+        failed = failed | (o1 != 0xffffffffu && o1 != E) | (o2 != 0xffffffffu && o2 != lane);
+    }
+    if (failed_m != 0ull || __ballot(failed | overflow) != 0ull) {
+        a.front_ok[s] = 0u;
+        if (ok == URF_FRONT_ROWS)
+            a.table_redo[s] = 1u;
+    }
+}
+
+template <unsigned L, unsigned CP>
 __device__ __forceinline__ void urf_front_kernel(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
 {
-    if (!dp.p.star_shaped_method)
-        urf_front_body<false, false, L>(a, dp, cbuf);
-    else if (!dp.p.starbeam_filter)
-        urf_front_body<true, false, L>(a, dp, cbuf);
-    else
-        urf_front_body<true, true, L>(a, dp, cbuf);
+    if constexpr (CP == 5u) {
+        if (!dp.p.star_shaped_method)
+            urf_front_body<false, false, L>(a, dp, cbuf);
+        else if (!dp.p.starbeam_filter)
+            urf_front_body<true, false, L>(a, dp, cbuf);
+        else
+            urf_front_body<true, true, L>(a, dp, cbuf);
+    } else {
+        static_assert(CP == 5u || L == 64u, "curbPoints other than 5: 64 lasers per firing");
+        if (!dp.p.star_shaped_method)
+            urf_front_body_cp<false, false, L, CP>(a, dp, cbuf);
+        else if (!dp.p.starbeam_filter)
+            urf_front_body_cp<true, false, L, CP>(a, dp, cbuf);
+        else
+            urf_front_body_cp<true, true, L, CP>(a, dp, cbuf);
+    }
 }
-/* one kernel per laser count, each under a name of its own (tools/kernel_resources.py lists kernels by their base identifier) */
-#define URF_FRONT_KERNEL(name, L)                                                                                                             \
-    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT_WAVES, URF_FRONT_WAVES))) void name(urf_kargs a, urf_dev_params dp) \
+/* one kernel per laser count and per curbPoints, each under a name of its own (tools/kernel_resources.py lists kernels by their base
+ * identifier) and with its own waves per SIMD */
+#define URF_FRONT_KERNEL(name, L, CP, WAVES)                                                                                                  \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void name(urf_kargs a, urf_dev_params dp)             \
     {                                                                                                                                         \
         __shared__ urf_u2 cbuf[URF_FRONT_CBUF];                                                                                               \
-        urf_front_kernel<L>(a, dp, cbuf);                                                                                                     \
+        urf_front_kernel<L, CP>(a, dp, cbuf);                                                                                                 \
     }
-URF_FRONT_KERNEL(k_front, 64u)
-URF_FRONT_KERNEL(k_front32, 32u)
-URF_FRONT_KERNEL(k_front16, 16u)
+URF_FRONT_KERNEL(k_front, 64u, 5u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front32, 32u, 5u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front16, 16u, 5u, URF_FRONT_WAVES)
+/* urf_set_front_mode(ctx, 3): curbPoints 1..8 at 64 lasers.  The window is 2 * CP + 1 registers: 1..4 fit k_front's budget, 6..8 (13, 15, 17 heights and
+ * a fourth / fifth register of firing numbers) get the next one (four waves per SIMD, 128 registers) */
+#ifndef URF_FRONT_WAVES_WIDE
+#define URF_FRONT_WAVES_WIDE 4
+#endif
+URF_FRONT_KERNEL(k_front_cp1, 64u, 1u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front_cp2, 64u, 2u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front_cp3, 64u, 3u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front_cp4, 64u, 4u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front_cp6, 64u, 6u, URF_FRONT_WAVES_WIDE)
+URF_FRONT_KERNEL(k_front_cp7, 64u, 7u, URF_FRONT_WAVES_WIDE)
+URF_FRONT_KERNEL(k_front_cp8, 64u, 8u, URF_FRONT_WAVES_WIDE)
 
 /* ------------------------------------------------------------------------- */
 /* k_front_finish                                                              */
@@ -657,11 +1117,14 @@ __device__ __forceinline__ unsigned urf_front_next(const unsigned* P, unsigned l
 /* part 0: everything.  Parts 1 and 2 (r6): what does not depend on the star-shaped search -- positions, ring sizes, the candidates of the
  * two detectors and their marks -- as a launch of its own on a SECOND stream, next to k_index / k_star_sort_* / k_star_walk (it waits for
  * scattered loads, they for vector issue: urf_api.hip), and the star-shaped hits, the lists' hand-over to k_beams and the overflow tables
- * behind the walk.  The counters travel from part 1 to part 2 through front_st. */
-__global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a, urf_dev_params dp, unsigned part)
+ * behind the walk.  The counters travel from part 1 to part 2 through front_st.
+ * CP = params.curbPoints (h = CP / 2): the ring positions both detectors accept and how far their neighbours lie, as in the march. */
+template <unsigned CP>
+__device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_params dp, unsigned part)
 {
     __shared__ urf_finish_shared S;
     extern __shared__ unsigned sh_finish[];   /* P[tiles][64] presence words | B[tiles][64] (u16) ring points of the lane in the tiles before */
+    constexpr unsigned H = CP / 2u;
     const unsigned s = blockIdx.x, tid = threadIdx.x;
     const unsigned ok = a.front_ok[s];
     if (!ok)
@@ -790,23 +1253,25 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
         }
         __syncthreads();
         const unsigned nx = S.nx, nz = S.nz;
-        /* phase X: x_zero_method.cpp:30-68 marks p = j + 2 for j = p - 2 in [curbPoints, n - 1 - curbPoints] */
+        /* phase X: x_zero_method.cpp:30-68 marks p = j + h for j = p - h in [curbPoints, n - 1 - curbPoints] */
         if (dp.p.x_zero_method)
             for (unsigned e = tid; e < nx; e += URF_FINISH_THREADS) {
                 const urf_u2 cd = chunk[e];
                 const unsigned idx = cd.x, l = idx & lm, f = idx >> lsh;
                 const unsigned n = S.n[l];
                 const unsigned p = (unsigned)B[((f >> 5) << lsh) + l] + (unsigned)__popc(P[((f >> 5) << lsh) + l] & ((1u << (f & 31u)) - 1u));
-                if (!(p >= 7u && p + 3u < n))
+                if (!(p >= CP + H && p + (CP - H) < n))
                     continue;
-                unsigned fj = urf_front_prev(P, lsh, l, f);
-                fj = urf_front_prev(P, lsh, l, fj);
-                unsigned f3 = urf_front_next(P, lsh, npt, l, f);
-                f3 = urf_front_next(P, lsh, npt, l, f3);
-                f3 = urf_front_next(P, lsh, npt, l, f3);
+                unsigned fj = f, f3 = f;
+#pragma unroll
+                for (unsigned k = 0; k < H; k++)
+                    fj = urf_front_prev(P, lsh, l, fj);
+#pragma unroll
+                for (unsigned k = 0; k < CP - H; k++)
+                    f3 = urf_front_next(P, lsh, npt, l, f3);
                 const unsigned ij = (fj << lsh) + l, i3 = (f3 << lsh) + l;
                 const float pz = gz[idx], xj = gx[ij], yj = gy[ij], zj = gz[ij], x3 = gx[i3], y3 = gy[i3], z3 = gz[i3];
-                const float nyj = a.newY[p - 2u], ny2 = a.newY[p], ny3 = a.newY[p + 3u];
+                const float nyj = a.newY[p - H], ny2 = a.newY[p], ny3 = a.newY[p + (CP - H)];
                 bool heights = true;
                 if (cd.y & URF_FC_EDGE_X)   /* (the march has not looked at the heights) */
                     heights = (__builtin_fabsf(zj - pz) >= dp.p.curbHeight || __builtin_fabsf(z3 - pz) >= dp.p.curbHeight) &&
@@ -821,28 +1286,31 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
                 const unsigned idx = cd.x, l = idx & lm, f = idx >> lsh;
                 const unsigned n = S.n[l];
                 const unsigned p = (unsigned)B[((f >> 5) << lsh) + l] + (unsigned)__popc(P[((f >> 5) << lsh) + l] & ((1u << (f & 31u)) - 1u));
-                if (!(p >= 5u && p + 5u < n))
+                if (!(p >= CP && p + CP < n))
                     continue;
-                unsigned im[5], ip[5];
+                unsigned im[CP], ip[CP];
                 {
                     unsigned g = f;
 #pragma unroll
-                    for (unsigned k = 0; k < 5; k++) {
+                    for (unsigned k = 0; k < CP; k++) {
                         g = urf_front_prev(P, lsh, l, g);
                         im[k] = (g << lsh) + l;
                     }
                     g = f;
 #pragma unroll
-                    for (unsigned k = 0; k < 5; k++) {
+                    for (unsigned k = 0; k < CP; k++) {
                         g = urf_front_next(P, lsh, npt, l, g);
                         ip[k] = (g << lsh) + l;
                     }
                 }
                 const bool needz = (cd.y & URF_FC_EDGE_Z) != 0u;   /* (the march has not looked at the heights) */
-                float xm[5], ym[5], zm[5] = { 0.f, 0.f, 0.f, 0.f, 0.f }, xp[5], yp[5], zp[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };
+                float xm[CP], ym[CP], zm[CP], xp[CP], yp[CP], zp[CP];
+#pragma unroll
+                for (unsigned k = 0; k < CP; k++)
+                    zm[k] = zp[k] = 0.f;
                 const float px = gx[idx], py = gy[idx], pz = gz[idx];
 #pragma unroll
-                for (unsigned k = 0; k < 5; k++) {
+                for (unsigned k = 0; k < CP; k++) {
                     xm[k] = gx[im[k]];
                     ym[k] = gy[im[k]];
                     xp[k] = gx[ip[k]];
@@ -852,7 +1320,7 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
                  * instruction: the heights are only asked for by a wave that holds such an item) */
                 if (__ballot(needz) != 0ull) {
 #pragma unroll
-                    for (unsigned k = 0; k < 5; k++) {
+                    for (unsigned k = 0; k < CP; k++) {
                         zm[k] = gz[needz ? im[k] : idx];
                         zp[k] = gz[needz ? ip[k] : idx];
                     }
@@ -862,7 +1330,7 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
                     const float azp = __builtin_fabsf(pz);
                     float max1 = azp, max2 = azp;
 #pragma unroll
-                    for (unsigned k = 0; k < 5; k++) {
+                    for (unsigned k = 0; k < CP; k++) {
                         const float za = __builtin_fabsf(zm[k]), zb = __builtin_fabsf(zp[k]);
                         max1 = za > max1 ? za : max1;
                         max2 = zb > max2 ? zb : max2;
@@ -875,7 +1343,7 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
                         xx = rel < 0 ? xm[-rel - 1] : xp[rel - 1];
                         yy = rel < 0 ? ym[-rel - 1] : yp[rel - 1];
                     };
-                    if (urf_z_zero_angle(dp.inv_cp, dp.p.angleFilter2, dp.z_angle_thr, xy, (int)p, 5, px, py))
+                    if (urf_z_zero_angle(dp.inv_cp, dp.p.angleFilter2, dp.z_angle_thr, xy, (int)p, (int)CP, px, py))
                         passed(idx, 4u);
                 }
             }
@@ -1012,6 +1480,20 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish(urf_kargs a
         }
     }
 }
+/* one kernel per curbPoints, as for k_front (k_front_finish: 5) */
+#define URF_FRONT_FINISH_KERNEL(name, CP)                                                                     \
+    __global__ __launch_bounds__(URF_FINISH_THREADS) void name(urf_kargs a, urf_dev_params dp, unsigned part) \
+    {                                                                                                         \
+        urf_front_finish_body<CP>(a, dp, part);                                                               \
+    }
+URF_FRONT_FINISH_KERNEL(k_front_finish, 5u)
+URF_FRONT_FINISH_KERNEL(k_front_finish_cp1, 1u)
+URF_FRONT_FINISH_KERNEL(k_front_finish_cp2, 2u)
+URF_FRONT_FINISH_KERNEL(k_front_finish_cp3, 3u)
+URF_FRONT_FINISH_KERNEL(k_front_finish_cp4, 4u)
+URF_FRONT_FINISH_KERNEL(k_front_finish_cp6, 6u)
+URF_FRONT_FINISH_KERNEL(k_front_finish_cp7, 7u)
+URF_FRONT_FINISH_KERNEL(k_front_finish_cp8, 8u)
 
 /* ------------------------------------------------------------------------- */
 /* k_label_front                                                               */

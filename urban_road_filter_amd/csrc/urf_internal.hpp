@@ -193,7 +193,7 @@ struct urf_kargs {
                                    needed it into URF_STATUS_REDO_*, which urf_classify_pc2_wait() answers with the full sequence */
     uint32_t capture;           /* 0 production; 1 every point takes the exact sequence, values recorded;
                                    2 production decisions, ring / sector keys recorded */
-    uint32_t  front;            /* this call launches it (urf_api.hip decides: 64 channels, curbPoints 5, no stage capture, a batch) */
+    uint32_t  front;            /* this call launches it (urf_api.hip decides: 64 / 32 / 16 channels, curbPoints 5 -- mode 3 and 64 channels: 1..8 --, no stage capture, a batch) */
     uint32_t  front_tpb;        /* tiles per block of k_front */
     uint32_t  front_cand_cap;   /* entries per scan of front_cand / front_all */
     uint32_t  front_pad_;
