@@ -520,9 +520,22 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * scan back launches the general kernels as full grids next to the fused ones from then on, and one that has handed a
  * whole batch back (unorganised clouds) stops trying in mode 1; urf_set_params with other parameters and
  * urf_set_front_mode with another mode forget both.  urf_front_scans: how many scans of the last batch call took the
- * fused front end (synchronises). */
+ * fused front end (synchronises).
+ *
+ * 128 lasers per firing (urf_set_front_lasers128, urban_road_filter_amd/csrc/urf_front128.hpp): with the switch on, channels == 128 and
+ * curbPoints == 5, modes 2 and 3 -- never modes 0 and 1 -- also take sweeps of 128 lasers per firing, in firing order (point f * 128 + l)
+ * or row-major (128 rows; sighted by one call, fused from the next on, the callback path included): one wave per block of the march, two
+ * lasers (l and l + 64) per lane.  Everything above holds for them as well -- per-scan hand-back, identical labels and summaries,
+ * urf_front_scans -- and so does the limit of 128 x 2048 points per scan: a 128 x 4096 sweep keeps the general kernels.  Every
+ * 128-laser table entry is a ring to these kernels, entry 127 included (their records keep the ring in eight bits).  curbPoints != 5
+ * keeps the general kernels at 128 lasers.  The switch is off by default and opt-in whatever tools/front_lasers_bench.py --lasers128
+ * measures; turning it on allocates the per-scan tables these kernels need (URF_ERR_OOM: it stays off). */
 int urf_set_front_mode(urf_ctx* ctx, int mode);
 int urf_front_scans(urf_ctx* ctx, uint32_t* n_fused);
+/* 0 (default): as today.  1: with channels == 128 and curbPoints == 5, front modes 2 and 3 also send sweeps of 128 lasers per
+ * firing (firing order: point f * 128 + l; row-major: 128 rows) through the fused front end.  Forgets sightings / hand-backs
+ * like urf_set_front_mode.  Anything else: URF_ERR_INVALID_ARG. */
+int urf_set_front_lasers128(urf_ctx* ctx, int on);
 
 /* ---- per-kernel timing (benchmark) ------------------------------------------
  * With timing on, every classify call brackets each kernel of the pipeline

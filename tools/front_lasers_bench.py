@@ -8,7 +8,15 @@ For L in --lasers and storage order in {firing, rows}: --scans resident L x 2048
 alternating, seed), params.channels = L.  First a parity gate: the labels of a few sampled scans against oracle B (tests/oracles.py).
 Then urf_set_front_mode 0 and 2, warm-up, --steps calls between device events: median ms per call, scans/s, urf_front_scans.
 "sweep": mode 0 / 1 / 2 over batch sizes 32 .. 1024 of the firing-order sweeps, the numbers mode 1's threshold per laser count
-(urf_front.hpp: urf_front_min_scans) is set from.  Uses only entry points every build since the fused front end has."""
+(urf_front.hpp: urf_front_min_scans) is set from.  Uses only entry points every build since the fused front end has.
+
+    timeout 900 python tools/front_lasers_bench.py --lasers128 [--scans 256] [--steps 20] [--warmup 3]
+
+128 lasers per firing (urf_set_front_lasers128, urf_front128.hpp): --scans resident 128 x 2048 and 128 x 1024 sweeps (channels = 128,
+interval = 0.05), firing order and row-major, in TWO contexts of one process, both in front mode 2 -- one with the switch on, one with it
+off: the same binary's general kernels, the baseline -- timed interleaved call by call (on, off, on, off, ...), behind a label gate
+against oracle B for both.  Per case: the medians, the 10th / 90th percentiles of either side (the run's own spread) and the median and
+percentiles of the per-pair ratio off / on.  Recorded under profiles/front_lasers128_bench.json."""
 import argparse
 import json
 import os
@@ -23,6 +31,65 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 COLS = 2048
 
 
+def lasers128(args):
+    import torch
+    import urban_road_filter_amd as u
+    import oracles as O
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: nothing is measured here")
+    L, S = 128, args.scans if args.scans != 1024 else 256
+    dev = torch.device("cuda:0")
+    out = {"metric": "front_lasers128", "device": torch.cuda.get_device_name(0), "scans": S, "front_mode": 2,
+           "timing": "device events per call, switch on / off interleaved call by call in one process; ms", "results": []}
+    t0 = time.time()
+    st = torch.cuda.Stream()
+    p = u.default_params().wide_roi()
+    p.channels = L
+    p.interval = 0.05
+    pct = lambda v: [float(np.percentile(v, q)) for q in (10, 50, 90)]
+    with torch.cuda.stream(st):
+        for cols in (2048, 1024):
+            n = L * cols
+            base = [u.synth_cloud(L, cols, 1 + (s % 2) * 2, 100 + s) for s in range(min(args.distinct, S))]
+            for order in ("firing", "rows"):
+                src = base if order == "firing" else [tuple(np.ascontiguousarray(a.reshape(-1, L).T.reshape(-1)) for a in c) for c in base]
+                one = [torch.from_numpy(np.concatenate([c[k] for c in src])).to(dev) for k in range(3)]
+                reps = (S + len(src) - 1) // len(src)
+                dx, dy, dz = (t.repeat(reps)[:S * n].contiguous() for t in one)
+                labels = torch.empty(S * n, dtype=torch.uint8, device=dev)
+                want = {k: O.run_b(*src[k % len(src)], p)[0] for k in (0, 1, S - 1)}
+                with u.Context(n, S, params=p) as on, u.Context(n, S, params=p) as off:
+                    ctxs = {"on": on, "off": off}
+                    fused = {}
+                    for name, ctx in ctxs.items():
+                        ctx.set_stream(st.cuda_stream)
+                        ctx.set_front_lasers128(1 if name == "on" else 0)
+                        ctx.set_front_mode(2)
+                        for call in range(max(3, args.warmup)):   # the label gate (row-major: the first call sights the layout), and the warm-up
+                            ctx.classify_batch_soa(dx, dy, dz, n, S, labels, None)
+                            torch.cuda.synchronize()
+                            got = labels.cpu().numpy().reshape(S, n)
+                            for k, lb in want.items():
+                                if not np.array_equal(got[k], lb):
+                                    raise SystemExit("label gate: 128 x %d %s switch %s call %d scan %d differs from oracle B" % (cols, order, name, call, k))
+                        fused[name] = int(ctx.front_scans())
+                    ts = {"on": [], "off": []}
+                    for _ in range(args.steps):
+                        for name, ctx in ctxs.items():
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record()
+                            ctx.classify_batch_soa(dx, dy, dz, n, S, labels, None)
+                            e1.record()
+                            e1.synchronize()
+                            ts[name].append(e0.elapsed_time(e1))
+                    ratio = [b / a for a, b in zip(ts["on"], ts["off"])]
+                    out["results"].append({"cols": cols, "order": order, "on_front_scans": fused["on"], "off_front_scans": fused["off"],
+                                           "on_ms_p10_p50_p90": pct(ts["on"]), "off_ms_p10_p50_p90": pct(ts["off"]),
+                                           "off_over_on_p10_p50_p90": pct(ratio)})
+    out["wall_s"] = time.time() - t0
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scans", type=int, default=1024)
@@ -31,7 +98,10 @@ def main():
     ap.add_argument("--lasers", default="16,32,64")
     ap.add_argument("--distinct", type=int, default=32, help="distinct sweeps the batch is built from")
     ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--lasers128", action="store_true", help="the 128-laser switch on against off, two contexts interleaved")
     args = ap.parse_args()
+    if args.lasers128:
+        return lasers128(args)
     import torch
     import urban_road_filter_amd as u
     import oracles as O

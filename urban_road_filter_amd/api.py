@@ -175,6 +175,7 @@ def lib(hooks=False):
         "urf_abi_version": [],
         "urf_set_front_mode": [vp, C.c_int],
         "urf_front_scans": [vp, C.c_void_p],
+        "urf_set_front_lasers128": [vp, C.c_int],
         "urf_callback_path_preset": [vp, C.c_uint32],
     }
     for name, args in sig.items():
@@ -388,6 +389,11 @@ class Context:
         size, and on the callback path; 2 every batch call it applies to; 3 as 2, and with 64 lasers per firing curb_points 1..8 instead
         of 5 only (9..30, and 16 / 32 lasers with curb_points != 5, keep the general kernels in every mode)."""
         self._check(self._lib.urf_set_front_mode(self._h, int(mode)), "urf_set_front_mode")
+
+    def set_front_lasers128(self, on):
+        """urf_set_front_lasers128: 1 lets front modes 2 and 3 take sweeps of 128 lasers per firing too (channels == 128, curb_points == 5,
+        firing order or row-major, at most 128 x 2048 points; include/urf.h); 0 (default) keeps them on the general kernels.  Opt-in."""
+        self._check(self._lib.urf_set_front_lasers128(self._h, int(on)), "urf_set_front_lasers128")
 
     def callback_path_preset(self, sequence_bits):
         """urf_callback_path_preset: 2 work-list kernels | 4 NaN-azimuth rings | 16 std::sort's tie order, ahead of the first sweep that needs them."""

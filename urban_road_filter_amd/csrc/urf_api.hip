@@ -24,6 +24,7 @@
 #include "urf_internal.hpp"
 #include "urf_kernels.hpp"
 #include "urf_front.hpp"
+#include "urf_front128.hpp"
 
 #define URF_ASYNC_SLOTS 4
 static_assert(URF_ASYNC_SLOTS == URF_MAX_IN_FLIGHT, "include/urf.h documents the number of sweeps in flight");
@@ -52,7 +53,8 @@ struct lazy_buf {
  * (kargs_row).  Most arrays have max_batch rows; the two per-call counters (SLOTS: the URF_LIST_COUNT work-list lengths and the
  * ring-count hint) have URF_ASYNC_SLOTS, one per sweep in flight, whatever max_batch is.  urf_create allocates SCANS and SLOTS;
  * CAPTURE comes with the first urf_enable_stage_capture, ROW_MAJOR (the firing-order copies of row-major organised sweeps) once
- * such a sweep has been sighted (rows_state_update).  sstride, max_tiles and front_cand_cap are the context's (scratch_walk). */
+ * such a sweep has been sighted (rows_state_update), LASERS128 (what the fused front end sizes for 64 lanes, sized for 128: urf_front128.hpp)
+ * with the first urf_set_front_lasers128(ctx, 1).  sstride, max_tiles and front_cand_cap are the context's (scratch_walk). */
 #define URF_SCRATCH_SCANS(X)                                                                                                     \
     X(rx, sstride) X(ry, sstride) X(rz, sstride) X(rec, sstride)                                                                 \
     X(sr, sstride) X(sz, sstride) X(sslot, sstride) X(ssrt16, sstride) X(ssrt, sstride) X(wsg, sstride)                          \
@@ -79,11 +81,15 @@ struct lazy_buf {
 #define URF_SCRATCH_SLOTS(X) X(list_len, URF_LIST_COUNT) X(ring_hint, 1)
 #define URF_SCRATCH_CAPTURE(X) X(valpha, sstride) X(seckey, sstride) X(ringkey, sstride) X(rd2, sstride) X(caz, sstride)
 #define URF_SCRATCH_ROW_MAJOR(X) X(tx, sstride) X(ty, sstride) X(tz, sstride) X(rows_v, 64) X(rows_ok, 1)
-enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR };
+#define URF_SCRATCH_LASERS128(X)                                                                                                  \
+    X(front_pres128, URF_FRONT128_TILES2(max_tiles) * 64) X(front_maxs128, URF_FRONT128_TILES2(max_tiles) * 64)                  \
+    X(front_lane_ring128, URF_FRONT128_L) X(front_st128, URF_FRONT128_ST_WORDS) X(rows_v128, URF_FRONT128_L)                     \
+    X(front_cand128, URF_FRONT128_CAND_CAP(max_points)) X(front_all128, URF_FRONT128_CAND_CAP(max_points))
+enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR, URF_SCR_LASERS128 };
 
 
 /* curbPoints the fused front end has an instance for: 5 in every mode; with urf_set_front_mode(3) and 64 lasers per firing the values of
- * URF_FRONT_CP_MASK (urf_front.hpp).  16 / 32 lasers and 9..30 keep the general kernels. */
+ * URF_FRONT_CP_MASK (urf_front.hpp).  16 / 32 / 128 lasers and 9..30 keep the general kernels. */
 static bool front_curb_points_ok(int front_mode, unsigned L, int cp)
 {
     return cp == 5 || (front_mode == 3 && L == 64u && cp >= 1 && cp <= 8 && ((URF_FRONT_CP_MASK >> cp) & 1u) != 0u);
@@ -140,6 +146,7 @@ struct __attribute__((visibility("hidden"))) urf_policy {
      * last_call). */
     int front_mode = 1;
     bool every_batch() const { return front_mode >= 2; }
+    bool lasers128 = false;         /* urf_set_front_lasers128: modes 2 and 3 take sweeps of 128 lasers per firing too (urf_front128.hpp; its scratch is there) */
     uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
     bool want_ring_sorted = false;
     /* k_front hands a scan without the shape back to the general kernels: launched list-driven until a call has done so
@@ -207,8 +214,8 @@ struct __attribute__((visibility("hidden"))) urf_policy {
          * sweeps, the fused ones 0.26, tools/r6_min_scans.py --rows), sweeps in firing order only from 192 per call on, and not as single
          * sweeps of the callback path (tools/r6_single_sweep.py). */
         const unsigned L = (unsigned)dp.p.channels;
-        const bool lasers = L == 64u || L == 32u || L == 16u;
-        a.front_lsh = L == 16u ? 4u : (L == 32u ? 5u : 6u);
+        const bool lasers = L == 64u || L == 32u || L == 16u || (L == 128u && lasers128 && every_batch());
+        a.front_lsh = L == 16u ? 4u : (L == 32u ? 5u : (L == 128u ? 7u : 6u));
         const bool shape = front_mode != 0 && !front_off && !general_only && !want_ring_sorted && a.capture == 0 &&
                            lasers && front_curb_points_ok(front_mode, L, dp.p.curbPoints) && a.tiles <= URF_FRONT_MAX_TILES;
         /* (16 / 32 lasers: nothing below mode 2 until their crossover has been measured -- no batch size, no row-major sighting, no callback path) */
@@ -216,6 +223,8 @@ struct __attribute__((visibility("hidden"))) urf_policy {
         a.front = (shape && (slot ? small_ok : (every_batch() || small_ok || a.n_scans >= (L == 64u ? URF_FRONT_MIN_SCANS : (L == 32u ? URF_FRONT_MIN_SCANS_32 : URF_FRONT_MIN_SCANS_16))))) ? 1u : 0u;
         a.front_sight = (shape && !a.front && !front_rows && !rows_oom && (L == 64u || every_batch())) ? 1u : 0u;
         a.front_tpb = front_tpb ? front_tpb : (a.n_scans >= URF_FRONT_TPB_SCANS ? URF_FRONT_TPB_LARGE : (a.n_scans >= 16u ? URF_FRONT_TPB_SMALL : 1u));
+        if (a.front_lsh == 7u)   /* (a presence word of k_front128 covers two tiles: no block may end inside one) */
+            a.front_tpb = a.front_tpb < 2u ? 2u : (a.front_tpb & ~1u);
         a.front_lists = (a.front && !front_direct && !slot) ? 1u : 0u;   /* (the callback path's sequence holds the general kernels as grids anyway) */
         a.front_rows = (a.front && front_rows) ? 1u : 0u;   /* (independent of the two other speculations: the repair kernels come with it) */
     }
@@ -362,19 +371,22 @@ static int grow(urf_ctx* c, lazy_buf<T, Host>& b, size_t count, hipStream_t st =
 template <class F>
 static void scratch_walk(const urf_ctx* c, urf_kargs& k, F&& f)
 {
-    const size_t sstride = c->sstride, max_tiles = c->max_tiles, front_cand_cap = k.front_cand_cap;
+    const size_t sstride = c->sstride, max_tiles = c->max_tiles, max_points = c->max_points, front_cand_cap = k.front_cand_cap;
 #define URF_X_SCANS(field, n) f(URF_SCR_ALWAYS, k.field, (size_t)c->max_batch, (size_t)(n));
 #define URF_X_SLOTS(field, n) f(URF_SCR_ALWAYS, k.field, (size_t)URF_ASYNC_SLOTS, (size_t)(n));
 #define URF_X_CAPTURE(field, n) f(URF_SCR_CAPTURE, k.field, (size_t)c->max_batch, (size_t)(n));
 #define URF_X_ROW_MAJOR(field, n) f(URF_SCR_ROW_MAJOR, k.field, (size_t)c->max_batch, (size_t)(n));
+#define URF_X_LASERS128(field, n) f(URF_SCR_LASERS128, k.field, (size_t)c->max_batch, (size_t)(n));
     URF_SCRATCH_SCANS(URF_X_SCANS)
     URF_SCRATCH_SLOTS(URF_X_SLOTS)
     URF_SCRATCH_CAPTURE(URF_X_CAPTURE)
     URF_SCRATCH_ROW_MAJOR(URF_X_ROW_MAJOR)
+    URF_SCRATCH_LASERS128(URF_X_LASERS128)
 #undef URF_X_SCANS
 #undef URF_X_SLOTS
 #undef URF_X_CAPTURE
 #undef URF_X_ROW_MAJOR
+#undef URF_X_LASERS128
 }
 
 /* Allocates the arrays of `group` that are missing (URF_OK: all of them are there). */
@@ -725,6 +737,24 @@ extern "C" int urf_set_front_mode(urf_ctx* c, int mode)
     return URF_OK;
 }
 
+extern "C" int urf_set_front_lasers128(urf_ctx* c, int on)
+{
+    if (!c || (on != 0 && on != 1))
+        return URF_ERR_INVALID_ARG;
+    if (on) {   /* what the fused kernels size for 64 lanes, sized for 128: allocated once, with the first call that turns the switch on */
+        URF_HIP(c, hipSetDevice(c->device));
+        const int rc = scratch_alloc(c, URF_SCR_LASERS128);
+        if (rc != URF_OK)
+            return rc;
+    }
+    if ((on != 0) != c->pol.lasers128)   /* (a new start) */
+        c->pol.forget_front();
+    c->pol.set(c->pol.lasers128, on != 0);
+    if (on)
+        c->pol.set(c->pol.want_ring_sorted, false);
+    return URF_OK;
+}
+
 extern "C" int urf_front_scans(urf_ctx* c, uint32_t* n_fused)
 {
     if (!c || !n_fused)
@@ -932,15 +962,27 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
         stage++;
     };
     mark();
-    if (a.front_rows)
+    const bool l128 = a.front_lsh == 7u;   /* 128 lasers per firing: the kernels of urf_front128.hpp */
+    if (l128 && a.front) {   /* ... and their candidate lists (URF_FRONT128_CAND_CAP) */
+        a.front_cand = a.front_cand128;
+        a.front_all = a.front_all128;
+        a.front_cand_cap = URF_FRONT128_CAND_CAP(c->max_points);
+    }
+    if (a.front_rows && l128)
+        hipLaunchKernelGGL(k_rows_probe128, g_scan, dim3(256), 0, st, a, dp);
+    else if (a.front_rows)
         hipLaunchKernelGGL(k_rows_probe, g_scan, dim3(256), 0, st, a, dp);
     hipLaunchKernelGGL(k_ring_table, g_scan, dim3(URF_TABLE_THREADS), 0, st, a, dp);
     mark();
-    if (a.front_rows)
+    if (a.front_rows && l128)
+        hipLaunchKernelGGL(k_transpose128, g_tiles, dim3(256), 0, st, a);
+    else if (a.front_rows)
         hipLaunchKernelGGL(k_transpose, g_tiles, dim3(256), 0, st, a);
     if (a.front) {   /* (a tile is URF_TILE points, whatever the laser count: URF_TILE / L firings) */
         const dim3 g_front((a.tiles + a.front_tpb - 1) / a.front_tpb, n_scans);
-        if (a.front_lsh == 6u)
+        if (l128)
+            hipLaunchKernelGGL(k_front128, g_front, dim3(64), 0, st, a, dp);
+        else if (a.front_lsh == 6u)
             hipLaunchKernelGGL(front_kernel(dp.p.curbPoints), g_front, dim3(64), 0, st, a, dp);
         else if (a.front_lsh == 5u)
             hipLaunchKernelGGL(k_front32, g_front, dim3(64), 0, st, a, dp);
@@ -963,9 +1005,10 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
      * own), they are bound by vector issue.  With the per-kernel event brackets on (urf_enable_kernel_timing) everything stays on one
      * stream, so that the brackets add up to the step. */
     bool side = false, part1 = false;
-    const size_t finish_lds = (size_t)a.tiles * 384 + 2 * URF_FINISH_CHUNK * sizeof(urf_u2);
+    const size_t finish_lds = (size_t)(l128 ? URF_FRONT128_TILES2(a.tiles) : a.tiles) * 384 + 2 * URF_FINISH_CHUNK * sizeof(urf_u2);
+    const urf_front_finish_fn finish = l128 ? k_front_finish128 : front_finish_kernel(dp.p.curbPoints);
     if (a.front && !ev && !slot && side_fork(c, st)) {
-        hipLaunchKernelGGL(front_finish_kernel(dp.p.curbPoints), g_scan, dim3(URF_FINISH_THREADS), finish_lds, c->side_stream, a, dp, 1u);
+        hipLaunchKernelGGL(finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, c->side_stream, a, dp, 1u);
         part1 = true;
         side = hipEventRecord(c->ev_join, c->side_stream) == hipSuccess;
         if (!side)   /* (cannot be joined by an event: wait for it here) */
@@ -1018,7 +1061,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
     if (a.front) {
         if (side && hipStreamWaitEvent(st, c->ev_join, 0) != hipSuccess)
             (void)hipStreamSynchronize(c->side_stream);
-        hipLaunchKernelGGL(front_finish_kernel(dp.p.curbPoints), g_scan, dim3(URF_FINISH_THREADS), finish_lds, st, a, dp, part1 ? 2u : 0u);   /* (2: the star-shaped hits, the hand-over to k_beams) */
+        hipLaunchKernelGGL(finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, st, a, dp, part1 ? 2u : 0u);   /* (2: the star-shaped hits, the hand-over to k_beams) */
     }
     /* the rings that hold a point with a NaN azimuth (k_split listed them: normally none, the kernel returns at once) */
     if (!(a.optimistic & URF_OPT_NO_NAN))
@@ -1030,7 +1073,9 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
         hipLaunchKernelGGL(k_label_list, dim3(c->n_cus * 4), dim3(URF_LABEL_TILE_THREADS), 0, st, a, dp);
     else
         hipLaunchKernelGGL(k_label, g_tiles, dim3(URF_LABEL_TILE_THREADS), 0, st, a, dp);
-    if (a.front)
+    if (a.front && l128)
+        hipLaunchKernelGGL(k_label_front128, g_tiles, dim3(URF_LABEL_TILE_THREADS), 0, st, a, dp);
+    else if (a.front)
         hipLaunchKernelGGL(k_label_front, g_tiles, dim3(URF_LABEL_TILE_THREADS), 0, st, a, dp);
     mark();
     URF_HIP(c, hipGetLastError());

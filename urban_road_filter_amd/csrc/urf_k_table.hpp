@@ -220,6 +220,8 @@ __device__ void urf_ring_table_scan(const urf_kargs& a, const urf_dev_params& dp
     unsigned off, len;
     urf_scan_range(a, s, off, len);
     const unsigned C = (unsigned)dp.p.channels;
+    if (first_walk && a.front && a.front_lsh == 7u && tid < 128u)
+        a.front_lane_ring128[(size_t)s * 128u + tid] = 0xffffffffu;   /* (128 lasers per firing, urf_front128.hpp: the laser slots' rings, as k_ring_table does for 64) */
     if (tid == 0) {
         urf_scan_info in;
         in.status = URF_OK;      /* k_offsets turns it into URF_TOO_FEW_POINTS when piece < 30 */
@@ -355,13 +357,13 @@ __device__ void urf_ring_table_scan(const urf_kargs& a, const urf_dev_params& dp
      * Tried when the walk's first step (64 points: one row's) has shown at most one ring; given up as soon as the 64 points around
      * a row's first one show a second ring (a sweep in firing order whose first firing lies outside the region of interest). */
     bool rows = false;
-    bool rows_try = first_walk && (a.front || a.front_sight) && C == (1u << a.front_lsh) && len >= 2u * C && (len & (C - 1u)) == 0u;   /* (C = 64, 32, 16 rows) */   /* (not k_table_repair's walk: that one follows a failure) */
+    bool rows_try = first_walk && (a.front || a.front_sight) && C == (1u << a.front_lsh) && len >= 2u * C && (len & (C - 1u)) == 0u;   /* (C = 128, 64, 32, 16 rows) */   /* (not k_table_repair's walk: that one follows a failure) */
     if (rows_try && a.front_rows) {
         /* k_rows_probe has found the rows' first points and put them through the reference's insertion: rows_ok[s] - 1 leaders, in row order */
         const unsigned nr = a.rows_ok[s];   /* (uniform) */
         if (nr) {
             if (tid < nr - 1u)
-                L[tid] = a.rows_v[(size_t)s * 64u + tid];
+                L[tid] = a.front_lsh == 7u ? a.rows_v128[(size_t)s * 128u + tid] : a.rows_v[(size_t)s * 64u + tid];   /* (128 rows: k_rows_probe128) */
             if (tid == 0) {
                 sh_nL = nr - 1u;
                 a.front_ok[s] = URF_FRONT_ROWS;
