@@ -363,13 +363,15 @@ int urf_compact_indices_batch(urf_ctx* ctx, const uint8_t* d_labels, uint32_t n_
  * literally by a single wave -- the ring is nearly sorted by then, Lomuto's scheme is quadratic on that: about 1 ms per ring of
  * 2048 points (the same holds for urf_marker_points and for a ring with a NaN azimuth).  A sensor that delivers exact duplicates
  * (dual returns written twice) in many rings makes these two entry points tens of milliseconds slower; the labels are not affected.
- * LIFETIME: urf_ordered_indices*, urf_marker_points* and urf_read_stage run kernels over the LAST
- * classify call's results, which include the caller's own buffers of that call: d_labels (all three)
- * and, for calls with ragged offsets, nothing else -- the x / y / z these kernels need were copied
- * into the context's scratch by the call itself.  d_labels of the last classify call must therefore
- * stay allocated and unmodified until the last of these calls on it has completed (for a sweep of the
- * callback path the library owns that buffer: nothing to keep alive).  urf_clouds_batch_* (above) read the last batch
- * call's inputs as well: x / y / z of a SoA call, the message bytes of a PointCloud2 call. */
+ * LIFETIME: urf_ordered_indices*, urf_marker_points* and urf_read_stage run kernels over the LAST classify call's results, which
+ * include buffers of the caller's.  d_labels of that call is always among them and must stay allocated and unmodified until the last of
+ * these calls on it has completed (for a sweep of the callback path the library owns that buffer: nothing to keep alive).  After a call
+ * through the general kernels nothing else is: the x / y / z these kernels need were copied into the context's scratch by the call
+ * itself.  A call that took the fused front end (below) kept no such copies, so its INPUT must stay alive as well -- x / y / z of a
+ * SoA call; a PointCloud2 call's staged copy is the context's -- in either position of urf_set_front_outputs: with the switch off the
+ * call is run again from it (and d_labels rewritten with the same bytes), with the switch on x / y / z and d_labels are read where
+ * they are and nothing of the caller's is written.  urf_clouds_batch_* (above) read the last batch call's inputs in any case:
+ * x / y / z of a SoA call, the message bytes of a PointCloud2 call. */
 int urf_ordered_indices(urf_ctx* ctx, uint32_t scan, uint32_t* road, uint32_t* curb, uint32_t* ring10,
                         uint32_t* counts);
 /* Every scan of the last classify call at once, results on the DEVICE (asynchronous on the
@@ -516,11 +518,13 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * its times are in profiles/curb_points_bench.json.  urf_read_stage / urf_ordered_indices* / urf_marker_points* read ring-sorted intermediate
  * results: after a call that took the fused front end they first run that call again through the general kernels
  * (the call's INPUT arrays must then still be alive, like its label buffer), and the context stays with the general
- * kernels afterwards (until urf_set_front_mode is called again with a mode other than 0).  A context that has handed a
+ * kernels afterwards (until urf_set_front_mode is called again with a mode other than 0).  urf_set_front_outputs(ctx, 1) spares
+ * urf_ordered_indices*, urf_clouds_batch_* (reference order) and urf_marker_points* that second run and its consequence.  A context that has handed a
  * scan back launches the general kernels as full grids next to the fused ones from then on, and one that has handed a
  * whole batch back (unorganised clouds) stops trying in mode 1; urf_set_params with other parameters and
  * urf_set_front_mode with another mode forget both.  urf_front_scans: how many scans of the last batch call took the
- * fused front end (synchronises).
+ * fused front end (synchronises); a scan that kept its flag but has no result -- fewer than 30 points in the region of interest: nothing
+ * is published for it by either kind of kernel -- is counted.
  *
  * 128 lasers per firing (urf_set_front_lasers128, urban_road_filter_amd/csrc/urf_front128.hpp): with the switch on, channels == 128 and
  * curbPoints == 5, modes 2 and 3 -- never modes 0 and 1 -- also take sweeps of 128 lasers per firing, in firing order (point f * 128 + l)
@@ -536,6 +540,17 @@ int urf_front_scans(urf_ctx* ctx, uint32_t* n_fused);
  * firing (firing order: point f * 128 + l; row-major: 128 rows) through the fused front end.  Forgets sightings / hand-backs
  * like urf_set_front_mode.  Anything else: URF_ERR_INVALID_ARG. */
 int urf_set_front_lasers128(urf_ctx* ctx, int on);
+/* 0 (default): after a call that took the fused front end, urf_ordered_indices*, urf_clouds_batch_* with
+ * URF_ORDER_REFERENCE and urf_marker_points* first run that call again through the general kernels, and the context stays with those.
+ * 1: these read-outs take a fused call's results as they are (urban_road_filter_amd/csrc/urf_k_front_outputs.hpp: the rings' points
+ * in order from the front end's presence words, per scan on the device; a scan that was handed back is read as ever): no second
+ * run, urf_front_scans still reports the call, the next batch call is fused again without a urf_set_front_mode, the caller's d_labels
+ * and x / y / z (SoA; PointCloud2: the context's staged copy) are read and never written -- they must stay alive and unmodified until
+ * the read-out has completed.  Same lists and marker points, bit for bit; 16, 32, 64 and 128 lasers, every fused curbPoints, firing
+ * order and row-major, the callback path's fused sweeps included.  urf_read_stage keeps the second run in either position: stage
+ * values are defined as the general kernels'.  The switch decides nothing about which kernels classify and forgets no sighting or
+ * hand-back.  The read-outs' scratch grows with their first use (URF_ERR_OOM from that call).  Anything else: URF_ERR_INVALID_ARG. */
+int urf_set_front_outputs(urf_ctx* ctx, int on);
 
 /* ---- per-kernel timing (benchmark) ------------------------------------------
  * With timing on, every classify call brackets each kernel of the pipeline

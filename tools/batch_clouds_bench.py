@@ -2,7 +2,7 @@
 """tools/batch_clouds_bench.py -- ragged PointCloud2 batches and the published clouds of a batch on the device
 (urf_classify_batch_pc2_ragged, urf_clouds_batch_pc2), measured on one MI355X.  Prints ONE JSON line.
 
-    python tools/batch_clouds_bench.py [--scans 1024] [--steps 20] [--warmup 3] [--parity-scans 3] [--profile]
+    python tools/batch_clouds_bench.py [--scans 1024] [--steps 20] [--warmup 3] [--parity-scans 3] [--profile] [--front-outputs]
 
 Workload 1 (cfg3): S synthetic 64 x 2048 street sweeps (scene 1), resident, as 32-byte pcl::PointXYZI PointCloud2 records
 with intensity.  Timed with device events after warm-up, mean per call:
@@ -16,6 +16,9 @@ output record; the reference order adds one 4-byte list entry per gathered recor
 (k_ring_order, k_ordered_lists) uncounted.  GB/s = bytes / call time; share of the 8 TB/s HBM peak.
 Workload 2: S sensor-like sweeps (scene 3) with their drop-outs removed (every message has another length), 32-byte records.
 A parity gate runs first: the records of --parity-scans sampled scans of each workload against the CPU oracle (tests/oracles.py).
+--front-outputs: urf_set_front_outputs(ctx, 1) -- the reference order takes the fused batch as it is (no second run, the context stays
+fused; the flag also adds classify_after_reference_ms, the classify call behind that read-out, and front_scans_after_reference).
+Without the flag the tool does what it did before the flag existed.
 --profile: only a few calls of each, for `rocprofv3 --kernel-trace --stats` (per-kernel times come from that run, not this one).
 """
 import argparse
@@ -159,6 +162,10 @@ def run_workload(torch, u, ctx, scans, p, args, name, ragged_only):
         res["clouds_input_ms_runs"] = t_in[0]
         res["clouds_input_nt_ms_runs"] = t_in[NT_FLAG]
     res["clouds_reference_ms"] = timed(clouds(u.ORDER_REFERENCE), steps, warmup)
+    if args.front_outputs:   # the classify call behind the read-out stays fused: timed, then the state the counts below are read from again
+        res["classify_after_reference_ms"] = timed(classify, steps, warmup)
+        res["front_scans_after_reference"] = ctx.front_scans()
+        clouds(u.ORDER_REFERENCE)()
     cnt = d_cnt.cpu().numpy().astype(np.int64).reshape(S, 4)
     n_rec = int(cnt.sum())
     n_roi = int(cnt[:, 2].sum())
@@ -183,6 +190,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--parity-scans", type=int, default=3)
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--front-outputs", action="store_true")
     args = ap.parse_args()
     import torch
     import urban_road_filter_amd as u
@@ -192,15 +200,21 @@ def main():
     p = O.cfg_params("cfg2")
     t0 = time.time()
     out = {"metric": "batch_clouds", "device": torch.cuda.get_device_name(0), "timing": "device events, mean per call after warm-up"}
+    if args.front_outputs:
+        out["front_outputs"] = True
     # one non-default stream for torch's copies, the library's kernels and the timing events (the null stream's handle would
     # leave the library on a stream of its own)
     st = torch.cuda.Stream()
     with torch.cuda.stream(st):
         with u.Context(N_PTS, args.scans, params=p, hooks=True) as ctx:
             ctx.set_stream(st.cuda_stream)
+            if args.front_outputs:
+                ctx.set_front_outputs(1)
             out["cfg3"] = run_workload(torch, u, ctx, gen(args.scans, 1, 1, False), p, args, "cfg3", False)
         with u.Context(N_PTS, args.scans, params=p, hooks=True) as ctx:
             ctx.set_stream(st.cuda_stream)
+            if args.front_outputs:
+                ctx.set_front_outputs(1)
             out["sensor_ragged"] = run_workload(torch, u, ctx, gen(args.scans, 3, 1, True), p, args, "sensor_ragged", True)
     out["wall_s"] = time.time() - t0
     print(json.dumps(out))

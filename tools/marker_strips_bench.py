@@ -2,7 +2,7 @@
 """tools/marker_strips_bench.py -- road_marker's line strips for a resident batch (urf_marker_strips_batch), measured on one MI355X.
 Prints ONE JSON line.
 
-    python tools/marker_strips_bench.py [--scans 1024] [--repeats 7] [--warmup 3] [--baseline-root DIR]
+    python tools/marker_strips_bench.py [--scans 1024] [--repeats 7] [--warmup 3] [--baseline-root DIR] [--front-outputs]
 
 S synthetic 64 x 2048 street sweeps (scenes 1 and 2 alternating), resident; urf_classify_batch_soa + urf_marker_points_batch
 run first (not timed), then:
@@ -18,6 +18,9 @@ run first (not timed), then:
                             (baseline_build_ms: tools/marker_builder_baseline.cpp compiled against --baseline-root, the root of a
                             checkout of the parent commit with its library built; default: this checkout, whose MarkerBuilder
                             runs the new host code -- say which one a recorded figure used)
+--front-outputs: urf_set_front_outputs(ctx, 1) -- urf_marker_points_batch takes the fused batch as it is (marker_points_ms: the call by
+itself, device events, median, only with the flag; every repeat after the first finds the pre-pass done).  Without the flag the tool does
+what it did before the flag existed.
 A parity gate runs first: every scan's records against urf_marker_strips on the copied marker points.
 """
 import argparse
@@ -59,6 +62,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--baseline-root", default=ROOT)
+    ap.add_argument("--front-outputs", action="store_true")
     args = ap.parse_args()
     import torch
     import urban_road_filter_amd as u
@@ -75,6 +79,8 @@ def main():
     st = torch.cuda.Stream()
     with torch.cuda.stream(st), u.Context(N_PTS, S, params=p) as ctx:
         ctx.set_stream(st.cuda_stream)
+        if args.front_outputs:
+            ctx.set_front_outputs(1)
         d_xyz_in = [torch.from_numpy(np.concatenate([s[k] for s in scans])).to(dev) for k in range(3)]
         labels = torch.empty(S * N_PTS, dtype=torch.uint8, device=dev)
         d_pts = torch.empty(S * u.MARKER_MAX_POINTS * 4, dtype=torch.float32, device=dev)
@@ -89,6 +95,17 @@ def main():
         ctx.classify_batch_soa(d_xyz_in[0], d_xyz_in[1], d_xyz_in[2], N_PTS, S, labels)
         ctx.marker_points_batch(d_pts, d_cnt)
         torch.cuda.synchronize()
+        if args.front_outputs:   # the read-out the flag changes, by itself
+            mk_ms = []
+            for _ in range(args.warmup + args.repeats):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                ctx.marker_points_batch(d_pts, d_cnt)
+                e1.record()
+                torch.cuda.synchronize()
+                mk_ms.append(e0.elapsed_time(e1))
+            out.update({"front_outputs": True, "marker_points_ms": statistics.median(mk_ms[args.warmup:]),
+                        "front_scans_after_marker_points": ctx.front_scans()})
 
         def call():
             d_ghost.zero_()

@@ -176,6 +176,7 @@ def lib(hooks=False):
         "urf_set_front_mode": [vp, C.c_int],
         "urf_front_scans": [vp, C.c_void_p],
         "urf_set_front_lasers128": [vp, C.c_int],
+        "urf_set_front_outputs": [vp, C.c_int],
         "urf_callback_path_preset": [vp, C.c_uint32],
     }
     for name, args in sig.items():
@@ -394,6 +395,12 @@ class Context:
         """urf_set_front_lasers128: 1 lets front modes 2 and 3 take sweeps of 128 lasers per firing too (channels == 128, curb_points == 5,
         firing order or row-major, at most 128 x 2048 points; include/urf.h); 0 (default) keeps them on the general kernels.  Opt-in."""
         self._check(self._lib.urf_set_front_lasers128(self._h, int(on)), "urf_set_front_lasers128")
+
+    def set_front_outputs(self, on):
+        """urf_set_front_outputs: 1 lets ordered_indices*, clouds_batch_* in the reference order and marker_points* take the results of a call
+        that went through the fused front end as they are (no second run through the general kernels, the context stays fused, the
+        caller's labels are only read; include/urf.h); 0 (default) keeps the second run.  read_stage keeps it either way."""
+        self._check(self._lib.urf_set_front_outputs(self._h, int(on)), "urf_set_front_outputs")
 
     def callback_path_preset(self, sequence_bits):
         """urf_callback_path_preset: 2 work-list kernels | 4 NaN-azimuth rings | 16 std::sort's tie order, ahead of the first sweep that needs them."""

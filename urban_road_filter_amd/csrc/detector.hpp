@@ -94,6 +94,14 @@ public:
      * azimuth inside a ring -- lidar_segmentation.cpp:289-291, 354-367) instead of input order.
      * Costs one extra per-ring sort on the GPU; roi is in input order either way. */
     void setReferenceOrder(bool on) { reference_order_ = on; }
+    /* urf_set_front_outputs: the reference order and road_marker of a sweep that took the fused front end (a row-major organised
+     * stream) come from that run as it is, instead of a second one through the general kernels that keeps the context on them. */
+    void setFrontOutputs(bool on)
+    {
+        const int rc = urf_set_front_outputs(ctx_, on ? 1 : 0);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_set_front_outputs");
+    }
 
     /* Also build the "road_marker" MarkerArray (lidar_segmentation.cpp:295-351, 369-602, topic :59,601);
      * fixedFrame = params::fixedFrame (cfg:10).  Off by default: the polygon is a visualisation product. */
@@ -196,6 +204,13 @@ public:
     void setParams(const urf_params& p);
     urf_params params() const;
     void setReferenceOrder(bool on) { reference_order_ = on; }
+    /* as Detector's: with it, batches that take the fused front end keep taking it with setReferenceOrder(true) / enableRoadMarker(true) */
+    void setFrontOutputs(bool on)
+    {
+        const int rc = urf_set_front_outputs(ctx_, on ? 1 : 0);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_set_front_outputs");
+    }
 
     /* As Detector's: also build "road_marker" for every message (off by default; the polygon parameters start from
      * urf_default_marker_params, as Detector's do).  Switching it on starts a new drive. */

@@ -25,6 +25,7 @@
 #include "urf_kernels.hpp"
 #include "urf_front.hpp"
 #include "urf_front128.hpp"
+#include "urf_k_front_outputs.hpp"
 
 #define URF_ASYNC_SLOTS 4
 static_assert(URF_ASYNC_SLOTS == URF_MAX_IN_FLIGHT, "include/urf.h documents the number of sweeps in flight");
@@ -149,6 +150,10 @@ struct __attribute__((visibility("hidden"))) urf_policy {
     bool lasers128 = false;         /* urf_set_front_lasers128: modes 2 and 3 take sweeps of 128 lasers per firing too (urf_front128.hpp; its scratch is there) */
     uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
     bool want_ring_sorted = false;
+    /* urf_set_front_outputs: the published order and the marker points of a fused call come from what it left on the device
+     * (urf_k_front_outputs.hpp) instead of a second run through the general kernels.  Decides no launch of a classify call: not part of
+     * the epoch. */
+    bool front_outputs = false;
     /* k_front hands a scan without the shape back to the general kernels: launched list-driven until a call has done so
      * (URF_FLAG_FRONT_HANDED_BACK: front_direct, full grids from then on); mode 1 stops trying once a whole batch has been handed back
      * (URF_FLAG_FRONT_ALL_HANDED_BACK: front_off, unorganised clouds).  forget_front() starts over. */
@@ -302,6 +307,13 @@ struct urf_ctx {
     lazy_buf<uint32_t> ord_pos;
     lazy_buf<uint32_t> ord_cls;     /* [scans][URF_MAX_CHANNELS][2] road / curb points per ring (k_ring_order -> k_ordered_lists) */
     lazy_buf<uint32_t> ord_lists;   /* single-scan entry point: 3 x sstride + 4 */
+    /* the read-outs of a fused call (urf_k_front_outputs.hpp): [scans][sstride] per ring-major position the exact azimuth's bits, the entry
+     * input index | class << 30 and the planar distance.  k_front_out_prep fills them once per recorded call and range of scans (fo_prep:
+     * the call's number and the range they hold; nobody writes them afterwards), for urf_ordered_indices* and urf_marker_points* alike. */
+    lazy_buf<uint32_t> fo_az, fo_ent;
+    lazy_buf<float> fo_d;
+    struct { uint64_t seq = 0; uint32_t s0 = 0, n = 0; } fo_prep;
+    uint64_t last_seq = 0;          /* bumped whenever `last` is written */
     lazy_buf<float> mk_d;
     lazy_buf<uint32_t> mk_pos;
     lazy_buf<uint8_t> mk_red;       /* ... and one flag per ring and scan behind the cells (k_marker_ring_literal) */
@@ -667,6 +679,7 @@ extern "C" int urf_set_stream(urf_ctx* c, void* hip_stream)
         return URF_ERR_INVALID_ARG;
     c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     c->pol.epoch++;
+    c->fo_prep.seq = 0;   /* (what k_front_out_prep wrote on the stream before is not ordered in front of this one) */
     return URF_OK;
 }
 
@@ -752,6 +765,14 @@ extern "C" int urf_set_front_lasers128(urf_ctx* c, int on)
     c->pol.set(c->pol.lasers128, on != 0);
     if (on)
         c->pol.set(c->pol.want_ring_sorted, false);
+    return URF_OK;
+}
+
+extern "C" int urf_set_front_outputs(urf_ctx* c, int on)
+{
+    if (!c || (on != 0 && on != 1))
+        return URF_ERR_INVALID_ARG;
+    c->pol.front_outputs = on != 0;   /* (the read-outs' scratch grows with their first use: front_out_prepare) */
     return URF_OK;
 }
 
@@ -1089,6 +1110,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
 static void publish_last(urf_ctx* c, int kind, uint32_t scans, const urf_kargs& a, const urf_dev_params& dp, uint32_t row = 0, uint64_t gen = 0)
 {
     c->last = urf_last_call{ kind, scans, a, dp, row, gen };
+    c->last_seq++;
 }
 
 /* a call of the public batch entry points: published after a successful call that was not empty (an empty one leaves the last call as it was) */
@@ -1539,7 +1561,8 @@ static const urf_last_call* last_valid(urf_ctx* c, uint32_t scan = 0, int kind =
 /* The readers' way to the last call and its scratch ROW: valid, on the context's device, the row intact and ring-sorted, the context's
  * stream behind the sweeps in flight.  A sweep's row is only intact while no later sweep has been submitted on it (slots that share a
  * row: max_batch < URF_MAX_IN_FLIGHT and more sweeps in flight than rows). */
-static int last_call(urf_ctx* c, uint32_t scan, const urf_last_call*& out)
+enum urf_last_need { URF_NEED_RING_SORTED, URF_NEED_RING_ORDER };   /* the row's ring-sorted copies (urf_read_stage) | the rings' points in order, from either path */
+static int last_call(urf_ctx* c, uint32_t scan, const urf_last_call*& out, urf_last_need need)
 {
     urf_last_call& l = c->last;
     if (!(out = last_valid(c, scan)))
@@ -1551,15 +1574,18 @@ static int last_call(urf_ctx* c, uint32_t scan, const urf_last_call*& out)
         return URF_ERR_BUSY;
     }
     int rc = URF_OK;
-    if (l.a.front) {
+    if (l.a.front && !(need == URF_NEED_RING_ORDER && c->pol.front_outputs)) {
         /* the last call went through the fused front end (urf_front.hpp), which keeps no ring-sorted copies: once more on its row through
          * the general kernels, as a batch call with every repair kernel in the sequence (same inputs -- a batch caller's arrays must still
          * be alive, a sweep of the callback path is still in its slot's device buffer and its row has not been resubmitted (checked
          * above) --, same parameters, same labels), and the context stays with them: a caller that reads ring-sorted results pays for
-         * them once, not per call.  Only the record's arguments and parameters change: a sweep stays the sweep it was. */
+         * them once, not per call.  Only the record's arguments and parameters change: a sweep stays the sweep it was.
+         * With urf_set_front_outputs on, the entry points that only need the rings' points in order (URF_NEED_RING_ORDER) take the fused
+         * call as it is: launch_ordered / launch_markers run the kernels of urf_k_front_outputs.hpp next to the general ones. */
         c->pol.set(c->pol.want_ring_sorted, true);
         rc = run_pipeline(c, urf_call{ l.a.x, l.a.y, l.a.z, l.a.offsets, l.a.n_per_scan, l.a.max_len, l.a.n_scans, l.a.labels, nullptr, l.row,
                                        nullptr, &l.dp, (int)l.a.capture, true }, l.a, l.dp);
+        c->last_seq++;
     }
     return rc != URF_OK ? rc : order_after_slots(c);
 }
@@ -1606,17 +1632,46 @@ static int ensure_order_scratch(urf_ctx* c, uint32_t n_scans)
     return grow(c, c->ord_cls, (size_t)n_scans * URF_MAX_CHANNELS * 2, c->stream);
 }
 
+/* The pre-pass of the read-outs of a fused call (urf_k_front_outputs.hpp) for scans [s0, s0 + n) of the last call: scratch, then
+ * k_front_out_prep unless the arrays already hold exactly that (same recorded call, same range). */
+static int front_out_prepare(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t n)
+{
+    const size_t cnt = (size_t)n * c->sstride;
+    const bool regrow = cnt > c->fo_az.cap || cnt > c->fo_ent.cap || cnt > c->fo_d.cap;
+    int rc;
+    if ((rc = grow(c, c->fo_az, cnt, c->stream)) != URF_OK || (rc = grow(c, c->fo_ent, cnt, c->stream)) != URF_OK ||
+        (rc = grow(c, c->fo_d, cnt, c->stream)) != URF_OK) {
+        c->fo_prep.seq = 0;
+        return rc;
+    }
+    if (!regrow && c->fo_prep.seq == c->last_seq && c->fo_prep.s0 == s0 && c->fo_prep.n == n)
+        return URF_OK;
+    c->fo_prep.seq = 0;
+    hipLaunchKernelGGL(k_front_out_prep, dim3(l.a.tiles, n), dim3(256), 0, c->stream, l.a, l.dp, s0, c->fo_az.p, c->fo_ent.p, c->fo_d.p);
+    URF_HIP(c, hipGetLastError());   /* (the mark only behind a launch that was accepted) */
+    c->fo_prep.seq = c->last_seq;
+    c->fo_prep.s0 = s0;
+    c->fo_prep.n = n;
+    return URF_OK;
+}
+
 /* scans [s0, s0 + n) of the last classify call (l: from last_call), lists of `stride` entries per scan on the device */
 static int launch_ordered(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t n, uint32_t* d_road, uint32_t* d_curb, uint32_t* d_r10,
                           uint32_t stride, uint32_t* d_counts)
 {
-    const int rc = ensure_order_scratch(c, n);
-    if (rc != URF_OK)
-        return rc;
     const urf_kargs& a = l.a;   /* the call's own arguments and parameters, whatever was set since */
     const urf_dev_params& dp = l.dp;
+    const bool fused = a.front != 0;   /* (last_call: only with urf_set_front_outputs on) a scan is either kind's, decided on the device */
+    int rc = ensure_order_scratch(c, n);
+    if (rc == URF_OK && fused)
+        rc = front_out_prepare(c, l, s0, n);
+    if (rc != URF_OK)
+        return rc;
     hipLaunchKernelGGL(k_ring_order, dim3((unsigned)dp.p.channels, n), dim3(256), (2 * (size_t)a.tiles + 1) * sizeof(unsigned), c->stream, a, dp,
                        s0, c->ord_keys.p, c->ord_pos.p, c->ord_cls.p);
+    if (fused)
+        hipLaunchKernelGGL(k_ring_order_front, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, c->fo_az.p, c->fo_ent.p,
+                           c->ord_pos.p, c->ord_cls.p);
     hipLaunchKernelGGL(k_ordered_lists, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, c->ord_pos.p, c->ord_cls.p, d_road,
                        d_curb, d_r10, stride, d_counts);
     URF_HIP(c, hipGetLastError());
@@ -1629,7 +1684,7 @@ extern "C" int urf_ordered_indices_batch(urf_ctx* c, uint32_t* d_road, uint32_t*
     const urf_last_call* l = c ? last_valid(c) : nullptr;
     if (!l || !d_counts || stride < l->a.max_len)
         return URF_ERR_INVALID_ARG;
-    const int rc = last_call(c, 0, l);
+    const int rc = last_call(c, 0, l, URF_NEED_RING_ORDER);
     return rc != URF_OK ? rc : launch_ordered(c, *l, 0, l->scans, d_road, d_curb, d_ring10, stride, d_counts);
 }
 
@@ -1641,7 +1696,7 @@ extern "C" int urf_ordered_indices(urf_ctx* c, uint32_t scan, uint32_t* road, ui
     const size_t mp = c->sstride;
     const urf_last_call* l;
     int rc;
-    if ((rc = last_call(c, scan, l)) != URF_OK || (rc = grow(c, c->ord_lists, mp * 3 + 4)) != URF_OK)
+    if ((rc = last_call(c, scan, l, URF_NEED_RING_ORDER)) != URF_OK || (rc = grow(c, c->ord_lists, mp * 3 + 4)) != URF_OK)
         return rc;
     uint32_t* d_road = c->ord_lists.p;
     uint32_t* d_curb = d_road + mp;
@@ -1693,7 +1748,7 @@ static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, ur
         return rc;
     if (ref) {   /* urf_ordered_indices_batch's kernels (after a fused call: the documented rerun through the general kernels) */
         uint32_t* const o = c->cl_lists.p;
-        if ((rc = last_call(c, 0, l)) == URF_OK)
+        if ((rc = last_call(c, 0, l, URF_NEED_RING_ORDER)) == URF_OK)
             rc = launch_ordered(c, *l, 0, S, o, o + (size_t)S * stride, o + 2 * (size_t)S * stride, stride, o + 3 * (size_t)S * stride);
     } else {
         rc = order_after_slots(c);   /* cl_tiles is the context's; the input order needs nothing ring-sorted of the row */
@@ -1788,12 +1843,23 @@ static int launch_markers(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint3
         return rc;
     const urf_kargs& a = l.a;
     const urf_dev_params& dp = l.dp;
+    const bool fused = a.front != 0;   /* (as in launch_ordered) */
+    if (fused && (rc = front_out_prepare(c, l, s0, n)) != URF_OK)
+        return rc;
     uint8_t* const mk_lit = c->mk_red.p + n * cells;
     hipLaunchKernelGGL(k_marker_ring, dim3((unsigned)dp.p.channels, n), dim3(256), (2 * (size_t)a.tiles + 1) * sizeof(unsigned), c->stream, a, dp, s0,
                        c->mk_d.p, c->mk_pos.p, c->mk_red.p, mk_lit);
     /* rings in which the ORDER of equal azimuths decides a marker point (normally none: every workgroup returns at once) */
     hipLaunchKernelGGL(k_marker_ring_literal, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, mk_lit, c->mk_d.p, c->mk_pos.p, c->mk_red.p);
+    if (fused) {
+        hipLaunchKernelGGL(k_marker_ring_front, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, c->fo_az.p, c->fo_ent.p,
+                           c->fo_d.p, c->mk_d.p, c->mk_pos.p, c->mk_red.p, mk_lit);
+        hipLaunchKernelGGL(k_marker_ring_literal_front, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, mk_lit, c->fo_az.p,
+                           c->fo_ent.p, c->fo_d.p, c->mk_d.p, c->mk_pos.p, c->mk_red.p);
+    }
     hipLaunchKernelGGL(k_marker_bins, dim3(n), dim3(384), 0, c->stream, a, dp, s0, c->mk_d.p, c->mk_pos.p, c->mk_red.p, d_pts, d_counts);
+    if (fused)
+        hipLaunchKernelGGL(k_marker_bins_front, dim3(n), dim3(384), 0, c->stream, a, dp, s0, c->mk_d.p, c->mk_pos.p, c->mk_red.p, d_pts, d_counts);
     URF_HIP(c, hipGetLastError());
     return URF_OK;
 }
@@ -1803,7 +1869,7 @@ extern "C" int urf_marker_points_batch(urf_ctx* c, float* d_pts, uint32_t* d_cou
     if (!c || !d_pts || !d_counts)
         return URF_ERR_INVALID_ARG;
     const urf_last_call* l;
-    const int rc = last_call(c, 0, l);
+    const int rc = last_call(c, 0, l, URF_NEED_RING_ORDER);
     return rc != URF_OK ? rc : launch_markers(c, *l, 0, l->scans, d_pts, d_counts);
 }
 
@@ -1813,7 +1879,7 @@ extern "C" int urf_marker_points(urf_ctx* c, uint32_t scan, float* pts, uint32_t
         return URF_ERR_INVALID_ARG;
     const urf_last_call* l;
     int rc;
-    if ((rc = last_call(c, scan, l)) != URF_OK || (rc = grow(c, c->mk_out, URF_DEG_CELLS * 4 + 4)) != URF_OK)
+    if ((rc = last_call(c, scan, l, URF_NEED_RING_ORDER)) != URF_OK || (rc = grow(c, c->mk_out, URF_DEG_CELLS * 4 + 4)) != URF_OK)
         return rc;
     hipStream_t st = c->stream;
     unsigned* d_cnt = (unsigned*)(c->mk_out.p + URF_DEG_CELLS * 4);
@@ -1895,7 +1961,7 @@ extern "C" int urf_read_stage(urf_ctx* c, urf_stage what, uint32_t scan, void* h
     if (!c || !host_dst)
         return URF_ERR_INVALID_ARG;
     const urf_last_call* l;
-    int rc = last_call(c, scan, l);
+    int rc = last_call(c, scan, l, URF_NEED_RING_SORTED);   /* (stage values are the general kernels', whatever urf_set_front_outputs says) */
     if (rc != URF_OK)
         return rc;
     URF_HIP(c, hipStreamSynchronize(c->stream));

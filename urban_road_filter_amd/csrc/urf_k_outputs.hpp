@@ -5,6 +5,15 @@
 #ifndef URF_K_OUTPUTS_HPP
 #define URF_K_OUTPUTS_HPP
 
+/* A scan whose read-outs come from what the fused front end left on the device (urf_k_front_outputs.hpp, urf_set_front_outputs): the call was
+ * fused (the host runs a fused call again through the general kernels unless that switch is on, and the record then says front == 0), the
+ * scan kept its flag and has a result.  The kernels below that read ring-sorted copies return at once for such a scan, their siblings
+ * for every other. */
+__device__ __forceinline__ bool urf_scan_fused(const urf_kargs& a, unsigned s, const urf_scan_info& in)
+{
+    return a.front != 0u && in.status == URF_OK && a.front_ok[s] != 0u;
+}
+
 /* ------------------------------------------------------------------------- */
 /* index lists                                                                 */
 /* ------------------------------------------------------------------------- */
@@ -121,6 +130,8 @@ __global__ __launch_bounds__(256) void k_ring_order(urf_kargs a, urf_dev_params 
     unsigned* rord = rord_all + (size_t)blockIdx.y * a.sstride;
     unsigned* rcls = rcls_all + ((size_t)blockIdx.y * URF_MAX_CHANNELS + c) * 2;   /* road / curb points of the ring */
     const urf_scan_info in = a.info[s];
+    if (urf_scan_fused(a, s, in))
+        return;   /* (uniform) k_ring_order_front's */
     if (in.status != URF_OK || c >= in.n_rings) {
         if (tid < 2)
             rcls[tid] = 0;
@@ -368,6 +379,8 @@ __global__ __launch_bounds__(256) void k_marker_ring(urf_kargs a, urf_dev_params
     unsigned* m_pos = m_pos_all + blockIdx.y * cells;
     uint8_t* m_red = m_red_all + blockIdx.y * cells;
     const urf_scan_info in = a.info[s];
+    if (urf_scan_fused(a, s, in))
+        return;   /* (uniform) k_marker_ring_front's */
     if (in.status != URF_OK || c >= in.n_rings) {
         if (tid == 0)
             m_lit_all[(size_t)blockIdx.y * URF_MAX_CHANNELS + c] = 0;
@@ -535,6 +548,8 @@ __global__ __launch_bounds__(256) void k_marker_ring_literal(urf_kargs a, urf_de
                                                              float* m_d_all, unsigned* m_pos_all, uint8_t* m_red_all)
 {
     const unsigned c = blockIdx.x, s = s0 + blockIdx.y, tid = threadIdx.x;
+    if (urf_scan_fused(a, s, a.info[s]))
+        return;   /* (uniform) k_marker_ring_literal_front's; its flag is not written yet */
     if (!m_lit_all[(size_t)blockIdx.y * URF_MAX_CHANNELS + c])
         return;
     __shared__ int nrmin[URF_DEG_CELLS];
@@ -615,6 +630,8 @@ __global__ __launch_bounds__(384) void k_marker_bins(urf_kargs a, urf_dev_params
     unsigned* count = count_all + blockIdx.x;
     const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const urf_scan_info in = a.info[s];
+    if (urf_scan_fused(a, s, in))
+        return;   /* (uniform) k_marker_bins_front's */
     const unsigned nR = in.status == URF_OK ? in.n_rings : 0;
     unsigned id = 0xffffffffu;
     float red = 0.f;
