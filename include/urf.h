@@ -502,7 +502,8 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * in registers).  Decided per scan on the device; a scan without that shape takes the general kernels in the same
  * call; labels and summaries are identical either way.  Applies with channels == 64, 32 or 16 (the caller states the sensor's
  * laser count through `channels`, as the reference's user does in lidar_segmentation.cpp:4; a 32-laser sweep classified with channels
- * == 64 is handed back to the general kernels), curbPoints == 5, no stage capture, at most 128 x 2048 points per scan.  Row-major
+ * == 64 is handed back to the general kernels), curbPoints == 5, no stage capture, at most 128 x 2048 points per scan (128 tiles of 2048
+ * points; 256 tiles with urf_set_front_long_sweeps, below).  Row-major
  * organised clouds (below) have `channels` rows: point l * W + f.  mode 0: never; 1 (default): batch calls of at least 192 scans with channels == 64; with channels == 16 or 32 mode 1 never takes the fused
  * kernels -- no batch size, no row-major sighting, not on the callback path: they are opt-in through mode 2 until their crossover has been
  * measured (tools/front_lasers_bench.py) -- (below that the general kernels are faster: a sweep's fused kernels are
@@ -530,16 +531,31 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * curbPoints == 5, modes 2 and 3 -- never modes 0 and 1 -- also take sweeps of 128 lasers per firing, in firing order (point f * 128 + l)
  * or row-major (128 rows; sighted by one call, fused from the next on, the callback path included): one wave per block of the march, two
  * lasers (l and l + 64) per lane.  Everything above holds for them as well -- per-scan hand-back, identical labels and summaries,
- * urf_front_scans -- and so does the limit of 128 x 2048 points per scan: a 128 x 4096 sweep keeps the general kernels.  Every
+ * urf_front_scans -- and so does the limit of 128 x 2048 points per scan: a 128 x 4096 sweep keeps the general kernels unless
+ * urf_set_front_long_sweeps is on as well.  Every
  * 128-laser table entry is a ring to these kernels, entry 127 included (their records keep the ring in eight bits).  curbPoints != 5
  * keeps the general kernels at 128 lasers.  The switch is off by default and opt-in whatever tools/front_lasers_bench.py --lasers128
- * measures; turning it on allocates the per-scan tables these kernels need (URF_ERR_OOM: it stays off). */
+ * measures; turning it on allocates the per-scan tables these kernels need (URF_ERR_OOM: it stays off).
+ *
+ * Long sweeps (urf_set_front_long_sweeps): the limit of 128 tiles is the finish step's, which keeps a presence word and a count per
+ * (tile, laser slot) in LDS.  With the switch on, modes 2 and 3 -- never modes 0 and 1 -- also take batch calls whose longest scan has
+ * 129..256 tiles of 2048 points (256 tiles: a 128 x 4096 sweep; a 128-laser unit at 0.1 degree steps delivers 225, a 64-laser unit at
+ * 0.08 degrees 141), at every laser count the front end knows (16, 32, 64; 128 behind urf_set_front_lasers128), in firing order and
+ * row-major, ragged batches, the callback path's row-major sweeps and the read-outs of urf_set_front_outputs included: the same
+ * kernels, the finish step with the LDS that many tiles need (108 KiB at 256 tiles: one workgroup per CU).  A call of at most 128 tiles
+ * launches exactly what it launches with the switch off; a call of more than 256 tiles keeps the general kernels.  Opt-in: its times
+ * are in profiles/front_long_bench.json. */
 int urf_set_front_mode(urf_ctx* ctx, int mode);
 int urf_front_scans(urf_ctx* ctx, uint32_t* n_fused);
 /* 0 (default): as today.  1: with channels == 128 and curbPoints == 5, front modes 2 and 3 also send sweeps of 128 lasers per
  * firing (firing order: point f * 128 + l; row-major: 128 rows) through the fused front end.  Forgets sightings / hand-backs
  * like urf_set_front_mode.  Anything else: URF_ERR_INVALID_ARG. */
 int urf_set_front_lasers128(urf_ctx* ctx, int on);
+/* 0 (default): as today, the fused front end takes scans of at most 128 tiles (128 x 2048 points).  1: front modes 2 and 3 also send
+ * batch calls whose longest scan has 129..256 tiles through it (longer ones keep the general kernels).  Forgets sightings / hand-backs
+ * like urf_set_front_mode.  A device that does not grant a workgroup the LDS the finish step needs at 256 tiles: URF_ERR_OOM, and the
+ * switch stays off.  Anything else: URF_ERR_INVALID_ARG. */
+int urf_set_front_long_sweeps(urf_ctx* ctx, int on);
 /* 0 (default): after a call that took the fused front end, urf_ordered_indices*, urf_clouds_batch_* with
  * URF_ORDER_REFERENCE and urf_marker_points* first run that call again through the general kernels, and the context stays with those.
  * 1: these read-outs take a fused call's results as they are (urban_road_filter_amd/csrc/urf_k_front_outputs.hpp: the rings' points

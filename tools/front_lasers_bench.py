@@ -16,7 +16,14 @@ Then urf_set_front_mode 0 and 2, warm-up, --steps calls between device events: m
 interval = 0.05), firing order and row-major, in TWO contexts of one process, both in front mode 2 -- one with the switch on, one with it
 off: the same binary's general kernels, the baseline -- timed interleaved call by call (on, off, on, off, ...), behind a label gate
 against oracle B for both.  Per case: the medians, the 10th / 90th percentiles of either side (the run's own spread) and the median and
-percentiles of the per-pair ratio off / on.  Recorded under profiles/front_lasers128_bench.json."""
+percentiles of the per-pair ratio off / on.  Recorded under profiles/front_lasers128_bench.json.
+
+    timeout 900 python tools/front_lasers_bench.py --lasers128 --cols 4096 [--scans 256]
+
+--cols W: sweeps of W columns instead (both modes; default 2048, with --lasers128 2048 and 1024).  Above 2048 columns a 128-laser sweep
+has more than 128 tiles: the "on" context then also turns urf_set_front_long_sweeps on, "off" stays the general kernels, and "brackets"
+holds the per-kernel event brackets (urf_enable_kernel_timing; the fused finish step runs inside "k_ring") of the "on" side at W and at
+2048 columns, ms per call, in the same process.  Recorded under profiles/front_long_bench.json."""
 import argparse
 import json
 import os
@@ -28,7 +35,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-COLS = 2048
 
 
 def lasers128(args):
@@ -48,8 +54,9 @@ def lasers128(args):
     p.interval = 0.05
     pct = lambda v: [float(np.percentile(v, q)) for q in (10, 50, 90)]
     with torch.cuda.stream(st):
-        for cols in (2048, 1024):
+        for cols in ((2048, 1024) if args.cols is None else (args.cols,)):
             n = L * cols
+            long = n > 128 * 2048   # more than 128 tiles: urf_set_front_long_sweeps
             base = [u.synth_cloud(L, cols, 1 + (s % 2) * 2, 100 + s) for s in range(min(args.distinct, S))]
             for order in ("firing", "rows"):
                 src = base if order == "firing" else [tuple(np.ascontiguousarray(a.reshape(-1, L).T.reshape(-1)) for a in c) for c in base]
@@ -64,6 +71,8 @@ def lasers128(args):
                     for name, ctx in ctxs.items():
                         ctx.set_stream(st.cuda_stream)
                         ctx.set_front_lasers128(1 if name == "on" else 0)
+                        if long:
+                            ctx.set_front_long_sweeps(1 if name == "on" else 0)
                         ctx.set_front_mode(2)
                         for call in range(max(3, args.warmup)):   # the label gate (row-major: the first call sights the layout), and the warm-up
                             ctx.classify_batch_soa(dx, dy, dz, n, S, labels, None)
@@ -86,6 +95,29 @@ def lasers128(args):
                     out["results"].append({"cols": cols, "order": order, "on_front_scans": fused["on"], "off_front_scans": fused["off"],
                                            "on_ms_p10_p50_p90": pct(ts["on"]), "off_ms_p10_p50_p90": pct(ts["off"]),
                                            "off_over_on_p10_p50_p90": pct(ratio)})
+            if long:   # the fused call kernel by kernel, at `cols` and at 2048 columns (firing order)
+                out["brackets"] = []
+                for bc in (cols, 2048):
+                    bn = L * bc
+                    src = [u.synth_cloud(L, bc, 1 + (s % 2) * 2, 100 + s) for s in range(min(args.distinct, S))]
+                    one = [torch.from_numpy(np.concatenate([c[k] for c in src])).to(dev) for k in range(3)]
+                    reps = (S + len(src) - 1) // len(src)
+                    dx, dy, dz = (t.repeat(reps)[:S * bn].contiguous() for t in one)
+                    labels = torch.empty(S * bn, dtype=torch.uint8, device=dev)
+                    with u.Context(bn, S, params=p) as ctx:
+                        ctx.set_stream(st.cuda_stream)
+                        ctx.set_front_lasers128(1)
+                        ctx.set_front_long_sweeps(1)
+                        ctx.set_front_mode(2)
+                        for _ in range(max(3, args.warmup)):
+                            ctx.classify_batch_soa(dx, dy, dz, bn, S, labels, None)
+                        torch.cuda.synchronize()
+                        ctx.enable_kernel_timing(True)
+                        for _ in range(args.steps):
+                            ctx.classify_batch_soa(dx, dy, dz, bn, S, labels, None)
+                        ms, calls = ctx.kernel_timing()
+                        out["brackets"].append({"cols": bc, "front_scans": int(ctx.front_scans()), "calls": int(calls),
+                                                "ms_per_call": {k: v / calls for k, v in ms.items()}})
     out["wall_s"] = time.time() - t0
     print(json.dumps(out))
 
@@ -98,6 +130,7 @@ def main():
     ap.add_argument("--lasers", default="16,32,64")
     ap.add_argument("--distinct", type=int, default=32, help="distinct sweeps the batch is built from")
     ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--cols", type=int, default=None, help="columns per sweep (default 2048; --lasers128: 2048 and 1024)")
     ap.add_argument("--lasers128", action="store_true", help="the 128-laser switch on against off, two contexts interleaved")
     args = ap.parse_args()
     if args.lasers128:
@@ -107,6 +140,7 @@ def main():
     import oracles as O
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: nothing is measured here")
+    COLS = args.cols if args.cols is not None else 2048
     dev = torch.device("cuda:0")
     out = {"metric": "front_lasers", "device": torch.cuda.get_device_name(0), "scans": args.scans, "cols": COLS,
            "timing": "device events, median ms per call after warm-up", "results": [], "sweep": []}

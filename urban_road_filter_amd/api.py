@@ -176,6 +176,7 @@ def lib(hooks=False):
         "urf_set_front_mode": [vp, C.c_int],
         "urf_front_scans": [vp, C.c_void_p],
         "urf_set_front_lasers128": [vp, C.c_int],
+        "urf_set_front_long_sweeps": [vp, C.c_int],
         "urf_set_front_outputs": [vp, C.c_int],
         "urf_callback_path_preset": [vp, C.c_uint32],
     }
@@ -395,6 +396,12 @@ class Context:
         """urf_set_front_lasers128: 1 lets front modes 2 and 3 take sweeps of 128 lasers per firing too (channels == 128, curb_points == 5,
         firing order or row-major, at most 128 x 2048 points; include/urf.h); 0 (default) keeps them on the general kernels.  Opt-in."""
         self._check(self._lib.urf_set_front_lasers128(self._h, int(on)), "urf_set_front_lasers128")
+
+    def set_front_long_sweeps(self, on):
+        """urf_set_front_long_sweeps: 1 lets front modes 2 and 3 take batch calls whose longest scan has 129..256 tiles of 2048 points too
+        (256 tiles: a 128 x 4096 sweep; every laser count the fused front end knows, firing order or row-major; include/urf.h); 0 (default)
+        keeps the limit of 128 tiles.  Opt-in."""
+        self._check(self._lib.urf_set_front_long_sweeps(self._h, int(on)), "urf_set_front_long_sweeps")
 
     def set_front_outputs(self, on):
         """urf_set_front_outputs: 1 lets ordered_indices*, clouds_batch_* in the reference order and marker_points* take the results of a call

@@ -102,6 +102,20 @@ public:
         if (rc != URF_OK)
             throw Error(rc, "urf_set_front_outputs");
     }
+    /* urf_set_front_lasers128 / urf_set_front_long_sweeps: front modes 2 and 3 also take sweeps of 128 lasers per firing (channels == 128,
+     * curbPoints == 5) / of 129..256 tiles of 2048 points (a 128 x 4096 sweep is 256).  Both are off by default and opt-in. */
+    void setFrontLasers128(bool on)
+    {
+        const int rc = urf_set_front_lasers128(ctx_, on ? 1 : 0);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_set_front_lasers128");
+    }
+    void setFrontLongSweeps(bool on)
+    {
+        const int rc = urf_set_front_long_sweeps(ctx_, on ? 1 : 0);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_set_front_long_sweeps");
+    }
 
     /* Also build the "road_marker" MarkerArray (lidar_segmentation.cpp:295-351, 369-602, topic :59,601);
      * fixedFrame = params::fixedFrame (cfg:10).  Off by default: the polygon is a visualisation product. */
@@ -210,6 +224,20 @@ public:
         const int rc = urf_set_front_outputs(ctx_, on ? 1 : 0);
         if (rc != URF_OK)
             throw Error(rc, "urf_set_front_outputs");
+    }
+    /* urf_set_front_lasers128 / urf_set_front_long_sweeps: front modes 2 and 3 also take sweeps of 128 lasers per firing (channels == 128,
+     * curbPoints == 5) / of 129..256 tiles of 2048 points (a 128 x 4096 sweep is 256).  Both are off by default and opt-in. */
+    void setFrontLasers128(bool on)
+    {
+        const int rc = urf_set_front_lasers128(ctx_, on ? 1 : 0);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_set_front_lasers128");
+    }
+    void setFrontLongSweeps(bool on)
+    {
+        const int rc = urf_set_front_long_sweeps(ctx_, on ? 1 : 0);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_set_front_long_sweeps");
     }
 
     /* As Detector's: also build "road_marker" for every message (off by default; the polygon parameters start from

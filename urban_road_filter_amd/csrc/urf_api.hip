@@ -125,6 +125,19 @@ static urf_front_finish_fn front_finish_kernel(int cp)
     return k_front_finish;
 }
 
+/* Scans of 129..256 tiles (urf_set_front_long_sweeps; 256 tiles: a 128 x 4096 sweep): the same finish kernels with the dynamic LDS their
+ * layout needs for that many tiles -- a presence word and a 16-bit count per (tile, lane), 384 B per tile, and the chunk of the candidate
+ * list: 108 KiB at 256 tiles, one workgroup per CU instead of four.  A call of at most URF_FRONT_MAX_TILES tiles asks for what it always
+ * asked for.  Nothing else in the fused kernels counts tiles: the 16-bit counts hold a lane's ring points in the tiles before, at most
+ * 255 x 2048 / 16 < 65536 (16 lasers per firing). */
+#define URF_FRONT_LONG_MAX_TILES 256u
+static constexpr size_t urf_finish_lds_bytes(unsigned tiles)
+{
+    return (size_t)tiles * 384 + 2 * URF_FINISH_CHUNK * sizeof(urf_u2);
+}
+static_assert(urf_finish_lds_bytes(URF_FRONT_LONG_MAX_TILES) + sizeof(urf_finish128_shared) <= 160u * 1024u, "a CU's LDS");
+static_assert(URF_FRONT128_TILES2(URF_FRONT_LONG_MAX_TILES) == URF_FRONT_LONG_MAX_TILES, "an even number: k_front_finish128's layout is as large");
+
 /* The launch policy: which kernels a call launches, decided on the host from what the kernels of earlier calls reported through the
  * host-mapped flag words (enum urf_flag).  fold() is the only reader of the words: a batch call runs it in run_pipeline, a sweep of the
  * callback path in urf_classify_pc2_async, before either launches anything.  plan() turns the fields into a call's urf_kargs.  Every
@@ -148,6 +161,8 @@ struct __attribute__((visibility("hidden"))) urf_policy {
     int front_mode = 1;
     bool every_batch() const { return front_mode >= 2; }
     bool lasers128 = false;         /* urf_set_front_lasers128: modes 2 and 3 take sweeps of 128 lasers per firing too (urf_front128.hpp; its scratch is there) */
+    bool long_sweeps = false;       /* urf_set_front_long_sweeps: modes 2 and 3 take scans of up to URF_FRONT_LONG_MAX_TILES tiles (the finish kernels with more dynamic LDS) */
+    uint32_t front_max_tiles() const { return long_sweeps && every_batch() ? URF_FRONT_LONG_MAX_TILES : URF_FRONT_MAX_TILES; }
     uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
     bool want_ring_sorted = false;
     /* urf_set_front_outputs: the published order and the marker points of a fused call come from what it left on the device
@@ -222,7 +237,7 @@ struct __attribute__((visibility("hidden"))) urf_policy {
         const bool lasers = L == 64u || L == 32u || L == 16u || (L == 128u && lasers128 && every_batch());
         a.front_lsh = L == 16u ? 4u : (L == 32u ? 5u : (L == 128u ? 7u : 6u));
         const bool shape = front_mode != 0 && !front_off && !general_only && !want_ring_sorted && a.capture == 0 &&
-                           lasers && front_curb_points_ok(front_mode, L, dp.p.curbPoints) && a.tiles <= URF_FRONT_MAX_TILES;
+                           lasers && front_curb_points_ok(front_mode, L, dp.p.curbPoints) && a.tiles <= front_max_tiles();
         /* (16 / 32 lasers: nothing below mode 2 until their crossover has been measured -- no batch size, no row-major sighting, no callback path) */
         const bool small_ok = front_rows && (rows_used || rows_probation > 0) && (L == 64u || every_batch());
         a.front = (shape && (slot ? small_ok : (every_batch() || small_ok || a.n_scans >= (L == 64u ? URF_FRONT_MIN_SCANS : (L == 32u ? URF_FRONT_MIN_SCANS_32 : URF_FRONT_MIN_SCANS_16))))) ? 1u : 0u;
@@ -768,6 +783,31 @@ extern "C" int urf_set_front_lasers128(urf_ctx* c, int on)
     return URF_OK;
 }
 
+extern "C" int urf_set_front_long_sweeps(urf_ctx* c, int on)
+{
+    if (!c || (on != 0 && on != 1))
+        return URF_ERR_INVALID_ARG;
+    if (on) {
+        /* The finish kernels' dynamic LDS at URF_FRONT_LONG_MAX_TILES tiles: a device that does not grant a workgroup that much keeps the
+         * switch off.  Measured on the MI355X: the HIP runtime grants a workgroup the whole 160 KiB without being
+         * asked -- a launch with 110 592 B succeeds without hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize), and the call
+         * changes neither that nor the occupancy below 129 tiles -- so the attribute is not set: this limit is the only condition. */
+        URF_HIP(c, hipSetDevice(c->device));
+        int lds_max = 0;
+        URF_HIP(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+        if ((size_t)lds_max < urf_finish_lds_bytes(URF_FRONT_LONG_MAX_TILES) + sizeof(urf_finish128_shared)) {
+            c->last_error = "urf_set_front_long_sweeps: the device grants a workgroup " + std::to_string(lds_max) + " bytes of LDS";
+            return URF_ERR_OOM;
+        }
+    }
+    if ((on != 0) != c->pol.long_sweeps)   /* (a new start) */
+        c->pol.forget_front();
+    c->pol.set(c->pol.long_sweeps, on != 0);
+    if (on)
+        c->pol.set(c->pol.want_ring_sorted, false);
+    return URF_OK;
+}
+
 extern "C" int urf_set_front_outputs(urf_ctx* c, int on)
 {
     if (!c || (on != 0 && on != 1))
@@ -1026,7 +1066,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
      * own), they are bound by vector issue.  With the per-kernel event brackets on (urf_enable_kernel_timing) everything stays on one
      * stream, so that the brackets add up to the step. */
     bool side = false, part1 = false;
-    const size_t finish_lds = (size_t)(l128 ? URF_FRONT128_TILES2(a.tiles) : a.tiles) * 384 + 2 * URF_FINISH_CHUNK * sizeof(urf_u2);
+    const size_t finish_lds = urf_finish_lds_bytes(l128 ? URF_FRONT128_TILES2(a.tiles) : a.tiles);   /* (above URF_FRONT_MAX_TILES tiles: urf_set_front_long_sweeps has asked the device) */
     const urf_front_finish_fn finish = l128 ? k_front_finish128 : front_finish_kernel(dp.p.curbPoints);
     if (a.front && !ev && !slot && side_fork(c, st)) {
         hipLaunchKernelGGL(finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, c->side_stream, a, dp, 1u);
