@@ -68,7 +68,9 @@ extern "C" {
  * PointCloud2 batches), urf_clouds_batch_soa / urf_clouds_batch_pc2 with struct urf_point_xyzi, URF_ORDER_INPUT and
  * URF_ORDER_REFERENCE (the four published clouds of a batch as device-resident records); urf_marker_strips /
  * urf_marker_strips_batch with struct urf_marker_strip, URF_MARKER_MAX_STRIPS, URF_MARKER_MAX_STRIP_POINTS (the line strips of
- * road_marker: one sweep on the host, a batch of sweeps on the device).
+ * road_marker: one sweep on the host, a batch of sweeps on the device); urf_classify_batch_soa_dense / urf_classify_batch_pc2_dense with
+ * urf_set_dense_slots and urf_dense_scans (dense sweeps put back into firing slots by laser id on the device, then classified as
+ * organised ones).
  * WHICH std::sort (4 above): the one of libstdc++ as shipped with GCC 5 .. 13 (bits/stl_algo.h: __sort = __introsort_loop with
  * _S_threshold 16, __move_median_to_first on (first + 1, mid, last - 1), __unguarded_partition, depth limit 2 * floor(log2 n),
  * __partial_sort as the fallback, then __final_insertion_sort); tests/test_stdsort.py pins the restatement against the std::sort
@@ -567,6 +569,56 @@ int urf_set_front_long_sweeps(urf_ctx* ctx, int on);
  * values are defined as the general kernels'.  The switch decides nothing about which kernels classify and forgets no sighting or
  * hand-back.  The read-outs' scratch grows with their first use (URF_ERR_OOM from that call).  Anything else: URF_ERR_INVALID_ARG. */
 int urf_set_front_outputs(urf_ctx* ctx, int on);
+
+/* ---- dense sweeps: put back into firing slots by laser id, on the device ---------
+ * The fused front end above wants point f * L + l to be laser slot l of firing f (L = channels), non-returns left in place as holes.  A
+ * driver that DROPS non-returns (velodyne_pointcloud's default mode, any is_dense cloud) publishes firings of unequal length back to
+ * back: lane is no longer laser, and such a sweep keeps the general kernels.  The same drivers write a laser id per point (the `ring`
+ * field: UINT16 in Velodyne's PointXYZIR, UINT8 or UINT16 in Ouster's).  These entry points use it to rebuild the holes.
+ * THE RULE.  Point i = 0..n-1 of a dense scan has slot s_i < L (its id, through the slot map below).  A firing starts at i = 0 and
+ * wherever s_i <= s_{i-1}; f_i = the number of starts up to and including i, minus 1.  The padded scan has W * L points (W =
+ * max_firings: what the sensor delivers per revolution, e.g. 1808 or 2048), all NaN, with point i written at f_i * L + s_i.
+ * WHY IT IS EXACT.  f_i * L + s_i grows strictly with i (inside a firing the slot grows, a new firing adds L and takes at most L - 1
+ * away), so the padded scan holds the dense points in their input order with holes between them.  The reference drops such holes
+ * before anything else (ConditionalRemoval, lidar_segmentation.cpp:100-117) and never looks at an input index: its labels at those
+ * positions, and its summary counts, are those of the dense scan.  This holds for ANY ids; nothing depends on their being right.
+ * Wrong ids cost speed only: the fused front end finds lane != ring and hands the scan back to the general kernels, as it does for any
+ * scan without the shape.  (Adjacent short firings whose slots keep growing merge into one; that loses the sector alignment of those
+ * points, nothing else.)
+ * THE CALLS.  Inputs, offsets, labels and infos exactly as for urf_classify_batch_soa_ragged / urf_classify_batch_pc2_ragged (scan s =
+ * [d_offsets[s], d_offsets[s+1]); d_labels and d_info index the DENSE points and scans) and the same bytes come out.  d_laser: one id
+ * per point, laid out like d_x, laser_bytes = 1 (uint8) or 2 (uint16); PointCloud2: a little-endian UINT8 / UINT16 at off_laser of
+ * every record, any alignment.  W * L > max_points, max_len > W * L or n_scans > max_batch: URF_ERR_CAPACITY; laser_bytes not 1 or 2,
+ * off_laser + laser_bytes > point_step or a NULL pointer: URF_ERR_INVALID_ARG; n_scans == 0 is a no-op (max_firings == 0 with scans
+ * to classify: URF_ERR_CAPACITY by the rule above, URF_ERR_INVALID_ARG when all of them are empty).  The padded
+ * batch (n_scans scans of W * L points in the context's own staging) then goes through the pipeline as a plain batch call:
+ * urf_set_front_mode, urf_set_front_lasers128, urf_set_front_long_sweeps, hand-back, sightings and urf_front_scans mean what they mean
+ * for urf_classify_batch_soa.  The first dense call allocates what the re-alignment needs (4 + 1 bytes per point of max_points *
+ * max_batch next to the SoA staging; URF_ERR_OOM from that call); a context that never makes one allocates and launches nothing new.
+ * A SCAN THAT IS NOT ALIGNED -- a slot >= L, an id the map does not hold, or more than W firings -- is no error: its points are
+ * written unpadded (point i at position i, NaN behind them) and classified by whichever kernels take it, with the same labels.
+ * urf_dense_scans: how many scans of the last dense call were aligned (synchronises, like urf_front_scans).
+ * urf_set_dense_slots: the driver's id -> the laser's position inside a firing, n_ids <= 256 entries (Velodyne's `ring` counts by
+ * elevation while its lasers fire in laser-number order); NULL: the identity (default).  An id at or beyond n_ids is held by no slot.
+ * The map is copied; the next dense call takes it to the device.
+ * AFTER A DENSE CALL the context's record of "the last call" is the padded batch, every buffer of it the context's own:
+ * urf_marker_points / urf_marker_points_batch work as ever (marker points are coordinates) and need nothing of the caller's kept
+ * alive; urf_clouds_batch_soa / urf_clouds_batch_pc2 with URF_ORDER_INPUT read the caller's dense labels and inputs (LIFETIME as
+ * above) and give the records the ragged call gives.  urf_ordered_indices*, urf_clouds_batch_* with URF_ORDER_REFERENCE and
+ * urf_read_stage would answer in padded indices: they return URF_ERR_INVALID_ARG (urf_last_error says why) and leave the context
+ * as it was.  Mapping padded indices back to the dense ones is left to a later version.
+ * The kernels are urban_road_filter_amd/csrc/urf_k_dense.hpp; they run outside the timing brackets below. */
+int urf_classify_batch_soa_dense(urf_ctx* ctx, const float* d_x, const float* d_y, const float* d_z,
+                                 const void* d_laser, uint32_t laser_bytes,
+                                 const uint32_t* d_offsets, uint32_t max_len, uint32_t n_scans,
+                                 uint32_t max_firings, uint8_t* d_labels, urf_scan_info* d_info);
+int urf_classify_batch_pc2_dense(urf_ctx* ctx, const uint8_t* d_data, const uint32_t* d_offsets, uint64_t n_total,
+                                 uint32_t max_len, uint32_t n_scans, uint32_t point_step,
+                                 uint32_t off_x, uint32_t off_y, uint32_t off_z,
+                                 uint32_t off_laser, uint32_t laser_bytes,
+                                 uint32_t max_firings, uint8_t* d_labels, urf_scan_info* d_info);
+int urf_set_dense_slots(urf_ctx* ctx, const uint8_t* slot_of_id, uint32_t n_ids);
+int urf_dense_scans(urf_ctx* ctx, uint32_t* n_aligned);
 
 /* ---- per-kernel timing (benchmark) ------------------------------------------
  * With timing on, every classify call brackets each kernel of the pipeline

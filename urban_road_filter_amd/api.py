@@ -179,6 +179,11 @@ def lib(hooks=False):
         "urf_set_front_long_sweeps": [vp, C.c_int],
         "urf_set_front_outputs": [vp, C.c_int],
         "urf_callback_path_preset": [vp, C.c_uint32],
+        "urf_classify_batch_soa_dense": [vp, fp, fp, fp, vp, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp],
+        "urf_classify_batch_pc2_dense": [vp, u8p, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp],
+        "urf_set_dense_slots": [vp, u8p, C.c_uint32],
+        "urf_dense_scans": [vp, C.c_void_p],
     }
     for name, args in sig.items():
         if name in HOOK_SYMBOLS and not has_hooks:
@@ -512,6 +517,37 @@ class Context:
         self._check(self._lib.urf_classify_batch_pc2_ragged(self._h, _ptr(d_data), _ptr(d_offsets), n_total, max_len, n_scans,
                                                             point_step, off_x, off_y, off_z, _ptr(d_labels), _ptr(d_info)),
                     "urf_classify_batch_pc2_ragged")
+
+    # -- dense sweeps (non-returns dropped): put back into firing slots by laser id on the device, then the pipeline ----
+    def classify_batch_soa_dense(self, d_x, d_y, d_z, d_laser, laser_bytes, d_offsets, max_len, n_scans, max_firings, d_labels,
+                                 d_info=None):
+        """urf_classify_batch_soa_dense: as classify_batch_soa_ragged, plus one laser id per point (d_laser: uint8 or uint16 as laser_bytes
+        says) and the sensor's firings per revolution; same labels and infos (include/urf.h)."""
+        self._check(self._lib.urf_classify_batch_soa_dense(self._h, _ptr(d_x), _ptr(d_y), _ptr(d_z), _ptr(d_laser), laser_bytes,
+                                                           _ptr(d_offsets), max_len, n_scans, max_firings, _ptr(d_labels), _ptr(d_info)),
+                    "urf_classify_batch_soa_dense")
+
+    def classify_batch_pc2_dense(self, d_data, d_offsets, n_total, max_len, n_scans, point_step, off_x, off_y, off_z, off_laser,
+                                 laser_bytes, max_firings, d_labels, d_info=None):
+        """urf_classify_batch_pc2_dense: as classify_batch_pc2_ragged, with the laser id read from every record (UINT8 / UINT16 at
+        off_laser, any alignment)."""
+        self._check(self._lib.urf_classify_batch_pc2_dense(self._h, _ptr(d_data), _ptr(d_offsets), n_total, max_len, n_scans, point_step,
+                                                           off_x, off_y, off_z, off_laser, laser_bytes, max_firings, _ptr(d_labels),
+                                                           _ptr(d_info)), "urf_classify_batch_pc2_dense")
+
+    def set_dense_slots(self, slots):
+        """urf_set_dense_slots: slots[id] = position of laser `id` inside a firing (at most 256 entries); None: the identity."""
+        if slots is None:
+            self._check(self._lib.urf_set_dense_slots(self._h, None, 0), "urf_set_dense_slots")
+            return
+        m = np.ascontiguousarray(slots, np.uint8)
+        self._check(self._lib.urf_set_dense_slots(self._h, m.ctypes.data, m.size), "urf_set_dense_slots")
+
+    def dense_scans(self):
+        """Scans of the last dense call that were aligned (put back into firing slots)."""
+        n = C.c_uint32(0)
+        self._check(self._lib.urf_dense_scans(self._h, C.addressof(n)), "urf_dense_scans")
+        return n.value
 
     def clouds_batch_soa(self, d_intensity, order, d_records, capacity, d_counts, d_offsets):
         """The four published clouds of every scan of the last (SoA) batch call as 32-byte records on the device:

@@ -439,9 +439,33 @@ void* BatchDetector::grow(void*& p, size_t& cap, size_t bytes)
     return p;
 }
 
+void BatchDetector::setDenseRealign(uint32_t max_firings, const std::vector<uint8_t>& slot_of_ring)
+{
+    if (slot_of_ring.size() > 256)
+        throw Error(URF_ERR_INVALID_ARG, "BatchDetector: a slot map holds at most 256 rings");
+    check(urf_set_dense_slots(ctx_, slot_of_ring.empty() ? nullptr : slot_of_ring.data(), (uint32_t)slot_of_ring.size()), "urf_set_dense_slots");
+    dense_firings_ = max_firings;
+}
+
+/* the `ring` field of a record layout: UINT8 or UINT16, count 1, inside the record; bytes = 0: none */
+static void ringField(const PointCloud2& m, uint32_t& off, uint32_t& bytes)
+{
+    off = bytes = 0;
+    for (const PointField& f : m.fields)
+        if (f.name == "ring" && f.count == 1 && (f.datatype == PointField::UINT8 || f.datatype == PointField::UINT16)) {
+            const uint32_t b = f.datatype == PointField::UINT8 ? 1u : 2u;
+            if ((uint64_t)f.offset + b <= m.point_step) {
+                off = f.offset;
+                bytes = b;
+            }
+            return;
+        }
+}
+
 size_t BatchDetector::filtered(const std::vector<PointCloud2>& msgs)
 {
     const size_t S = msgs.size();
+    dense_aligned_ = 0;
     infos_.assign(S, urf_scan_info{});
     clouds_.resize(4 * S);
     markers_.resize(S);
@@ -507,8 +531,28 @@ size_t BatchDetector::filtered(const std::vector<PointCloud2>& msgs)
     if (hipMemcpyAsync(d_data, h_data_.data(), h_data_.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(d_offsets, offsets.data(), (S + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess)
         throw Error(URF_ERR_HIP, "BatchDetector: upload failed");
-    check(urf_classify_batch_pc2_ragged(ctx_, d_data, d_offsets, total, max_len, (uint32_t)S, step, off[0], off[1], off[2], d_labels, d_info),
-          "urf_classify_batch_pc2_ragged");
+    /* setDenseRealign: every message carries the same `ring` field, input order, and the sensor's padded sweep fits the context */
+    uint32_t ring_off = 0, ring_bytes = 0;
+    if (dense_firings_ != 0 && !reference_order_) {
+        ringField(msgs[0], ring_off, ring_bytes);
+        for (size_t i = 1; i < S && ring_bytes; i++) {
+            uint32_t o = 0, b = 0;
+            ringField(msgs[i], o, b);
+            if (o != ring_off || b != ring_bytes)
+                ring_bytes = 0;
+        }
+        const uint64_t padded = (uint64_t)dense_firings_ * (uint32_t)params().channels;
+        if (padded > max_points_ || max_len > padded)
+            ring_bytes = 0;
+    }
+    if (ring_bytes) {
+        check(urf_classify_batch_pc2_dense(ctx_, d_data, d_offsets, total, max_len, (uint32_t)S, step, off[0], off[1], off[2], ring_off, ring_bytes,
+                                           dense_firings_, d_labels, d_info),
+              "urf_classify_batch_pc2_dense");
+    } else {
+        check(urf_classify_batch_pc2_ragged(ctx_, d_data, d_offsets, total, max_len, (uint32_t)S, step, off[0], off[1], off[2], d_labels, d_info),
+              "urf_classify_batch_pc2_ragged");
+    }
     check(urf_clouds_batch_pc2(ctx_, d_data, step, off[0], off[1], off[2], (int32_t)oi, reference_order_ ? URF_ORDER_REFERENCE : URF_ORDER_INPUT,
                                d_rec, capacity, d_counts, d_roffs),
           "urf_clouds_batch_pc2");
@@ -525,6 +569,11 @@ size_t BatchDetector::filtered(const std::vector<PointCloud2>& msgs)
     if (n_rec && (hipMemcpyAsync(h_records_.data(), d_rec, n_rec * sizeof(urf_point_xyzi), hipMemcpyDeviceToHost, st) != hipSuccess ||
                   hipStreamSynchronize(st) != hipSuccess))
         throw Error(URF_ERR_HIP, "BatchDetector: read-back failed");
+    if (ring_bytes) {
+        uint32_t n_aligned = 0;
+        check(urf_dense_scans(ctx_, &n_aligned), "urf_dense_scans");
+        dense_aligned_ = n_aligned;
+    }
     if (marker_on_)
         buildMarkers(S);
     size_t n_pub = 0;

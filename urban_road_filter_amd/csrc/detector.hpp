@@ -240,6 +240,15 @@ public:
             throw Error(rc, "urf_set_front_long_sweeps");
     }
 
+    /* Dense messages (the driver dropped the non-returns) with a field named "ring" (UINT8 or UINT16, count 1) are put back into firing
+     * slots on the device and classified as organised sweeps (urf_classify_batch_pc2_dense, include/urf.h): max_firings = the sensor's
+     * firings per revolution, slot_of_ring[ring] = the laser's position inside a firing (empty: the ring is the position).  Same clouds,
+     * headers and road_marker either way; off by default, max_firings == 0 turns it off.  Messages without such a field, the reference
+     * order (setReferenceOrder) and a sensor whose max_firings * channels sweep does not fit max_points keep the ragged call. */
+    void setDenseRealign(uint32_t max_firings, const std::vector<uint8_t>& slot_of_ring = {});
+    /* messages of the last filtered() call that were put back into firing slots (0 when it took the ragged call) */
+    size_t denseAligned() const { return dense_aligned_; }
+
     /* As Detector's: also build "road_marker" for every message (off by default; the polygon parameters start from
      * urf_default_marker_params, as Detector's do).  Switching it on starts a new drive. */
     void enableRoadMarker(bool on, const std::string& fixed_frame = "left_os1/os1_lidar");
@@ -267,6 +276,8 @@ private:
     void* stream_ = nullptr;
     uint32_t max_points_ = 0, max_batch_ = 0;
     bool reference_order_ = false;
+    uint32_t dense_firings_ = 0;   /* setDenseRealign */
+    size_t dense_aligned_ = 0;
     /* device buffers (grown on demand) */
     void* d_data_ = nullptr;
     size_t d_data_cap_ = 0;

@@ -260,6 +260,14 @@ struct urf_last_call {
     urf_dev_params dp;
     uint32_t row = 0;               /* the scratch row of a.* (a batch call: 0) */
     uint64_t gen = 0;               /* a sweep: the row's submission number it was (urf_ctx::row_gen) */
+    /* a dense call (urf_classify_batch_*_dense): `a` is the padded batch -- staging, padded labels, all the context's own --, and
+     * this is what the caller handed in, for urf_clouds_batch_* in input order (offsets: the context's copy) */
+    struct {
+        bool on = false;
+        const float *x = nullptr, *y = nullptr, *z = nullptr;   /* a SoA call's */
+        uint8_t* labels = nullptr;
+        uint32_t max_len = 0;
+    } dense;
 };
 
 struct urf_ctx {
@@ -339,6 +347,15 @@ struct urf_ctx {
      * reference order: 3 x scans x stride entries + 3 counts per scan */
     lazy_buf<urf_u32x4> cl_tiles;   /* 2 x [max_batch][max_tiles] */
     lazy_buf<uint32_t> cl_lists;
+    /* dense sweeps put back into firing slots (urf_k_dense.hpp), grown by the first dense call: every dense point's position inside its
+     * padded scan and the padded batch's labels ([max_batch][max_points] each; the padded x / y / z are the SoA staging), the per-tile
+     * and per-scan words (2 x [max_batch][max_tiles] + [max_batch] + 1), the slot map's device copy */
+    lazy_buf<uint32_t> dn_pos;
+    lazy_buf<uint8_t> dn_labels;
+    lazy_buf<uint32_t> dn_words;
+    lazy_buf<uint8_t> dn_map;
+    uint8_t dense_map[256];         /* urf_set_dense_slots (urf_create: the identity); 0xff: no such id */
+    bool dense_map_dirty = true;    /* ... not yet in dn_map */
     float* d_newY = nullptr;
     urf_beam* d_beams = nullptr;
     uint32_t beams_cap = 0;
@@ -551,6 +568,8 @@ extern "C" int urf_create(urf_ctx** out, int device_id, uint32_t max_points, uin
     c->max_batch = max_batch;
     c->max_tiles = (uint32_t)max_tiles;
     c->sstride = (uint32_t)sstride;
+    for (unsigned i = 0; i < 256; i++)
+        c->dense_map[i] = (uint8_t)i;
     int rc = URF_OK;
     auto fail = [&](int code) {
         urf_destroy(c);
@@ -1243,6 +1262,151 @@ extern "C" int urf_classify_batch_pc2_ragged(urf_ctx* c, const uint8_t* d_data, 
     return classify_batch_pc2(c, d_data, d_offsets, n_total, 0, max_len, n_scans, point_step, off_x, off_y, off_z, d_labels, d_info);
 }
 
+/* ---- dense sweeps: put back into firing slots by laser id, then the pipeline (urf_k_dense.hpp) ------------------------------- */
+extern "C" int urf_set_dense_slots(urf_ctx* c, const uint8_t* slot_of_id, uint32_t n_ids)
+{
+    if (!c || n_ids > 256u)
+        return URF_ERR_INVALID_ARG;
+    for (unsigned i = 0; i < 256u; i++)   /* (a copy; the device gets it with the next dense call, outside every captured sequence) */
+        c->dense_map[i] = !slot_of_id ? (uint8_t)i : i < n_ids ? slot_of_id[i] : (uint8_t)0xff;
+    c->dense_map_dirty = true;
+    return URF_OK;
+}
+
+/* the per-scan words of a dense call inside dn_words: per-tile counts and bases, the aligned flags, the call's aligned count */
+static uint32_t* dense_word(urf_ctx* c, int which)
+{
+    const size_t per_tile = (size_t)c->max_batch * c->max_tiles;
+    return c->dn_words.p + (which == 0 ? 0 : which == 1 ? per_tile : which == 2 ? 2 * per_tile : 2 * per_tile + c->max_batch);
+}
+
+extern "C" int urf_dense_scans(urf_ctx* c, uint32_t* n_aligned)
+{
+    if (!c || !n_aligned)
+        return URF_ERR_INVALID_ARG;
+    *n_aligned = 0;
+    if (!c->dn_words.p)   /* (no dense call yet) */
+        return URF_OK;
+    URF_HIP(c, hipSetDevice(c->device));
+    URF_HIP(c, hipStreamSynchronize(c->stream));
+    URF_HIP(c, hipMemcpy(n_aligned, dense_word(c, 3), sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return URF_OK;
+}
+
+/* d: where ids and points come from (id*, x / y / z or data and its layout; the rest is filled in here).  The padded batch -- n_scans
+ * scans of W * L points in the SoA staging, NaN wherever no point landed -- is a plain batch call to everything behind the scatter. */
+static int classify_batch_dense(urf_ctx* c, int kind, urf_dense_args d, const uint32_t* d_offsets, uint32_t max_len, uint32_t n_scans,
+                                uint32_t max_firings, uint8_t* d_labels, urf_scan_info* d_info)
+{
+    const uint64_t WL = (uint64_t)max_firings * (uint32_t)c->params.channels;
+    if (WL > c->max_points || max_len > WL || n_scans > c->max_batch)
+        return URF_ERR_CAPACITY;
+    if (n_scans == 0)
+        return URF_OK;
+    if (max_firings == 0)   /* (and max_len == 0: a padded scan of no points is no batch call) */
+        return URF_ERR_INVALID_ARG;
+    URF_HIP(c, hipSetDevice(c->device));
+    const size_t n_all = (size_t)c->max_points * c->max_batch, per_tile = (size_t)c->max_batch * c->max_tiles;
+    int rc;
+    if ((rc = ensure_soa_staging(c)) != URF_OK || (rc = grow(c, c->dn_pos, n_all)) != URF_OK || (rc = grow(c, c->dn_labels, n_all)) != URF_OK ||
+        (rc = grow(c, c->dn_words, 2 * per_tile + c->max_batch + 1)) != URF_OK || (rc = grow(c, c->dn_map, 256)) != URF_OK)
+        return rc;
+    if ((rc = order_after_slots(c)) != URF_OK)   /* the staging arrays are shared with the callback path */
+        return rc;
+    hipStream_t st = c->stream;
+    if (c->dense_map_dirty) {   /* (rare: behind whatever still reads the old map) */
+        URF_HIP(c, hipStreamSynchronize(st));
+        URF_HIP(c, hipMemcpy(c->dn_map.p, c->dense_map, sizeof(c->dense_map), hipMemcpyHostToDevice));
+        c->dense_map_dirty = false;
+    }
+    d.offsets = d_offsets;
+    d.max_len = max_len;
+    d.n_scans = n_scans;
+    d.tiles = (max_len + URF_TILE - 1) / URF_TILE;
+    if (d.tiles == 0)
+        d.tiles = 1;
+    d.L = (uint32_t)c->params.channels;
+    d.W = max_firings;
+    d.slot_of_id = c->dn_map.p;
+    d.tile_cnt = dense_word(c, 0);
+    d.tile_base = dense_word(c, 1);
+    d.aligned = dense_word(c, 2);
+    d.n_aligned = dense_word(c, 3);
+    d.px = c->sx.p;
+    d.py = c->sy.p;
+    d.pz = c->sz.p;
+    d.pos = c->dn_pos.p;
+    d.padded_labels = c->dn_labels.p;
+    d.labels = d_labels;
+    /* the holes are NaN: the call's range of the staging as all-ones bytes, every call (a shorter batch must not see an earlier one's points) */
+    const size_t fill = (size_t)n_scans * (size_t)WL * sizeof(float);
+    URF_HIP(c, hipMemsetAsync(c->sx.p, 0xff, fill, st));
+    URF_HIP(c, hipMemsetAsync(c->sy.p, 0xff, fill, st));
+    URF_HIP(c, hipMemsetAsync(c->sz.p, 0xff, fill, st));
+    URF_HIP(c, hipMemsetAsync(d.n_aligned, 0, sizeof(uint32_t), st));
+    const dim3 g_tiles(d.tiles, n_scans);
+    hipLaunchKernelGGL(k_dense_count, g_tiles, dim3(URF_DENSE_THREADS), 0, st, d);
+    hipLaunchKernelGGL(k_dense_scan, dim3(n_scans), dim3(URF_DENSE_THREADS), 0, st, d);
+    if (kind == URF_LAST_PC2)
+        hipLaunchKernelGGL(k_dense_scatter_pc2, g_tiles, dim3(URF_DENSE_THREADS), 0, st, d);
+    else
+        hipLaunchKernelGGL(k_dense_scatter_soa, g_tiles, dim3(URF_DENSE_THREADS), 0, st, d);
+    URF_HIP(c, hipGetLastError());
+    rc = classify_batch(c, kind, urf_call{ c->sx.p, c->sy.p, c->sz.p, nullptr, (uint32_t)WL, (uint32_t)WL, n_scans, c->dn_labels.p, d_info });
+    if (rc != URF_OK)
+        return rc;
+    hipLaunchKernelGGL(k_dense_labels, g_tiles, dim3(URF_DENSE_THREADS), 0, st, d);
+    URF_HIP(c, hipGetLastError());
+    /* the record of the last call: the padded batch (all buffers the context's), marked dense, with what urf_clouds_batch_* in input
+     * order read -- the caller's labels and inputs, the offsets as the context's copy (the padded call has none of its own) */
+    URF_HIP(c, hipMemcpyAsync(c->offsets_copy, d_offsets, ((size_t)n_scans + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    c->last.dense.on = true;
+    c->last.dense.x = d.x;
+    c->last.dense.y = d.y;
+    c->last.dense.z = d.z;
+    c->last.dense.labels = d_labels;
+    c->last.dense.max_len = max_len;
+    return URF_OK;
+}
+
+extern "C" int urf_classify_batch_soa_dense(urf_ctx* c, const float* d_x, const float* d_y, const float* d_z, const void* d_laser,
+                                            uint32_t laser_bytes, const uint32_t* d_offsets, uint32_t max_len, uint32_t n_scans,
+                                            uint32_t max_firings, uint8_t* d_labels, urf_scan_info* d_info)
+{
+    if (!c || !d_x || !d_y || !d_z || !d_laser || !d_offsets || !d_labels || (laser_bytes != 1u && laser_bytes != 2u))
+        return URF_ERR_INVALID_ARG;
+    urf_dense_args d{};
+    d.id = (const uint8_t*)d_laser;
+    d.id_stride = laser_bytes;
+    d.id_bytes = laser_bytes;
+    d.x = d_x;
+    d.y = d_y;
+    d.z = d_z;
+    return classify_batch_dense(c, URF_LAST_SOA, d, d_offsets, max_len, n_scans, max_firings, d_labels, d_info);
+}
+
+extern "C" int urf_classify_batch_pc2_dense(urf_ctx* c, const uint8_t* d_data, const uint32_t* d_offsets, uint64_t n_total, uint32_t max_len,
+                                            uint32_t n_scans, uint32_t point_step, uint32_t off_x, uint32_t off_y, uint32_t off_z,
+                                            uint32_t off_laser, uint32_t laser_bytes, uint32_t max_firings, uint8_t* d_labels,
+                                            urf_scan_info* d_info)
+{
+    if (!c || !d_data || !d_offsets || !d_labels || !pc2_layout_ok(point_step, off_x, off_y, off_z) || (laser_bytes != 1u && laser_bytes != 2u) ||
+        (uint64_t)off_laser + laser_bytes > point_step)
+        return URF_ERR_INVALID_ARG;
+    if (n_total > (uint64_t)c->max_points * c->max_batch)
+        return URF_ERR_CAPACITY;
+    urf_dense_args d{};
+    d.id = d_data + off_laser;
+    d.id_stride = point_step;
+    d.id_bytes = laser_bytes;
+    d.data = d_data;
+    d.step = point_step;
+    d.ox = off_x;
+    d.oy = off_y;
+    d.oz = off_z;
+    return classify_batch_dense(c, URF_LAST_PC2, d, d_offsets, max_len, n_scans, max_firings, d_labels, d_info);
+}
+
 /* ---- the callback path: one sweep, host buffers ------------------------------- */
 /* Slot i of the callback path works on scratch row i % rows, rows = min(max_batch, URF_ASYNC_SLOTS), and on
  * that row's compute stream (row 0: the context's stream): with a context created for several scans the
@@ -1598,6 +1762,16 @@ static const urf_last_call* last_valid(urf_ctx* c, uint32_t scan = 0, int kind =
     return scan < l.scans && l.a.labels ? &l : nullptr;   /* (no call yet: no scans) */
 }
 
+/* After a dense call (urf_classify_batch_*_dense) the record is the PADDED batch: what answers in padded indices -- urf_ordered_indices*,
+ * urf_clouds_batch_* in the reference order, urf_read_stage -- is refused (mapping them back is not built). */
+static bool refuse_dense(urf_ctx* c, const char* what)
+{
+    if (!c->last.dense.on)
+        return false;
+    c->last_error = std::string(what) + ": not available after a dense call (urf_classify_batch_*_dense): its results index the padded sweeps";
+    return true;
+}
+
 /* The readers' way to the last call and its scratch ROW: valid, on the context's device, the row intact and ring-sorted, the context's
  * stream behind the sweeps in flight.  A sweep's row is only intact while no later sweep has been submitted on it (slots that share a
  * row: max_batch < URF_MAX_IN_FLIGHT and more sweeps in flight than rows). */
@@ -1722,7 +1896,7 @@ extern "C" int urf_ordered_indices_batch(urf_ctx* c, uint32_t* d_road, uint32_t*
                                          uint32_t* d_counts)
 {
     const urf_last_call* l = c ? last_valid(c) : nullptr;
-    if (!l || !d_counts || stride < l->a.max_len)
+    if (!l || !d_counts || stride < l->a.max_len || refuse_dense(c, "urf_ordered_indices_batch"))
         return URF_ERR_INVALID_ARG;
     const int rc = last_call(c, 0, l, URF_NEED_RING_ORDER);
     return rc != URF_OK ? rc : launch_ordered(c, *l, 0, l->scans, d_road, d_curb, d_ring10, stride, d_counts);
@@ -1731,7 +1905,7 @@ extern "C" int urf_ordered_indices_batch(urf_ctx* c, uint32_t* d_road, uint32_t*
 extern "C" int urf_ordered_indices(urf_ctx* c, uint32_t scan, uint32_t* road, uint32_t* curb, uint32_t* ring10,
                                    uint32_t* counts)
 {
-    if (!c || !counts)
+    if (!c || !counts || refuse_dense(c, "urf_ordered_indices"))
         return URF_ERR_INVALID_ARG;
     const size_t mp = c->sstride;
     const urf_last_call* l;
@@ -1778,7 +1952,10 @@ static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, ur
     const urf_last_call* l;
     if (!d_counts || !d_offsets || (order != URF_ORDER_INPUT && order != URF_ORDER_REFERENCE) || !(l = last_valid(c, 0, kind)))
         return URF_ERR_INVALID_ARG;
-    const uint32_t S = l->scans, max_len = l->a.max_len, stride = max_len ? max_len : 1u;
+    const bool dense = l->dense.on;   /* input order: the caller's dense labels, inputs and offsets; the reference order is the padded batch's */
+    if (dense && order == URF_ORDER_REFERENCE && refuse_dense(c, "urf_clouds_batch_* with URF_ORDER_REFERENCE"))
+        return URF_ERR_INVALID_ARG;
+    const uint32_t S = l->scans, max_len = dense ? l->dense.max_len : l->a.max_len, stride = max_len ? max_len : 1u;
     if (d_records && capacity < 3ull * S * max_len)
         return URF_ERR_CAPACITY;
     URF_HIP(c, hipSetDevice(c->device));
@@ -1802,6 +1979,18 @@ static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, ur
     src.n_per_scan = a.n_per_scan;
     src.max_len = a.max_len;
     src.tiles = a.tiles;
+    if (dense) {
+        src.labels = l->dense.labels;
+        src.offsets = c->offsets_copy;
+        src.n_per_scan = 0;
+        src.max_len = max_len;
+        src.tiles = max_len ? (max_len + URF_TILE - 1) / URF_TILE : 1u;
+        if (kind == URF_LAST_SOA) {
+            src.x = (const unsigned*)l->dense.x;
+            src.y = (const unsigned*)l->dense.y;
+            src.z = (const unsigned*)l->dense.z;
+        }
+    }
     src.n_scans = S;
     src.tile_cnt = c->cl_tiles.p;
     src.tile_base = src.tile_cnt + (size_t)c->max_batch * c->max_tiles;
@@ -1812,7 +2001,7 @@ static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, ur
     src.list_cnt = c->cl_lists.p ? c->cl_lists.p + 3 * (size_t)S * stride : nullptr;
     src.stride = stride;
     hipStream_t st = c->stream;
-    const dim3 g_tiles(a.tiles, S);
+    const dim3 g_tiles(src.tiles, S);
     hipLaunchKernelGGL(k_clouds_count, g_tiles, dim3(URF_CLOUDS_COUNT_THREADS), 0, st, src);
     hipLaunchKernelGGL(k_clouds_scan, dim3(S), dim3(URF_CLOUDS_THREADS), 0, st, src);
     hipLaunchKernelGGL(k_clouds_offsets, dim3(1), dim3(URF_CLOUDS_OFF_THREADS), 0, st, src);
@@ -1998,7 +2187,7 @@ static int ring_slot_sources(urf_ctx* c, const urf_last_call& l, uint32_t scan, 
 
 extern "C" int urf_read_stage(urf_ctx* c, urf_stage what, uint32_t scan, void* host_dst, size_t bytes)
 {
-    if (!c || !host_dst)
+    if (!c || !host_dst || refuse_dense(c, "urf_read_stage"))
         return URF_ERR_INVALID_ARG;
     const urf_last_call* l;
     int rc = last_call(c, scan, l, URF_NEED_RING_SORTED);   /* (stage values are the general kernels', whatever urf_set_front_outputs says) */
