@@ -70,7 +70,7 @@ extern "C" {
  * urf_marker_strips_batch with struct urf_marker_strip, URF_MARKER_MAX_STRIPS, URF_MARKER_MAX_STRIP_POINTS (the line strips of
  * road_marker: one sweep on the host, a batch of sweeps on the device); urf_classify_batch_soa_dense / urf_classify_batch_pc2_dense with
  * urf_set_dense_slots and urf_dense_scans (dense sweeps put back into firing slots by laser id on the device, then classified as
- * organised ones).
+ * organised ones); urf_set_front_curb_points (front mode 3's curbPoints 1..8 at 16, 32 and 128 lasers per firing as well).
  * WHICH std::sort (4 above): the one of libstdc++ as shipped with GCC 5 .. 13 (bits/stl_algo.h: __sort = __introsort_loop with
  * _S_threshold 16, __move_median_to_first on (first + 1, mid, last - 1), __unguarded_partition, depth limit 2 * floor(log2 n),
  * __partial_sort as the fallback, then __final_insertion_sort); tests/test_stdsort.py pins the restatement against the std::sort
@@ -515,7 +515,8 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * batch call it applies to; 3: as 2 in everything (batch sizes, row-major sweeps, 16 / 32 lasers), and with channels == 64 additionally
  * curbPoints 1..8 instead of 5 only: one instance of the march and of its finish per value, the detectors' window of 2 * curbPoints + 1
  * heights in registers; chosen per call from the parameters in force (with curbPoints == 5 mode 3 launches the very kernels of modes 1
- * and 2).  curbPoints 9..30, and channels 16 / 32 with curbPoints != 5, keep the general kernels in every mode; modes 1 and 2 keep them
+ * and 2).  curbPoints 9..30 keep the general kernels in every mode; channels 16 / 32 with curbPoints != 5 keep them in every mode unless
+ * urf_set_front_curb_points (below) is on, which extends mode 3 to them; modes 1 and 2 keep them
  * for every curbPoints != 5.  urf_set_params starts the captured per-slot sequences of the callback path afresh, so a row-major
  * context in mode 3 whose curbPoints changes stays on the fused kernels there, with the instance for the new value.  Mode 3 is opt-in:
  * its times are in profiles/curb_points_bench.json.  urf_read_stage / urf_ordered_indices* / urf_marker_points* read ring-sorted intermediate
@@ -536,7 +537,7 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * urf_front_scans -- and so does the limit of 128 x 2048 points per scan: a 128 x 4096 sweep keeps the general kernels unless
  * urf_set_front_long_sweeps is on as well.  Every
  * 128-laser table entry is a ring to these kernels, entry 127 included (their records keep the ring in eight bits).  curbPoints != 5
- * keeps the general kernels at 128 lasers.  The switch is off by default and opt-in whatever tools/front_lasers_bench.py --lasers128
+ * keeps the general kernels at 128 lasers unless urf_set_front_curb_points (below) is on as well, in mode 3.  The switch is off by default and opt-in whatever tools/front_lasers_bench.py --lasers128
  * measures; turning it on allocates the per-scan tables these kernels need (URF_ERR_OOM: it stays off).
  *
  * Long sweeps (urf_set_front_long_sweeps): the limit of 128 tiles is the finish step's, which keeps a presence word and a count per
@@ -546,7 +547,17 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * row-major, ragged batches, the callback path's row-major sweeps and the read-outs of urf_set_front_outputs included: the same
  * kernels, the finish step with the LDS that many tiles need (108 KiB at 256 tiles: one workgroup per CU).  A call of at most 128 tiles
  * launches exactly what it launches with the switch off; a call of more than 256 tiles keeps the general kernels.  Opt-in: its times
- * are in profiles/front_long_bench.json. */
+ * are in profiles/front_long_bench.json.
+ *
+ * curbPoints 1..8 at 16, 32 and 128 lasers (urf_set_front_curb_points): mode 3's instances for curbPoints other than 5 exist at 64 lasers
+ * only unless this switch is on.  With it, mode 3 -- never modes 0, 1 and 2 -- also takes curbPoints 1..8 with channels == 16 or 32
+ * (k_front32_cp*, k_front16_cp*: the march of mode 3 with half or a quarter of the wave's lanes; the finish step is the 64-laser one, which
+ * takes the laser count at run time), and with channels == 128 when urf_set_front_lasers128 is on as well (k_front128_cp*,
+ * k_front_finish128_cp*, urban_road_filter_amd/csrc/urf_front128_cp.hpp: two windows of 2 * curbPoints + 1 heights per lane).  Everything
+ * above keeps its meaning with these instances: per-scan hand-back, identical labels and summaries, urf_front_scans, ragged batches,
+ * row-major sightings and the callback path's row-major sweeps, urf_set_front_long_sweeps, urf_set_front_outputs, the dense entry
+ * points.  curbPoints 9..30 keep the general kernels everywhere; with the switch off every call launches exactly what it launched
+ * before the switch existed.  Opt-in: its times are in profiles/curb_points_lasers_bench.json. */
 int urf_set_front_mode(urf_ctx* ctx, int mode);
 int urf_front_scans(urf_ctx* ctx, uint32_t* n_fused);
 /* 0 (default): as today.  1: with channels == 128 and curbPoints == 5, front modes 2 and 3 also send sweeps of 128 lasers per
@@ -558,6 +569,10 @@ int urf_set_front_lasers128(urf_ctx* ctx, int on);
  * like urf_set_front_mode.  A device that does not grant a workgroup the LDS the finish step needs at 256 tiles: URF_ERR_OOM, and the
  * switch stays off.  Anything else: URF_ERR_INVALID_ARG. */
 int urf_set_front_long_sweeps(urf_ctx* ctx, int on);
+/* 0 (default): as today, front mode 3 takes curbPoints other than 5 with channels == 64 only.  1: front mode 3 also takes curbPoints
+ * 1..8 with channels == 16 or 32, and with channels == 128 when urf_set_front_lasers128 is on; modes 0, 1 and 2 never do.  Forgets
+ * sightings / hand-backs like urf_set_front_mode.  Anything else: URF_ERR_INVALID_ARG. */
+int urf_set_front_curb_points(urf_ctx* ctx, int on);
 /* 0 (default): after a call that took the fused front end, urf_ordered_indices*, urf_clouds_batch_* with
  * URF_ORDER_REFERENCE and urf_marker_points* first run that call again through the general kernels, and the context stays with those.
  * 1: these read-outs take a fused call's results as they are (urban_road_filter_amd/csrc/urf_k_front_outputs.hpp: the rings' points

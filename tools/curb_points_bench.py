@@ -10,7 +10,15 @@ mode 3 existed: the general kernels (k_split + k_ring_general + k_label); with c
 difference is the noise floor of the method.  Per curbPoints: a label-equality gate (mode 3 == mode 2 on every scan of the batch, sampled
 scans == oracle B), warm-up, then --rounds rounds of ONE call of each context, interleaved, between device events.  Reported per arm:
 median and minimum ms per call, and the spread (max - min) / median over the rounds; "wins" = mode 3's median is below mode 2's by more
-than the larger of the two spreads.  The register counts and waves per SIMD of the instances come from tools/kernel_resources.py."""
+than the larger of the two spreads.  The register counts and waves per SIMD of the instances come from tools/kernel_resources.py.
+
+    timeout 900 python tools/curb_points_bench.py --lasers 16,32,128 [--scans 1024] [--scans128 256] [--out profiles/curb_points_lasers_bench.json]
+
+--lasers (default 64: the run above, unchanged): for another laser count L the workload is --scans (128 lasers: --scans128) resident
+urf_synth_cloud(L, 2048, scene, seed) sweeps under the wide region of interest (channels = L; 128: interval 0.05), in firing order and
+row-major, and the two arms are urf_set_front_curb_points on against off, BOTH in mode 3 (128: urf_set_front_lasers128 on in both) --
+off is what these parameters launch without the switch, the general kernels.  The interleaving, the label-equality gate and the
+"wins" rule are the same; the rows carry "lasers" and the arms are called "on" and "off" (p10 / p90 of the rounds next to the median)."""
 import argparse
 import json
 import os
@@ -35,6 +43,8 @@ def main():
     ap.add_argument("--cps", default="1,2,3,4,5,6,7,8")
     ap.add_argument("--distinct", type=int, default=16, help="distinct sweeps the batch is built from")
     ap.add_argument("--orders", default="firing,rows")
+    ap.add_argument("--lasers", default="64", help="laser counts (64: mode 3 against mode 2 on cfg2; 16, 32, 128: the curb-points switch on against off)")
+    ap.add_argument("--scans128", type=int, default=256, help="resident sweeps at 128 lasers")
     ap.add_argument("--no-resources", action="store_true")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -62,9 +72,78 @@ def main():
         ts = np.asarray(ts)
         return {"median_ms": float(np.median(ts)), "min_ms": float(ts.min()), "spread": float((ts.max() - ts.min()) / np.median(ts))}
 
-    base = [O.cfg_cloud("cfg2", 1 + s) for s in range(min(args.distinct, args.scans))]
-    with torch.cuda.stream(st):
+    def one_of(ctx, bufs, labels, n, scans):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ctx.classify_batch_soa(bufs[0], bufs[1], bufs[2], n, scans, labels, None)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def stats_p(ts):
+        r = stats(ts)
+        r["p10_ms"], r["p90_ms"] = float(np.percentile(ts, 10)), float(np.percentile(ts, 90))
+        return r
+
+    def lasers_run(L):
+        """urf_set_front_curb_points on against off, both in mode 3, at L lasers per firing."""
+        S, n = (args.scans128 if L == 128 else args.scans), L * COLS
+        clouds = [u.synth_cloud(L, COLS, 1 + s % 4, 100 + s) for s in range(min(args.distinct, S))]
         for order in args.orders.split(","):
+            src = clouds if order == "firing" else [tuple(np.ascontiguousarray(a.reshape(-1, L).T.reshape(-1)) for a in c) for c in clouds]
+            parts = [torch.from_numpy(np.concatenate([c[k] for c in src])).to(dev) for k in range(3)]
+            reps = (S + len(src) - 1) // len(src)
+            bufs = [t.repeat(reps)[:S * n].contiguous() for t in parts]
+            lab_on = torch.empty(S * n, dtype=torch.uint8, device=dev)
+            lab_off = torch.empty(S * n, dtype=torch.uint8, device=dev)
+            with u.Context(n, S) as c_on, u.Context(n, S) as c_off:
+                for c, on in ((c_on, 1), (c_off, 0)):
+                    c.set_stream(st.cuda_stream)
+                    if L == 128:
+                        c.set_front_lasers128(1)
+                    c.set_front_curb_points(on)
+                    c.set_front_mode(3)
+                for cp in [int(v) for v in args.cps.split(",")]:
+                    p = u.default_params().wide_roi()
+                    p.channels = L
+                    if L == 128:
+                        p.interval = 0.05
+                    p.curbPoints = cp
+                    c_on.set_params(p)
+                    c_off.set_params(p)
+                    for _ in range(max(args.warmup, 2)):
+                        one_of(c_on, bufs, lab_on, n, S)
+                        one_of(c_off, bufs, lab_off, n, S)
+                    torch.cuda.synchronize()
+                    if not torch.equal(lab_on, lab_off):
+                        raise SystemExit("label gate: %d lasers %s curbPoints %d: switch on and off differ" % (L, order, cp))
+                    got = lab_on[:2 * n].cpu().numpy().reshape(2, n)
+                    for k in (0, 1):
+                        if not np.array_equal(got[k], O.run_b(*src[k % len(src)], p)[0]):
+                            raise SystemExit("label gate: %d lasers %s curbPoints %d scan %d differs from oracle B" % (L, order, cp, k))
+                    t_on, t_off = [], []
+                    for _ in range(args.rounds):
+                        t_on.append(one_of(c_on, bufs, lab_on, n, S))
+                        t_off.append(one_of(c_off, bufs, lab_off, n, S))
+                    row = {"lasers": L, "scans": S, "order": order, "curbPoints": cp, "on": stats_p(t_on), "off": stats_p(t_off),
+                           "on_front_scans": int(c_on.front_scans()), "off_front_scans": int(c_off.front_scans())}
+                    row["on_scans_per_s"] = S / row["on"]["median_ms"] * 1e3
+                    row["off_scans_per_s"] = S / row["off"]["median_ms"] * 1e3
+                    row["speedup"] = row["off"]["median_ms"] / row["on"]["median_ms"]
+                    row["wins"] = bool(row["off"]["median_ms"] - row["on"]["median_ms"] >
+                                       max(row["on"]["spread"], row["off"]["spread"]) * row["off"]["median_ms"])
+                    out["results"].append(row)
+
+    lasers = [int(v) for v in args.lasers.split(",")]
+    if lasers != [64]:
+        out["metric"] = "curb_points_front_lasers"
+        out["workload"] = "urf_synth_cloud(L, %d, scene, seed), wide region of interest; 128 lasers: %d sweeps" % (COLS, args.scans128)
+    base = [O.cfg_cloud("cfg2", 1 + s) for s in range(min(args.distinct, args.scans))] if 64 in lasers else []
+    with torch.cuda.stream(st):
+        for L in lasers:
+            if L != 64:
+                lasers_run(L)
+        for order in (args.orders.split(",") if 64 in lasers else []):
             src = base if order == "firing" else [tuple(np.ascontiguousarray(a.reshape(-1, 64).T.reshape(-1)) for a in c) for c in base]
             parts = [torch.from_numpy(np.concatenate([c[k] for c in src])).to(dev) for k in range(3)]
             reps = (args.scans + len(src) - 1) // len(src)

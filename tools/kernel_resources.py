@@ -10,7 +10,17 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+_MEMO = {}   # flags -> rows: one compilation per process (the test modules that pin budgets share it), rows handed out as copies
+
+
 def resources(extra=()):
+    key = tuple(extra)
+    if key not in _MEMO:
+        _MEMO[key] = _resources(extra)
+    return [dict(r) for r in _MEMO[key]]
+
+
+def _resources(extra=()):
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-gpu-rdc",
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "urban_road_filter_amd", "csrc"),
            "-c", os.path.join(ROOT, "urban_road_filter_amd", "csrc", "urf_api.hip"), "-o", "/dev/null",

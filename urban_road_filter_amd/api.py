@@ -177,6 +177,7 @@ def lib(hooks=False):
         "urf_front_scans": [vp, C.c_void_p],
         "urf_set_front_lasers128": [vp, C.c_int],
         "urf_set_front_long_sweeps": [vp, C.c_int],
+        "urf_set_front_curb_points": [vp, C.c_int],
         "urf_set_front_outputs": [vp, C.c_int],
         "urf_callback_path_preset": [vp, C.c_uint32],
         "urf_classify_batch_soa_dense": [vp, fp, fp, fp, vp, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp],
@@ -394,7 +395,8 @@ class Context:
         count; include/urf.h): 0 never; 1 (default) batch calls of at least 192 scans of 64 lasers (16 / 32 lasers: never in mode 1, in either layout or on the callback path; opt in with mode 2)
         -- row-major sweeps are the exception to the 192: a context whose sweeps have turned out to be row-major takes it at any batch
         size, and on the callback path; 2 every batch call it applies to; 3 as 2, and with 64 lasers per firing curb_points 1..8 instead
-        of 5 only (9..30, and 16 / 32 lasers with curb_points != 5, keep the general kernels in every mode)."""
+        of 5 only (9..30 keep the general kernels in every mode; so do 16 / 32 / 128 lasers with curb_points != 5 unless
+        set_front_curb_points is on, which extends mode 3 to them)."""
         self._check(self._lib.urf_set_front_mode(self._h, int(mode)), "urf_set_front_mode")
 
     def set_front_lasers128(self, on):
@@ -407,6 +409,12 @@ class Context:
         (256 tiles: a 128 x 4096 sweep; every laser count the fused front end knows, firing order or row-major; include/urf.h); 0 (default)
         keeps the limit of 128 tiles.  Opt-in."""
         self._check(self._lib.urf_set_front_long_sweeps(self._h, int(on)), "urf_set_front_long_sweeps")
+
+    def set_front_curb_points(self, on):
+        """urf_set_front_curb_points: 1 lets front mode 3 take curb_points 1..8 with 16 or 32 lasers per firing too, and with 128 when
+        set_front_lasers128 is on (modes 0, 1 and 2 never; 9..30 keep the general kernels; include/urf.h); 0 (default) keeps curb_points
+        other than 5 to 64 lasers.  Opt-in."""
+        self._check(self._lib.urf_set_front_curb_points(self._h, int(on)), "urf_set_front_curb_points")
 
     def set_front_outputs(self, on):
         """urf_set_front_outputs: 1 lets ordered_indices*, clouds_batch_* in the reference order and marker_points* take the results of a call

@@ -116,6 +116,14 @@ public:
         if (rc != URF_OK)
             throw Error(rc, "urf_set_front_long_sweeps");
     }
+    /* urf_set_front_curb_points: front mode 3 also takes curbPoints 1..8 with channels == 16 or 32, and with 128 when setFrontLasers128
+     * is on (otherwise 64 lasers only).  Off by default and opt-in. */
+    void setFrontCurbPoints(bool on)
+    {
+        const int rc = urf_set_front_curb_points(ctx_, on ? 1 : 0);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_set_front_curb_points");
+    }
 
     /* Also build the "road_marker" MarkerArray (lidar_segmentation.cpp:295-351, 369-602, topic :59,601);
      * fixedFrame = params::fixedFrame (cfg:10).  Off by default: the polygon is a visualisation product. */
@@ -238,6 +246,14 @@ public:
         const int rc = urf_set_front_long_sweeps(ctx_, on ? 1 : 0);
         if (rc != URF_OK)
             throw Error(rc, "urf_set_front_long_sweeps");
+    }
+    /* urf_set_front_curb_points: front mode 3 also takes curbPoints 1..8 with channels == 16 or 32, and with 128 when setFrontLasers128
+     * is on (otherwise 64 lasers only).  Off by default and opt-in. */
+    void setFrontCurbPoints(bool on)
+    {
+        const int rc = urf_set_front_curb_points(ctx_, on ? 1 : 0);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_set_front_curb_points");
     }
 
     /* Dense messages (the driver dropped the non-returns) with a field named "ring" (UINT8 or UINT16, count 1) are put back into firing

@@ -90,40 +90,46 @@ enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR, URF
 
 
 /* curbPoints the fused front end has an instance for: 5 in every mode; with urf_set_front_mode(3) and 64 lasers per firing the values of
- * URF_FRONT_CP_MASK (urf_front.hpp).  16 / 32 / 128 lasers and 9..30 keep the general kernels. */
-static bool front_curb_points_ok(int front_mode, unsigned L, int cp)
+ * URF_FRONT_CP_MASK (urf_front.hpp); with urf_set_front_curb_points on top of that (cp_lasers) the same values at 16, 32 and 128 lasers (whether
+ * 128 lasers are taken at all is urf_set_front_lasers128's business: urf_policy::plan).  9..30 keep the general kernels everywhere. */
+static bool front_curb_points_ok(int front_mode, bool cp_lasers, unsigned L, int cp)
 {
-    return cp == 5 || (front_mode == 3 && L == 64u && cp >= 1 && cp <= 8 && ((URF_FRONT_CP_MASK >> cp) & 1u) != 0u);
+    return cp == 5 || (front_mode == 3 && (L == 64u || cp_lasers) && cp >= 1 && cp <= 8 && ((URF_FRONT_CP_MASK >> cp) & 1u) != 0u);
 }
-/* ... and the instances (64 lasers), chosen per call from the parameters in force: 5 is k_front / k_front_finish in every mode */
+/* ... and the instances, chosen per call from the laser count (lsh: 4, 5, 6, 7) and the parameters in force: 5 is k_front / k_front32 /
+ * k_front16 / k_front128 and k_front_finish / k_front_finish128 in every mode */
 using urf_front_fn = void (*)(urf_kargs, urf_dev_params);
 using urf_front_finish_fn = void (*)(urf_kargs, urf_dev_params, unsigned);
-static urf_front_fn front_kernel(int cp)
+#define URF_BY_CP(prefix, five)                                                                                                 \
+    switch (cp) {                                                                                                               \
+    case 1: return prefix##_cp1;                                                                                                \
+    case 2: return prefix##_cp2;                                                                                                \
+    case 3: return prefix##_cp3;                                                                                                \
+    case 4: return prefix##_cp4;                                                                                                \
+    case 6: return prefix##_cp6;                                                                                                \
+    case 7: return prefix##_cp7;                                                                                                \
+    case 8: return prefix##_cp8;                                                                                                \
+    }                                                                                                                           \
+    return five;
+static urf_front_fn front_kernel(unsigned lsh, int cp)
 {
-    switch (cp) {
-    case 1: return k_front_cp1;
-    case 2: return k_front_cp2;
-    case 3: return k_front_cp3;
-    case 4: return k_front_cp4;
-    case 6: return k_front_cp6;
-    case 7: return k_front_cp7;
-    case 8: return k_front_cp8;
+    if (lsh == 7u) {
+        URF_BY_CP(k_front128, k_front128)
+    } else if (lsh == 5u) {
+        URF_BY_CP(k_front32, k_front32)
+    } else if (lsh == 4u) {
+        URF_BY_CP(k_front16, k_front16)
     }
-    return k_front;
+    URF_BY_CP(k_front, k_front)
 }
-static urf_front_finish_fn front_finish_kernel(int cp)
+static urf_front_finish_fn front_finish_kernel(unsigned lsh, int cp)
 {
-    switch (cp) {
-    case 1: return k_front_finish_cp1;
-    case 2: return k_front_finish_cp2;
-    case 3: return k_front_finish_cp3;
-    case 4: return k_front_finish_cp4;
-    case 6: return k_front_finish_cp6;
-    case 7: return k_front_finish_cp7;
-    case 8: return k_front_finish_cp8;
+    if (lsh == 7u) {
+        URF_BY_CP(k_front_finish128, k_front_finish128)
     }
-    return k_front_finish;
+    URF_BY_CP(k_front_finish, k_front_finish)   /* (the laser count at run time: front_lsh) */
 }
+#undef URF_BY_CP
 
 /* Scans of 129..256 tiles (urf_set_front_long_sweeps; 256 tiles: a 128 x 4096 sweep): the same finish kernels with the dynamic LDS their
  * layout needs for that many tiles -- a presence word and a 16-bit count per (tile, lane), 384 B per tile, and the chunk of the candidate
@@ -161,6 +167,7 @@ struct __attribute__((visibility("hidden"))) urf_policy {
     int front_mode = 1;
     bool every_batch() const { return front_mode >= 2; }
     bool lasers128 = false;         /* urf_set_front_lasers128: modes 2 and 3 take sweeps of 128 lasers per firing too (urf_front128.hpp; its scratch is there) */
+    bool curb_points = false;       /* urf_set_front_curb_points: mode 3 takes curbPoints 1..8 at 16, 32 and (lasers128) 128 lasers per firing too (k_front32_cp*, k_front16_cp*, urf_front128_cp.hpp) */
     bool long_sweeps = false;       /* urf_set_front_long_sweeps: modes 2 and 3 take scans of up to URF_FRONT_LONG_MAX_TILES tiles (the finish kernels with more dynamic LDS) */
     uint32_t front_max_tiles() const { return long_sweeps && every_batch() ? URF_FRONT_LONG_MAX_TILES : URF_FRONT_MAX_TILES; }
     uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
@@ -230,14 +237,14 @@ struct __attribute__((visibility("hidden"))) urf_policy {
         a.optimistic = slot ? ((speculate ? URF_OPT_NO_REPAIR : 0u) | (slot_lists ? 0u : URF_OPT_NO_LISTS) | (slot_nan ? 0u : URF_OPT_NO_NAN) |
                                (slot_ties ? 0u : URF_OPT_NO_TIES)) : 0u;
         /* The fused front end: a firing of 64, 32 or 16 lasers (params.channels) = the first lanes of a wave, the detectors' window of
-         * curbPoints == 5 (mode 3, 64 lasers: 1..8, URF_FRONT_CP_MASK; the instance is chosen per call, front_kernel()) in registers, no stage capture (its values are the general kernels').  Row-major sweeps gain from it at any batch size (the general kernels need 0.64 ms for four such
+         * curbPoints == 5 (mode 3, 64 lasers -- with urf_set_front_curb_points every laser count --: 1..8, URF_FRONT_CP_MASK; the instance is chosen per call, front_kernel()) in registers, no stage capture (its values are the general kernels').  Row-major sweeps gain from it at any batch size (the general kernels need 0.64 ms for four such
          * sweeps, the fused ones 0.26, tools/r6_min_scans.py --rows), sweeps in firing order only from 192 per call on, and not as single
          * sweeps of the callback path (tools/r6_single_sweep.py). */
         const unsigned L = (unsigned)dp.p.channels;
         const bool lasers = L == 64u || L == 32u || L == 16u || (L == 128u && lasers128 && every_batch());
         a.front_lsh = L == 16u ? 4u : (L == 32u ? 5u : (L == 128u ? 7u : 6u));
         const bool shape = front_mode != 0 && !front_off && !general_only && !want_ring_sorted && a.capture == 0 &&
-                           lasers && front_curb_points_ok(front_mode, L, dp.p.curbPoints) && a.tiles <= front_max_tiles();
+                           lasers && front_curb_points_ok(front_mode, curb_points, L, dp.p.curbPoints) && a.tiles <= front_max_tiles();
         /* (16 / 32 lasers: nothing below mode 2 until their crossover has been measured -- no batch size, no row-major sighting, no callback path) */
         const bool small_ok = front_rows && (rows_used || rows_probation > 0) && (L == 64u || every_batch());
         a.front = (shape && (slot ? small_ok : (every_batch() || small_ok || a.n_scans >= (L == 64u ? URF_FRONT_MIN_SCANS : (L == 32u ? URF_FRONT_MIN_SCANS_32 : URF_FRONT_MIN_SCANS_16))))) ? 1u : 0u;
@@ -827,6 +834,18 @@ extern "C" int urf_set_front_long_sweeps(urf_ctx* c, int on)
     return URF_OK;
 }
 
+extern "C" int urf_set_front_curb_points(urf_ctx* c, int on)
+{
+    if (!c || (on != 0 && on != 1))
+        return URF_ERR_INVALID_ARG;
+    if ((on != 0) != c->pol.curb_points)   /* (a new start) */
+        c->pol.forget_front();
+    c->pol.set(c->pol.curb_points, on != 0);
+    if (on)
+        c->pol.set(c->pol.want_ring_sorted, false);
+    return URF_OK;
+}
+
 extern "C" int urf_set_front_outputs(urf_ctx* c, int on)
 {
     if (!c || (on != 0 && on != 1))
@@ -1060,14 +1079,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
         hipLaunchKernelGGL(k_transpose, g_tiles, dim3(256), 0, st, a);
     if (a.front) {   /* (a tile is URF_TILE points, whatever the laser count: URF_TILE / L firings) */
         const dim3 g_front((a.tiles + a.front_tpb - 1) / a.front_tpb, n_scans);
-        if (l128)
-            hipLaunchKernelGGL(k_front128, g_front, dim3(64), 0, st, a, dp);
-        else if (a.front_lsh == 6u)
-            hipLaunchKernelGGL(front_kernel(dp.p.curbPoints), g_front, dim3(64), 0, st, a, dp);
-        else if (a.front_lsh == 5u)
-            hipLaunchKernelGGL(k_front32, g_front, dim3(64), 0, st, a, dp);
-        else
-            hipLaunchKernelGGL(k_front16, g_front, dim3(64), 0, st, a, dp);
+        hipLaunchKernelGGL(front_kernel(a.front_lsh, dp.p.curbPoints), g_front, dim3(64), 0, st, a, dp);
     }
     if (a.front_lists) {   /* what k_front handed back (normally nothing) */
         hipLaunchKernelGGL(k_table_repair, g_scan, dim3(URF_TABLE_THREADS), 0, st, a, dp, 1u);
@@ -1086,7 +1098,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
      * stream, so that the brackets add up to the step. */
     bool side = false, part1 = false;
     const size_t finish_lds = urf_finish_lds_bytes(l128 ? URF_FRONT128_TILES2(a.tiles) : a.tiles);   /* (above URF_FRONT_MAX_TILES tiles: urf_set_front_long_sweeps has asked the device) */
-    const urf_front_finish_fn finish = l128 ? k_front_finish128 : front_finish_kernel(dp.p.curbPoints);
+    const urf_front_finish_fn finish = front_finish_kernel(a.front_lsh, dp.p.curbPoints);
     if (a.front && !ev && !slot && side_fork(c, st)) {
         hipLaunchKernelGGL(finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, c->side_stream, a, dp, 1u);
         part1 = true;

@@ -1035,7 +1035,7 @@ __device__ __forceinline__ void urf_front_kernel(const urf_kargs& a, const urf_d
         else
             urf_front_body<true, true, L>(a, dp, cbuf);
     } else {
-        static_assert(CP == 5u || L == 64u, "curbPoints other than 5: 64 lasers per firing");
+        static_assert(L == 64u || L == 32u || L == 16u, "curbPoints other than 5: the laser counts urf_front_body_cp is written for");
         if (!dp.p.star_shaped_method)
             urf_front_body_cp<false, false, L, CP>(a, dp, cbuf);
         else if (!dp.p.starbeam_filter)
@@ -1067,6 +1067,25 @@ URF_FRONT_KERNEL(k_front_cp4, 64u, 4u, URF_FRONT_WAVES)
 URF_FRONT_KERNEL(k_front_cp6, 64u, 6u, URF_FRONT_WAVES_WIDE)
 URF_FRONT_KERNEL(k_front_cp7, 64u, 7u, URF_FRONT_WAVES_WIDE)
 URF_FRONT_KERNEL(k_front_cp8, 64u, 8u, URF_FRONT_WAVES_WIDE)
+/* urf_set_front_curb_points(ctx, 1): the same at 32 and 16 lasers per firing (mode 3).  Nothing in the body counts per wave what is counted per
+ * firing: the halos (HPRE, HPRE_WIDE, HPOST) are firings, and a lane meets at most one ring point per firing whatever L is; fw[] holds firings
+ * relative to Fs (at most front_tpb * URF_TILE / 16 + 20 < 65536); candidate indices are (firing) * L + lane; the region-of-interest words and
+ * the steps' keys (128 steps per tile at 16 lasers: stepkey_w) are urf_front_body's, which these laser counts have run with since k_front32 /
+ * k_front16.  The finish step is k_front_finish_cp*: it takes the laser count at run time (front_lsh). */
+URF_FRONT_KERNEL(k_front32_cp1, 32u, 1u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front32_cp2, 32u, 2u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front32_cp3, 32u, 3u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front32_cp4, 32u, 4u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front32_cp6, 32u, 6u, URF_FRONT_WAVES_WIDE)
+URF_FRONT_KERNEL(k_front32_cp7, 32u, 7u, URF_FRONT_WAVES_WIDE)
+URF_FRONT_KERNEL(k_front32_cp8, 32u, 8u, URF_FRONT_WAVES_WIDE)
+URF_FRONT_KERNEL(k_front16_cp1, 16u, 1u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front16_cp2, 16u, 2u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front16_cp3, 16u, 3u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front16_cp4, 16u, 4u, URF_FRONT_WAVES)
+URF_FRONT_KERNEL(k_front16_cp6, 16u, 6u, URF_FRONT_WAVES_WIDE)
+URF_FRONT_KERNEL(k_front16_cp7, 16u, 7u, URF_FRONT_WAVES_WIDE)
+URF_FRONT_KERNEL(k_front16_cp8, 16u, 8u, URF_FRONT_WAVES_WIDE)
 
 /* ------------------------------------------------------------------------- */
 /* k_front_finish                                                              */

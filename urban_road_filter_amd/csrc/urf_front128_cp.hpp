@@ -1,193 +1,44 @@
 /*
- * urf_front128.hpp -- the fused front end (urf_front.hpp) for sweeps of 128 lasers per firing (urf_set_front_lasers128): firing order
- * (point f * 128 + l) or row-major (128 rows).  The kernels of urf_front.hpp keep their source word for word -- their code generation is
- * what tests/test_kernel_resources.py and the benchmark pin -- and these stand beside them, each under a name of its own:
+ * urf_front128_cp.hpp -- the fused front end for 128 lasers per firing (urf_front128.hpp) and curbPoints 1..8 other than 5
+ * (urf_set_front_mode(ctx, 3) with urf_set_front_lasers128 and urf_set_front_curb_points on).  urf_front128_body and k_front_finish128
+ * keep their source word for word -- their code generation is what tests/test_front_lasers128_resources.py and the benchmark pin -- and
+ * these are their general forms, as urf_front_body_cp is urf_front_body's (urf_front.hpp): the constants 5, 3, 6, 4 and 11 as functions
+ * of CP.
  *
- *   k_front128          ONE wave per block, TWO lasers per lane: lane j marches lasers j and j + 64 (half 0 and half 1 of a firing), with
- *                       two windows and two sets of per-ring state.  The two halves of a firing are worked off back to back inside one
- *                       step, so that everything that crosses lanes -- the slot rank of a star participant, the one-sector test, the
- *                       step's key and count -- spans the 128 lasers in input order with two ballots and no LDS traffic or barrier, and
- *                       the candidate buffer stays "the workgroup is the wave".  The price is registers.
- *   k_front_finish128   k_front_finish with 128 rings' sizes, positions, largest ranges and curb lists.
- *   k_label_front128    k_label_front with the record's ring in EIGHT bits (URF_FRONT128_RING_*: table entry 127 is a ring, 0xff is
- *                       "none"; bits 7..10 of an input-order record are free) and a row-major store-back tile of 128 x 24 bytes.
- *   k_transpose128      k_transpose with 128 x 17 floats per plane.
- *   k_rows_probe128     k_rows_probe over 128 rows.
+ *   k_front128_cp{1,2,3,4,6,7,8}          the march: two windows of 2 * CP + 1 heights per lane, (CP + 2) / 2 registers of 16-bit firing
+ *                                         numbers per laser, URF_FRONT_HPRE_WIDE firings in front of a block for CP > 5.
+ *   k_front_finish128_cp{1,2,3,4,6,7,8}   k_front_finish128 with the ring positions both detectors accept and how far their neighbours
+ *                                         lie as functions of CP.
  *
- * What they leave behind keeps the layout its readers know, indexed by f * 128 + l: region-of-interest bits (two 64-bit words per
- * firing), slots (stp * 128 + l < 2048), tsoff, candidate indices.  What was sized for 64 lanes has a sibling sized for 128
- * (urf_kargs::*128), allocated when the switch is turned on.  A tile is 16 firings and a presence word 32 of them: word
- * (f >> 5) * 128 + l covers two tiles, so the words per scan are counted for an even number of tiles (URF_FRONT128_TILES2), and a
- * block of the march holds an even number of tiles (front_tpb, urf_api.hip) -- no presence word is shared between two blocks.
+ * k_label_front128, k_transpose128, k_rows_probe128 and the read-out kernels (urf_k_front_outputs.hpp) read records, presence words and
+ * lists: none of them knows curbPoints.  Included by urf_front128.hpp.
  */
-#ifndef URF_FRONT128_HPP
-#define URF_FRONT128_HPP
+#ifndef URF_FRONT128_CP_HPP
+#define URF_FRONT128_CP_HPP
 
-#define URF_FRONT128_L 128u
-#define URF_FRONT128_LSH 7u
-#define URF_FRONT128_STEPS (URF_TILE / URF_FRONT128_L)   /* firings per tile: 16 */
-#define URF_FRONT128_RING_MASK 0xffu   /* ring field of an input-order record of these kernels */
-#define URF_FRONT128_RING_NONE 0xffu
-#define URF_FRONT128_TILES2(tiles) (((tiles) + 1u) & ~1u)
-#define URF_FRONT128_ST_WORDS 136u     /* k_front_finish128 part 1 -> part 2: 128 list lengths, 4 quadrant values, list length, two counts */
-/* Entries per scan of the candidate lists of these kernels.  The points that pass the march's height tests are counted per LASER, not per
- * column: a ring that crosses a curb hands on up to eleven centres (z_zero) and six marked points (x_zero) per crossing, a street has four
- * crossings per ring -- 128 x 68 = 8 704 for 128 lasers however short the sweep is (a 128 x 256 street of urf_synth_cloud: 5 200 - 5 600),
- * above the context's max(max_points / 8, 4096) for sweeps below 128 x 544.  Twice that for range noise; a list that overflows still only
- * hands its scan back.
- * curbPoints 1..8 (urf_set_front_curb_points): 2 * CP + 1 centres and CP + 1 marked points per crossing, at 8 that is 17 and 9 -- 4 x 26 = 104 per
- * laser: 128 x 104 = 13 312 here, below the cap as it is; 32 x 104 = 3 328 and 16 x 104 = 1 664 at 32 and 16 lasers, below the context's floor of
- * 4096 (a block's border adds at most 2 * CP edge items per laser: 16 more per block).  No cap grows for the new instances. */
-#define URF_FRONT128_CAND_CAP(max_points) ((max_points) / 8u > 16384u ? (max_points) / 8u : 16384u)
-#ifndef URF_FRONT128_WAVES
-#define URF_FRONT128_WAVES 3           /* 168 registers: two windows, two sets of prefetched points */
+/* waves per SIMD of the instances: 1..4 hold k_front128's budget (three waves, 168 registers), 6..8 -- 2 x (13, 15, 17) heights and 2 x (4, 4, 5)
+ * registers of firing numbers -- the next one (two waves, 256 registers) */
+#ifndef URF_FRONT128_WAVES_WIDE
+#define URF_FRONT128_WAVES_WIDE 2
 #endif
 
-__global__ __launch_bounds__(256) void k_transpose128(urf_kargs a)
-{
-    /* [row][16 + 1]: a wave stores four rows x 16 columns (addresses 17 r + c: 64 different ones over a span of 67, three banks twice) and
-     * reads 64 rows of one column (stride 17: odd, no conflict) */
-    __shared__ float T[3][128 * 17];
-    const unsigned s = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
-    constexpr unsigned lsh = URF_FRONT128_LSH, L = 128u, wsh = 4u, W = 16u, RS = W + 1u;
-    static_assert(URF_TILE == 2048u, "a tile's columns: 1 << (11 - lsh)");
-    if (a.front_ok[s] != URF_FRONT_ROWS)
-        return;
-    unsigned off, len;
-    urf_scan_range(a, s, off, len);
-    const unsigned F = len >> lsh, f0 = t * W;
-    if (f0 >= F)
-        return;
-    const unsigned c = tid & (W - 1u), r8 = tid >> wsh, RP = 256u >> wsh;   /* 16 rows per pass, eight passes */
-    const bool in = f0 + c < F;
-    float vx[8], vy[8], vz[8];
-#pragma unroll
-    for (unsigned j = 0; j < 8; j++) {
-        const size_t i = (size_t)off + (size_t)(j * RP + r8) * F + f0 + (in ? c : 0u);
-        vx[j] = a.x[i];
-        vy[j] = a.y[i];
-        vz[j] = a.z[i];
-    }
-#pragma unroll
-    for (unsigned j = 0; j < 8; j++) {
-        T[0][(j * RP + r8) * RS + c] = vx[j];
-        T[1][(j * RP + r8) * RS + c] = vy[j];
-        T[2][(j * RP + r8) * RS + c] = vz[j];
-    }
-    __syncthreads();
-    const size_t ob = (size_t)urf_sbase(a, s) + (size_t)f0 * L;
-    const unsigned nf = F - f0 < W ? F - f0 : W;
-#pragma unroll
-    for (unsigned j = 0; j < 8; j++) {
-        const unsigned v = j * 256u + tid, f = v >> lsh, l = v & (L - 1u);
-        if (f < nf) {
-            a.tx[ob + v] = T[0][l * RS + f];
-            a.ty[ob + v] = T[1][l * RS + f];
-            a.tz[ob + v] = T[2][l * RS + f];
-        }
-    }
-}
-
-/* k_rows_probe (urf_k_table.hpp) over 128 rows: wave w takes rows 32 w .. 32 w + 31, four at a time; rows_v128[s][0 .. n) the leaders */
-__global__ __launch_bounds__(256) void k_rows_probe128(urf_kargs a, urf_dev_params dp)
-{
-    __shared__ unsigned sh_alive, sh_bad;
-    __shared__ float rowv[128];
-    const unsigned s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned off, len;
-    urf_scan_range(a, s, off, len);
-    constexpr unsigned lsh = URF_FRONT128_LSH, L = 128u;
-    if (len < 2u * L || (len & (L - 1u)) != 0u) {
-        if (tid == 0)
-            a.rows_ok[s] = 0u;
-        return;
-    }
-    const unsigned F = len >> lsh;
-    volatile unsigned* const alive = &sh_alive;
-    if (tid == 0) {
-        sh_alive = 1u;
-        sh_bad = 0u;
-    }
-    __syncthreads();
-    const float tol = 2.0f * dp.p.interval * 0.017453292f;
-    for (unsigned g = 0; g < 32u && *alive; g += 4u) {
-        const unsigned r0 = wave * 32u + g;
-        unsigned found = 0;   /* bit q: row r0 + q is settled */
-        for (unsigned c0 = 0; c0 < F && found != 15u && *alive; c0 += 64u) {
-            float px[4], py[4], pz[4];
-            const bool in = c0 + lane < F;
-#pragma unroll
-            for (unsigned q = 0; q < 4; q++) {
-                const size_t i = (size_t)off + (size_t)(r0 + q) * F + c0 + (in ? lane : 0u);
-                px[q] = a.x[i];
-                py[q] = a.y[i];
-                pz[q] = a.z[i];
-            }
-#pragma unroll
-            for (unsigned q = 0; q < 4; q++) {
-                if ((found >> q) & 1u)
-                    continue;   /* (uniform) */
-                const bool roi = in && urf_in_roi(dp.p, px[q], py[q], pz[q]);
-                const unsigned long long m = __ballot(roi);
-                if (m == 0ull)
-                    continue;
-                const int src = (int)__ffsll((long long)m) - 1;
-                /* one ring?  (cot of the vertical angle, to twice the interval: a hint -- k_front128 is the check) */
-                const float u = -pz[q] * __builtin_amdgcn_rsqf(px[q] * px[q] + py[q] * py[q]), u0 = __shfl(u, src);
-                if (__ballot(roi && !(__builtin_fabsf(u - u0) <= tol * (1.0f + u0 * u0))) != 0ull) {
-                    if (lane == 0)
-                        *alive = 0u;
-                    break;
-                }
-                const float v = urf_vertical_angle(__shfl(px[q], src), __shfl(py[q], src), __shfl(pz[q], src));
-                if (lane == 0)
-                    rowv[r0 + q] = v;
-                found |= 1u << q;
-            }
-        }
-#pragma unroll
-        for (unsigned q = 0; q < 4; q++)
-            if (!((found >> q) & 1u) && lane == 0)
-                rowv[r0 + q] = -1.0f;
-    }
-    __syncthreads();
-    /* put through the reference's insertion in row order, every one of them becomes a leader (k_rows_probe's (a)) */
-    float v = -1.0f;
-    unsigned before = 0;
-    if (tid < L) {
-        v = rowv[tid];
-        bool bad = v == 0.0f;
-        for (unsigned j = 0; j < L; j++) {
-            const float w = rowv[j];
-            bad = bad || (j < tid && v >= 0.0f && w >= 0.0f && __builtin_fabsf(w - v) <= dp.p.interval);
-            before += (j < tid && w >= 0.0f) ? 1u : 0u;
-        }
-        if (bad)
-            sh_bad = 1u;
-    }
-    __syncthreads();
-    const bool ok = sh_alive != 0u && sh_bad == 0u;
-    if (tid < L && ok && v >= 0.0f)
-        a.rows_v128[(size_t)s * L + before] = v;   /* compacted: the reference's angle[] before its sort */
-    if (tid == L - 1u)
-        a.rows_ok[s] = ok ? before + (v >= 0.0f ? 1u : 0u) + 1u : 0u;
-}
-
-/* The march of urf_front_body (urf_front.hpp) for 128 lasers, curbPoints == 5: h = 0, 1 is the half of the firing, laser h * 64 + lane.
- * Every array of two below is indexed by constants only (the loops over h are unrolled): registers. */
-struct urf_front128_ring {
+template <unsigned CP>
+struct urf_front128_ring_cp {
     unsigned E;          /* the table entry this laser's points are expected on */
     bool econf;          /* ... and a point of this march has confirmed it */
     urf_front_thr th;
-    float w[11];         /* the window: w[10] the newest ring point */
-    unsigned fwA, fwB, fwC;
+    float w[2u * CP + 1u];         /* the window: w[2 * CP] the newest ring point */
+    unsigned fw[(CP + 2u) / 2u];   /* firing (relative to Fs) of the CP + 1 newest, 16 bits each, the newest in the upper half of the last */
     unsigned wc, tot, nin;
     double maxs;
     unsigned pw;
 };
 
-template <bool STAR, bool BEAM>
-__device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
+/* The march of urf_front128_body for any curbPoints of 1..8: h = 0, 1 is the half of the firing, laser h * 64 + lane; CP, H = CP / 2 as in
+ * urf_front_body_cp -- z_zero's centre is w[CP], x_zero's triple (w[CP], w[CP + H], w[2 CP]) and the point it marks the one CP - H back
+ * (CP == 1: the triple is (j, j, j + 1)).  Every array below is indexed by constants only (the loops are unrolled): registers. */
+template <bool STAR, bool BEAM, unsigned CP>
+__device__ __forceinline__ void urf_front128_body_cp(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
 {
     const unsigned s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
     unsigned off, len;
@@ -200,15 +51,18 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
     if (ok == 0u)
         return;
     constexpr unsigned L = URF_FRONT128_L, C = L, STEPS = URF_FRONT128_STEPS;
+    static_assert(CP >= 1u && CP <= 8u && URF_FRONT_HPOST >= CP, "the halo behind a block completes the last centre's window");
+    constexpr unsigned H = CP / 2u, NW = 2u * CP + 1u, NFW = (CP + 2u) / 2u;
+    constexpr unsigned HPRE = CP <= 5u ? URF_FRONT_HPRE : URF_FRONT_HPRE_WIDE;   /* CP + H ring points in front of a block's first marked point */
     const unsigned K = (unsigned)dp.p.sectors;
     const unsigned nf = (len + L - 1u) / L;                                 /* firings of the scan */
     const unsigned F0 = t_first * STEPS;
     const unsigned F1 = F0 + TPB * STEPS < nf ? F0 + TPB * STEPS : nf;
-    const unsigned Fs = F0 > URF_FRONT_HPRE ? F0 - URF_FRONT_HPRE : 0u;
+    const unsigned Fs = F0 > HPRE ? F0 - HPRE : 0u;
     const unsigned Fe = F1 + URF_FRONT_HPOST < nf ? F1 + URF_FRONT_HPOST : nf;
     const bool from_start = Fs == 0u;   /* the window count IS the ring position + 1 */
     const bool to_end = Fe == nf;       /* no point of the scan lies behind the march */
-    static_assert(URF_FRONT_HPRE % 4u == 0u && STEPS % 4u == 0u, "the march runs in groups of four firings");
+    static_assert(HPRE % 4u == 0u && STEPS % 4u == 0u, "the march runs in groups of four firings");
     const unsigned sb = urf_sbase(a, s);
     const unsigned tiles2 = URF_FRONT128_TILES2(a.tiles);
     const float *gx, *gy, *gz;
@@ -223,20 +77,26 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
     const float curbH = dp.p.curbHeight;
     const bool use_x = dp.p.x_zero_method != 0, use_z = dp.p.z_zero_method != 0;
 
-    urf_front128_ring R[2];
+    urf_front128_ring_cp<CP> R[2];
 #pragma unroll
     for (unsigned h = 0; h < 2; h++) {
         R[h].E = h * 64u + lane;
         R[h].econf = false;
         R[h].th = urf_front_load_thr(a, s, C, R[h].E, nR);
 #pragma unroll
-        for (unsigned k = 0; k < 11; k++)
+        for (unsigned k = 0; k < NW; k++)
             R[h].w[k] = 0.f;
-        R[h].fwA = R[h].fwB = R[h].fwC = 0u;
+#pragma unroll
+        for (unsigned k = 0; k < NFW; k++)
+            R[h].fw[k] = 0u;
         R[h].wc = R[h].tot = R[h].nin = 0u;
         R[h].maxs = 0.0;
         R[h].pw = 0u;
     }
+    auto fwat = [](const urf_front128_ring_cp<CP>& r, auto back) -> unsigned {   /* firing of the point `back` places behind the newest */
+        constexpr unsigned SL = 2u * NFW - 1u - decltype(back)::value;
+        return (SL & 1u) ? r.fw[SL / 2u] >> 16 : r.fw[SL / 2u] & 0xffffu;
+    };
     bool failed = false, overflow = false;
     unsigned long long failed_m = 0;   /* what the hot path finds wrong, as lane masks (wave-uniform) */
     unsigned ncb = 0;                  /* candidates in the wave's buffer */
@@ -265,7 +125,7 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
         unsigned long long psm[2] = { 0ull, 0ull };
 #pragma unroll
         for (unsigned h = 0; h < 2; h++) {
-            urf_front128_ring& r = R[h];
+            urf_front128_ring_cp<CP>& r = R[h];
             const float x = X[h], y = Y[h], z = Z[h];
             const unsigned i = f * L + h * 64u + lane;
             rho2[h] = x * x + y * y;
@@ -340,7 +200,7 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
         /* the lasers' windows move on by their new ring points; what has become decidable is decided */
 #pragma unroll
         for (unsigned h = 0; h < 2; h++) {
-            urf_front128_ring& r = R[h];
+            urf_front128_ring_cp<CP>& r = R[h];
             if (on[h]) {
                 if (PH == 1u) {
                     const double s2 = (double)X[h] * (double)X[h] + (double)Y[h] * (double)Y[h];
@@ -349,13 +209,14 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
                 }
                 r.econf = true;
 #pragma unroll
-                for (unsigned k = 0; k < 10; k++)
+                for (unsigned k = 0; k + 1u < NW; k++)
                     r.w[k] = r.w[k + 1u];
-                r.w[10] = Z[h];
-                r.fwA = __builtin_amdgcn_alignbit(r.fwB, r.fwA, 16);
-                r.fwB = __builtin_amdgcn_alignbit(r.fwC, r.fwB, 16);
-                r.fwC = __builtin_amdgcn_alignbit(f - Fs, r.fwC, 16);
-                r.wc = r.wc < 11u ? r.wc + 1u : 11u;
+                r.w[NW - 1u] = Z[h];
+#pragma unroll
+                for (unsigned k = 0; k + 1u < NFW; k++)
+                    r.fw[k] = __builtin_amdgcn_alignbit(r.fw[k + 1u], r.fw[k], 16);
+                r.fw[NFW - 1u] = __builtin_amdgcn_alignbit(f - Fs, r.fw[NFW - 1u], 16);
+                r.wc = r.wc < NW ? r.wc + 1u : NW;
                 if (PH >= 1u)
                     r.tot++;
                 if (PH == 1u)
@@ -363,17 +224,18 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
             }
             if (PH == 0u)
                 continue;
-            const bool full = r.wc == 11u;
-            /* the centre (five points back) and the point x_zero marks (three back): are they this block's */
-            const bool c_in = on[h] & (r.tot >= 6u) & (r.tot - 5u <= r.nin);
-            const bool p_in = on[h] & (r.tot >= 4u) & (r.tot - 3u <= r.nin);
+            const bool full = r.wc == NW;
+            /* the centre (CP points back) and the point x_zero marks (CP - H back): are they this block's */
+            const bool c_in = on[h] & (r.tot >= CP + 1u) & (r.tot - CP <= r.nin);
+            const bool p_in = on[h] & (r.tot >= CP - H + 1u) & (r.tot - (CP - H) <= r.nin);
             /* z_zero_method.cpp:39-40, 48-49, 67-69 */
-            const float a5 = __builtin_fabsf(r.w[5]);
-            const float m1 = urf_front_absmax<6u, 0, 1>(r.w);     /* the five older points, then the centre */
-            const float m2 = urf_front_absmax<6u, 10, -1>(r.w);   /* the five newer points from the newest on, then the centre */
+            const float a5 = __builtin_fabsf(r.w[CP]);
+            const float m1 = urf_front_absmax<CP + 1u, 0, 1>(r.w);                 /* the CP older points, then the centre */
+            const float m2 = urf_front_absmax<CP + 1u, (int)(2u * CP), -1>(r.w);   /* the CP newer points from the newest on, then the centre */
             const bool hz = ((m1 - a5 >= curbH) | (m2 - a5 >= curbH)) & (__builtin_fabsf(m1 - m2) >= 0.05f);
-            /* x_zero_method.cpp:62-64 for the triple (w5, w7, w10) = (j, j + 2, j + 5) */
-            const bool hx = ((__builtin_fabsf(r.w[5] - r.w[7]) >= curbH) | (__builtin_fabsf(r.w[10] - r.w[7]) >= curbH)) & (__builtin_fabsf(r.w[5] - r.w[10]) >= 0.05f);
+            /* x_zero_method.cpp:62-64 for the triple (w[CP], w[CP + H], w[2 CP]) = (j, j + H, j + CP) */
+            const bool hx = ((__builtin_fabsf(r.w[CP] - r.w[CP + H]) >= curbH) | (__builtin_fabsf(r.w[2u * CP] - r.w[CP + H]) >= curbH)) &
+                            (__builtin_fabsf(r.w[CP] - r.w[2u * CP]) >= 0.05f);
             bool zz = false, xz = false, ez = false, ex = false;
             if (use_z) {   /* (uniform) */
                 zz = c_in && full && hz;
@@ -386,8 +248,8 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
                     ex = p_in && !full;
             }
             if (__ballot(zz | xz | ez | ex) != 0ull) {   /* (uniform) */
-                urf_front_push(cbuf, ncb, zz | ez, ((r.fwA & 0xffffu) + Fs) * L + h * 64u + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
-                urf_front_push(cbuf, ncb, xz | ex, ((r.fwB & 0xffffu) + Fs) * L + h * 64u + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
+                urf_front_push(cbuf, ncb, zz | ez, (fwat(r, std::integral_constant<unsigned, CP>{}) + Fs) * L + h * 64u + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
+                urf_front_push(cbuf, ncb, xz | ex, (fwat(r, std::integral_constant<unsigned, CP - H>{}) + Fs) * L + h * 64u + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
                 if (ncb > URF_FRONT_CBUF - 128u)
                     urf_front_flush(a, s, cbuf, ncb, overflow);
             }
@@ -492,19 +354,26 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
     }
 #pragma unroll
     for (unsigned h = 0; h < 2; h++) {
-        urf_front128_ring& r = R[h];
+        urf_front128_ring_cp<CP>& r = R[h];
         /* the block's last ring points of every laser: their windows reach behind the march */
         if (!to_end) {
-            const unsigned fr[5] = { r.fwA >> 16, r.fwB & 0xffffu, r.fwB >> 16, r.fwC & 0xffffu, r.fwC >> 16 };   /* entries 6..10 */
-#pragma unroll
-            for (unsigned e = 0; e < 5; e++) {
-                const unsigned back = 4u - e;   /* entry 6 + e is `back` points behind the newest */
+            /* the CP newest, oldest first: none has been a centre, the CP - H newest have not been x_zero's marked point either */
+            auto tail = [&](auto bk) {
+                constexpr unsigned back = decltype(bk)::value;
                 const bool in = r.tot > back && r.tot - back <= r.nin;
-                const unsigned what = (use_z ? URF_FC_EDGE_Z : 0u) | ((use_x && e >= 2u) ? URF_FC_EDGE_X : 0u);
+                const unsigned what = (use_z ? URF_FC_EDGE_Z : 0u) | ((use_x && back < CP - H) ? URF_FC_EDGE_X : 0u);
                 if (ncb > URF_FRONT_CBUF - 64u)
                     urf_front_flush(a, s, cbuf, ncb, overflow);
-                urf_front_push(cbuf, ncb, in && what != 0u, (fr[e] + Fs) * L + h * 64u + lane, what);
-            }
+                urf_front_push(cbuf, ncb, in && what != 0u, (fwat(r, bk) + Fs) * L + h * 64u + lane, what);
+            };
+            if constexpr (CP >= 8u) tail(std::integral_constant<unsigned, 7u>{});
+            if constexpr (CP >= 7u) tail(std::integral_constant<unsigned, 6u>{});
+            if constexpr (CP >= 6u) tail(std::integral_constant<unsigned, 5u>{});
+            if constexpr (CP >= 5u) tail(std::integral_constant<unsigned, 4u>{});
+            if constexpr (CP >= 4u) tail(std::integral_constant<unsigned, 3u>{});
+            if constexpr (CP >= 3u) tail(std::integral_constant<unsigned, 2u>{});
+            if constexpr (CP >= 2u) tail(std::integral_constant<unsigned, 1u>{});
+            tail(std::integral_constant<unsigned, 0u>{});
         }
         a.front_maxs128[(size_t)s * tiles2 * 64u + (size_t)b * L + h * 64u + lane] = (unsigned long long)__double_as_longlong(r.maxs);
         /* one laser, one ring -- over the whole scan: the blocks agree through the scan's two tables */
@@ -519,18 +388,23 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
         give_back();
 }
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT128_WAVES, URF_FRONT128_WAVES))) void k_front128(urf_kargs a, urf_dev_params dp)
-{
-    __shared__ urf_u2 cbuf[URF_FRONT_CBUF];
-    if (!dp.p.star_shaped_method)
-        urf_front128_body<false, false>(a, dp, cbuf);
-    else if (!dp.p.starbeam_filter)
-        urf_front128_body<true, false>(a, dp, cbuf);
-    else
-        urf_front128_body<true, true>(a, dp, cbuf);
-}
+#define URF_FRONT128_KERNEL(name, CP, WAVES)                                                                                          \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void name(urf_kargs a, urf_dev_params dp)     \
+    {                                                                                                                                 \
+        __shared__ urf_u2 cbuf[URF_FRONT_CBUF];                                                                                       \
+        if (!dp.p.star_shaped_method)                                                                                                 \
+            urf_front128_body_cp<false, false, CP>(a, dp, cbuf);                                                                      \
+        else if (!dp.p.starbeam_filter)                                                                                               \
+            urf_front128_body_cp<true, false, CP>(a, dp, cbuf);                                                                       \
+        else                                                                                                                          \
+            urf_front128_body_cp<true, true, CP>(a, dp, cbuf);                                                                        \
+    }
+URF_FRONT128_KERNEL(k_front128_cp1, 1u, URF_FRONT128_WAVES)
+URF_FRONT128_KERNEL(k_front128_cp2, 2u, URF_FRONT128_WAVES)
+URF_FRONT128_KERNEL(k_front128_cp3, 3u, URF_FRONT128_WAVES)
+URF_FRONT128_KERNEL(k_front128_cp4, 4u, URF_FRONT128_WAVES)
+URF_FRONT128_KERNEL(k_front128_cp6, 6u, URF_FRONT128_WAVES)
+URF_FRONT128_KERNEL(k_front128_cp7, 7u, URF_FRONT128_WAVES)
+URF_FRONT128_KERNEL(k_front128_cp8, 8u, URF_FRONT128_WAVES_WIDE)
 
-#include "urf_front128_cp.hpp"
-#include "urf_front128_finish.hpp"
-
-#endif /* URF_FRONT128_HPP */
+#endif /* URF_FRONT128_CP_HPP */

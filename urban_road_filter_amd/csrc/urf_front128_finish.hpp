@@ -1,5 +1,5 @@
 /*
- * urf_front128_finish.hpp -- k_front_finish and k_label_front (urf_front.hpp) for 128 lasers per firing, curbPoints == 5: the same
+ * urf_front128_finish.hpp -- k_front_finish and k_label_front (urf_front.hpp) for 128 lasers per firing (curbPoints 5; the others of 1..8: k_front_finish128_cp*): the same
  * phases and the same arithmetic, with 128 rings' sizes, positions, largest ranges and curb lists, the 128-laser siblings of the
  * arrays that are sized for 64 lanes (urf_kargs::*128) and the record's ring in eight bits.  Included by urf_front128.hpp.
  */
@@ -18,12 +18,16 @@ struct urf_finish128_shared {
 };
 
 /* parts as in urf_front_finish_body.  Dynamic LDS: P[tiles2][64] presence words | B[tiles2][64] (u16) | a chunk of the candidate list
- * (tiles2 = the scan's tiles rounded up to an even number: a presence word covers two tiles) */
+ * (tiles2 = the scan's tiles rounded up to an even number: a presence word covers two tiles).
+ * CP = params.curbPoints (k_front_finish128: 5, the default; k_front_finish128_cp*: the others of 1..8), H = CP / 2: the ring positions both
+ * detectors accept and how far their neighbours lie, as in urf_front_finish_body.  Nothing else in here knows CP, and nothing that uses
+ * it knows the laser count. */
+template <unsigned CP = 5u>
 __device__ __forceinline__ void urf_front128_finish_body(urf_kargs a, urf_dev_params dp, unsigned part)
 {
     __shared__ urf_finish128_shared S;
     extern __shared__ unsigned sh_finish[];   /* P[tiles][64] presence words | B[tiles][64] (u16) ring points of the lane in the tiles before */
-    constexpr unsigned CP = 5u, H = CP / 2u;
+    constexpr unsigned H = CP / 2u;
     const unsigned tiles2 = URF_FRONT128_TILES2(a.tiles);
     const unsigned s = blockIdx.x, tid = threadIdx.x;
     const unsigned ok = a.front_ok[s];
@@ -384,6 +388,19 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish128(urf_karg
 {
     urf_front128_finish_body(a, dp, part);
 }
+/* one kernel per curbPoints, as k_front_finish_cp* (urf_set_front_curb_points) */
+#define URF_FRONT128_FINISH_KERNEL(name, CP)                                                                  \
+    __global__ __launch_bounds__(URF_FINISH_THREADS) void name(urf_kargs a, urf_dev_params dp, unsigned part) \
+    {                                                                                                         \
+        urf_front128_finish_body<CP>(a, dp, part);                                                            \
+    }
+URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp1, 1u)
+URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp2, 2u)
+URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp3, 3u)
+URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp4, 4u)
+URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp6, 6u)
+URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp7, 7u)
+URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp8, 8u)
 
 /* k_label_front (urf_front.hpp) for the records of k_front128: the ring in eight bits, 128 rows of 16 + 8 label bytes for a row-major tile. */
 __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_label_front128(urf_kargs a, urf_dev_params dp)
