@@ -553,7 +553,7 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * only unless this switch is on.  With it, mode 3 -- never modes 0, 1 and 2 -- also takes curbPoints 1..8 with channels == 16 or 32
  * (k_front32_cp*, k_front16_cp*: the march of mode 3 with half or a quarter of the wave's lanes; the finish step is the 64-laser one, which
  * takes the laser count at run time), and with channels == 128 when urf_set_front_lasers128 is on as well (k_front128_cp*,
- * k_front_finish128_cp*, urban_road_filter_amd/csrc/urf_front128_cp.hpp: two windows of 2 * curbPoints + 1 heights per lane).  Everything
+ * k_front_finish128_cp*, urban_road_filter_amd/csrc/urf_front128.hpp: two windows of 2 * curbPoints + 1 heights per lane).  Everything
  * above keeps its meaning with these instances: per-scan hand-back, identical labels and summaries, urf_front_scans, ragged batches,
  * row-major sightings and the callback path's row-major sweeps, urf_set_front_long_sweeps, urf_set_front_outputs, the dense entry
  * points.  curbPoints 9..30 keep the general kernels everywhere; with the switch off every call launches exactly what it launched

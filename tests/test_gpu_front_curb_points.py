@@ -110,7 +110,7 @@ def test_detector_switches(cp, tweak):
         check_against_b(labels, infos, scans, p)
 
 
-@pytest.mark.parametrize("cp", (2, 6, 8))
+@pytest.mark.parametrize("cp", (2, 5, 6, 8))
 def test_holes_in_the_halos(cp):
     """Firings 24..40 and 58..70 of some lasers missing: the gaps straddle the tile borders at 32 and 64 -- the halos of one-tile blocks --
     and are wider (17) and narrower (13) than the window of 2 * cp + 1: windows that begin inside a march, decided by k_front_finish."""
@@ -127,7 +127,7 @@ def test_holes_in_the_halos(cp):
         check_against_b(labels, infos, [sw, sw], p)
 
 
-@pytest.mark.parametrize("cp", (1, 3, 8))
+@pytest.mark.parametrize("cp", (1, 3, 5, 8))
 def test_rings_barely_long_enough(cp):
     """Lasers that keep exactly 2 cp, 2 cp + 1 and 2 cp + 2 points (no centre, one, two): the detectors' [cp, n - 1 - cp] bounds."""
     x, y, z = (a.copy().reshape(64, 64) for a in u.synth_cloud(64, 64, 1, 9))

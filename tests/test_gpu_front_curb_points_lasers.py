@@ -1,5 +1,5 @@
 """urf_set_front_curb_points(ctx, 1): front mode 3's instances for curbPoints 1..8 at 16, 32 and 128 lasers per firing (urf_front.hpp:
-k_front32_cp*, k_front16_cp*; urf_front128_cp.hpp: k_front128_cp*, k_front_finish128_cp*; 128 lasers with urf_set_front_lasers128 on)
+k_front32_cp*, k_front16_cp*; urf_front128.hpp / urf_front128_finish.hpp: k_front128_cp*, k_front_finish128_cp*; 128 lasers with urf_set_front_lasers128 on)
 through the C ABI: labels and the seven summary fields against oracle B, exact.  What takes them (firing order and row-major, batches
 and the callback path, block borders crossed with and without holes in the halos, rings barely long enough for one window, long
 sweeps, the read-outs of urf_set_front_outputs, sensor models) and what must not (the switch off, modes 1 and 2, curbPoints 9).
@@ -138,7 +138,7 @@ def test_detector_switches(L, cp, tweak):
 
 # ---- 4. holes in the halos ----
 @pytest.mark.parametrize("L", LASERS)
-@pytest.mark.parametrize("cp", (2, 6, 8))
+@pytest.mark.parametrize("cp", (2, 5, 6, 8))
 def test_holes_in_the_halos(L, cp):
     """Some lasers lose all firings of two runs that straddle the block borders of the small shape -- 17 firings (as wide as the widest
     window, 2 * 8 + 1) around the first, 13 (wider than the windows of 2 and 6, narrower than that of 8) around the second: windows that
@@ -159,7 +159,7 @@ def test_holes_in_the_halos(L, cp):
 
 # ---- 5. rings barely long enough ----
 @pytest.mark.parametrize("L", LASERS)
-@pytest.mark.parametrize("cp", (1, 3, 8))
+@pytest.mark.parametrize("cp", (1, 3, 5, 8))
 def test_rings_barely_long_enough(L, cp):
     """Lasers that keep exactly 2 cp, 2 cp + 1 and 2 cp + 2 points (no centre, one, two): the detectors' [cp, n - 1 - cp] bounds."""
     cols = SMALL[L]

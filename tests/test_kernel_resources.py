@@ -24,7 +24,7 @@ def table():
 BUDGET = {"k_ring_table": (128, 4), "k_split": (85, 6), "k_index": (128, 4), "k_star_sort_small": (80, 6),
           "k_star_walk": (168, 3), "k_ring": (85, 6), "k_ring_general": (128, 4), "k_beams": (64, 6), "k_label": (64, 8),
           "k_star_sort_mid": (64, 8), "k_star_walk_few": (240, 2),
-          "k_front": (96, 5), "k_label_front": (64, 8)}   # k_star_walk_few: five waves on an empty device, occupancy is not its concern; k_beams: one workgroup of 768 threads per scan, two of them (24 waves) per CU
+          "k_front": (96, 5), "k_front32": (96, 5), "k_front16": (96, 5), "k_label_front": (64, 8)}   # k_front32 / k_front16: k_front's body at 32 / 16 lasers; k_star_walk_few: five waves on an empty device, occupancy is not its concern; k_beams: one workgroup of 768 threads per scan, two of them (24 waves) per CU
 
 
 @pytest.mark.parametrize("kernel", sorted(BUDGET))

@@ -100,36 +100,26 @@ static bool front_curb_points_ok(int front_mode, bool cp_lasers, unsigned L, int
  * k_front16 / k_front128 and k_front_finish / k_front_finish128 in every mode */
 using urf_front_fn = void (*)(urf_kargs, urf_dev_params);
 using urf_front_finish_fn = void (*)(urf_kargs, urf_dev_params, unsigned);
-#define URF_BY_CP(prefix, five)                                                                                                 \
-    switch (cp) {                                                                                                               \
-    case 1: return prefix##_cp1;                                                                                                \
-    case 2: return prefix##_cp2;                                                                                                \
-    case 3: return prefix##_cp3;                                                                                                \
-    case 4: return prefix##_cp4;                                                                                                \
-    case 6: return prefix##_cp6;                                                                                                \
-    case 7: return prefix##_cp7;                                                                                                \
-    case 8: return prefix##_cp8;                                                                                                \
-    }                                                                                                                           \
-    return five;
 static urf_front_fn front_kernel(unsigned lsh, int cp)
 {
-    if (lsh == 7u) {
-        URF_BY_CP(k_front128, k_front128)
-    } else if (lsh == 5u) {
-        URF_BY_CP(k_front32, k_front32)
-    } else if (lsh == 4u) {
-        URF_BY_CP(k_front16, k_front16)
+    switch (cp) {
+#define URF_FRONT_CP_X(n) \
+    case n: return lsh == 7u ? k_front128_cp##n : lsh == 5u ? k_front32_cp##n : lsh == 4u ? k_front16_cp##n : k_front_cp##n;
+        URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
+#undef URF_FRONT_CP_X
     }
-    URF_BY_CP(k_front, k_front)
+    return lsh == 7u ? k_front128 : lsh == 5u ? k_front32 : lsh == 4u ? k_front16 : k_front;
 }
 static urf_front_finish_fn front_finish_kernel(unsigned lsh, int cp)
 {
-    if (lsh == 7u) {
-        URF_BY_CP(k_front_finish128, k_front_finish128)
+    switch (cp) {   /* (64, 32 and 16 lasers: one kernel, the laser count at run time -- front_lsh) */
+#define URF_FRONT_CP_X(n) \
+    case n: return lsh == 7u ? k_front_finish128_cp##n : k_front_finish_cp##n;
+        URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
+#undef URF_FRONT_CP_X
     }
-    URF_BY_CP(k_front_finish, k_front_finish)   /* (the laser count at run time: front_lsh) */
+    return lsh == 7u ? k_front_finish128 : k_front_finish;
 }
-#undef URF_BY_CP
 
 /* Scans of 129..256 tiles (urf_set_front_long_sweeps; 256 tiles: a 128 x 4096 sweep): the same finish kernels with the dynamic LDS their
  * layout needs for that many tiles -- a presence word and a 16-bit count per (tile, lane), 384 B per tile, and the chunk of the candidate
@@ -167,7 +157,7 @@ struct __attribute__((visibility("hidden"))) urf_policy {
     int front_mode = 1;
     bool every_batch() const { return front_mode >= 2; }
     bool lasers128 = false;         /* urf_set_front_lasers128: modes 2 and 3 take sweeps of 128 lasers per firing too (urf_front128.hpp; its scratch is there) */
-    bool curb_points = false;       /* urf_set_front_curb_points: mode 3 takes curbPoints 1..8 at 16, 32 and (lasers128) 128 lasers per firing too (k_front32_cp*, k_front16_cp*, urf_front128_cp.hpp) */
+    bool curb_points = false;       /* urf_set_front_curb_points: mode 3 takes curbPoints 1..8 at 16, 32 and (lasers128) 128 lasers per firing too (k_front32_cp*, k_front16_cp*, k_front128_cp*) */
     bool long_sweeps = false;       /* urf_set_front_long_sweeps: modes 2 and 3 take scans of up to URF_FRONT_LONG_MAX_TILES tiles (the finish kernels with more dynamic LDS) */
     uint32_t front_max_tiles() const { return long_sweeps && every_batch() ? URF_FRONT_LONG_MAX_TILES : URF_FRONT_MAX_TILES; }
     uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */

@@ -9,8 +9,8 @@
  *
  * The legacy path sorts every tile by ring so that a workgroup per ring can stream its points (k_split: 39 B/point,
  * k_ring: 7 B/point more).  Here LANE l of a wave IS laser l: the wave marches along the firings of its block, 64
- * points (one firing) per step, coalesced 256-byte loads per array, and the lane keeps the last eleven points of ITS
- * ring in registers -- the window both detectors look at for curbPoints == 5 (x_zero_method.cpp:30-67: the triple
+ * points (one firing) per step, coalesced 256-byte loads per array, and the lane keeps the last 2 * curbPoints + 1 points of
+ * ITS ring in registers -- the window both detectors look at, eleven points for curbPoints == 5 (x_zero_method.cpp:30-67: the triple
  * (j, j + 2, j + 5); z_zero_method.cpp:21-72: the centre and five points on either side).  A lane whose point is
  * missing simply does not shift its window: a hole costs nothing and needs no compaction.  Nothing is sorted by ring,
  * nothing is transposed, x / y / z are read once and only the 4-byte record (input order) and the star-shaped search's
@@ -36,6 +36,16 @@
  * sectors that fall inside a tile, a ring point on the sensor's axis, an incomplete speculative ring table) clears
  * front_ok[s] and takes the legacy kernels, which skip every scan whose flag is still set.  Labels are the same
  * either way, bit for bit: the arithmetic is the legacy path's (urf_device.hpp, urf_x_zero_angle, urf_z_zero_angle).
+ *
+ * ONE march body per lane layout.  urf_front_body<STAR, BEAM, L, CP> is every k_front* of 64, 32 and 16 lasers, urf_front128_body<STAR,
+ * BEAM, CP> (urf_front128.hpp: two lasers per lane) every k_front128*; CP = params.curbPoints, 1..8, and 5 -- k_front, k_front32,
+ * k_front16, k_front128, the symbols of every front mode -- is an instance like the other seven (URF_FRONT_CP_OTHERS: the fused front
+ * modes 3 and urf_set_front_curb_points).  What depends on CP lives in urf_front_window<CP>, shared by both bodies: the 2 CP + 1 heights,
+ * the packed firing numbers, the detectors' height tests.  Until this layout the body for 5 was a copy with eleven named registers,
+ * because "with CP as a parameter" k_front had come out with 96 registers and a spill.  The parameter was not the cause: named scalars,
+ * arrays and a struct of arrays give the same code.  The cause is the few lines of the block-end tail (URF_FRONT_TAIL_CALLS), which tip the
+ * register allocation of the whole function one way or the other; tests/test_kernel_resources.py and its siblings hold every instance to
+ * its register budget and to no scratch, so a change that tips it back fails there.
  */
 #ifndef URF_FRONT_HPP
 #define URF_FRONT_HPP
@@ -58,7 +68,10 @@
 #define URF_FRONT_TPB_LARGE 4u    /* ... and from there on (less halo): 256 sweeps 0.663 / 0.703 ms at 2 / 4, 1024 sweeps 0.829 / 0.820 */
 #define URF_FRONT_TPB_SCANS 512u
 #define URF_FRONT_CP_MASK 0x1feu   /* curbPoints with a fused instance at 64 lasers (bit cp; 5 in every mode, the others with urf_set_front_mode(3)) */
-#define URF_FRONT_MAX_TILES 128u   /* k_front_finish keeps a presence word per (tile, lane) in LDS */
+/* ... and the values besides 5, for everything that exists once per value: the march at four laser counts (k_front*_cp<n>), the finish
+ * kernels (k_front_finish*_cp<n>) and the host's choice among them (urf_api.hip) */
+#define URF_FRONT_CP_OTHERS(X) X(1) X(2) X(3) X(4) X(6) X(7) X(8)
+#define URF_FRONT_MAX_TILES 128u  /* k_front_finish keeps a presence word per (tile, lane) in LDS */
 #define URF_FRONT_RING_NONE 0x7fu  /* ring field of an input-order record */
 /* candidate kinds */
 #define URF_FC_XZ 1u       /* passed x_zero's height tests as the marked point: angle test pending */
@@ -241,12 +254,104 @@ __device__ __forceinline__ void urf_front_push(urf_u2* cbuf, unsigned& ncb, bool
     ncb += (unsigned)__popcll(m);
 }
 
-/* L = the lasers of a firing (params.channels: 64, 32, 16).  Point f * L + l is laser slot l of firing f: everything the march leaves behind
+/* The window of one laser, for both marches (urf_front_body: one per lane; urf_front128_body, urf_front128.hpp: two).  CP =
+ * params.curbPoints, H = CP / 2.  It holds the laser's last 2 * CP + 1 ring points, w[2 * CP] the newest: z_zero's centre is w[CP] (CP points
+ * on either side, z_zero_method.cpp:21-50), x_zero's triple (j, j + H, j + CP) is (w[CP], w[CP + H], w[2 * CP]) and the point it marks the
+ * one CP - H back (x_zero_method.cpp:30-34; CP == 1: the triple is (j, j, j + 1)).  Both loops start at j = CP: a decision needs the FULL
+ * window.  fw[] keeps the firing numbers (relative to the march's first firing) of the newest CP + 1 points, 16 bits each, the newest in
+ * the upper half of the last register: the point `back` places behind it sits in half 2 * NFW - 1 - back.  Every index below is a
+ * constant once the loops are unrolled: registers. */
+template <unsigned CP>
+struct urf_front_window {
+    static_assert(CP >= 1u && CP <= 8u && URF_FRONT_HPOST >= CP, "the halo behind a block completes the last centre's window");
+    static constexpr unsigned H = CP / 2u, NW = 2u * CP + 1u, NFW = (CP + 2u) / 2u;
+    static constexpr unsigned HPRE = CP <= 5u ? URF_FRONT_HPRE : URF_FRONT_HPRE_WIDE;   /* CP + H ring points in front of a block's first marked point */
+    /* (the counters in front of the arrays: in the other order k_front128 needs a register more and k_front128_cp7 spills) */
+    unsigned wc;                           /* points in the window, at most NW */
+    unsigned tot, nin;                     /* ring points of this laser since the block's first firing / inside the block */
+    unsigned fw[NFW];                      /* (CP == 5: (f6 << 16 | f5), (f8 << 16 | f7), (f10 << 16 | f9)) */
+    float w[NW];
+
+    __device__ __forceinline__ void clear()
+    {
+#pragma unroll
+        for (unsigned k = 0; k < NW; k++)
+            w[k] = 0.f;
+#pragma unroll
+        for (unsigned k = 0; k < NFW; k++)
+            fw[k] = 0u;
+        wc = tot = nin = 0u;
+    }
+    /* a new ring point, met in firing `fr` of the march; PH: urf_front_body's phase */
+    template <unsigned PH>
+    __device__ __forceinline__ void push(const float z, const unsigned fr)
+    {
+#pragma unroll
+        for (unsigned k = 0; k + 1u < NW; k++)
+            w[k] = w[k + 1u];
+        w[NW - 1u] = z;
+#pragma unroll
+        for (unsigned k = 0; k + 1u < NFW; k++)
+            fw[k] = __builtin_amdgcn_alignbit(fw[k + 1u], fw[k], 16);
+        fw[NFW - 1u] = __builtin_amdgcn_alignbit(fr, fw[NFW - 1u], 16);
+        wc = wc < NW ? wc + 1u : NW;
+        if (PH >= 1u)
+            tot++;
+        if (PH == 1u)
+            nin++;
+    }
+    __device__ __forceinline__ bool full() const { return wc == NW; }
+    /* the centre (CP points back) and the point x_zero marks (CP - H back): are they this block's */
+    __device__ __forceinline__ bool c_in(const bool on) const { return on & (tot >= CP + 1u) & (tot - CP <= nin); }
+    __device__ __forceinline__ bool p_in(const bool on) const { return on & (tot >= CP - H + 1u) & (tot - (CP - H) <= nin); }
+    /* ... and the point `back` places behind the newest */
+    __device__ __forceinline__ bool in_block(const unsigned back) const { return tot > back && tot - back <= nin; }
+    /* z_zero_method.cpp:39-40, 48-49, 67-69.  (Window values are region-of-interest points' heights, never NaN: v_max3 with |.| modifiers,
+     * three instructions per side for CP == 5 -- the compiler's fmaxf quiets the first two operands of every chain with a v_max x, x each: five) */
+    __device__ __forceinline__ bool hz(const float curbH) const
+    {
+        const float a5 = __builtin_fabsf(w[CP]);
+        const float m1 = urf_front_absmax<CP + 1u, 0, 1>(w);                 /* the CP older points, then the centre */
+        const float m2 = urf_front_absmax<CP + 1u, (int)(2u * CP), -1>(w);   /* the CP newer points from the newest on, then the centre */
+        return ((m1 - a5 >= curbH) | (m2 - a5 >= curbH)) & (__builtin_fabsf(m1 - m2) >= 0.05f);   /* ((double)v >= 0.05 <=> v >= 0.05f: the float above 0.05) */
+    }
+    /* x_zero_method.cpp:62-64 for the triple (w[CP], w[CP + H], w[2 CP]) = (j, j + H, j + CP) */
+    __device__ __forceinline__ bool hx(const float curbH) const
+    {
+        return ((__builtin_fabsf(w[CP] - w[CP + H]) >= curbH) | (__builtin_fabsf(w[2u * CP] - w[CP + H]) >= curbH)) & (__builtin_fabsf(w[CP] - w[2u * CP]) >= 0.05f);
+    }
+    /* firing of the point `back` places behind the newest, of the centre, of the point x_zero marks */
+    __device__ __forceinline__ unsigned firing(const unsigned back) const
+    {
+        const unsigned sl = 2u * NFW - 1u - back;
+        return (sl & 1u) ? fw[sl / 2u] >> 16 : fw[sl / 2u] & 0xffffu;
+    }
+    __device__ __forceinline__ unsigned centre_firing() const { return firing(CP); }
+    __device__ __forceinline__ unsigned marked_firing() const { return firing(CP - H); }
+};
+
+/* The block-end tail of both marches: tail(CP - 1), ..., tail(0), each index a std::integral_constant, written out as calls of a NAMED
+ * lambda.  The form of these few lines decides the code of the WHOLE march at curbPoints 5 and 64 / 32 / 16 lanes: as a `#pragma unroll`
+ * loop (over an array of firing numbers taken out of fw[] first, or over firing(back)), or handed to a helper template that does the
+ * counting, k_front comes out with 96 registers, a 16-byte spill and 380 more v_mov_b32; like this with 92 and none.
+ * profiles/front_one_march.md has the table. */
+#define URF_FRONT_TAIL_CALLS(CP, tail)                                         \
+    if constexpr ((CP) >= 8u) tail(std::integral_constant<unsigned, 7u>{});    \
+    if constexpr ((CP) >= 7u) tail(std::integral_constant<unsigned, 6u>{});    \
+    if constexpr ((CP) >= 6u) tail(std::integral_constant<unsigned, 5u>{});    \
+    if constexpr ((CP) >= 5u) tail(std::integral_constant<unsigned, 4u>{});    \
+    if constexpr ((CP) >= 4u) tail(std::integral_constant<unsigned, 3u>{});    \
+    if constexpr ((CP) >= 3u) tail(std::integral_constant<unsigned, 2u>{});    \
+    if constexpr ((CP) >= 2u) tail(std::integral_constant<unsigned, 1u>{});    \
+    tail(std::integral_constant<unsigned, 0u>{});
+
+/* The march.  L = the lasers of a firing (params.channels: 64, 32, 16).  Point f * L + l is laser slot l of firing f: everything the march leaves behind
  * -- records, region-of-interest bits, the sector-sorted copies and their slots, candidate indices -- is indexed by the point's place in
  * the input, a tile is URF_TILE points = URF_TILE / L firings, and k_index and the star-shaped search read a scan of any L alike.  Only
  * the presence words count in firings: word (f >> 5) * L + l.  For L < 64 the lanes from L on are idle (no point, never in the region of
- * interest): one march per wave, the chain of a block URF_TILE / L steps per tile. */
-template <bool STAR, bool BEAM, unsigned L>
+ * interest): one march per wave, the chain of a block URF_TILE / L steps per tile.  CP = params.curbPoints, 1..8: 5 is an instance like
+ * the others (urf_front_window). */
+template <bool STAR, bool BEAM, unsigned L, unsigned CP>
 __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
 {
     const unsigned s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
@@ -262,393 +367,7 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
     constexpr unsigned C = L;                     /* table entries per scan: params.channels */
     constexpr unsigned STEPS = URF_TILE / L;      /* firings per tile */
     static_assert(L == 64u || L == 32u || L == 16u, "a firing fills the wave, half of it or a quarter");
-    const unsigned K = (unsigned)dp.p.sectors;
-    const unsigned nf = (len + L - 1u) / L;                                 /* firings of the scan */
-    const unsigned F0 = t_first * STEPS;
-    const unsigned F1 = F0 + TPB * STEPS < nf ? F0 + TPB * STEPS : nf;
-    const unsigned Fs = F0 > URF_FRONT_HPRE ? F0 - URF_FRONT_HPRE : 0u;
-    const unsigned Fe = F1 + URF_FRONT_HPOST < nf ? F1 + URF_FRONT_HPOST : nf;
-    const bool from_start = Fs == 0u;   /* the window count IS the ring position + 1 */
-    const bool to_end = Fe == nf;       /* no point of the scan lies behind the march */
-    static_assert(URF_FRONT_HPRE % 4u == 0u && STEPS % 4u == 0u, "the march runs in groups of four firings");
-    const unsigned sb = urf_sbase(a, s);
-    const float *gx, *gy, *gz;
-    urf_front_src(a, s, off, ok, gx, gy, gz);
-    const __amdgpu_buffer_rsrc_t brec = urf_buf(a.rec + sb, len * 4u);
-    const __amdgpu_buffer_rsrc_t bsr = urf_buf(a.sr + sb, a.tiles * URF_TILE * 4u), bsz = urf_buf(a.sz + sb, a.tiles * URF_TILE * 4u);
-    const __amdgpu_buffer_rsrc_t bss = urf_buf(a.sslot + sb, a.tiles * URF_TILE * 2u);
-    const unsigned nR = a.info[s].n_rings;
-    const unsigned upto_v = a.table_upto[s];
-    /* (a row-major scan's table rests on EVERY point lying on its row's entry -- k_ring_table's third rule: a point on none asks for the long walk) */
-    const unsigned upto = ok == URF_FRONT_ROWS ? 0u : (nR < C ? upto_v : 0xffffffffu);
-    const float* const tab = a.angle + (size_t)s * dp.p.channels;
-    const float curbH = dp.p.curbHeight;
-    const bool use_x = dp.p.x_zero_method != 0, use_z = dp.p.z_zero_method != 0;
-
-    unsigned E = lane;        /* the table entry this lane's points are expected on */
-    bool econf = false;       /* ... and a point of this march has confirmed it */
-    urf_front_thr th = urf_front_load_thr(a, s, C, E, nR);
-    bool failed = false, overflow = false;
-    unsigned long long failed_m = 0;   /* ... what the hot path finds wrong, as lane masks (wave-uniform) */
-    unsigned ncb = 0;         /* candidates in the wave's buffer */
-
-    /* the lane's window: w10 = its newest ring point, w0 the one ten before; firing (relative to Fs) of the six newest */
-    float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f, w4 = 0.f, w5 = 0.f, w6 = 0.f, w7 = 0.f, w8 = 0.f, w9 = 0.f, w10 = 0.f;
-    unsigned fwA = 0, fwB = 0, fwC = 0;   /* (f6 << 16 | f5), (f8 << 16 | f7), (f10 << 16 | f9) */
-    unsigned wc = 0;                       /* points in the window, at most 11 */
-    unsigned tot = 0, nin = 0;             /* ring points of this lane since the block's first firing / inside the block */
-    double maxs = 0.0;                     /* largest x*x + y*y among the lane's ring points of the block (maxDistance, lidar_segmentation.cpp:271-274) */
-    unsigned pw = 0;                       /* presence bits of the tile at hand */
-    /* per tile (wave-uniform) */
-    unsigned troi = 0, tstar = 0;
-    int stepkey_v = (int)URF_SEC_NONE, stepcnt_v = 0;   /* lane j: sector / participating points of step j of the tile */
-    int stepkey_w = (int)URF_SEC_NONE, stepcnt_w = 0;   /* (L = 16, 128 steps per tile) ... of step 64 + j */
-
-    /* one firing.  PH 0: the halo in front of the block (windows fill), 1: the block, 2: the halo behind it (windows complete) */
-    auto step = [&](auto ph, const unsigned f, const float x, const float y, const float z) {
-        constexpr unsigned PH = decltype(ph)::value;
-        const unsigned stp = f % STEPS;
-        const unsigned i = f * L + lane;
-        const bool roi = (L == 64u || lane < L) && i < len && urf_in_roi(dp.p, x, y, z);
-        const unsigned long long roim = __ballot(roi);
-        if (PH == 1u && lane == 0u) {   /* bit i of the scan's words: input point i */
-            if (L == 64u)
-                a.roi_bits[((size_t)s * a.tiles + f / STEPS) * STEPS + stp] = roim;
-            else if (L == 32u)
-                ((uint32_t*)(a.roi_bits + (size_t)s * a.tiles * (URF_TILE / 64u)))[f] = (uint32_t)roim;
-            else
-                ((uint16_t*)(a.roi_bits + (size_t)s * a.tiles * (URF_TILE / 64u)))[f] = (uint16_t)roim;
-        }
-        if (roim == 0ull)
-            return;   /* (uniform) nothing of this firing lies in the region of interest */
-        const float rho2 = x * x + y * y;
-        const float u = -z * __builtin_amdgcn_rsqf(rho2);   /* urf_fast_cot */
-        const bool fast = (rho2 >= URF_FAST_MIN2) & (rho2 <= URF_FAST_MAX2) & (__builtin_fabsf(u) <= URF_LUT_UMAX) & roi;
-        const bool on_f = fast & (u >= th.y) & (u <= th.z) & (u < th.below);
-        float fi = 0.f;
-        int fs = -1;
-        if (PH == 1u) {
-            fi = urf_fast_polar(x, y);
-            if (STAR)
-                fs = fast ? urf_fast_sector_ranged(fi, dp.Kfi, K, dp.sector_margin) : -1;
-        }
-        bool on = on_f;
-        const bool open = roi && !(on_f && (PH != 1u || !STAR || fs >= 0));
-        /* (r6, vector-issue diet: a ballot of anything but a direct compare costs two vector instructions -- v_cndmask 0 / 1, v_cmp -- to
-         * mask it with exec; a plain divergent branch skips its block when no lane takes it for two SCALAR instructions.  Wave-level
-         * flags (failed, overflow) are OR-ed up as masks, per-lane state that only rare paths read (econf) likewise.) */
-        if (open) {   /* rare: the reference's exact sequence for the lanes that need it */
-            const unsigned r = urf_front_open(tab, nR, dp.p.interval, x, y, z, (PH == 1u && STAR) ? K : 0u, dp.Kfi, E, econf ? 1u : 0u);
-            on = (r & 1u) != 0u;
-            fs = (int)((r >> 1) & 0x7ffu) - 1;
-            if (r & URF_FO_FAIL)
-                failed = true;
-            if (PH == 1u && (r & URF_FO_NONE) && i >= upto)
-                a.table_redo[s] = 1u;   /* the speculative ring table is incomplete (k_table_repair, legacy path) */
-            if (r & URF_FO_ADOPT) {   /* this lane's laser sits on another table entry: learned from its first point */
-                E = (r >> 12) & 0x7fu;
-                th = urf_front_load_thr(a, s, C, E, nR);
-            }
-        }
-        if (PH == 1u) {
-            /* the record, input order: ring | azimuth code (URF_REC_*; detector hits are OR-ed in by k_front_finish) */
-            const unsigned azc_v = urf_az_code(urf_fast_azimuth_of(fi));   /* (unconditionally, then a select: a branch around eight instructions costs more) */
-            const unsigned azc = urf_fast_az_ok(x, y) ? azc_v : URF_REC_AZ_UNKNOWN;
-            __builtin_amdgcn_raw_buffer_store_b32((azc << URF_REC_AZ_SHIFT) | (on ? E : URF_FRONT_RING_NONE), brec, (L == 64u || lane < L) ? i * 4u : URF_OOB, 0, URF_FRONT_NT);
-            if (STAR) {
-                /* star-shaped search: the firing's participants share one sector */
-                unsigned sk = (unsigned)fs;
-                if (BEAM && roi && !urf_in_beam(a.beams[fs < 0 ? 0 : fs], x, y))
-                    sk = URF_SEC_NONE;
-                /* (every lane is active here: the masks of direct compares need no exec) */
-                const unsigned long long psm = roim & __builtin_amdgcn_ballot_w64(sk != URF_SEC_NONE) & __builtin_amdgcn_ballot_w64((int)sk >= 0);
-                const bool ons = roi && sk != URF_SEC_NONE && (int)sk >= 0;
-                const unsigned src = psm ? (unsigned)__ffsll((long long)psm) - 1u : 0u;
-                const unsigned f0 = psm ? (unsigned)__builtin_amdgcn_readlane((int)sk, (int)src) : URF_SEC_NONE;
-                failed_m |= psm & __builtin_amdgcn_ballot_w64(sk != f0);
-                const unsigned so = (f / STEPS) * URF_TILE + tstar + urf_popc_below(psm);
-                const unsigned o4 = ons ? so * 4u : URF_OOB;
-                const float pr = urf_sqrt_rn_normal(rho2);   /* star_shaped_search.cpp:164: sqrtf(x * x + y * y) */
-                failed_m |= psm & ~(__builtin_amdgcn_ballot_w64(rho2 >= 0x1p-90f) & __builtin_amdgcn_ballot_w64(rho2 <= 0x1p126f));   /* (outside the shortcut's interval: the legacy kernels) */
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pr), bsr, o4, 0, URF_FRONT_NT);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(z), bsz, o4, 0, URF_FRONT_NT);
-                __builtin_amdgcn_raw_buffer_store_b16((short)((stp * L + lane) | (on ? 0u : URF_SLOT_OFF)), bss, ons ? so * 2u : URF_OOB, 0, URF_FRONT_NT);
-                if (STEPS <= 64u || stp < 64u) {   /* (uniform) */
-                    stepkey_v = lane == stp ? (int)f0 : stepkey_v;
-                    stepcnt_v = lane == stp ? (int)__popcll(psm) : stepcnt_v;
-                } else {
-                    stepkey_w = lane == stp - 64u ? (int)f0 : stepkey_w;
-                    stepcnt_w = lane == stp - 64u ? (int)__popcll(psm) : stepcnt_w;
-                }
-                tstar += (unsigned)__popcll(psm);
-            }
-            troi += (unsigned)__popcll(roim);
-        }
-        /* the lane's window moves on by its new ring point; what has become decidable is decided */
-        if (on) {
-            if (PH == 1u) {
-                const double s2 = (double)x * (double)x + (double)y * (double)y;
-                maxs = s2 > maxs ? s2 : maxs;
-                pw |= 1u << (f & 31u);
-            }
-            econf = true;
-            w0 = w1; w1 = w2; w2 = w3; w3 = w4; w4 = w5; w5 = w6; w6 = w7; w7 = w8; w8 = w9; w9 = w10;
-            w10 = z;
-            fwA = __builtin_amdgcn_alignbit(fwB, fwA, 16);
-            fwB = __builtin_amdgcn_alignbit(fwC, fwB, 16);
-            fwC = __builtin_amdgcn_alignbit(f - Fs, fwC, 16);
-            wc = wc < 11u ? wc + 1u : 11u;
-            if (PH >= 1u)
-                tot++;
-            if (PH == 1u)
-                nin++;
-        }
-        if (PH == 0u)
-            return;
-        /* (straight-line: every lane computes, the lanes without a new point are masked out at the end -- branches around the
-         * tests put the four results through registers and selects) */
-        const bool full = wc == 11u;
-        /* the centre (five points back) and the point x_zero marks (three back): are they this block's */
-        const bool c_in = on & (tot >= 6u) & (tot - 5u <= nin);
-        const bool p_in = on & (tot >= 4u) & (tot - 3u <= nin);
-        /* z_zero_method.cpp:39-40, 48-49, 67-69 */
-        const float a5 = __builtin_fabsf(w5);
-        /* (window values are region-of-interest points' heights, never NaN: v_max3 with |.| modifiers, three instructions per side --
-         * the compiler's fmaxf quiets the first two operands of every chain with a v_max x, x each: five) */
-        float m1, m2, t1, t2;
-        asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(t1) : "v"(w0), "v"(w1), "v"(w2));
-        asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(t1) : "v"(t1), "v"(w3), "v"(w4));
-        asm("v_max_f32_e64 %0, %1, |%2|" : "=v"(m1) : "v"(t1), "v"(w5));
-        asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(t2) : "v"(w10), "v"(w9), "v"(w8));
-        asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(t2) : "v"(t2), "v"(w7), "v"(w6));
-        asm("v_max_f32_e64 %0, %1, |%2|" : "=v"(m2) : "v"(t2), "v"(w5));
-        const bool hz = ((m1 - a5 >= curbH) | (m2 - a5 >= curbH)) & (__builtin_fabsf(m1 - m2) >= 0.05f);   /* ((double)v >= 0.05 <=> v >= 0.05f: the float above 0.05) */
-        /* x_zero_method.cpp:62-64 for the triple (w5, w7, w10) = (j, j + 2, j + 5) */
-        const bool hx = ((__builtin_fabsf(w5 - w7) >= curbH) | (__builtin_fabsf(w10 - w7) >= curbH)) & (__builtin_fabsf(w5 - w10) >= 0.05f);
-        /* (lane masks combined as masks: `&` on bools mixed with the wave-uniform switches went through 0 / 1 integers in vector
-         * registers -- v_cndmask, v_and, v_cmp per term) */
-        bool zz = false, xz = false, ez = false, ex = false;
-        /* a window that began inside this march (a block border with a hole in the halo, a ring that has just entered the
-         * region of interest): positions unknown here, k_front_finish decides */
-        if (use_z) {   /* (uniform) */
-            zz = c_in && full && hz;
-            if (!from_start)
-                ez = c_in && !full;
-        }
-        if (use_x) {
-            xz = p_in && full && hx;
-            if (!from_start)
-                ex = p_in && !full;
-        }
-        if (__ballot(zz | xz | ez | ex) != 0ull) {   /* (uniform) */
-            urf_front_push(cbuf, ncb, zz | ez, ((fwA & 0xffffu) + Fs) * L + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
-            urf_front_push(cbuf, ncb, xz | ex, ((fwB & 0xffffu) + Fs) * L + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
-            if (ncb > URF_FRONT_CBUF - 128u)
-                urf_front_flush(a, s, cbuf, ncb, overflow);
-        }
-    };
-    /* the presence words of 32 firings (L = 64: the tile's, tile_end) */
-    auto pres_end = [&](const unsigned pt) {
-        if (lane < L)
-            a.front_pres[(size_t)s * a.tiles * 64u + (size_t)pt * L + lane] = pw;
-        pw = 0;
-    };
-    auto tile_end = [&](const unsigned t) {
-        const size_t row = (size_t)s * a.tiles + t;
-        if (L == 64u) {
-            a.front_pres[row * 64u + lane] = pw;
-            pw = 0;
-        }
-        if (lane == 0)
-            a.tile_roi[row] = troi;
-        if (STAR && STEPS > 32u) {
-            /* the same construction as below over 64 or 128 steps: a register per 64 of them, the running values carried from one to the
-             * next.  (The 32-step form below is kept word for word for the 64-laser kernel: its code and its register budget are what
-             * tests/test_kernel_resources.py and the benchmark pin.) */
-            constexpr unsigned NH = STEPS > 64u ? 2u : 1u;
-            unsigned fk[NH], sbase_h[NH];
-            unsigned carry = 0, total = 0;
-#pragma unroll
-            for (unsigned h = 0; h < NH; h++) {
-                const unsigned key = (unsigned)(h ? stepkey_w : stepkey_v), sc = (unsigned)(h ? stepcnt_w : stepcnt_v);
-                const unsigned k1 = key != URF_SEC_NONE ? key + 1u : 0u;
-                unsigned m = urf_wave_scan_max(k1);
-                m = m > carry ? m : carry;
-                unsigned exc = (unsigned)__shfl_up((int)m, 1);
-                exc = lane == 0 ? carry : exc;
-                if (__ballot(k1 != 0u && k1 < exc) != 0ull)
-                    failed = true;   /* (uniform) the sectors fall inside the tile */
-                fk[h] = m;
-                carry = (unsigned)__builtin_amdgcn_readlane((int)m, 63);
-                const unsigned sinc = urf_wave_scan_add(sc) + total;
-                sbase_h[h] = sinc - sc;
-                total = (unsigned)__builtin_amdgcn_readlane((int)sinc, 63);
-            }
-            for (unsigned k0 = 0; k0 <= K; k0 += 64u) {
-                const unsigned k = k0 + lane;
-                unsigned cnt = 0;   /* number of steps whose filled-in key + 1 is < k + 1 (the keys do not fall: a count per register adds up) */
-#pragma unroll
-                for (unsigned h = 0; h < NH; h++) {
-                    unsigned lo = 0;
-#pragma unroll
-                    for (unsigned st = 32u; st > 0; st >>= 1) {
-                        const unsigned v = (unsigned)__shfl((int)fk[h], (int)(lo + st - 1u));
-                        lo += v < k + 1u ? st : 0u;
-                    }
-                    const unsigned v = (unsigned)__shfl((int)fk[h], (int)lo);
-                    lo += (lo == 63u && v < k + 1u) ? 1u : 0u;
-                    cnt += lo;
-                }
-                unsigned so = total;
-#pragma unroll
-                for (unsigned h = 0; h < NH; h++) {
-                    const unsigned v = (unsigned)__shfl((int)sbase_h[h], (int)(cnt & 63u));
-                    so = (cnt >> 6) == h ? v : so;
-                }
-                if (k <= K)
-                    a.tsoff[row * (K + 1) + k] = (uint16_t)so;
-            }
-        }
-        if (STAR && STEPS == 32u) {
-            /* sector k starts with the first step whose sector is >= k (urf_split_holey's construction: the steps' keys
-             * with the empty steps filled in from the left must not fall; bisection over the 32 of them) */
-            const unsigned k1 = (lane < URF_FRONT_STEPS && (unsigned)stepkey_v != URF_SEC_NONE) ? (unsigned)stepkey_v + 1u : 0u;
-            const unsigned fk = urf_wave_scan_max(k1);
-            unsigned exc = (unsigned)__shfl_up((int)fk, 1);
-            exc = lane == 0 ? 0u : exc;
-            if (__ballot(k1 != 0u && k1 < exc) != 0ull)
-                failed = true;   /* (uniform) the sectors fall inside the tile (the sweep's seam, an unorganised cloud) */
-            const unsigned sc = lane < URF_FRONT_STEPS ? (unsigned)stepcnt_v : 0u;
-            const unsigned sinc = urf_wave_scan_add(sc);
-            const unsigned sbase_l = sinc - sc;   /* lane j: participating points of the steps in front of step j; lane 32: all */
-            for (unsigned k0 = 0; k0 <= K; k0 += 64u) {
-                const unsigned k = k0 + lane;
-                unsigned lo = 0;   /* number of steps whose filled-in key + 1 is < k + 1 */
-#pragma unroll
-                for (unsigned st = URF_FRONT_STEPS / 2; st > 0; st >>= 1) {
-                    const unsigned v = (unsigned)__shfl((int)fk, (int)(lo + st - 1u));
-                    lo += v < k + 1u ? st : 0u;
-                }
-                {
-                    const unsigned v = (unsigned)__shfl((int)fk, (int)lo);
-                    lo += (lo == URF_FRONT_STEPS - 1u && v < k + 1u) ? 1u : 0u;
-                }
-                const unsigned so = (unsigned)__shfl((int)sbase_l, (int)lo);   /* (lane 32 holds the tile's total) */
-                if (k <= K)
-                    a.tsoff[row * (K + 1) + k] = (uint16_t)so;
-            }
-        }
-        troi = 0;
-        tstar = 0;
-        stepkey_v = (int)URF_SEC_NONE;
-        stepcnt_v = 0;
-        stepkey_w = (int)URF_SEC_NONE;
-        stepcnt_w = 0;
-    };
-
-    /* The points arrive four firings ahead, in four register sets that are refilled as soon as they have been used: no
-     * copies between sets (a copy waits for its source), every wait is for a load issued three firings ago. */
-    float px[4], py[4], pz[4];
-    auto ld = [&](const unsigned j, const unsigned f) {
-        /* (a lane behind the scan's end, a lane without a laser: one point of the scan for all of them, never looked at) */
-        const unsigned i = f * L + lane, o = ((L == 64u || lane < L) && i < len) ? i : len - 1u;
-        px[j] = gx[o];
-        py[j] = gy[o];
-        pz[j] = gz[o];
-    };
-#pragma unroll
-    for (unsigned j = 0; j < 4; j++)
-        ld(j, Fs + j);
-    for (unsigned f = Fs; f < F0; f += 4) {
-#pragma unroll
-        for (unsigned j = 0; j < 4; j++) {
-            step(std::integral_constant<unsigned, 0u>{}, f + j, px[j], py[j], pz[j]);
-            ld(j, f + j + 4u);
-        }
-    }
-    for (unsigned f = F0; f < F1; f += 4) {
-#pragma unroll
-        for (unsigned j = 0; j < 4; j++) {
-            if (f + j < F1)   /* (uniform: the scan's last tile may end anywhere) */
-                step(std::integral_constant<unsigned, 1u>{}, f + j, px[j], py[j], pz[j]);
-            ld(j, f + j + 4u);
-        }
-        if (L != 64u && (((f + 4u) & 31u) == 0u || f + 4u >= F1))   /* (uniform) */
-            pres_end(f >> 5);
-        if (((f + 4u) % STEPS) == 0u || f + 4u >= F1) {   /* (uniform) the tile is complete */
-            tile_end(f / STEPS);
-            if (failed_m != 0ull || __ballot(failed | overflow) != 0ull) {   /* (uniform) */
-                a.front_ok[s] = 0u;
-                if (ok == URF_FRONT_ROWS)
-                    a.table_redo[s] = 1u;   /* (nobody has checked the rest of the scan against the rows' table) */
-                return;
-            }
-        }
-    }
-    for (unsigned f = F1; f < Fe; f += 4) {
-#pragma unroll
-        for (unsigned j = 0; j < 4; j++) {
-            if (f + j < Fe)
-                step(std::integral_constant<unsigned, 2u>{}, f + j, px[j], py[j], pz[j]);
-            ld(j, f + j + 4u);
-        }
-    }
-    /* the block's last ring points of every lane: their windows reach behind the march */
-    if (!to_end) {
-        const unsigned fr[5] = { fwA >> 16, fwB & 0xffffu, fwB >> 16, fwC & 0xffffu, fwC >> 16 };   /* entries 6..10 */
-#pragma unroll
-        for (unsigned e = 0; e < 5; e++) {
-            const unsigned back = 4u - e;   /* entry 6 + e is `back` points behind the newest */
-            const bool in = tot > back && tot - back <= nin;
-            const unsigned what = (use_z ? URF_FC_EDGE_Z : 0u) | ((use_x && e >= 2u) ? URF_FC_EDGE_X : 0u);
-            if (ncb > URF_FRONT_CBUF - 64u)
-                urf_front_flush(a, s, cbuf, ncb, overflow);
-            urf_front_push(cbuf, ncb, in && what != 0u, (fr[e] + Fs) * L + lane, what);
-        }
-    }
-    urf_front_flush(a, s, cbuf, ncb, overflow);
-    a.front_maxs[((size_t)s * a.tiles + b) * 64u + lane] = (unsigned long long)__double_as_longlong(maxs);
-    /* one lane, one ring -- over the whole scan: the blocks agree through the scan's two tables */
-    if (econf) {
-        const unsigned o1 = atomicCAS(&a.front_lane_ring[(size_t)s * 64u + lane], 0xffffffffu, E);
-        const unsigned o2 = atomicCAS(&a.front_ring_lane[(size_t)s * C + E], 0xffffffffu, lane);
-        failed = failed | (o1 != 0xffffffffu && o1 != E) | (o2 != 0xffffffffu && o2 != lane);
-    }
-    if (failed_m != 0ull || __ballot(failed | overflow) != 0ull) {
-        a.front_ok[s] = 0u;
-        if (ok == URF_FRONT_ROWS)
-            a.table_redo[s] = 1u;
-    }
-}
-
-/* The same march for any curbPoints of 1..8 (urf_set_front_mode(ctx, 3), 64 lasers per firing).  The body above stays word for word what it
- * was -- its code generation is what tests/test_kernel_resources.py and the benchmark pin, and written with CP as a parameter it came out
- * with four more registers and a spill -- this one is its general form, the constants 5, 3, 6, 4 and 11 as functions of CP.
- *
- * CP = params.curbPoints, h = CP / 2.  The lane's window holds its last 2 * CP + 1 ring points, w[2 * CP] the newest: z_zero's centre is
- * w[CP] (CP points on either side, z_zero_method.cpp:21-50), x_zero's triple (j, j + h, j + CP) is (w[CP], w[CP + h], w[2 * CP]) and the
- * point it marks the one CP - h back (x_zero_method.cpp:30-34; CP == 1: the triple is (j, j, j + 1)).  Both loops start at j = CP: a
- * decision needs the FULL window.  The march keeps the firing numbers of the newest CP + 1 points, 16 bits each, the newest in the upper
- * half of the last register: the point `back` places behind it sits in half 2 * NFW - 1 - back. */
-template <bool STAR, bool BEAM, unsigned L, unsigned CP>
-__device__ __forceinline__ void urf_front_body_cp(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
-{
-    const unsigned s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
-    unsigned off, len;
-    urf_scan_range(a, s, off, len);
-    const unsigned TPB = a.front_tpb;
-    const unsigned t_first = b * TPB;
-    if (t_first * URF_TILE >= len)
-        return;
-    const unsigned ok = a.front_ok[s];
-    if (ok == 0u)
-        return;
-    constexpr unsigned C = L;                     /* table entries per scan: params.channels */
-    constexpr unsigned STEPS = URF_TILE / L;      /* firings per tile */
-    static_assert(L == 64u || L == 32u || L == 16u, "a firing fills the wave, half of it or a quarter");
-    static_assert(CP >= 1u && CP <= 8u && URF_FRONT_HPOST >= CP, "the halo behind a block completes the last centre's window");
-    constexpr unsigned H = CP / 2u, NW = 2u * CP + 1u, NFW = (CP + 2u) / 2u;
-    constexpr unsigned HPRE = CP <= 5u ? URF_FRONT_HPRE : URF_FRONT_HPRE_WIDE;   /* CP + H ring points in front of a block's first marked point */
+    constexpr unsigned H = urf_front_window<CP>::H, HPRE = urf_front_window<CP>::HPRE;
     const unsigned K = (unsigned)dp.p.sectors;
     const unsigned nf = (len + L - 1u) / L;                                 /* firings of the scan */
     const unsigned F0 = t_first * STEPS;
@@ -679,21 +398,8 @@ __device__ __forceinline__ void urf_front_body_cp(const urf_kargs& a, const urf_
     unsigned long long failed_m = 0;   /* ... what the hot path finds wrong, as lane masks (wave-uniform) */
     unsigned ncb = 0;         /* candidates in the wave's buffer */
 
-    /* the lane's window: w[2 * CP] = its newest ring point, w[0] the one 2 * CP before; firing (relative to Fs) of the CP + 1 newest */
-    float w[NW];
-    unsigned fw[NFW];                      /* (CP == 5: (f6 << 16 | f5), (f8 << 16 | f7), (f10 << 16 | f9)) */
-#pragma unroll
-    for (unsigned k = 0; k < NW; k++)
-        w[k] = 0.f;
-#pragma unroll
-    for (unsigned k = 0; k < NFW; k++)
-        fw[k] = 0u;
-    auto fwat = [&](auto back) -> unsigned {   /* firing of the point `back` places behind the newest */
-        constexpr unsigned SL = 2u * NFW - 1u - decltype(back)::value;
-        return (SL & 1u) ? fw[SL / 2u] >> 16 : fw[SL / 2u] & 0xffffu;
-    };
-    unsigned wc = 0;                       /* points in the window, at most 2 * CP + 1 */
-    unsigned tot = 0, nin = 0;             /* ring points of this lane since the block's first firing / inside the block */
+    urf_front_window<CP> win;              /* the lane's last 2 * CP + 1 ring points, firings relative to Fs */
+    win.clear();
     double maxs = 0.0;                     /* largest x*x + y*y among the lane's ring points of the block (maxDistance, lidar_segmentation.cpp:271-274) */
     unsigned pw = 0;                       /* presence bits of the tile at hand */
     /* per tile (wave-uniform) */
@@ -789,38 +495,15 @@ __device__ __forceinline__ void urf_front_body_cp(const urf_kargs& a, const urf_
                 pw |= 1u << (f & 31u);
             }
             econf = true;
-#pragma unroll
-            for (unsigned k = 0; k + 1u < NW; k++)
-                w[k] = w[k + 1u];
-            w[NW - 1u] = z;
-#pragma unroll
-            for (unsigned k = 0; k + 1u < NFW; k++)
-                fw[k] = __builtin_amdgcn_alignbit(fw[k + 1u], fw[k], 16);
-            fw[NFW - 1u] = __builtin_amdgcn_alignbit(f - Fs, fw[NFW - 1u], 16);
-            wc = wc < NW ? wc + 1u : NW;
-            if (PH >= 1u)
-                tot++;
-            if (PH == 1u)
-                nin++;
+            win.template push<PH>(z, f - Fs);
         }
         if (PH == 0u)
             return;
         /* (straight-line: every lane computes, the lanes without a new point are masked out at the end -- branches around the
          * tests put the four results through registers and selects) */
-        const bool full = wc == NW;
-        /* the centre (CP points back) and the point x_zero marks (CP - h back): are they this block's */
-        const bool c_in = on & (tot >= CP + 1u) & (tot - CP <= nin);
-        const bool p_in = on & (tot >= CP - H + 1u) & (tot - (CP - H) <= nin);
-        /* z_zero_method.cpp:39-40, 48-49, 67-69 */
-        const float a5 = __builtin_fabsf(w[CP]);
-        /* (window values are region-of-interest points' heights, never NaN: v_max3 with |.| modifiers, three instructions per side for
-         * CP == 5 -- the compiler's fmaxf quiets the first two operands of every chain with a v_max x, x each: five) */
-        const float m1 = urf_front_absmax<CP + 1u, 0, 1>(w);               /* the CP older points, then the centre */
-        const float m2 = urf_front_absmax<CP + 1u, (int)(2u * CP), -1>(w);   /* the CP newer points from the newest on, then the centre */
-        const bool hz = ((m1 - a5 >= curbH) | (m2 - a5 >= curbH)) & (__builtin_fabsf(m1 - m2) >= 0.05f);   /* ((double)v >= 0.05 <=> v >= 0.05f: the float above 0.05) */
-        /* x_zero_method.cpp:62-64 for the triple (w[CP], w[CP + h], w[2 CP]) = (j, j + h, j + CP) */
-        const bool hx = ((__builtin_fabsf(w[CP] - w[CP + H]) >= curbH) | (__builtin_fabsf(w[2u * CP] - w[CP + H]) >= curbH)) &
-                        (__builtin_fabsf(w[CP] - w[2u * CP]) >= 0.05f);
+        const bool full = win.full();
+        const bool c_in = win.c_in(on), p_in = win.p_in(on);
+        const bool hz = win.hz(curbH), hx = win.hx(curbH);
         /* (lane masks combined as masks: `&` on bools mixed with the wave-uniform switches went through 0 / 1 integers in vector
          * registers -- v_cndmask, v_and, v_cmp per term) */
         bool zz = false, xz = false, ez = false, ex = false;
@@ -837,8 +520,8 @@ __device__ __forceinline__ void urf_front_body_cp(const urf_kargs& a, const urf_
                 ex = p_in && !full;
         }
         if (__ballot(zz | xz | ez | ex) != 0ull) {   /* (uniform) */
-            urf_front_push(cbuf, ncb, zz | ez, (fwat(std::integral_constant<unsigned, CP>{}) + Fs) * L + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
-            urf_front_push(cbuf, ncb, xz | ex, (fwat(std::integral_constant<unsigned, CP - H>{}) + Fs) * L + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
+            urf_front_push(cbuf, ncb, zz | ez, (win.centre_firing() + Fs) * L + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
+            urf_front_push(cbuf, ncb, xz | ex, (win.marked_firing() + Fs) * L + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
             if (ncb > URF_FRONT_CBUF - 128u)
                 urf_front_flush(a, s, cbuf, ncb, overflow);
         }
@@ -859,8 +542,7 @@ __device__ __forceinline__ void urf_front_body_cp(const urf_kargs& a, const urf_
             a.tile_roi[row] = troi;
         if (STAR && STEPS > 32u) {
             /* the same construction as below over 64 or 128 steps: a register per 64 of them, the running values carried from one to the
-             * next.  (The 32-step form below is kept word for word for the 64-laser kernel: its code and its register budget are what
-             * tests/test_kernel_resources.py and the benchmark pin.) */
+             * next */
             constexpr unsigned NH = STEPS > 64u ? 2u : 1u;
             unsigned fk[NH], sbase_h[NH];
             unsigned carry = 0, total = 0;
@@ -991,23 +673,16 @@ __device__ __forceinline__ void urf_front_body_cp(const urf_kargs& a, const urf_
     }
     /* the block's last ring points of every lane: their windows reach behind the march */
     if (!to_end) {
-        /* the CP newest, oldest first: none has been a centre, the CP - h newest have not been x_zero's marked point either */
+        /* the CP newest, oldest first: none has been a centre, the CP - H newest have not been x_zero's marked point either */
         auto tail = [&](auto bk) {
             constexpr unsigned back = decltype(bk)::value;
-            const bool in = tot > back && tot - back <= nin;
+            const bool in = win.in_block(back);
             const unsigned what = (use_z ? URF_FC_EDGE_Z : 0u) | ((use_x && back < CP - H) ? URF_FC_EDGE_X : 0u);
             if (ncb > URF_FRONT_CBUF - 64u)
                 urf_front_flush(a, s, cbuf, ncb, overflow);
-            urf_front_push(cbuf, ncb, in && what != 0u, (fwat(bk) + Fs) * L + lane, what);
+            urf_front_push(cbuf, ncb, in && what != 0u, (win.firing(back) + Fs) * L + lane, what);
         };
-        if constexpr (CP >= 8u) tail(std::integral_constant<unsigned, 7u>{});
-        if constexpr (CP >= 7u) tail(std::integral_constant<unsigned, 6u>{});
-        if constexpr (CP >= 6u) tail(std::integral_constant<unsigned, 5u>{});
-        if constexpr (CP >= 5u) tail(std::integral_constant<unsigned, 4u>{});
-        if constexpr (CP >= 4u) tail(std::integral_constant<unsigned, 3u>{});
-        if constexpr (CP >= 3u) tail(std::integral_constant<unsigned, 2u>{});
-        if constexpr (CP >= 2u) tail(std::integral_constant<unsigned, 1u>{});
-        tail(std::integral_constant<unsigned, 0u>{});
+        URF_FRONT_TAIL_CALLS(CP, tail)
     }
     urf_front_flush(a, s, cbuf, ncb, overflow);
     a.front_maxs[((size_t)s * a.tiles + b) * 64u + lane] = (unsigned long long)__double_as_longlong(maxs);
@@ -1024,68 +699,36 @@ __device__ __forceinline__ void urf_front_body_cp(const urf_kargs& a, const urf_
     }
 }
 
-template <unsigned L, unsigned CP>
-__device__ __forceinline__ void urf_front_kernel(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
-{
-    if constexpr (CP == 5u) {
-        if (!dp.p.star_shaped_method)
-            urf_front_body<false, false, L>(a, dp, cbuf);
-        else if (!dp.p.starbeam_filter)
-            urf_front_body<true, false, L>(a, dp, cbuf);
-        else
-            urf_front_body<true, true, L>(a, dp, cbuf);
-    } else {
-        static_assert(L == 64u || L == 32u || L == 16u, "curbPoints other than 5: the laser counts urf_front_body_cp is written for");
-        if (!dp.p.star_shaped_method)
-            urf_front_body_cp<false, false, L, CP>(a, dp, cbuf);
-        else if (!dp.p.starbeam_filter)
-            urf_front_body_cp<true, false, L, CP>(a, dp, cbuf);
-        else
-            urf_front_body_cp<true, true, L, CP>(a, dp, cbuf);
-    }
-}
 /* one kernel per laser count and per curbPoints, each under a name of its own (tools/kernel_resources.py lists kernels by their base
- * identifier) and with its own waves per SIMD */
-#define URF_FRONT_KERNEL(name, L, CP, WAVES)                                                                                                  \
-    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void name(urf_kargs a, urf_dev_params dp)             \
-    {                                                                                                                                         \
-        __shared__ urf_u2 cbuf[URF_FRONT_CBUF];                                                                                               \
-        urf_front_kernel<L, CP>(a, dp, cbuf);                                                                                                 \
-    }
-URF_FRONT_KERNEL(k_front, 64u, 5u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front32, 32u, 5u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front16, 16u, 5u, URF_FRONT_WAVES)
-/* urf_set_front_mode(ctx, 3): curbPoints 1..8 at 64 lasers.  The window is 2 * CP + 1 registers: 1..4 fit k_front's budget, 6..8 (13, 15, 17 heights and
- * a fourth / fifth register of firing numbers) get the next one (four waves per SIMD, 128 registers) */
+ * identifier) and with its own waves per SIMD.  The window is 2 * CP + 1 registers: 1..5 fit five waves per SIMD, 6..8 (13, 15, 17 heights
+ * and a fourth / fifth register of firing numbers) get the next budget (four waves, 128 registers). */
 #ifndef URF_FRONT_WAVES_WIDE
 #define URF_FRONT_WAVES_WIDE 4
 #endif
-URF_FRONT_KERNEL(k_front_cp1, 64u, 1u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front_cp2, 64u, 2u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front_cp3, 64u, 3u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front_cp4, 64u, 4u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front_cp6, 64u, 6u, URF_FRONT_WAVES_WIDE)
-URF_FRONT_KERNEL(k_front_cp7, 64u, 7u, URF_FRONT_WAVES_WIDE)
-URF_FRONT_KERNEL(k_front_cp8, 64u, 8u, URF_FRONT_WAVES_WIDE)
-/* urf_set_front_curb_points(ctx, 1): the same at 32 and 16 lasers per firing (mode 3).  Nothing in the body counts per wave what is counted per
- * firing: the halos (HPRE, HPRE_WIDE, HPOST) are firings, and a lane meets at most one ring point per firing whatever L is; fw[] holds firings
- * relative to Fs (at most front_tpb * URF_TILE / 16 + 20 < 65536); candidate indices are (firing) * L + lane; the region-of-interest words and
- * the steps' keys (128 steps per tile at 16 lasers: stepkey_w) are urf_front_body's, which these laser counts have run with since k_front32 /
- * k_front16.  The finish step is k_front_finish_cp*: it takes the laser count at run time (front_lsh). */
-URF_FRONT_KERNEL(k_front32_cp1, 32u, 1u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front32_cp2, 32u, 2u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front32_cp3, 32u, 3u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front32_cp4, 32u, 4u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front32_cp6, 32u, 6u, URF_FRONT_WAVES_WIDE)
-URF_FRONT_KERNEL(k_front32_cp7, 32u, 7u, URF_FRONT_WAVES_WIDE)
-URF_FRONT_KERNEL(k_front32_cp8, 32u, 8u, URF_FRONT_WAVES_WIDE)
-URF_FRONT_KERNEL(k_front16_cp1, 16u, 1u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front16_cp2, 16u, 2u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front16_cp3, 16u, 3u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front16_cp4, 16u, 4u, URF_FRONT_WAVES)
-URF_FRONT_KERNEL(k_front16_cp6, 16u, 6u, URF_FRONT_WAVES_WIDE)
-URF_FRONT_KERNEL(k_front16_cp7, 16u, 7u, URF_FRONT_WAVES_WIDE)
-URF_FRONT_KERNEL(k_front16_cp8, 16u, 8u, URF_FRONT_WAVES_WIDE)
+#define URF_FRONT_WAVES_OF(CP) ((CP) <= 5 ? URF_FRONT_WAVES : URF_FRONT_WAVES_WIDE)
+#define URF_FRONT_KERNEL(name, L, CP)                                                                                                         \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT_WAVES_OF(CP), URF_FRONT_WAVES_OF(CP))))                     \
+    void name(urf_kargs a, urf_dev_params dp)                                                                                                 \
+    {                                                                                                                                       \
+        __shared__ urf_u2 cbuf[URF_FRONT_CBUF];                                                                                               \
+        if (!dp.p.star_shaped_method)                                                                                                         \
+            urf_front_body<false, false, L, CP>(a, dp, cbuf);                                                                                 \
+        else if (!dp.p.starbeam_filter)                                                                                                       \
+            urf_front_body<true, false, L, CP>(a, dp, cbuf);                                                                                  \
+        else                                                                                                                                  \
+            urf_front_body<true, true, L, CP>(a, dp, cbuf);                                                                                   \
+    }
+/* curbPoints 5 in every front mode ... */
+URF_FRONT_KERNEL(k_front, 64u, 5)
+URF_FRONT_KERNEL(k_front32, 32u, 5)
+URF_FRONT_KERNEL(k_front16, 16u, 5)
+/* ... and 1..8 with urf_set_front_mode(ctx, 3) (64 lasers) and urf_set_front_curb_points(ctx, 1) (32, 16 and 128: urf_front128.hpp).  Nothing in
+ * the body counts per wave what is counted per firing: the halos (HPRE, HPRE_WIDE, HPOST) are firings, and a lane meets at most one ring point per
+ * firing whatever L is; fw[] holds firings relative to Fs (at most front_tpb * URF_TILE / 16 + 20 < 65536); candidate indices are (firing) * L +
+ * lane.  The finish step is k_front_finish_cp*: it takes the laser count at run time (front_lsh). */
+#define URF_FRONT_CP_X(n) URF_FRONT_KERNEL(k_front_cp##n, 64u, n) URF_FRONT_KERNEL(k_front32_cp##n, 32u, n) URF_FRONT_KERNEL(k_front16_cp##n, 16u, n)
+URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
+#undef URF_FRONT_CP_X
 
 /* ------------------------------------------------------------------------- */
 /* k_front_finish                                                              */
@@ -1506,13 +1149,9 @@ __device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_param
         urf_front_finish_body<CP>(a, dp, part);                                                               \
     }
 URF_FRONT_FINISH_KERNEL(k_front_finish, 5u)
-URF_FRONT_FINISH_KERNEL(k_front_finish_cp1, 1u)
-URF_FRONT_FINISH_KERNEL(k_front_finish_cp2, 2u)
-URF_FRONT_FINISH_KERNEL(k_front_finish_cp3, 3u)
-URF_FRONT_FINISH_KERNEL(k_front_finish_cp4, 4u)
-URF_FRONT_FINISH_KERNEL(k_front_finish_cp6, 6u)
-URF_FRONT_FINISH_KERNEL(k_front_finish_cp7, 7u)
-URF_FRONT_FINISH_KERNEL(k_front_finish_cp8, 8u)
+#define URF_FRONT_CP_X(n) URF_FRONT_FINISH_KERNEL(k_front_finish_cp##n, n)
+URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
+#undef URF_FRONT_CP_X
 
 /* ------------------------------------------------------------------------- */
 /* k_label_front                                                               */

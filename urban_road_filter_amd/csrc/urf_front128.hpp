@@ -1,14 +1,16 @@
 /*
  * urf_front128.hpp -- the fused front end (urf_front.hpp) for sweeps of 128 lasers per firing (urf_set_front_lasers128): firing order
- * (point f * 128 + l) or row-major (128 rows).  The kernels of urf_front.hpp keep their source word for word -- their code generation is
- * what tests/test_kernel_resources.py and the benchmark pin -- and these stand beside them, each under a name of its own:
+ * (point f * 128 + l) or row-major (128 rows).  The kernels stand beside those of urf_front.hpp, each under a name of its own:
  *
  *   k_front128          ONE wave per block, TWO lasers per lane: lane j marches lasers j and j + 64 (half 0 and half 1 of a firing), with
- *                       two windows and two sets of per-ring state.  The two halves of a firing are worked off back to back inside one
- *                       step, so that everything that crosses lanes -- the slot rank of a star participant, the one-sector test, the
- *                       step's key and count -- spans the 128 lasers in input order with two ballots and no LDS traffic or barrier, and
- *                       the candidate buffer stays "the workgroup is the wave".  The price is registers.
- *   k_front_finish128   k_front_finish with 128 rings' sizes, positions, largest ranges and curb lists.
+ *                       two windows (urf_front_window, urf_front.hpp) and two sets of per-ring state.  The two halves of a firing are
+ *                       worked off back to back inside one step, so that everything that crosses lanes -- the slot rank of a star
+ *                       participant, the one-sector test, the step's key and count -- spans the 128 lasers in input order with two
+ *                       ballots and no LDS traffic or barrier, and the candidate buffer stays "the workgroup is the wave".  The price is
+ *                       registers.  k_front128_cp{1,2,3,4,6,7,8} are the same body, urf_front128_body, for the
+ *                       other curbPoints (urf_set_front_mode(ctx, 3) with urf_set_front_lasers128 and urf_set_front_curb_points on).
+ *   k_front_finish128   k_front_finish with 128 rings' sizes, positions, largest ranges and curb lists (urf_front128_finish.hpp; _cp*: the
+ *                       ring positions both detectors accept and how far their neighbours lie as functions of curbPoints).
  *   k_label_front128    k_label_front with the record's ring in EIGHT bits (URF_FRONT128_RING_*: table entry 127 is a ring, 0xff is
  *                       "none"; bits 7..10 of an input-order record are free) and a row-major store-back tile of 128 x 24 bytes.
  *   k_transpose128      k_transpose with 128 x 17 floats per plane.
@@ -173,20 +175,20 @@ __global__ __launch_bounds__(256) void k_rows_probe128(urf_kargs a, urf_dev_para
         a.rows_ok[s] = ok ? before + (v >= 0.0f ? 1u : 0u) + 1u : 0u;
 }
 
-/* The march of urf_front_body (urf_front.hpp) for 128 lasers, curbPoints == 5: h = 0, 1 is the half of the firing, laser h * 64 + lane.
- * Every array of two below is indexed by constants only (the loops over h are unrolled): registers. */
+/* what the march keeps per laser */
+template <unsigned CP>
 struct urf_front128_ring {
     unsigned E;          /* the table entry this laser's points are expected on */
     bool econf;          /* ... and a point of this march has confirmed it */
     urf_front_thr th;
-    float w[11];         /* the window: w[10] the newest ring point */
-    unsigned fwA, fwB, fwC;
-    unsigned wc, tot, nin;
+    urf_front_window<CP> win;   /* its last 2 * CP + 1 ring points (urf_front.hpp) */
     double maxs;
     unsigned pw;
 };
 
-template <bool STAR, bool BEAM>
+/* The march of urf_front_body (urf_front.hpp) for 128 lasers and curbPoints CP of 1..8: h = 0, 1 is the half of the firing, laser
+ * h * 64 + lane.  Every array of two below is indexed by constants only (the loops over h are unrolled): registers. */
+template <bool STAR, bool BEAM, unsigned CP>
 __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
 {
     const unsigned s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
@@ -200,15 +202,16 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
     if (ok == 0u)
         return;
     constexpr unsigned L = URF_FRONT128_L, C = L, STEPS = URF_FRONT128_STEPS;
+    constexpr unsigned H = urf_front_window<CP>::H, HPRE = urf_front_window<CP>::HPRE;
     const unsigned K = (unsigned)dp.p.sectors;
     const unsigned nf = (len + L - 1u) / L;                                 /* firings of the scan */
     const unsigned F0 = t_first * STEPS;
     const unsigned F1 = F0 + TPB * STEPS < nf ? F0 + TPB * STEPS : nf;
-    const unsigned Fs = F0 > URF_FRONT_HPRE ? F0 - URF_FRONT_HPRE : 0u;
+    const unsigned Fs = F0 > HPRE ? F0 - HPRE : 0u;
     const unsigned Fe = F1 + URF_FRONT_HPOST < nf ? F1 + URF_FRONT_HPOST : nf;
     const bool from_start = Fs == 0u;   /* the window count IS the ring position + 1 */
     const bool to_end = Fe == nf;       /* no point of the scan lies behind the march */
-    static_assert(URF_FRONT_HPRE % 4u == 0u && STEPS % 4u == 0u, "the march runs in groups of four firings");
+    static_assert(HPRE % 4u == 0u && STEPS % 4u == 0u, "the march runs in groups of four firings");
     const unsigned sb = urf_sbase(a, s);
     const unsigned tiles2 = URF_FRONT128_TILES2(a.tiles);
     const float *gx, *gy, *gz;
@@ -223,17 +226,13 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
     const float curbH = dp.p.curbHeight;
     const bool use_x = dp.p.x_zero_method != 0, use_z = dp.p.z_zero_method != 0;
 
-    urf_front128_ring R[2];
+    urf_front128_ring<CP> R[2];
 #pragma unroll
     for (unsigned h = 0; h < 2; h++) {
         R[h].E = h * 64u + lane;
         R[h].econf = false;
         R[h].th = urf_front_load_thr(a, s, C, R[h].E, nR);
-#pragma unroll
-        for (unsigned k = 0; k < 11; k++)
-            R[h].w[k] = 0.f;
-        R[h].fwA = R[h].fwB = R[h].fwC = 0u;
-        R[h].wc = R[h].tot = R[h].nin = 0u;
+        R[h].win.clear();
         R[h].maxs = 0.0;
         R[h].pw = 0u;
     }
@@ -265,7 +264,7 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
         unsigned long long psm[2] = { 0ull, 0ull };
 #pragma unroll
         for (unsigned h = 0; h < 2; h++) {
-            urf_front128_ring& r = R[h];
+            urf_front128_ring<CP>& r = R[h];
             const float x = X[h], y = Y[h], z = Z[h];
             const unsigned i = f * L + h * 64u + lane;
             rho2[h] = x * x + y * y;
@@ -340,7 +339,7 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
         /* the lasers' windows move on by their new ring points; what has become decidable is decided */
 #pragma unroll
         for (unsigned h = 0; h < 2; h++) {
-            urf_front128_ring& r = R[h];
+            urf_front128_ring<CP>& r = R[h];
             if (on[h]) {
                 if (PH == 1u) {
                     const double s2 = (double)X[h] * (double)X[h] + (double)Y[h] * (double)Y[h];
@@ -348,32 +347,13 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
                     r.pw |= 1u << (f & 31u);
                 }
                 r.econf = true;
-#pragma unroll
-                for (unsigned k = 0; k < 10; k++)
-                    r.w[k] = r.w[k + 1u];
-                r.w[10] = Z[h];
-                r.fwA = __builtin_amdgcn_alignbit(r.fwB, r.fwA, 16);
-                r.fwB = __builtin_amdgcn_alignbit(r.fwC, r.fwB, 16);
-                r.fwC = __builtin_amdgcn_alignbit(f - Fs, r.fwC, 16);
-                r.wc = r.wc < 11u ? r.wc + 1u : 11u;
-                if (PH >= 1u)
-                    r.tot++;
-                if (PH == 1u)
-                    r.nin++;
+                r.win.template push<PH>(Z[h], f - Fs);
             }
             if (PH == 0u)
                 continue;
-            const bool full = r.wc == 11u;
-            /* the centre (five points back) and the point x_zero marks (three back): are they this block's */
-            const bool c_in = on[h] & (r.tot >= 6u) & (r.tot - 5u <= r.nin);
-            const bool p_in = on[h] & (r.tot >= 4u) & (r.tot - 3u <= r.nin);
-            /* z_zero_method.cpp:39-40, 48-49, 67-69 */
-            const float a5 = __builtin_fabsf(r.w[5]);
-            const float m1 = urf_front_absmax<6u, 0, 1>(r.w);     /* the five older points, then the centre */
-            const float m2 = urf_front_absmax<6u, 10, -1>(r.w);   /* the five newer points from the newest on, then the centre */
-            const bool hz = ((m1 - a5 >= curbH) | (m2 - a5 >= curbH)) & (__builtin_fabsf(m1 - m2) >= 0.05f);
-            /* x_zero_method.cpp:62-64 for the triple (w5, w7, w10) = (j, j + 2, j + 5) */
-            const bool hx = ((__builtin_fabsf(r.w[5] - r.w[7]) >= curbH) | (__builtin_fabsf(r.w[10] - r.w[7]) >= curbH)) & (__builtin_fabsf(r.w[5] - r.w[10]) >= 0.05f);
+            const bool full = r.win.full();
+            const bool c_in = r.win.c_in(on[h]), p_in = r.win.p_in(on[h]);
+            const bool hz = r.win.hz(curbH), hx = r.win.hx(curbH);
             bool zz = false, xz = false, ez = false, ex = false;
             if (use_z) {   /* (uniform) */
                 zz = c_in && full && hz;
@@ -386,8 +366,8 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
                     ex = p_in && !full;
             }
             if (__ballot(zz | xz | ez | ex) != 0ull) {   /* (uniform) */
-                urf_front_push(cbuf, ncb, zz | ez, ((r.fwA & 0xffffu) + Fs) * L + h * 64u + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
-                urf_front_push(cbuf, ncb, xz | ex, ((r.fwB & 0xffffu) + Fs) * L + h * 64u + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
+                urf_front_push(cbuf, ncb, zz | ez, (r.win.centre_firing() + Fs) * L + h * 64u + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
+                urf_front_push(cbuf, ncb, xz | ex, (r.win.marked_firing() + Fs) * L + h * 64u + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
                 if (ncb > URF_FRONT_CBUF - 128u)
                     urf_front_flush(a, s, cbuf, ncb, overflow);
             }
@@ -492,19 +472,19 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
     }
 #pragma unroll
     for (unsigned h = 0; h < 2; h++) {
-        urf_front128_ring& r = R[h];
+        urf_front128_ring<CP>& r = R[h];
         /* the block's last ring points of every laser: their windows reach behind the march */
         if (!to_end) {
-            const unsigned fr[5] = { r.fwA >> 16, r.fwB & 0xffffu, r.fwB >> 16, r.fwC & 0xffffu, r.fwC >> 16 };   /* entries 6..10 */
-#pragma unroll
-            for (unsigned e = 0; e < 5; e++) {
-                const unsigned back = 4u - e;   /* entry 6 + e is `back` points behind the newest */
-                const bool in = r.tot > back && r.tot - back <= r.nin;
-                const unsigned what = (use_z ? URF_FC_EDGE_Z : 0u) | ((use_x && e >= 2u) ? URF_FC_EDGE_X : 0u);
+            /* the CP newest, oldest first: none has been a centre, the CP - H newest have not been x_zero's marked point either */
+            auto tail = [&](auto bk) {
+                constexpr unsigned back = decltype(bk)::value;
+                const bool in = r.win.in_block(back);
+                const unsigned what = (use_z ? URF_FC_EDGE_Z : 0u) | ((use_x && back < CP - H) ? URF_FC_EDGE_X : 0u);
                 if (ncb > URF_FRONT_CBUF - 64u)
                     urf_front_flush(a, s, cbuf, ncb, overflow);
-                urf_front_push(cbuf, ncb, in && what != 0u, (fr[e] + Fs) * L + h * 64u + lane, what);
-            }
+                urf_front_push(cbuf, ncb, in && what != 0u, (r.win.firing(back) + Fs) * L + h * 64u + lane, what);
+            };
+            URF_FRONT_TAIL_CALLS(CP, tail)
         }
         a.front_maxs128[(size_t)s * tiles2 * 64u + (size_t)b * L + h * 64u + lane] = (unsigned long long)__double_as_longlong(r.maxs);
         /* one laser, one ring -- over the whole scan: the blocks agree through the scan's two tables */
@@ -519,18 +499,29 @@ __device__ __forceinline__ void urf_front128_body(const urf_kargs& a, const urf_
         give_back();
 }
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT128_WAVES, URF_FRONT128_WAVES))) void k_front128(urf_kargs a, urf_dev_params dp)
-{
-    __shared__ urf_u2 cbuf[URF_FRONT_CBUF];
-    if (!dp.p.star_shaped_method)
-        urf_front128_body<false, false>(a, dp, cbuf);
-    else if (!dp.p.starbeam_filter)
-        urf_front128_body<true, false>(a, dp, cbuf);
-    else
-        urf_front128_body<true, true>(a, dp, cbuf);
-}
+/* one kernel per curbPoints (k_front128: 5).  Waves per SIMD: 1..7 hold three (168 registers; 7 fills them without a spill), 8 -- two
+ * windows of 17 heights and 2 x 5 registers of firing numbers -- gets two (256 registers) */
+#ifndef URF_FRONT128_WAVES_WIDE
+#define URF_FRONT128_WAVES_WIDE 2
+#endif
+#define URF_FRONT128_WAVES_OF(CP) ((CP) <= 7 ? URF_FRONT128_WAVES : URF_FRONT128_WAVES_WIDE)
+#define URF_FRONT128_KERNEL(name, CP)                                                                                                 \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT128_WAVES_OF(CP), URF_FRONT128_WAVES_OF(CP))))       \
+    void name(urf_kargs a, urf_dev_params dp)                                                                                         \
+    {                                                                                                                                 \
+        __shared__ urf_u2 cbuf[URF_FRONT_CBUF];                                                                                       \
+        if (!dp.p.star_shaped_method)                                                                                                 \
+            urf_front128_body<false, false, CP>(a, dp, cbuf);                                                                         \
+        else if (!dp.p.starbeam_filter)                                                                                               \
+            urf_front128_body<true, false, CP>(a, dp, cbuf);                                                                          \
+        else                                                                                                                          \
+            urf_front128_body<true, true, CP>(a, dp, cbuf);                                                                           \
+    }
+URF_FRONT128_KERNEL(k_front128, 5)
+#define URF_FRONT_CP_X(n) URF_FRONT128_KERNEL(k_front128_cp##n, n)
+URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
+#undef URF_FRONT_CP_X
 
-#include "urf_front128_cp.hpp"
 #include "urf_front128_finish.hpp"
 
 #endif /* URF_FRONT128_HPP */

@@ -394,13 +394,9 @@ __global__ __launch_bounds__(URF_FINISH_THREADS) void k_front_finish128(urf_karg
     {                                                                                                         \
         urf_front128_finish_body<CP>(a, dp, part);                                                            \
     }
-URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp1, 1u)
-URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp2, 2u)
-URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp3, 3u)
-URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp4, 4u)
-URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp6, 6u)
-URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp7, 7u)
-URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp8, 8u)
+#define URF_FRONT_CP_X(n) URF_FRONT128_FINISH_KERNEL(k_front_finish128_cp##n, n)
+URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
+#undef URF_FRONT_CP_X
 
 /* k_label_front (urf_front.hpp) for the records of k_front128: the ring in eight bits, 128 rows of 16 + 8 label bytes for a row-major tile. */
 __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_label_front128(urf_kargs a, urf_dev_params dp)
