@@ -188,9 +188,11 @@ def test_sweeps_of_128_tiles_are_fused_and_of_129_are_not():
 
 
 # ---- (h) row-major ----
-@pytest.mark.parametrize("cols,wide", [(1024, True), (256, True), (256, False)])
+@pytest.mark.parametrize("cols,wide", [(1024, True), (256, True), (256, False), (17, True), (48, True)])
 def test_row_major_clouds_take_the_fused_front_end_from_the_second_call(cols, wide):
-    """k_rows_probe128, k_transpose128 and k_label_front128's row-major stores: the first call sights the layout, the second takes it."""
+    """k_rows_probe128, k_transpose128 and k_label_front128's row-major stores: the first call sights the layout, the second takes it.
+    17 columns: two tiles of 16 firings, the second with one -- k_transpose128's partial tile and the store-back of one; 48 columns: three
+    tiles, an odd number, the last presence word half used."""
     p = params(wide)
     scans = [ring_major(c) for c in firing_scans(cols, wide)]
     says_something(scans, p)

@@ -20,6 +20,9 @@ percentiles of the per-pair ratio off / on.  Recorded under profiles/front_laser
 
     timeout 900 python tools/front_lasers_bench.py --lasers128 --cols 4096 [--scans 256]
 
+--brackets: per case also the per-kernel event brackets of the fused call (mode 2; --lasers128: the "on" context), ms per call: what
+profiles/front_one_finish.md compares between two builds (URF_LIB_PATH selects the library), process by process.
+
 --cols W: sweeps of W columns instead (both modes; default 2048, with --lasers128 2048 and 1024).  Above 2048 columns a 128-laser sweep
 has more than 128 tiles: the "on" context then also turns urf_set_front_long_sweeps on, "off" stays the general kernels, and "brackets"
 holds the per-kernel event brackets (urf_enable_kernel_timing; the fused finish step runs inside "k_ring") of the "on" side at W and at
@@ -35,6 +38,17 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def brackets(ctx, call, steps):
+    """--brackets: the fused call kernel by kernel -- the event brackets of urf_enable_kernel_timing, ms per call (the fused finish step runs
+    inside "k_ring", k_label_front inside "k_label", k_transpose inside "k_split", k_rows_probe inside "k_ring_table")."""
+    ctx.enable_kernel_timing(True)
+    for _ in range(steps):
+        call()
+    ms, calls = ctx.kernel_timing()
+    ctx.enable_kernel_timing(False)
+    return {k: v / calls for k, v in ms.items()}
 
 
 def lasers128(args):
@@ -95,6 +109,8 @@ def lasers128(args):
                     out["results"].append({"cols": cols, "order": order, "on_front_scans": fused["on"], "off_front_scans": fused["off"],
                                            "on_ms_p10_p50_p90": pct(ts["on"]), "off_ms_p10_p50_p90": pct(ts["off"]),
                                            "off_over_on_p10_p50_p90": pct(ratio)})
+                    if args.brackets:
+                        out["results"][-1]["on_brackets_ms"] = brackets(on, lambda: on.classify_batch_soa(dx, dy, dz, n, S, labels, None), args.steps)
             if long:   # the fused call kernel by kernel, at `cols` and at 2048 columns (firing order)
                 out["brackets"] = []
                 for bc in (cols, 2048):
@@ -131,6 +147,7 @@ def main():
     ap.add_argument("--distinct", type=int, default=32, help="distinct sweeps the batch is built from")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--cols", type=int, default=None, help="columns per sweep (default 2048; --lasers128: 2048 and 1024)")
+    ap.add_argument("--brackets", action="store_true", help="also the fused call's per-kernel event brackets (urf_enable_kernel_timing), ms per call")
     ap.add_argument("--lasers128", action="store_true", help="the 128-laser switch on against off, two contexts interleaved")
     args = ap.parse_args()
     if args.lasers128:
@@ -192,6 +209,8 @@ def main():
                         row["mode%d_ms" % mode] = ms
                         row["mode%d_scans_per_s" % mode] = args.scans / ms * 1e3
                         row["mode%d_front_scans" % mode] = int(ctx.front_scans())
+                    if args.brackets:   # (mode 2 is the one set last)
+                        row["mode2_brackets_ms"] = brackets(ctx, lambda: ctx.classify_batch_soa(dx, dy, dz, n, args.scans, labels, None), args.steps)
                     out["results"].append(row)
                     if order == "firing" and not args.no_sweep:
                         for S in (32, 64, 128, 192, 256, 384, 512, 768, 1024):

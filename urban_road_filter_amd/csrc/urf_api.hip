@@ -131,7 +131,7 @@ static constexpr size_t urf_finish_lds_bytes(unsigned tiles)
 {
     return (size_t)tiles * 384 + 2 * URF_FINISH_CHUNK * sizeof(urf_u2);
 }
-static_assert(urf_finish_lds_bytes(URF_FRONT_LONG_MAX_TILES) + sizeof(urf_finish128_shared) <= 160u * 1024u, "a CU's LDS");
+static_assert(urf_finish_lds_bytes(URF_FRONT_LONG_MAX_TILES) + sizeof(urf_finish_shared_t<URF_FRONT128_L>) <= 160u * 1024u, "a CU's LDS");
 static_assert(URF_FRONT128_TILES2(URF_FRONT_LONG_MAX_TILES) == URF_FRONT_LONG_MAX_TILES, "an even number: k_front_finish128's layout is as large");
 
 /* The launch policy: which kernels a call launches, decided on the host from what the kernels of earlier calls reported through the
@@ -811,7 +811,7 @@ extern "C" int urf_set_front_long_sweeps(urf_ctx* c, int on)
         URF_HIP(c, hipSetDevice(c->device));
         int lds_max = 0;
         URF_HIP(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
-        if ((size_t)lds_max < urf_finish_lds_bytes(URF_FRONT_LONG_MAX_TILES) + sizeof(urf_finish128_shared)) {
+        if ((size_t)lds_max < urf_finish_lds_bytes(URF_FRONT_LONG_MAX_TILES) + sizeof(urf_finish_shared_t<URF_FRONT128_L>)) {
             c->last_error = "urf_set_front_long_sweeps: the device grants a workgroup " + std::to_string(lds_max) + " bytes of LDS";
             return URF_ERR_OOM;
         }

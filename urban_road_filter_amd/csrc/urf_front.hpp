@@ -37,6 +37,13 @@
  * front_ok[s] and takes the legacy kernels, which skip every scan whose flag is still set.  Labels are the same
  * either way, bit for bit: the arithmetic is the legacy path's (urf_device.hpp, urf_x_zero_angle, urf_z_zero_angle).
  *
+ * ONE body per kernel around the march, for every laser count.  k_front_finish*, k_transpose (here) and k_rows_probe (urf_k_table.hpp) each
+ * exist as a named wrapper per family -- 64 / 32 / 16 lasers, the count read at run time, and 128 (k_front_finish128*, k_transpose128,
+ * k_rows_probe128), the count a constant -- around urf_front_finish_body<CP, W128>, urf_transpose_body<W128>, urf_rows_probe_body<W128>.  What
+ * differs between the families (the arrays and their strides, the hand-over words of front_st, the record's ring field) stands in
+ * urf_front_lay<W128>; the code differs in how the finish adds up a scan's ring points, under `if constexpr`.  k_label_front128 is still a copy
+ * of k_label_front (see there: folded, both lose 6 registers and 1 - 2.6 % of their time to the wrapper).
+ *
  * ONE march body per lane layout.  urf_front_body<STAR, BEAM, L, CP> is every k_front* of 64, 32 and 16 lasers, urf_front128_body<STAR,
  * BEAM, CP> (urf_front128.hpp: two lasers per lane) every k_front128*; CP = params.curbPoints, 1..8, and 5 -- k_front, k_front32,
  * k_front16, k_front128, the symbols of every front mode -- is an instance like the other seven (URF_FRONT_CP_OTHERS: the fused front
@@ -73,6 +80,14 @@
 #define URF_FRONT_CP_OTHERS(X) X(1) X(2) X(3) X(4) X(6) X(7) X(8)
 #define URF_FRONT_MAX_TILES 128u  /* k_front_finish keeps a presence word per (tile, lane) in LDS */
 #define URF_FRONT_RING_NONE 0x7fu  /* ring field of an input-order record */
+#define URF_FRONT_ST_WORDS 72u   /* k_front_finish part 1 -> part 2: 64 list lengths, 4 quadrant values, the length of the list of marks, two counts */
+/* ... and of the 128-laser family (urf_front128.hpp), whose arrays are the siblings sized for 128 (urf_kargs::*128) */
+#define URF_FRONT128_L 128u
+#define URF_FRONT128_LSH 7u
+#define URF_FRONT128_RING_MASK 0xffu   /* ring field of an input-order record of these kernels: table entry 127 is a ring, 0xff is "none" */
+#define URF_FRONT128_RING_NONE 0xffu
+#define URF_FRONT128_TILES2(tiles) (((tiles) + 1u) & ~1u)   /* a presence word covers 32 firings, two tiles of 128 lasers: words and block maxima are counted for an even number */
+#define URF_FRONT128_ST_WORDS 136u     /* k_front_finish128 part 1 -> part 2: 128 list lengths, 4 quadrant values, list length, two counts */
 /* candidate kinds */
 #define URF_FC_XZ 1u       /* passed x_zero's height tests as the marked point: angle test pending */
 #define URF_FC_ZZ 2u       /* passed z_zero's as the centre */
@@ -124,13 +139,80 @@ __device__ __forceinline__ void urf_front_src(const urf_kargs& a, unsigned s, un
     gz = (rows ? (const float*)a.tz : a.z) + o;
 }
 
-/* Row-major organised sweep of L = 1 << front_lsh rows -> firing order: tx[f * L + l] = x[l * F + f].  Grid (tiles, scans) x 256 threads, a tile =
- * URF_TILE / L firings: L rows x 128 / 256 / 512 bytes in, LDS, 8 KB out in one stretch; 24 B/point, HBM-bound. */
-__global__ __launch_bounds__(256) void k_transpose(urf_kargs a)
+/* The laser layout of a fused scan: what the kernels around the march have to know about the two families.  W128 = false is 64, 32 or 16
+ * lasers per firing, the count read at run time (front_lsh), the arrays sized for 64 lanes; W128 = true is 128 lasers, the count a constant,
+ * the arrays the siblings sized for 128.  Outside of this struct the difference is known to the two marches, which write the arrays, and to
+ * the rows' probe (urf_k_table.hpp: included in front of this header, it picks rows_v / rows_v128 itself). */
+template <bool W128>
+struct urf_front_lay {
+    static constexpr unsigned NL = W128 ? URF_FRONT128_L : URF_FRONT_LANES;   /* the ARRAYS' lasers per scan (the firing's: L) */
+    static constexpr unsigned RING_MASK = W128 ? URF_FRONT128_RING_MASK : 0x7fu;   /* ring field of an input-order record ... */
+    static constexpr unsigned RING_NONE = W128 ? URF_FRONT128_RING_NONE : URF_FRONT_RING_NONE;   /* ... and its "on no ring" */
+    /* front_st, part 1 -> part 2 of the finish kernel: the curb lists' lengths per laser slot from word 0 on, then */
+    static constexpr unsigned ST_QUAD = NL, ST_NPEND = NL + 4u, ST_RING_PTS = NL + 5u, ST_RING10 = NL + 6u;
+    static constexpr unsigned ST_WORDS = W128 ? URF_FRONT128_ST_WORDS : URF_FRONT_ST_WORDS;
+    static_assert(ST_RING10 < ST_WORDS, "the hand-over words fit");
+
+    /* L = 1 << lsh lasers per firing */
+    static __device__ __forceinline__ unsigned lsh(const urf_kargs& a)
+    {
+        if constexpr (W128)
+            return URF_FRONT128_LSH;
+        else
+            return a.front_lsh;
+    }
+    /* the tiles the presence words and the blocks' maxima are counted for */
+    static __device__ __forceinline__ unsigned tiles(const urf_kargs& a)
+    {
+        if constexpr (W128)
+            return URF_FRONT128_TILES2(a.tiles);
+        else
+            return a.tiles;
+    }
+    /* the scan's presence words: word (f >> 5) * L + l */
+    static __device__ __forceinline__ const uint32_t* pres(const urf_kargs& a, unsigned s)
+    {
+        return (W128 ? a.front_pres128 : a.front_pres) + (size_t)s * tiles(a) * 64u;
+    }
+    /* the largest x * x + y * y of laser slot `l` in block `b` of the march */
+    static __device__ __forceinline__ unsigned long long maxs(const urf_kargs& a, unsigned s, unsigned b, unsigned l)
+    {
+        if constexpr (W128)
+            return a.front_maxs128[(size_t)s * tiles(a) * 64u + (size_t)b * NL + l];
+        else
+            return a.front_maxs[((size_t)s * a.tiles + b) * 64u + l];
+    }
+    static __device__ __forceinline__ const uint32_t* lane_ring(const urf_kargs& a, unsigned s)
+    {
+        return (W128 ? a.front_lane_ring128 : a.front_lane_ring) + (size_t)s * NL;
+    }
+    static __device__ __forceinline__ uint32_t* st(const urf_kargs& a, unsigned s)
+    {
+        return (W128 ? a.front_st128 : a.front_st) + (size_t)s * ST_WORDS;
+    }
+};
+/* ... for a kernel that serves both families (the read-outs, urf_k_front_outputs.hpp): the family from front_lsh */
+__device__ __forceinline__ const uint32_t* urf_front_pres_of(const urf_kargs& a, unsigned s)
 {
-    __shared__ float T[3][64 * 33];   /* [row][W + 1], W = URF_TILE / L columns: 64 x 33, 32 x 65, 16 x 129 */
+    return a.front_lsh == URF_FRONT128_LSH ? urf_front_lay<true>::pres(a, s) : urf_front_lay<false>::pres(a, s);
+}
+__device__ __forceinline__ const uint32_t* urf_front_lane_ring_of(const urf_kargs& a, unsigned s)
+{
+    return a.front_lsh == URF_FRONT128_LSH ? urf_front_lay<true>::lane_ring(a, s) : urf_front_lay<false>::lane_ring(a, s);
+}
+
+/* Row-major organised sweep of L = 1 << lsh rows -> firing order: tx[f * L + l] = x[l * F + f].  Grid (tiles, scans) x 256 threads, a tile =
+ * URF_TILE / L firings: L rows x 64 / 128 / 256 / 512 bytes in, LDS, 8 KB out in one stretch; 24 B/point, HBM-bound. */
+template <bool W128>
+__device__ __forceinline__ void urf_transpose_body(urf_kargs a)
+{
+    using LAY = urf_front_lay<W128>;
+    /* [row][W + 1], W = URF_TILE / L columns: 64 x 33 (and in it 32 x 65, 16 x 129), 128 x 17.  (128 x 17: a wave stores four rows x 16 columns
+     * -- addresses 17 r + c: 64 different ones over a span of 67, three banks twice -- and reads 64 rows of one column: stride 17, odd, no
+     * conflict) */
+    __shared__ float T[3][LAY::NL * (URF_TILE / LAY::NL + 1u)];
     const unsigned s = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
-    const unsigned lsh = a.front_lsh, L = 1u << lsh, wsh = 11u - lsh, W = 1u << wsh, RS = W + 1u;
+    const unsigned lsh = LAY::lsh(a), L = 1u << lsh, wsh = 11u - lsh, W = 1u << wsh, RS = W + 1u;
     static_assert(URF_TILE == 2048u, "a tile's columns: 1 << (11 - lsh)");
     if (a.front_ok[s] != URF_FRONT_ROWS)
         return;
@@ -167,6 +249,14 @@ __global__ __launch_bounds__(256) void k_transpose(urf_kargs a)
             a.tz[ob + v] = T[2][l * RS + f];
         }
     }
+}
+__global__ __launch_bounds__(256) void k_transpose(urf_kargs a)
+{
+    urf_transpose_body<false>(a);
+}
+__global__ __launch_bounds__(256) void k_transpose128(urf_kargs a)
+{
+    urf_transpose_body<true>(a);
 }
 
 /* What the fast decisions of a firing leave open -- a point that is not SURELY on its lane's table entry, whose sector is within
@@ -733,20 +823,21 @@ URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
 /* ------------------------------------------------------------------------- */
 /* k_front_finish                                                              */
 /* ------------------------------------------------------------------------- */
-#define URF_FRONT_ST_WORDS 72u   /* k_front_finish part 1 -> part 2: 64 list lengths, 4 quadrant values, the length of the list of marks */
 #define URF_FINISH_CHUNK 768u   /* candidates per chunk (each may be listed twice): 12 KB of LDS */
 #ifndef URF_FINISH_THREADS
 #define URF_FINISH_THREADS 256   /* four waves and <= 40 KB of LDS per scan: four workgroups per CU, a batch of 1024 scans in one round (A/B 256 / 512 /
                                     * 1024 threads: cfg3 0.186 / 0.184 / 0.206 ms, the reference's default region of interest 0.210 / 0.241 / 0.264) */
 #endif
-struct urf_finish_shared {
-    unsigned n[64];              /* ring points of lane l */
-    unsigned ring[64];           /* its ring (0xffffffff: the lane holds no ring point) */
-    unsigned ncurb[URF_FRONT_LANES];   /* curb points of ring r (the fused front end runs with 64 channels) */
+template <unsigned NL>   /* urf_front_lay::NL: 64 or 128 */
+struct urf_finish_shared_t {
+    unsigned n[NL];              /* ring points of laser slot l */
+    unsigned ring[NL];           /* its ring (0xffffffff: the slot holds no ring point) */
+    unsigned ncurb[NL];          /* curb points of ring r (channels <= NL) */
     int q[4];
     unsigned n_pend;             /* entries of the scan's list of points to mark */
     unsigned nx, nz;             /* x_zero / z_zero items of the chunk at hand */
-    unsigned qsum[URF_FINISH_THREADS / 64][64];
+    unsigned tot[NL > 64u ? 1 : 0];   /* ring points of the scan, where two waves add them up (up to 64 slots: a wave shuffle, and no word here) */
+    unsigned qsum[URF_FINISH_THREADS / NL][NL];
 };
 
 /* firing of the ring point in front of / behind firing f in lane l; 0xffffffff: none */
@@ -780,13 +871,18 @@ __device__ __forceinline__ unsigned urf_front_next(const unsigned* P, unsigned l
  * two detectors and their marks -- as a launch of its own on a SECOND stream, next to k_index / k_star_sort_* / k_star_walk (it waits for
  * scattered loads, they for vector issue: urf_api.hip), and the star-shaped hits, the lists' hand-over to k_beams and the overflow tables
  * behind the walk.  The counters travel from part 1 to part 2 through front_st.
- * CP = params.curbPoints (h = CP / 2): the ring positions both detectors accept and how far their neighbours lie, as in the march. */
-template <unsigned CP>
+ * CP = params.curbPoints (h = CP / 2): the ring positions both detectors accept and how far their neighbours lie, as in the march.  Nothing
+ * else in here knows CP, and what knows the laser count asks the layout (urf_front_lay<W128>: k_front_finish*, k_front_finish128*).  The two
+ * families differ in ONE piece of code besides: how the scan's ring points are added up (64 slots: a wave shuffle; 128: an LDS atomic). */
+template <unsigned CP, bool W128>
 __device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_params dp, unsigned part)
 {
-    __shared__ urf_finish_shared S;
-    extern __shared__ unsigned sh_finish[];   /* P[tiles][64] presence words | B[tiles][64] (u16) ring points of the lane in the tiles before */
+    using LAY = urf_front_lay<W128>;
+    constexpr unsigned NL = LAY::NL;
+    __shared__ urf_finish_shared_t<NL> S;
+    extern __shared__ unsigned sh_finish[];   /* P[tiles][64] presence words | B[tiles][64] (u16) ring points of the lane in the tiles before (tiles: LAY::tiles) */
     constexpr unsigned H = CP / 2u;
+    const unsigned tiles = LAY::tiles(a);
     const unsigned s = blockIdx.x, tid = threadIdx.x;
     const unsigned ok = a.front_ok[s];
     if (!ok)
@@ -795,16 +891,16 @@ __device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_param
     urf_scan_range(a, s, off, len);
     const unsigned ntiles = (len + URF_TILE - 1) / URF_TILE;
     /* L lasers per firing: candidate index = firing * L + laser slot (its place in the input), presence words per 32 firings and slot */
-    const unsigned lsh = a.front_lsh, L = 1u << lsh, lm = L - 1u;
-    const unsigned npt = (((len + lm) >> lsh) + 31u) >> 5;   /* (L = 64: ntiles; always npt * L <= ntiles * 64) */
+    const unsigned lsh = LAY::lsh(a), L = 1u << lsh, lm = L - 1u;
+    const unsigned npt = (((len + lm) >> lsh) + 31u) >> 5;   /* (L = 64: ntiles; always npt * L <= tiles * 64) */
     const unsigned C = (unsigned)dp.p.channels, K = (unsigned)dp.p.sectors;
     const urf_scan_info in = a.info[s];
     if (in.status != URF_OK)
         return;
     unsigned* const P = sh_finish;
-    uint16_t* const B = (uint16_t*)(sh_finish + a.tiles * 64u);
-    urf_u2* const chunk = (urf_u2*)(sh_finish + a.tiles * 96u);   /* [2 * URF_FINISH_CHUNK] a chunk of the candidate list, by kind */
-    unsigned* const st = a.front_st + (size_t)s * URF_FRONT_ST_WORDS;   /* [0..63] ncurb, [64..67] quadrants, [68] list length: part 1 -> part 2 */
+    uint16_t* const B = (uint16_t*)(sh_finish + tiles * 64u);
+    urf_u2* const chunk = (urf_u2*)(sh_finish + tiles * 96u);   /* [2 * URF_FINISH_CHUNK] a chunk of the candidate list, by kind */
+    unsigned* const st = LAY::st(a, s);   /* [0..NL) ncurb, then LAY::ST_*: part 1 -> part 2 */
     urf_u2* const pend = a.front_all + (size_t)s * a.front_cand_cap;   /* (index, flags) of what phase M has to mark; later the list of all curb points */
     const unsigned sb = urf_sbase(a, s);
     const float *gx, *gy, *gz;
@@ -820,13 +916,15 @@ __device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_param
     const unsigned nc_raw = a.front_ncand[s];
     const unsigned nc = nc_raw < a.front_cand_cap ? nc_raw : a.front_cand_cap;
     for (unsigned k = tid; k < npt * L; k += URF_FINISH_THREADS)
-        P[k] = a.front_pres[(size_t)s * a.tiles * 64u + k];
-    if (tid < URF_FRONT_LANES)
+        P[k] = LAY::pres(a, s)[k];
+    if (tid < NL) {
         S.ncurb[tid] = 0;
-    if (tid < 64)
-        S.ring[tid] = a.front_lane_ring[(size_t)s * 64u + tid];
+        S.ring[tid] = LAY::lane_ring(a, s)[tid];
+    }
     if (tid == 0) {
-        st[70] = 0;
+        st[LAY::ST_RING10] = 0;
+        if constexpr (W128)
+            S.tot[0] = 0;
         S.q[0] = (int)urf_fbits(0.f);
         S.q[1] = (int)urf_fbits(180.f);
         S.q[2] = (int)urf_fbits(180.f);
@@ -836,9 +934,9 @@ __device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_param
     __syncthreads();
     /* positions: the tiles in as many stretches as the workgroup has waves, per lane; then the stretches' sums */
     {
-        constexpr unsigned NP = URF_FINISH_THREADS / 64u;
-        const unsigned l = tid & 63u, prt = tid >> 6;
-        const unsigned nt = l < L ? npt : 0u;   /* (the lanes from L on hold no laser) */
+        constexpr unsigned NP = URF_FINISH_THREADS / NL;
+        const unsigned l = tid & (NL - 1u), prt = tid / NL;
+        const unsigned nt = l < L ? npt : 0u;   /* (the slots from L on hold no laser) */
         const unsigned tq = (nt + NP - 1u) / NP, ta = prt * tq < nt ? prt * tq : nt, tb = ta + tq < nt ? ta + tq : nt;
         unsigned run = 0;
         for (unsigned t = ta; t < tb; t++)
@@ -861,12 +959,15 @@ __device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_param
     if (tid < C)
         a.ring_cnt[(size_t)s * C + tid] = 0;
     __syncthreads();
-    if (tid < 64) {
+    if (tid < NL) {
         const unsigned r = S.ring[tid], n = r != 0xffffffffu ? S.n[tid] : 0u;
-        unsigned tot = n;
-        for (int o = 32; o > 0; o >>= 1)
-            tot += __shfl_xor(tot, o);
+        unsigned tot = n;   /* the scan's ring points: one wave holds every slot, or two waves add them up in LDS */
+        if constexpr (!W128)
+            for (int o = 32; o > 0; o >>= 1)
+                tot += __shfl_xor(tot, o);
         if (r != 0xffffffffu) {
+            if constexpr (W128)
+                atomicAdd(&S.tot[0], n);
             a.ring_cnt[(size_t)s * C + r] = n;
             unsigned long long m = 0;
             const unsigned nblk = (ntiles + a.front_tpb - 1u) / a.front_tpb;
@@ -874,7 +975,7 @@ __device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_param
                 unsigned long long v[8];
 #pragma unroll
                 for (unsigned b = 0; b < 8; b++)
-                    v[b] = a.front_maxs[((size_t)s * a.tiles + (b0 + b < nblk ? b0 + b : b0)) * 64u + tid];
+                    v[b] = LAY::maxs(a, s, b0 + b < nblk ? b0 + b : b0, tid);
 #pragma unroll
                 for (unsigned b = 0; b < 8; b++)
                     m = v[b] > m ? v[b] : m;
@@ -882,10 +983,17 @@ __device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_param
             a.maxdist[(size_t)s * C + r] = (float)__builtin_sqrt(__longlong_as_double((long long)m));
             a.vis[(size_t)s * C + r] = urf_vis{ __builtin_inff(), -__builtin_inff() };
             if (r == 10u)
-                st[70] = n;
+                st[LAY::ST_RING10] = n;
         }
+        /* (the summary's two counts are written behind k_index -- below -- which may still find the scan below the 30-point threshold) */
+        if constexpr (!W128)
+            if (tid == 0)
+                st[LAY::ST_RING_PTS] = tot;
+    }
+    if constexpr (W128) {
+        __syncthreads();
         if (tid == 0)
-            st[69] = tot;   /* (the summary's two counts are written behind k_index -- below -- which may still find the scan below the 30-point threshold) */
+            st[LAY::ST_RING_PTS] = S.tot[0];
     }
     /* The candidates.  One wave-instruction costs the same with one busy lane as with sixty-four, and every kind of candidate has
      * its own expensive chain (x_zero: three f64 roots and a division; z_zero: ten differences, two roots, a division; a passed
@@ -1013,15 +1121,15 @@ __device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_param
     }
     } else {
         /* part 2: the counters of part 1 */
-        if (tid < URF_FRONT_LANES) {
+        if (tid < NL) {
             S.ncurb[tid] = st[tid];
-            S.ring[tid] = a.front_lane_ring[(size_t)s * 64u + tid];
+            S.ring[tid] = LAY::lane_ring(a, s)[tid];
         }
         if (tid < 4)
-            S.q[tid] = (int)st[64u + tid];
+            S.q[tid] = (int)st[LAY::ST_QUAD + tid];
         if (tid == 0)
-            S.n_pend = st[68];
-        m_from = st[68];
+            S.n_pend = st[LAY::ST_NPEND];
+        m_from = st[LAY::ST_NPEND];
         __syncthreads();
     }
     /* lidar_segmentation.cpp:235-242: the star-shaped hits (the walk reported them as input indices; -1: none or on no ring) */
@@ -1066,18 +1174,18 @@ __device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_param
     }
     __syncthreads();
     if (part == 1u) {   /* (uniform) the counters for part 2 */
-        if (tid < URF_FRONT_LANES)
+        if (tid < NL)
             st[tid] = S.ncurb[tid];
         if (tid < 4)
-            st[64u + tid] = (unsigned)S.q[tid];
+            st[LAY::ST_QUAD + tid] = (unsigned)S.q[tid];
         if (tid == 0)
-            st[68] = n_pend;
+            st[LAY::ST_NPEND] = n_pend;
         return;
     }
     /* the scan's summary (lidar_segmentation.cpp:605-608: road_probably = every point of sorted ring 10) */
     if (tid == 0) {
-        a.info[s].n_ring_pts = st[69];
-        a.info[s].n_ring10 = in.n_rings > 10 ? st[70] : 0u;
+        a.info[s].n_ring_pts = st[LAY::ST_RING_PTS];
+        a.info[s].n_ring10 = in.n_rings > 10 ? st[LAY::ST_RING10] : 0u;
     }
     /* what k_beams reads (k_ring's epilogue) */
     if (tid < 4 && dp.p.blind_spots && in.n_rings > 1)
@@ -1142,14 +1250,15 @@ __device__ __forceinline__ void urf_front_finish_body(urf_kargs a, urf_dev_param
         }
     }
 }
-/* one kernel per curbPoints, as for k_front (k_front_finish: 5) */
-#define URF_FRONT_FINISH_KERNEL(name, CP)                                                                     \
+/* one kernel per family and per curbPoints, as for k_front (k_front_finish, k_front_finish128: 5; urf_set_front_curb_points: the others) */
+#define URF_FRONT_FINISH_KERNEL(name, CP, W128)                                                               \
     __global__ __launch_bounds__(URF_FINISH_THREADS) void name(urf_kargs a, urf_dev_params dp, unsigned part) \
     {                                                                                                         \
-        urf_front_finish_body<CP>(a, dp, part);                                                               \
+        urf_front_finish_body<CP, W128>(a, dp, part);                                                         \
     }
-URF_FRONT_FINISH_KERNEL(k_front_finish, 5u)
-#define URF_FRONT_CP_X(n) URF_FRONT_FINISH_KERNEL(k_front_finish_cp##n, n)
+URF_FRONT_FINISH_KERNEL(k_front_finish, 5u, false)
+URF_FRONT_FINISH_KERNEL(k_front_finish128, 5u, true)
+#define URF_FRONT_CP_X(n) URF_FRONT_FINISH_KERNEL(k_front_finish_cp##n, n, false) URF_FRONT_FINISH_KERNEL(k_front_finish128_cp##n, n, true)
 URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
 #undef URF_FRONT_CP_X
 
@@ -1161,9 +1270,10 @@ URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
  * azimuth, the exact azimuth where that leaves a decision open). */
 __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_label_front(urf_kargs a, urf_dev_params dp)
 {
+    using LAY = urf_front_lay<false>;
     __shared__ unsigned cnt_road, cnt_curb, n_unsure;
     __shared__ unsigned un_idx[URF_LABEL_UNSURE], un_ring[URF_LABEL_UNSURE];
-    __shared__ __attribute__((aligned(8))) uint8_t lab_t[64 * 40];   /* (row-major scans) [laser][firings of the tile + 8]: 64 x 40, 32 x 72, 16 x 136 */
+    __shared__ __attribute__((aligned(8))) uint8_t lab_t[LAY::NL * (URF_TILE / LAY::NL + 8u)];   /* (row-major scans) [laser][firings of the tile + 8]: 64 x 40, 32 x 72, 16 x 136 */
     unsigned s = blockIdx.y, t = blockIdx.x;
     {   /* the tiles of one scan on one XCD (k_label: the scan's window table is fetched by one L2) */
         const unsigned T = gridDim.x, lin = blockIdx.y * T + blockIdx.x;
@@ -1245,7 +1355,7 @@ __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves
     } else {
 #pragma unroll
         for (unsigned e = 0; e < 8; e++)
-            rec[e] = URF_FRONT_RING_NONE;
+            rec[e] = LAY::RING_NONE;
     }
     unsigned lab[8];
     unsigned my_road = 0, my_curb = 0;
@@ -1256,8 +1366,8 @@ __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves
 #pragma unroll
     for (unsigned q = 0; q < 4; q++) {
         const unsigned e = h + q;
-        const bool on = ((bits >> e) & 1u) && (rec[e] & 0x7fu) != URF_FRONT_RING_NONE;
-        const unsigned c = on ? (rec[e] & 0x7fu) : 0u;
+        const bool on = ((bits >> e) & 1u) && (rec[e] & LAY::RING_MASK) != LAY::RING_NONE;
+        const unsigned c = on ? (rec[e] & LAY::RING_MASK) : 0u;
         const float az = urf_az_decode(rec[e] >> URF_REC_AZ_SHIFT);
         const bool num = az == az;
         int cf = num ? (int)__builtin_floorf(az) : 0, cb = num ? (int)__builtin_ceilf(az) : 0;
@@ -1270,8 +1380,193 @@ __global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves
     for (unsigned q = 0; q < 4; q++) {
         const unsigned e = h + q;
         const bool roi = (bits >> e) & 1u;
-        const bool on = roi && (rec[e] & 0x7fu) != URF_FRONT_RING_NONE;
-        const unsigned c = rec[e] & 0x7fu;
+        const bool on = roi && (rec[e] & LAY::RING_MASK) != LAY::RING_NONE;
+        const unsigned c = rec[e] & LAY::RING_MASK;
+        const bool curb = on && ((rec[e] >> URF_REC_FLAG_SHIFT) & 7u) != 0;
+        const float az = urf_az_decode(rec[e] >> URF_REC_AZ_SHIFT), eps = urf_fast_az_eps(az) + URF_REC_AZ_QERR;
+        const float fl = __builtin_floorf(az);
+        bool road = az <= whi[q] || az >= wlo[q];
+        const bool unsure = az < 0.0f || az - fl <= eps || (fl + 1.0f) - az <= eps || __builtin_fabsf(az - whi[q]) <= eps ||
+                            __builtin_fabsf(az - wlo[q]) <= eps;
+        /* (the label first, with a point whose decision is open as "not road"; THEN the branch for such a point: the lane masks above
+         * are dead by then -- they used to live across it, and the compiler parked fourteen scalar registers per point in a vector
+         * register's lanes, v_writelane by v_writelane) */
+        const bool uns = unsure && on && !curb;
+        road = road && on && !curb && !uns;
+        lab[e] = !roi ? 0u
+                      : (URF_FLAG_ROI | (on ? URF_FLAG_RING | (c == 10 ? URF_FLAG_RING10 : 0) | (curb ? URF_LABEL_CURB : 0) | (road ? URF_LABEL_ROAD : 0) : 0u));
+        my_curb += curb ? 1u : 0u;
+        my_road += road ? 1u : 0u;
+        if (uns) {
+            const unsigned u = atomicAdd(&n_unsure, 1u);
+            if (u < URF_LABEL_UNSURE) {
+                un_idx[u] = i0 + e;
+                un_ring[u] = c;   /* corrected below */
+            } else {   /* list full (pathological input) */
+                float d2;
+                bool dummy;
+                const float xaz = urf_azimuth(gx[i0 + e], gy[i0 + e], &d2);
+                if (urf_road_test(win + c * URF_DEG_CELLS, xaz, 0.0f, dummy)) {
+                    lab[e] |= URF_LABEL_ROAD;
+                    my_road++;
+                }
+            }
+        }
+    }
+    }
+    if (rows) {
+        store_rows(lab);
+    } else if (whole) {
+        *(uint2*)out = make_uint2(lab[0] | lab[1] << 8 | lab[2] << 16 | lab[3] << 24, lab[4] | lab[5] << 8 | lab[6] << 16 | lab[7] << 24);
+    } else {
+        for (unsigned e = 0; e < 8; e++)
+            if (i0 + e < len)
+                out[e] = (uint8_t)lab[e];
+    }
+    __syncthreads();   /* the tile's stores come first, the corrections second */
+    const unsigned nu = n_unsure < URF_LABEL_UNSURE ? n_unsure : URF_LABEL_UNSURE;
+    if (tid < nu) {
+        const unsigned i = un_idx[tid], c = un_ring[tid];
+        bool dummy;
+        float d2;
+        const float az = urf_azimuth(gx[i], gy[i], &d2);
+        if (urf_road_test(win + c * URF_DEG_CELLS, az, 0.0f, dummy)) {
+            a.labels[off + (rows ? (size_t)(i & ((1u << lsh) - 1u)) * F + (i >> lsh) : (size_t)i)] = URF_FLAG_ROI | URF_FLAG_RING | (c == 10 ? URF_FLAG_RING10 : 0) | URF_LABEL_ROAD;
+            my_road++;
+        }
+    }
+    if (my_road)
+        atomicAdd(&cnt_road, my_road);
+    if (my_curb)
+        atomicAdd(&cnt_curb, my_curb);
+    __syncthreads();
+    if (tid == 0) {
+        urf_scan_info* o = &a.info[s];
+        if (cnt_road)
+            atomicAdd(&o->n_road, cnt_road);
+        if (cnt_curb)
+            atomicAdd(&o->n_curb, cnt_curb);
+    }
+}
+
+/* k_label_front for the records of k_front128: the ring in eight bits (urf_front_lay<true>::RING_*), 128 rows of 16 + 8 label bytes for a
+ * row-major tile.  A COPY of the kernel above, and kept as one on purpose: as urf_label_front_body<W128> behind two wrappers both kernels
+ * came out with 58 registers instead of 52 and their event bracket 1 - 2.6 % longer (profiles/front_one_finish.md) -- the text was the same,
+ * the wrapper alone changes what the compiler makes of it.  What differs: lsh (a constant), the record's ring mask and "none", lab_t's shape. */
+__global__ __launch_bounds__(URF_LABEL_TILE_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_label_front128(urf_kargs a, urf_dev_params dp)
+{
+    using LAY = urf_front_lay<true>;
+    __shared__ unsigned cnt_road, cnt_curb, n_unsure;
+    __shared__ unsigned un_idx[URF_LABEL_UNSURE], un_ring[URF_LABEL_UNSURE];
+    __shared__ __attribute__((aligned(8))) uint8_t lab_t[LAY::NL * (URF_TILE / LAY::NL + 8u)];   /* (row-major scans) [laser][firings of the tile + 8] */
+    unsigned s = blockIdx.y, t = blockIdx.x;
+    {   /* the tiles of one scan on one XCD (k_label: the scan's window table is fetched by one L2) */
+        const unsigned T = gridDim.x, lin = blockIdx.y * T + blockIdx.x;
+        const unsigned grp = lin / (8u * T), r = lin - grp * (8u * T);
+        if ((grp + 1u) * 8u <= gridDim.y) {
+            s = grp * 8u + (r & 7u);
+            t = r >> 3;
+        }
+    }
+    const unsigned tid = threadIdx.x;
+    const unsigned ok = a.front_ok[s];
+    if (!ok)
+        return;
+    unsigned off, len;
+    urf_scan_range(a, s, off, len);
+    const unsigned tbase = t * URF_TILE;
+    if (tbase >= len)
+        return;
+    const bool rows = ok == URF_FRONT_ROWS;   /* (uniform) the labels go where the points came from: row l, column f */
+    constexpr unsigned lsh = URF_FRONT128_LSH, wsh = 11u - lsh;   /* L = 1 << lsh lasers per firing, 1 << wsh firings per tile */
+    const unsigned F = len >> lsh;
+    const float *gx, *gy, *gz;
+    urf_front_src(a, s, off, ok, gx, gy, gz);
+    const unsigned C = (unsigned)dp.p.channels;
+    const size_t row = (size_t)s * a.tiles + t;
+    const unsigned sb = urf_sbase(a, s);
+    const urf_scan_info in = a.info[s];
+    const unsigned troi = a.tile_roi[row];
+    const unsigned i0 = tbase + tid * 8u;   /* this thread's eight points: one eighth of a firing */
+    /* (the firings behind the scan's last one were never visited: their words hold whatever an earlier call left) */
+    const unsigned in_scan = i0 + 8u <= len ? 0xffu : (i0 < len ? (1u << (len - i0)) - 1u : 0u);
+    const unsigned bits = ((const uint8_t*)(a.roi_bits + row * URF_FRONT_STEPS))[tid] & in_scan;
+    uint8_t* const out = a.labels + off + i0;
+    const bool whole = tbase + URF_TILE <= len && ((uintptr_t)(a.labels + off + tbase) & 7u) == 0;   /* (uniform) */
+    /* row-major: the tile's firings x lasers through LDS, then 8 columns of a row per thread */
+    auto store_rows = [&](const unsigned (&lb)[8]) {
+        const unsigned RS = (1u << wsh) + 8u;
+        const unsigned stp = (tid * 8u) >> lsh, l0 = (tid * 8u) & ((1u << lsh) - 1u);
+#pragma unroll
+        for (unsigned e = 0; e < 8; e++)
+            lab_t[(l0 + e) * RS + stp] = (uint8_t)lb[e];
+        __syncthreads();
+        const unsigned l = tid >> (wsh - 3u), c0 = (tid & ((1u << (wsh - 3u)) - 1u)) * 8u, f0 = (t << wsh) + c0;
+        uint8_t* const o = a.labels + off + (size_t)l * F + f0;
+        const uint8_t* const src = &lab_t[l * RS + c0];
+        if (f0 + 8u <= F && ((uintptr_t)o & 7u) == 0) {
+            *(uint2*)o = *(const uint2*)src;
+        } else {
+            for (unsigned e = 0; e < 8; e++)
+                if (f0 + e < F)
+                    o[e] = src[e];
+        }
+    };
+    if (in.status != URF_OK || troi == 0) {
+        if (rows) {
+            const unsigned zero[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
+            store_rows(zero);
+        } else if (whole) {
+            *(uint2*)out = make_uint2(0u, 0u);
+        } else {
+            for (unsigned e = 0; e < 8; e++)
+                if (i0 + e < len)
+                    out[e] = 0;
+        }
+        return;
+    }
+    if (tid == 0) {
+        cnt_road = 0;
+        cnt_curb = 0;
+        n_unsure = 0;
+    }
+    __syncthreads();
+    const urf_win* win = a.win + (size_t)s * C * URF_DEG_CELLS;
+    unsigned rec[8];
+    if (bits) {   /* (the records of a firing without a point in the region of interest were never written) */
+        const uint4 r0 = *(const uint4*)(a.rec + sb + i0), r1 = *(const uint4*)(a.rec + sb + i0 + 4);
+        rec[0] = r0.x; rec[1] = r0.y; rec[2] = r0.z; rec[3] = r0.w;
+        rec[4] = r1.x; rec[5] = r1.y; rec[6] = r1.z; rec[7] = r1.w;
+    } else {
+#pragma unroll
+        for (unsigned e = 0; e < 8; e++)
+            rec[e] = LAY::RING_NONE;
+    }
+    unsigned lab[8];
+    unsigned my_road = 0, my_curb = 0;
+    /* (four points at a time: the window ends of four are requested before any of them is looked at) */
+#pragma unroll
+    for (unsigned h = 0; h < 8; h += 4) {
+    float whi[4], wlo[4];
+#pragma unroll
+    for (unsigned q = 0; q < 4; q++) {
+        const unsigned e = h + q;
+        const bool on = ((bits >> e) & 1u) && (rec[e] & LAY::RING_MASK) != LAY::RING_NONE;
+        const unsigned c = on ? (rec[e] & LAY::RING_MASK) : 0u;
+        const float az = urf_az_decode(rec[e] >> URF_REC_AZ_SHIFT);
+        const bool num = az == az;
+        int cf = num ? (int)__builtin_floorf(az) : 0, cb = num ? (int)__builtin_ceilf(az) : 0;
+        cf = cf < 0 ? 0 : (cf > 360 ? 360 : cf);
+        cb = cb < 0 ? 0 : (cb > 360 ? 360 : cb);
+        whi[q] = win[c * URF_DEG_CELLS + cf].hi;
+        wlo[q] = win[c * URF_DEG_CELLS + cb].lo;
+    }
+#pragma unroll
+    for (unsigned q = 0; q < 4; q++) {
+        const unsigned e = h + q;
+        const bool roi = (bits >> e) & 1u;
+        const bool on = roi && (rec[e] & LAY::RING_MASK) != LAY::RING_NONE;
+        const unsigned c = rec[e] & LAY::RING_MASK;
         const bool curb = on && ((rec[e] >> URF_REC_FLAG_SHIFT) & 7u) != 0;
         const float az = urf_az_decode(rec[e] >> URF_REC_AZ_SHIFT), eps = urf_fast_az_eps(az) + URF_REC_AZ_QERR;
         const float fl = __builtin_floorf(az);

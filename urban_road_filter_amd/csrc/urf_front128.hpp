@@ -1,6 +1,6 @@
 /*
  * urf_front128.hpp -- the fused front end (urf_front.hpp) for sweeps of 128 lasers per firing (urf_set_front_lasers128): firing order
- * (point f * 128 + l) or row-major (128 rows).  The kernels stand beside those of urf_front.hpp, each under a name of its own:
+ * (point f * 128 + l) or row-major (128 rows).  This header holds the march, the one kernel of the family with a body of its own:
  *
  *   k_front128          ONE wave per block, TWO lasers per lane: lane j marches lasers j and j + 64 (half 0 and half 1 of a firing), with
  *                       two windows (urf_front_window, urf_front.hpp) and two sets of per-ring state.  The two halves of a firing are
@@ -9,12 +9,11 @@
  *                       ballots and no LDS traffic or barrier, and the candidate buffer stays "the workgroup is the wave".  The price is
  *                       registers.  k_front128_cp{1,2,3,4,6,7,8} are the same body, urf_front128_body, for the
  *                       other curbPoints (urf_set_front_mode(ctx, 3) with urf_set_front_lasers128 and urf_set_front_curb_points on).
- *   k_front_finish128   k_front_finish with 128 rings' sizes, positions, largest ranges and curb lists (urf_front128_finish.hpp; _cp*: the
- *                       ring positions both detectors accept and how far their neighbours lie as functions of curbPoints).
- *   k_label_front128    k_label_front with the record's ring in EIGHT bits (URF_FRONT128_RING_*: table entry 127 is a ring, 0xff is
- *                       "none"; bits 7..10 of an input-order record are free) and a row-major store-back tile of 128 x 24 bytes.
- *   k_transpose128      k_transpose with 128 x 17 floats per plane.
- *   k_rows_probe128     k_rows_probe over 128 rows.
+ *
+ * The kernels around it -- k_front_finish128 (and _cp*), k_transpose128 (urf_front.hpp), k_rows_probe128 (urf_k_table.hpp) -- are the W128
+ * instances of the bodies they share with 64 / 32 / 16 lasers, each a named wrapper next to its body; what is different about 128 lasers
+ * there (the arrays, their strides, the record's ring in eight bits; the constants URF_FRONT128_L, _LSH, _TILES2, _ST_WORDS, _RING_*) is
+ * written down once, in urf_front_lay<true> (urf_front.hpp).  k_label_front128 stands next to k_label_front there, as a kernel of its own.
  *
  * What they leave behind keeps the layout its readers know, indexed by f * 128 + l: region-of-interest bits (two 64-bit words per
  * firing), slots (stp * 128 + l < 2048), tsoff, candidate indices.  What was sized for 64 lanes has a sibling sized for 128
@@ -25,13 +24,7 @@
 #ifndef URF_FRONT128_HPP
 #define URF_FRONT128_HPP
 
-#define URF_FRONT128_L 128u
-#define URF_FRONT128_LSH 7u
 #define URF_FRONT128_STEPS (URF_TILE / URF_FRONT128_L)   /* firings per tile: 16 */
-#define URF_FRONT128_RING_MASK 0xffu   /* ring field of an input-order record of these kernels */
-#define URF_FRONT128_RING_NONE 0xffu
-#define URF_FRONT128_TILES2(tiles) (((tiles) + 1u) & ~1u)
-#define URF_FRONT128_ST_WORDS 136u     /* k_front_finish128 part 1 -> part 2: 128 list lengths, 4 quadrant values, list length, two counts */
 /* Entries per scan of the candidate lists of these kernels.  The points that pass the march's height tests are counted per LASER, not per
  * column: a ring that crosses a curb hands on up to eleven centres (z_zero) and six marked points (x_zero) per crossing, a street has four
  * crossings per ring -- 128 x 68 = 8 704 for 128 lasers however short the sweep is (a 128 x 256 street of urf_synth_cloud: 5 200 - 5 600),
@@ -44,136 +37,6 @@
 #ifndef URF_FRONT128_WAVES
 #define URF_FRONT128_WAVES 3           /* 168 registers: two windows, two sets of prefetched points */
 #endif
-
-__global__ __launch_bounds__(256) void k_transpose128(urf_kargs a)
-{
-    /* [row][16 + 1]: a wave stores four rows x 16 columns (addresses 17 r + c: 64 different ones over a span of 67, three banks twice) and
-     * reads 64 rows of one column (stride 17: odd, no conflict) */
-    __shared__ float T[3][128 * 17];
-    const unsigned s = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
-    constexpr unsigned lsh = URF_FRONT128_LSH, L = 128u, wsh = 4u, W = 16u, RS = W + 1u;
-    static_assert(URF_TILE == 2048u, "a tile's columns: 1 << (11 - lsh)");
-    if (a.front_ok[s] != URF_FRONT_ROWS)
-        return;
-    unsigned off, len;
-    urf_scan_range(a, s, off, len);
-    const unsigned F = len >> lsh, f0 = t * W;
-    if (f0 >= F)
-        return;
-    const unsigned c = tid & (W - 1u), r8 = tid >> wsh, RP = 256u >> wsh;   /* 16 rows per pass, eight passes */
-    const bool in = f0 + c < F;
-    float vx[8], vy[8], vz[8];
-#pragma unroll
-    for (unsigned j = 0; j < 8; j++) {
-        const size_t i = (size_t)off + (size_t)(j * RP + r8) * F + f0 + (in ? c : 0u);
-        vx[j] = a.x[i];
-        vy[j] = a.y[i];
-        vz[j] = a.z[i];
-    }
-#pragma unroll
-    for (unsigned j = 0; j < 8; j++) {
-        T[0][(j * RP + r8) * RS + c] = vx[j];
-        T[1][(j * RP + r8) * RS + c] = vy[j];
-        T[2][(j * RP + r8) * RS + c] = vz[j];
-    }
-    __syncthreads();
-    const size_t ob = (size_t)urf_sbase(a, s) + (size_t)f0 * L;
-    const unsigned nf = F - f0 < W ? F - f0 : W;
-#pragma unroll
-    for (unsigned j = 0; j < 8; j++) {
-        const unsigned v = j * 256u + tid, f = v >> lsh, l = v & (L - 1u);
-        if (f < nf) {
-            a.tx[ob + v] = T[0][l * RS + f];
-            a.ty[ob + v] = T[1][l * RS + f];
-            a.tz[ob + v] = T[2][l * RS + f];
-        }
-    }
-}
-
-/* k_rows_probe (urf_k_table.hpp) over 128 rows: wave w takes rows 32 w .. 32 w + 31, four at a time; rows_v128[s][0 .. n) the leaders */
-__global__ __launch_bounds__(256) void k_rows_probe128(urf_kargs a, urf_dev_params dp)
-{
-    __shared__ unsigned sh_alive, sh_bad;
-    __shared__ float rowv[128];
-    const unsigned s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned off, len;
-    urf_scan_range(a, s, off, len);
-    constexpr unsigned lsh = URF_FRONT128_LSH, L = 128u;
-    if (len < 2u * L || (len & (L - 1u)) != 0u) {
-        if (tid == 0)
-            a.rows_ok[s] = 0u;
-        return;
-    }
-    const unsigned F = len >> lsh;
-    volatile unsigned* const alive = &sh_alive;
-    if (tid == 0) {
-        sh_alive = 1u;
-        sh_bad = 0u;
-    }
-    __syncthreads();
-    const float tol = 2.0f * dp.p.interval * 0.017453292f;
-    for (unsigned g = 0; g < 32u && *alive; g += 4u) {
-        const unsigned r0 = wave * 32u + g;
-        unsigned found = 0;   /* bit q: row r0 + q is settled */
-        for (unsigned c0 = 0; c0 < F && found != 15u && *alive; c0 += 64u) {
-            float px[4], py[4], pz[4];
-            const bool in = c0 + lane < F;
-#pragma unroll
-            for (unsigned q = 0; q < 4; q++) {
-                const size_t i = (size_t)off + (size_t)(r0 + q) * F + c0 + (in ? lane : 0u);
-                px[q] = a.x[i];
-                py[q] = a.y[i];
-                pz[q] = a.z[i];
-            }
-#pragma unroll
-            for (unsigned q = 0; q < 4; q++) {
-                if ((found >> q) & 1u)
-                    continue;   /* (uniform) */
-                const bool roi = in && urf_in_roi(dp.p, px[q], py[q], pz[q]);
-                const unsigned long long m = __ballot(roi);
-                if (m == 0ull)
-                    continue;
-                const int src = (int)__ffsll((long long)m) - 1;
-                /* one ring?  (cot of the vertical angle, to twice the interval: a hint -- k_front128 is the check) */
-                const float u = -pz[q] * __builtin_amdgcn_rsqf(px[q] * px[q] + py[q] * py[q]), u0 = __shfl(u, src);
-                if (__ballot(roi && !(__builtin_fabsf(u - u0) <= tol * (1.0f + u0 * u0))) != 0ull) {
-                    if (lane == 0)
-                        *alive = 0u;
-                    break;
-                }
-                const float v = urf_vertical_angle(__shfl(px[q], src), __shfl(py[q], src), __shfl(pz[q], src));
-                if (lane == 0)
-                    rowv[r0 + q] = v;
-                found |= 1u << q;
-            }
-        }
-#pragma unroll
-        for (unsigned q = 0; q < 4; q++)
-            if (!((found >> q) & 1u) && lane == 0)
-                rowv[r0 + q] = -1.0f;
-    }
-    __syncthreads();
-    /* put through the reference's insertion in row order, every one of them becomes a leader (k_rows_probe's (a)) */
-    float v = -1.0f;
-    unsigned before = 0;
-    if (tid < L) {
-        v = rowv[tid];
-        bool bad = v == 0.0f;
-        for (unsigned j = 0; j < L; j++) {
-            const float w = rowv[j];
-            bad = bad || (j < tid && v >= 0.0f && w >= 0.0f && __builtin_fabsf(w - v) <= dp.p.interval);
-            before += (j < tid && w >= 0.0f) ? 1u : 0u;
-        }
-        if (bad)
-            sh_bad = 1u;
-    }
-    __syncthreads();
-    const bool ok = sh_alive != 0u && sh_bad == 0u;
-    if (tid < L && ok && v >= 0.0f)
-        a.rows_v128[(size_t)s * L + before] = v;   /* compacted: the reference's angle[] before its sort */
-    if (tid == L - 1u)
-        a.rows_ok[s] = ok ? before + (v >= 0.0f ? 1u : 0u) + 1u : 0u;
-}
 
 /* what the march keeps per laser */
 template <unsigned CP>
@@ -522,6 +385,5 @@ URF_FRONT128_KERNEL(k_front128, 5)
 URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
 #undef URF_FRONT_CP_X
 
-#include "urf_front128_finish.hpp"
 
 #endif /* URF_FRONT128_HPP */

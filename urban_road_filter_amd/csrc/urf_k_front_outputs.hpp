@@ -64,8 +64,8 @@ __global__ __launch_bounds__(256) void k_front_out_prep(urf_kargs a, urf_dev_par
     const unsigned C = (unsigned)dp.p.channels;
     const bool rows = a.front_ok[s] == URF_FRONT_ROWS;   /* (uniform) labels and input indices are row-major: l * F + f */
     const unsigned F = len >> lsh;
-    const uint32_t* const pres = lsh == 7u ? a.front_pres128 + (size_t)s * URF_FRONT128_TILES2(a.tiles) * 64u : a.front_pres + (size_t)s * a.tiles * 64u;
-    const uint32_t* const lane_ring = lsh == 7u ? a.front_lane_ring128 + (size_t)s * 128u : a.front_lane_ring + (size_t)s * 64u;
+    const uint32_t* const pres = urf_front_pres_of(a, s);   /* (urf_front_lay, urf_front.hpp: either family's) */
+    const uint32_t* const lane_ring = urf_front_lane_ring_of(a, s);
     const float *gx, *gy, *gz;
     urf_front_src(a, s, off, a.front_ok[s], gx, gy, gz);
     const size_t ob = (size_t)blockIdx.y * a.sstride;

@@ -122,15 +122,19 @@ struct urf_table_shared {
  * their vertical angles, and through the reference's insertion in row order: rows_v[s][0 .. n) the leaders, rows_ok[s] = n + 1.  Given up
  * (rows_ok[s] = 0) when one of them would not become a leader, or as soon as the 64 points from a row's first one on show a second
  * ring: a sweep in firing order.  A kernel of its own, in the sequence of a context that has
- * sighted such a sweep: inside k_ring_table its registers cost that kernel a wave per SIMD (1024 scans no longer resident at once). */
-__global__ __launch_bounds__(256) void k_rows_probe(urf_kargs a, urf_dev_params dp)
+ * sighted such a sweep: inside k_ring_table its registers cost that kernel a wave per SIMD (1024 scans no longer resident at once).
+ * W128 = false (k_rows_probe): L = 1 << front_lsh rows of up to 64, rows_v; true (k_rows_probe128): 128 rows, rows_v128.  (This header comes in
+ * front of urf_front.hpp, whose urf_front_lay describes the two families to the other kernels: what the probe needs of it is these lines.) */
+template <bool W128>
+__device__ __forceinline__ void urf_rows_probe_body(urf_kargs a, urf_dev_params dp)
 {
-    __shared__ unsigned sh_alive;
-    __shared__ float rowv[64];
+    constexpr unsigned NL = W128 ? 128u : 64u, RPW = NL / 4u;   /* rows the arrays hold, rows per wave */
+    __shared__ unsigned sh_alive, sh_bad;
+    __shared__ float rowv[NL];
     const unsigned s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned off, len;
     urf_scan_range(a, s, off, len);
-    const unsigned lsh = a.front_lsh, L = 1u << lsh;   /* the rows of the cloud: params.channels (64, 32, 16) */
+    const unsigned lsh = W128 ? 7u : a.front_lsh, L = 1u << lsh;   /* the rows of the cloud: params.channels (128; 64, 32, 16) */
     if (len < 2u * L || (len & (L - 1u)) != 0u) {
         if (tid == 0)
             a.rows_ok[s] = 0u;
@@ -138,14 +142,16 @@ __global__ __launch_bounds__(256) void k_rows_probe(urf_kargs a, urf_dev_params 
     }
     const unsigned F = len >> lsh;
     volatile unsigned* const alive = &sh_alive;
-    if (tid == 0)
+    if (tid == 0) {
         sh_alive = 1u;
+        sh_bad = 0u;
+    }
     __syncthreads();
-    /* wave w takes rows 16 w .. 16 w + 15, four at a time */
+    /* wave w takes rows RPW w .. RPW w + RPW - 1, four at a time */
     const float tol = 2.0f * dp.p.interval * 0.017453292f;
-    for (unsigned g = 0; g < 16u && *alive; g += 4u) {
-        const unsigned r0 = wave * 16u + g;
-        if (r0 >= L) {   /* (uniform) a sensor with fewer rows: nothing there */
+    for (unsigned g = 0; g < RPW && *alive; g += 4u) {
+        const unsigned r0 = wave * RPW + g;
+        if (!W128 && r0 >= L) {   /* (uniform) a sensor with fewer rows: nothing there */
             if (lane < 4u)
                 rowv[r0 + lane] = -1.0f;
             continue;
@@ -190,21 +196,36 @@ __global__ __launch_bounds__(256) void k_rows_probe(urf_kargs a, urf_dev_params 
     }
     __syncthreads();
     /* (a) of the rule: put through the reference's insertion in row order, every one of them becomes a leader -- none matches an earlier one
-     * (lidar_segmentation.cpp:176-190: |angle[j] - alpha| <= interval), none is the table's end marker 0 (:176) */
-    if (wave == 0) {
-        const float v = rowv[lane];
+     * (lidar_segmentation.cpp:176-190: |angle[j] - alpha| <= interval), none is the table's end marker 0 (:176).  A thread per row: it also
+     * counts the leaders in front of its own.  (Up to 64 rows this used to be one wave with ballots; the form 128 rows need is no slower
+     * there -- profiles/front_one_finish.md -- so it is the only one.) */
+    float v = -1.0f;
+    unsigned before = 0;
+    if (tid < L) {
+        v = rowv[tid];
         bool bad = v == 0.0f;
-        for (unsigned j = 0; j < 63u; j++) {
+        for (unsigned j = 0; j < L; j++) {
             const float w = rowv[j];
-            bad = bad || (j < lane && v >= 0.0f && w >= 0.0f && __builtin_fabsf(w - v) <= dp.p.interval);
+            bad = bad || (j < tid && v >= 0.0f && w >= 0.0f && __builtin_fabsf(w - v) <= dp.p.interval);
+            before += (j < tid && w >= 0.0f) ? 1u : 0u;
         }
-        const unsigned long long have = __ballot(v >= 0.0f);
-        const bool ok = sh_alive != 0u && __ballot(bad) == 0ull;
-        if (ok && v >= 0.0f)
-            a.rows_v[(size_t)s * 64u + urf_popc_below(have)] = v;   /* compacted: the reference's angle[] before its sort */
-        if (lane == 0)
-            a.rows_ok[s] = ok ? (unsigned)__popcll(have) + 1u : 0u;
+        if (bad)
+            sh_bad = 1u;
     }
+    __syncthreads();
+    const bool ok = sh_alive != 0u && sh_bad == 0u;
+    if (tid < L && ok && v >= 0.0f)
+        (W128 ? a.rows_v128 : a.rows_v)[(size_t)s * NL + before] = v;   /* compacted: the reference's angle[] before its sort */
+    if (tid == L - 1u)
+        a.rows_ok[s] = ok ? before + (v >= 0.0f ? 1u : 0u) + 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_rows_probe(urf_kargs a, urf_dev_params dp)
+{
+    urf_rows_probe_body<false>(a, dp);
+}
+__global__ __launch_bounds__(256) void k_rows_probe128(urf_kargs a, urf_dev_params dp)
+{
+    urf_rows_probe_body<true>(a, dp);
 }
 
 __device__ void urf_ring_table_scan(const urf_kargs& a, const urf_dev_params& dp, unsigned s, unsigned lookahead, urf_table_shared& T, bool first_walk)
