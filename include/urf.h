@@ -530,7 +530,7 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * fused front end (synchronises); a scan that kept its flag but has no result -- fewer than 30 points in the region of interest: nothing
  * is published for it by either kind of kernel -- is counted.
  *
- * 128 lasers per firing (urf_set_front_lasers128, urban_road_filter_amd/csrc/urf_front128.hpp): with the switch on, channels == 128 and
+ * 128 lasers per firing (urf_set_front_lasers128, k_front128* in urban_road_filter_amd/csrc/urf_front.hpp): with the switch on, channels == 128 and
  * curbPoints == 5, modes 2 and 3 -- never modes 0 and 1 -- also take sweeps of 128 lasers per firing, in firing order (point f * 128 + l)
  * or row-major (128 rows; sighted by one call, fused from the next on, the callback path included): one wave per block of the march, two
  * lasers (l and l + 64) per lane.  Everything above holds for them as well -- per-scan hand-back, identical labels and summaries,
@@ -553,7 +553,7 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * only unless this switch is on.  With it, mode 3 -- never modes 0, 1 and 2 -- also takes curbPoints 1..8 with channels == 16 or 32
  * (k_front32_cp*, k_front16_cp*: the march of mode 3 with half or a quarter of the wave's lanes; the finish step is the 64-laser one, which
  * takes the laser count at run time), and with channels == 128 when urf_set_front_lasers128 is on as well (k_front128_cp*,
- * k_front_finish128_cp*, urban_road_filter_amd/csrc/urf_front128.hpp: two windows of 2 * curbPoints + 1 heights per lane).  Everything
+ * k_front_finish128_cp*, urban_road_filter_amd/csrc/urf_front.hpp: two windows of 2 * curbPoints + 1 heights per lane).  Everything
  * above keeps its meaning with these instances: per-scan hand-back, identical labels and summaries, urf_front_scans, ragged batches,
  * row-major sightings and the callback path's row-major sweeps, urf_set_front_long_sweeps, urf_set_front_outputs, the dense entry
  * points.  curbPoints 9..30 keep the general kernels everywhere; with the switch off every call launches exactly what it launched

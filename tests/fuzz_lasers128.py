@@ -1,4 +1,4 @@
-"""tests/fuzz_lasers.py's idea for 128 lasers per firing (urf_front128.hpp: two lasers per lane, a tile = 16 firings, a presence word = 32):
+"""tests/fuzz_lasers.py's idea for 128 lasers per firing (k_front128*, urf_front.hpp: two lasers per lane, a tile = 16 firings, a presence word = 32):
 a synthetic sweep of 128 rings in firing order, 96 .. 300 firings, with random drop-outs -- single points, whole firings, firings
 whose lasers 0..63 or 64..127 are all missing, whole rings, azimuth ranges, runs inside a ring, holes that straddle the borders of
 tiles (every 16 firings) and of the march's blocks (every 32) -- a few points moved off their ring or their sector, a scan that ends

@@ -1,5 +1,5 @@
 """The fused front end's instances for curbPoints other than 5 at 16, 32 and 128 lasers per firing (urf_set_front_curb_points: k_front32_cp*,
-k_front16_cp* and k_front_finish128_cp* in urf_front.hpp; k_front128_cp* in urf_front128.hpp) exist in the
+k_front16_cp*, k_front128_cp* and k_front_finish128_cp*, all in urf_front.hpp) exist in the
 gfx950 code object under their own names and keep their windows in registers: no scratch.  The register counts are a record (DESIGN.md
 section 4: what hipcc reports), pinned as the ceiling the instance's waves per SIMD leave each wave -- 512 registers per SIMD in blocks
 of 8: 96 at five waves, 128 at four, 168 at three, 256 at two; a workgroup of k_front_finish128_cp* is four waves, its floor the reported

@@ -1,4 +1,4 @@
-"""The 128-laser instances of the fused front end (urf_front128.hpp) exist in the gfx950 code object under their own names, do not
+"""The 128-laser instances of the fused front end (k_front128*, k_front_finish128*, urf_front.hpp) exist in the gfx950 code object under their own names, do not
 spill and stay inside the budgets DESIGN.md section 4 states: k_front128 -- one wave, two lasers per lane, two windows -- 151 VGPRs at
 three waves per SIMD (ceiling 168: what three waves leave each); its siblings the figures of the 64-lane kernels they mirror.  The
 kernels of urf_front.hpp keep their names and stay free of scratch.  hipcc cross-compiles without a GPU."""

@@ -45,7 +45,7 @@ def _contexts():
 def context(L):
     """One long-lived context per laser count, MAX_BATCH scans, front mode 2: 320 firings of 16 / 32 points, 300 of 128, and 2048 of 64 --
     the fused front end's candidate list holds max(max_points / 8, 4096) entries per scan, and a 64-laser street seen all around (the wide
-    region of interest) hands on about 64 x 68 of them however short the sweep is (urf_front128.hpp): a context sized for 64 x 300 points
+    region of interest) hands on about 64 x 68 of them however short the sweep is (URF_FRONT128_CAND_CAP, urf_front.hpp): a context sized for 64 x 300 points
     would hand every such sweep back for that reason alone."""
     if L not in _CTX:
         _CTX[L] = u.Context(L * {16: 320, 32: 320, 64: 2048, 128: 300}[L], MAX_BATCH)

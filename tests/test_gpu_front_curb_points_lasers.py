@@ -1,5 +1,5 @@
 """urf_set_front_curb_points(ctx, 1): front mode 3's instances for curbPoints 1..8 at 16, 32 and 128 lasers per firing (urf_front.hpp:
-k_front32_cp*, k_front16_cp*, k_front_finish128_cp*; urf_front128.hpp: k_front128_cp*; 128 lasers with urf_set_front_lasers128 on)
+k_front32_cp*, k_front16_cp*, k_front128_cp*, k_front_finish128_cp*; 128 lasers with urf_set_front_lasers128 on)
 through the C ABI: labels and the seven summary fields against oracle B, exact.  What takes them (firing order and row-major, batches
 and the callback path, block borders crossed with and without holes in the halos, rings barely long enough for one window, long
 sweeps, the read-outs of urf_set_front_outputs, sensor models) and what must not (the switch off, modes 1 and 2, curbPoints 9).

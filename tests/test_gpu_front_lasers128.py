@@ -1,4 +1,4 @@
-"""The fused front end for sweeps of 128 lasers per firing (urf_front128.hpp: k_front128 and its siblings, behind
+"""The fused front end for sweeps of 128 lasers per firing (urf_front.hpp: k_front128 and its siblings, behind
 urf_set_front_lasers128), in firing order and row-major: labels and summaries against oracle B on the same input -- on sweeps that
 take it (wide and default region of interest, lasers in any fixed order, the two halves of a firing swapped, partial last tiles, ragged
 batches, 128 tiles), on sweeps that must not take it next to ones that do, with the nine parameter tweaks of
@@ -121,6 +121,38 @@ def test_organised_sweeps_with_holes(seed):
     assert np.array_equal(labels[0], lb), "%d labels differ (fused %d)" % (int((labels[0] != lb).sum()), nf)
     assert {f: int(v) for f, v in zip(KEYS, infos[0][:7])} == {f: ib[f] for f in KEYS}
     assert p.curbPoints == 5 or nf == 0
+
+
+def half_empty(cloud):
+    """No return (NaN) from lasers 0..63 in firings 2 and 3 of every eight, from lasers 64..127 in firing 6, from any laser in firing 12 of
+    every sixteen."""
+    f = np.arange(len(cloud[0]) // L)
+    out = []
+    for a in cloud[:3]:
+        v = a.reshape(-1, L).copy()
+        v[np.isin(f % 8, (2, 3)), :64] = np.nan
+        v[f % 8 == 6, 64:] = np.nan
+        v[f % 16 == 12, :] = np.nan
+        out.append(np.ascontiguousarray(v.reshape(-1)))
+    return tuple(out)
+
+
+@pytest.mark.parametrize("beam", (0, 1))
+@pytest.mark.parametrize("wide", (True, False))
+def test_firings_with_an_empty_half(wide, beam):
+    """A lane marches two lasers, the halves of a firing, and the star-shaped search's bookkeeping crosses them: the firing's sector is its
+    first participant's -- half 0's, or else half 1's -- and a copy's place counts the participants of the half in front.  Firings whose
+    first half, second half or both hold no point at all, at 96 columns (six tiles) and 256."""
+    p = params(wide)
+    p.star_shaped_method = 1
+    p.starbeam_filter = beam
+    scans = [half_empty(u.synth_cloud(L, cols, scene, seed)) for cols in (96, 256) for scene, seed in ((1, 11), (3, 12))]
+    says_something(scans, p, rings=128 if wide else 122)
+    with u.Context(L * 256, len(scans)) as ctx:
+        labels, infos, nf = fused128(ctx, scans, p, ragged=True)
+        print("FUSED empty halves | wide %d beam %d: %d of %d" % (wide, beam, nf, len(scans)))
+        check_against_b(labels, infos, scans, p)
+        assert nf == len(scans)
 
 
 # ---- (e) shape ----

@@ -12,7 +12,7 @@ Then urf_set_front_mode 0 and 2, warm-up, --steps calls between device events: m
 
     timeout 900 python tools/front_lasers_bench.py --lasers128 [--scans 256] [--steps 20] [--warmup 3]
 
-128 lasers per firing (urf_set_front_lasers128, urf_front128.hpp): --scans resident 128 x 2048 and 128 x 1024 sweeps (channels = 128,
+128 lasers per firing (urf_set_front_lasers128, k_front128* in urf_front.hpp): --scans resident 128 x 2048 and 128 x 1024 sweeps (channels = 128,
 interval = 0.05), firing order and row-major, in TWO contexts of one process, both in front mode 2 -- one with the switch on, one with it
 off: the same binary's general kernels, the baseline -- timed interleaved call by call (on, off, on, off, ...), behind a label gate
 against oracle B for both.  Per case: the medians, the 10th / 90th percentiles of either side (the run's own spread) and the median and

@@ -24,7 +24,6 @@
 #include "urf_internal.hpp"
 #include "urf_kernels.hpp"
 #include "urf_front.hpp"
-#include "urf_front128.hpp"
 #include "urf_k_front_outputs.hpp"
 
 #define URF_ASYNC_SLOTS 4
@@ -54,7 +53,7 @@ struct lazy_buf {
  * (kargs_row).  Most arrays have max_batch rows; the two per-call counters (SLOTS: the URF_LIST_COUNT work-list lengths and the
  * ring-count hint) have URF_ASYNC_SLOTS, one per sweep in flight, whatever max_batch is.  urf_create allocates SCANS and SLOTS;
  * CAPTURE comes with the first urf_enable_stage_capture, ROW_MAJOR (the firing-order copies of row-major organised sweeps) once
- * such a sweep has been sighted (rows_state_update), LASERS128 (what the fused front end sizes for 64 lanes, sized for 128: urf_front128.hpp)
+ * such a sweep has been sighted (rows_state_update), LASERS128 (what the fused front end sizes for 64 lanes, sized for 128: urf_front.hpp)
  * with the first urf_set_front_lasers128(ctx, 1).  sstride, max_tiles and front_cand_cap are the context's (scratch_walk). */
 #define URF_SCRATCH_SCANS(X)                                                                                                     \
     X(rx, sstride) X(ry, sstride) X(rz, sstride) X(rec, sstride)                                                                 \
@@ -156,7 +155,7 @@ struct __attribute__((visibility("hidden"))) urf_policy {
      * last_call). */
     int front_mode = 1;
     bool every_batch() const { return front_mode >= 2; }
-    bool lasers128 = false;         /* urf_set_front_lasers128: modes 2 and 3 take sweeps of 128 lasers per firing too (urf_front128.hpp; its scratch is there) */
+    bool lasers128 = false;         /* urf_set_front_lasers128: modes 2 and 3 take sweeps of 128 lasers per firing too (k_front128*, urf_front.hpp; its scratch is there) */
     bool curb_points = false;       /* urf_set_front_curb_points: mode 3 takes curbPoints 1..8 at 16, 32 and (lasers128) 128 lasers per firing too (k_front32_cp*, k_front16_cp*, k_front128_cp*) */
     bool long_sweeps = false;       /* urf_set_front_long_sweeps: modes 2 and 3 take scans of up to URF_FRONT_LONG_MAX_TILES tiles (the finish kernels with more dynamic LDS) */
     uint32_t front_max_tiles() const { return long_sweeps && every_batch() ? URF_FRONT_LONG_MAX_TILES : URF_FRONT_MAX_TILES; }
@@ -1051,7 +1050,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
         stage++;
     };
     mark();
-    const bool l128 = a.front_lsh == 7u;   /* 128 lasers per firing: the kernels of urf_front128.hpp */
+    const bool l128 = a.front_lsh == 7u;   /* 128 lasers per firing: k_front128* and its siblings (urf_front.hpp) */
     if (l128 && a.front) {   /* ... and their candidate lists (URF_FRONT128_CAND_CAP) */
         a.front_cand = a.front_cand128;
         a.front_all = a.front_all128;

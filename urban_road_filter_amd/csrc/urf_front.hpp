@@ -44,11 +44,12 @@
  * urf_front_lay<W128>; the code differs in how the finish adds up a scan's ring points, under `if constexpr`.  k_label_front128 is still a copy
  * of k_label_front (see there: folded, both lose 6 registers and 1 - 2.6 % of their time to the wrapper).
  *
- * ONE march body per lane layout.  urf_front_body<STAR, BEAM, L, CP> is every k_front* of 64, 32 and 16 lasers, urf_front128_body<STAR,
- * BEAM, CP> (urf_front128.hpp: two lasers per lane) every k_front128*; CP = params.curbPoints, 1..8, and 5 -- k_front, k_front32,
- * k_front16, k_front128, the symbols of every front mode -- is an instance like the other seven (URF_FRONT_CP_OTHERS: the fused front
- * modes 3 and urf_set_front_curb_points).  What depends on CP lives in urf_front_window<CP>, shared by both bodies: the 2 CP + 1 heights,
- * the packed firing numbers, the detectors' height tests.  Until this layout the body for 5 was a copy with eleven named registers,
+ * ONE march body.  urf_front_body<STAR, BEAM, L, CP> is every k_front* -- 64, 32 and 16 lasers, one per lane, and 128 (k_front128*,
+ * behind urf_set_front_lasers128), two per lane: the body holds its per-laser state as urf_front_ring<CP> R[NH], NH = 1 or 2 halves of a
+ * firing, and writes down once what else the laser count decides (see there; profiles/front_one_body.md).  CP = params.curbPoints, 1..8, and
+ * 5 -- k_front, k_front32, k_front16, k_front128, the symbols of every front mode -- is an instance like the other seven
+ * (URF_FRONT_CP_OTHERS: the fused front modes 3 and urf_set_front_curb_points).  What depends on CP lives in urf_front_window<CP>: the 2 CP + 1
+ * heights, the packed firing numbers, the detectors' height tests.  Until that layout the body for 5 was a copy with eleven named registers,
  * because "with CP as a parameter" k_front had come out with 96 registers and a spill.  The parameter was not the cause: named scalars,
  * arrays and a struct of arrays give the same code.  The cause is the few lines of the block-end tail (URF_FRONT_TAIL_CALLS), which tip the
  * register allocation of the whole function one way or the other; tests/test_kernel_resources.py and its siblings hold every instance to
@@ -81,13 +82,26 @@
 #define URF_FRONT_MAX_TILES 128u  /* k_front_finish keeps a presence word per (tile, lane) in LDS */
 #define URF_FRONT_RING_NONE 0x7fu  /* ring field of an input-order record */
 #define URF_FRONT_ST_WORDS 72u   /* k_front_finish part 1 -> part 2: 64 list lengths, 4 quadrant values, the length of the list of marks, two counts */
-/* ... and of the 128-laser family (urf_front128.hpp), whose arrays are the siblings sized for 128 (urf_kargs::*128) */
+/* ... and of the 128-laser family (urf_set_front_lasers128), whose arrays are the siblings sized for 128 (urf_kargs::*128), allocated when
+ * the switch is turned on.  What these kernels leave behind keeps the layout its readers know, indexed by f * 128 + l: region-of-interest bits
+ * (two 64-bit words per firing), slots (stp * 128 + l < 2048), tsoff, candidate indices.  A tile is 16 firings and a presence word 32 of
+ * them: word (f >> 5) * 128 + l covers two tiles, so the words per scan are counted for an even number of tiles (URF_FRONT128_TILES2), and a
+ * block of the march holds an even number of tiles (front_tpb, urf_api.hip) -- no presence word is shared between two blocks. */
 #define URF_FRONT128_L 128u
 #define URF_FRONT128_LSH 7u
 #define URF_FRONT128_RING_MASK 0xffu   /* ring field of an input-order record of these kernels: table entry 127 is a ring, 0xff is "none" */
 #define URF_FRONT128_RING_NONE 0xffu
 #define URF_FRONT128_TILES2(tiles) (((tiles) + 1u) & ~1u)   /* a presence word covers 32 firings, two tiles of 128 lasers: words and block maxima are counted for an even number */
 #define URF_FRONT128_ST_WORDS 136u     /* k_front_finish128 part 1 -> part 2: 128 list lengths, 4 quadrant values, list length, two counts */
+/* Entries per scan of the candidate lists of these kernels.  The points that pass the march's height tests are counted per LASER, not per
+ * column: a ring that crosses a curb hands on up to eleven centres (z_zero) and six marked points (x_zero) per crossing, a street has four
+ * crossings per ring -- 128 x 68 = 8 704 for 128 lasers however short the sweep is (a 128 x 256 street of urf_synth_cloud: 5 200 - 5 600),
+ * above the context's max(max_points / 8, 4096) for sweeps below 128 x 544.  Twice that for range noise; a list that overflows still only
+ * hands its scan back.
+ * curbPoints 1..8 (urf_set_front_curb_points): 2 * CP + 1 centres and CP + 1 marked points per crossing, at 8 that is 17 and 9 -- 4 x 26 = 104 per
+ * laser: 128 x 104 = 13 312 here, below the cap as it is; 32 x 104 = 3 328 and 16 x 104 = 1 664 at 32 and 16 lasers, below the context's floor of
+ * 4096 (a block's border adds at most 2 * CP edge items per laser: 16 more per block).  No cap grows for the new instances. */
+#define URF_FRONT128_CAND_CAP(max_points) ((max_points) / 8u > 16384u ? (max_points) / 8u : 16384u)
 /* candidate kinds */
 #define URF_FC_XZ 1u       /* passed x_zero's height tests as the marked point: angle test pending */
 #define URF_FC_ZZ 2u       /* passed z_zero's as the centre */
@@ -170,19 +184,23 @@ struct urf_front_lay {
             return a.tiles;
     }
     /* the scan's presence words: word (f >> 5) * L + l */
-    static __device__ __forceinline__ const uint32_t* pres(const urf_kargs& a, unsigned s)
+    static __device__ __forceinline__ uint32_t* pres(const urf_kargs& a, unsigned s)
     {
         return (W128 ? a.front_pres128 : a.front_pres) + (size_t)s * tiles(a) * 64u;
     }
-    /* the largest x * x + y * y of laser slot `l` in block `b` of the march */
-    static __device__ __forceinline__ unsigned long long maxs(const urf_kargs& a, unsigned s, unsigned b, unsigned l)
+    /* the largest x * x + y * y of every laser slot in block `b` of the march: NL values, written there, read by the finish */
+    static __device__ __forceinline__ unsigned long long* maxs_of_block(const urf_kargs& a, unsigned s, unsigned b)
     {
         if constexpr (W128)
-            return a.front_maxs128[(size_t)s * tiles(a) * 64u + (size_t)b * NL + l];
+            return a.front_maxs128 + (size_t)s * tiles(a) * 64u + (size_t)b * NL;
         else
-            return a.front_maxs[((size_t)s * a.tiles + b) * 64u + l];
+            return a.front_maxs + ((size_t)s * a.tiles + b) * 64u;
     }
-    static __device__ __forceinline__ const uint32_t* lane_ring(const urf_kargs& a, unsigned s)
+    static __device__ __forceinline__ unsigned long long maxs(const urf_kargs& a, unsigned s, unsigned b, unsigned l)
+    {
+        return maxs_of_block(a, s, b)[l];
+    }
+    static __device__ __forceinline__ uint32_t* lane_ring(const urf_kargs& a, unsigned s)
     {
         return (W128 ? a.front_lane_ring128 : a.front_lane_ring) + (size_t)s * NL;
     }
@@ -344,8 +362,7 @@ __device__ __forceinline__ void urf_front_push(urf_u2* cbuf, unsigned& ncb, bool
     ncb += (unsigned)__popcll(m);
 }
 
-/* The window of one laser, for both marches (urf_front_body: one per lane; urf_front128_body, urf_front128.hpp: two).  CP =
- * params.curbPoints, H = CP / 2.  It holds the laser's last 2 * CP + 1 ring points, w[2 * CP] the newest: z_zero's centre is w[CP] (CP points
+/* The window of one laser (urf_front_body: one per lane, two at 128 lasers).  CP = params.curbPoints, H = CP / 2.  It holds the laser's last 2 * CP + 1 ring points, w[2 * CP] the newest: z_zero's centre is w[CP] (CP points
  * on either side, z_zero_method.cpp:21-50), x_zero's triple (j, j + H, j + CP) is (w[CP], w[CP + H], w[2 * CP]) and the point it marks the
  * one CP - H back (x_zero_method.cpp:30-34; CP == 1: the triple is (j, j, j + 1)).  Both loops start at j = CP: a decision needs the FULL
  * window.  fw[] keeps the firing numbers (relative to the march's first firing) of the newest CP + 1 points, 16 bits each, the newest in
@@ -420,7 +437,7 @@ struct urf_front_window {
     __device__ __forceinline__ unsigned marked_firing() const { return firing(CP - H); }
 };
 
-/* The block-end tail of both marches: tail(CP - 1), ..., tail(0), each index a std::integral_constant, written out as calls of a NAMED
+/* The block-end tail of the march: tail(CP - 1), ..., tail(0), each index a std::integral_constant, written out as calls of a NAMED
  * lambda.  The form of these few lines decides the code of the WHOLE march at curbPoints 5 and 64 / 32 / 16 lanes: as a `#pragma unroll`
  * loop (over an array of firing numbers taken out of fw[] first, or over firing(back)), or handed to a helper template that does the
  * counting, k_front comes out with 96 registers, a 16-byte spill and 380 more v_mov_b32; like this with 92 and none.
@@ -435,19 +452,44 @@ struct urf_front_window {
     if constexpr ((CP) >= 2u) tail(std::integral_constant<unsigned, 1u>{});    \
     tail(std::integral_constant<unsigned, 0u>{});
 
-/* The march.  L = the lasers of a firing (params.channels: 64, 32, 16).  Point f * L + l is laser slot l of firing f: everything the march leaves behind
- * -- records, region-of-interest bits, the sector-sorted copies and their slots, candidate indices -- is indexed by the point's place in
+/* what the march keeps per laser.  (Keep the members' order: it decides a spill at 128 lasers, profiles/front_one_march.md) */
+template <unsigned CP>
+struct urf_front_ring {
+    unsigned E;          /* the table entry this laser's points are expected on */
+    bool econf;          /* ... and a point of this march has confirmed it */
+    urf_front_thr th;
+    urf_front_window<CP> win;   /* its last 2 * CP + 1 ring points, firings relative to Fs */
+    double maxs;         /* largest x*x + y*y among its ring points of the block (maxDistance, lidar_segmentation.cpp:271-274) */
+    unsigned pw;         /* presence bits of the 32 firings at hand */
+};
+
+/* The march.  L = the lasers of a firing (params.channels: 128, 64, 32, 16).  Point f * L + l is laser slot l of firing f: everything the march leaves
+ * behind -- records, region-of-interest bits, the sector-sorted copies and their slots, candidate indices -- is indexed by the point's place in
  * the input, a tile is URF_TILE points = URF_TILE / L firings, and k_index and the star-shaped search read a scan of any L alike.  Only
- * the presence words count in firings: word (f >> 5) * L + l.  For L < 64 the lanes from L on are idle (no point, never in the region of
- * interest): one march per wave, the chain of a block URF_TILE / L steps per tile.  CP = params.curbPoints, 1..8: 5 is an instance like
- * the others (urf_front_window). */
+ * the presence words count in firings: word (f >> 5) * L + l.  CP = params.curbPoints, 1..8: 5 is an instance like the others
+ * (urf_front_window).
+ *
+ * ONE wave per block, whatever L is, and a lane marches NH lasers: laser h * 64 + lane for h < NH, the HALVES of a firing.  For L < 64 the
+ * lanes from L on are idle (no point, never in the region of interest): one march per wave, the chain of a block URF_TILE / L steps per tile.
+ * For L = 128 a firing is two wave-widths, NH = 2: lane j marches lasers j and j + 64, with two windows and two sets of per-ring state
+ * (R[NH]).  The two halves of a firing are worked off back to back inside one step, so that everything that crosses lanes -- the slot rank
+ * of a star participant, the one-sector test, the step's key and count -- spans the 128 lasers in input order with two ballots and no LDS
+ * traffic or barrier, and the candidate buffer stays "the workgroup is the wave".  The price is registers.  Every
+ * array of NH below is indexed by constants only (the loops over h are unrolled): registers, and for NH = 1 the code of scalars.
+ *
+ * What the laser count decides besides NH is named here once: the arrays sized for 64 or for 128 lanes and the record's "on no ring"
+ * (urf_front_lay<(L > 64)>), the width of a firing's region-of-interest word (step), which half the first star participant comes from and
+ * how many there are in front of a half (step), how many registers hold a tile's steps (NK). */
 template <bool STAR, bool BEAM, unsigned L, unsigned CP>
 __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
 {
+    static_assert(L == 128u || L == 64u || L == 32u || L == 16u, "a firing fills two waves, the wave, half of it or a quarter");
+    using LAY = urf_front_lay<(L > 64u)>;
+    constexpr unsigned NH = L > 64u ? 2u : 1u;    /* halves of a firing: lasers per lane */
     const unsigned s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
     unsigned off, len;
     urf_scan_range(a, s, off, len);
-    const unsigned TPB = a.front_tpb;
+    const unsigned TPB = a.front_tpb;   /* (128 lasers: even, urf_api.hip -- no presence word is shared between two blocks) */
     const unsigned t_first = b * TPB;
     if (t_first * URF_TILE >= len)
         return;
@@ -456,7 +498,7 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
         return;
     constexpr unsigned C = L;                     /* table entries per scan: params.channels */
     constexpr unsigned STEPS = URF_TILE / L;      /* firings per tile */
-    static_assert(L == 64u || L == 32u || L == 16u, "a firing fills the wave, half of it or a quarter");
+    constexpr unsigned W = STEPS < 64u ? STEPS : 64u, NK = STEPS / W;   /* a tile's steps: NK registers, W lanes of each */
     constexpr unsigned H = urf_front_window<CP>::H, HPRE = urf_front_window<CP>::HPRE;
     const unsigned K = (unsigned)dp.p.sectors;
     const unsigned nf = (len + L - 1u) / L;                                 /* firings of the scan */
@@ -480,249 +522,278 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
     const float* const tab = a.angle + (size_t)s * dp.p.channels;
     const float curbH = dp.p.curbHeight;
     const bool use_x = dp.p.x_zero_method != 0, use_z = dp.p.z_zero_method != 0;
+    const bool mine = L >= 64u || lane < L;   /* this lane has a laser */
+    const unsigned mylen = mine ? len : 0u;   /* ... and to a lane that has none the scan is empty: one compare where a point is looked at */
 
-    unsigned E = lane;        /* the table entry this lane's points are expected on */
-    bool econf = false;       /* ... and a point of this march has confirmed it */
-    urf_front_thr th = urf_front_load_thr(a, s, C, E, nR);
+    urf_front_ring<CP> R[NH];
+#pragma unroll
+    for (unsigned h = 0; h < NH; h++) {
+        R[h].E = h * 64u + lane;
+        R[h].econf = false;
+        R[h].th = urf_front_load_thr(a, s, C, R[h].E, nR);
+        R[h].win.clear();
+        R[h].maxs = 0.0;
+        R[h].pw = 0u;
+    }
     bool failed = false, overflow = false;
     unsigned long long failed_m = 0;   /* ... what the hot path finds wrong, as lane masks (wave-uniform) */
-    unsigned ncb = 0;         /* candidates in the wave's buffer */
-
-    urf_front_window<CP> win;              /* the lane's last 2 * CP + 1 ring points, firings relative to Fs */
-    win.clear();
-    double maxs = 0.0;                     /* largest x*x + y*y among the lane's ring points of the block (maxDistance, lidar_segmentation.cpp:271-274) */
-    unsigned pw = 0;                       /* presence bits of the tile at hand */
+    unsigned ncb = 0;                  /* candidates in the wave's buffer */
     /* per tile (wave-uniform) */
     unsigned troi = 0, tstar = 0;
-    int stepkey_v = (int)URF_SEC_NONE, stepcnt_v = 0;   /* lane j: sector / participating points of step j of the tile */
-    int stepkey_w = (int)URF_SEC_NONE, stepcnt_w = 0;   /* (L = 16, 128 steps per tile) ... of step 64 + j */
+    int stepkey_v[NK], stepcnt_v[NK];   /* register q, lane j < W: sector / participating points of step q * 64 + j of the tile */
+#pragma unroll
+    for (unsigned q = 0; q < NK; q++) {
+        stepkey_v[q] = (int)URF_SEC_NONE;
+        stepcnt_v[q] = 0;
+    }
 
     /* one firing.  PH 0: the halo in front of the block (windows fill), 1: the block, 2: the halo behind it (windows complete) */
-    auto step = [&](auto ph, const unsigned f, const float x, const float y, const float z) {
+    auto step = [&](auto ph, const unsigned f, const float (&X)[NH], const float (&Y)[NH], const float (&Z)[NH]) {
         constexpr unsigned PH = decltype(ph)::value;
         const unsigned stp = f % STEPS;
-        const unsigned i = f * L + lane;
-        const bool roi = (L == 64u || lane < L) && i < len && urf_in_roi(dp.p, x, y, z);
-        const unsigned long long roim = __ballot(roi);
-        if (PH == 1u && lane == 0u) {   /* bit i of the scan's words: input point i */
-            if (L == 64u)
-                a.roi_bits[((size_t)s * a.tiles + f / STEPS) * STEPS + stp] = roim;
-            else if (L == 32u)
-                ((uint32_t*)(a.roi_bits + (size_t)s * a.tiles * (URF_TILE / 64u)))[f] = (uint32_t)roim;
-            else
-                ((uint16_t*)(a.roi_bits + (size_t)s * a.tiles * (URF_TILE / 64u)))[f] = (uint16_t)roim;
+        bool roi[NH], on[NH];
+        unsigned long long roim[NH], roi_any = 0ull;
+#pragma unroll
+        for (unsigned h = 0; h < NH; h++) {
+            roi[h] = f * L + h * 64u + lane < mylen && urf_in_roi(dp.p, X[h], Y[h], Z[h]);
+            roim[h] = __ballot(roi[h]);
+            roi_any |= roim[h];
         }
-        if (roim == 0ull)
+        if (PH == 1u && lane < NH) {   /* bit i of the scan's words: input point i.  A firing is ... */
+            if constexpr (NH > 1u) {         /* ... two 64-bit words, written by two lanes */
+                a.roi_bits[((size_t)s * a.tiles + f / STEPS) * (URF_TILE / 64u) + stp * NH + lane] = lane ? roim[NH - 1u] : roim[0];
+            } else if constexpr (L == 64u) {   /* ... one */
+                a.roi_bits[((size_t)s * a.tiles + f / STEPS) * (URF_TILE / 64u) + stp] = roim[0];
+            } else {                         /* ... half or a quarter of one */
+                using word_t = std::conditional_t<L == 32u, uint32_t, uint16_t>;
+                ((word_t*)(a.roi_bits + (size_t)s * a.tiles * (URF_TILE / 64u)))[f] = (word_t)roim[0];
+            }
+        }
+        if (roi_any == 0ull)
             return;   /* (uniform) nothing of this firing lies in the region of interest */
-        const float rho2 = x * x + y * y;
-        const float u = -z * __builtin_amdgcn_rsqf(rho2);   /* urf_fast_cot */
-        const bool fast = (rho2 >= URF_FAST_MIN2) & (rho2 <= URF_FAST_MAX2) & (__builtin_fabsf(u) <= URF_LUT_UMAX) & roi;
-        const bool on_f = fast & (u >= th.y) & (u <= th.z) & (u < th.below);
-        float fi = 0.f;
-        int fs = -1;
-        if (PH == 1u) {
-            fi = urf_fast_polar(x, y);
-            if (STAR)
-                fs = fast ? urf_fast_sector_ranged(fi, dp.Kfi, K, dp.sector_margin) : -1;
-        }
-        bool on = on_f;
-        const bool open = roi && !(on_f && (PH != 1u || !STAR || fs >= 0));
-        /* (r6, vector-issue diet: a ballot of anything but a direct compare costs two vector instructions -- v_cndmask 0 / 1, v_cmp -- to
-         * mask it with exec; a plain divergent branch skips its block when no lane takes it for two SCALAR instructions.  Wave-level
-         * flags (failed, overflow) are OR-ed up as masks, per-lane state that only rare paths read (econf) likewise.) */
-        if (open) {   /* rare: the reference's exact sequence for the lanes that need it */
-            const unsigned r = urf_front_open(tab, nR, dp.p.interval, x, y, z, (PH == 1u && STAR) ? K : 0u, dp.Kfi, E, econf ? 1u : 0u);
-            on = (r & 1u) != 0u;
-            fs = (int)((r >> 1) & 0x7ffu) - 1;
-            if (r & URF_FO_FAIL)
-                failed = true;
-            if (PH == 1u && (r & URF_FO_NONE) && i >= upto)
-                a.table_redo[s] = 1u;   /* the speculative ring table is incomplete (k_table_repair, legacy path) */
-            if (r & URF_FO_ADOPT) {   /* this lane's laser sits on another table entry: learned from its first point */
-                E = (r >> 12) & 0x7fu;
-                th = urf_front_load_thr(a, s, C, E, nR);
-            }
-        }
-        if (PH == 1u) {
-            /* the record, input order: ring | azimuth code (URF_REC_*; detector hits are OR-ed in by k_front_finish) */
-            const unsigned azc_v = urf_az_code(urf_fast_azimuth_of(fi));   /* (unconditionally, then a select: a branch around eight instructions costs more) */
-            const unsigned azc = urf_fast_az_ok(x, y) ? azc_v : URF_REC_AZ_UNKNOWN;
-            __builtin_amdgcn_raw_buffer_store_b32((azc << URF_REC_AZ_SHIFT) | (on ? E : URF_FRONT_RING_NONE), brec, (L == 64u || lane < L) ? i * 4u : URF_OOB, 0, URF_FRONT_NT);
-            if (STAR) {
-                /* star-shaped search: the firing's participants share one sector */
-                unsigned sk = (unsigned)fs;
-                if (BEAM && roi && !urf_in_beam(a.beams[fs < 0 ? 0 : fs], x, y))
-                    sk = URF_SEC_NONE;
-                /* (every lane is active here: the masks of direct compares need no exec) */
-                const unsigned long long psm = roim & __builtin_amdgcn_ballot_w64(sk != URF_SEC_NONE) & __builtin_amdgcn_ballot_w64((int)sk >= 0);
-                const bool ons = roi && sk != URF_SEC_NONE && (int)sk >= 0;
-                const unsigned src = psm ? (unsigned)__ffsll((long long)psm) - 1u : 0u;
-                const unsigned f0 = psm ? (unsigned)__builtin_amdgcn_readlane((int)sk, (int)src) : URF_SEC_NONE;
-                failed_m |= psm & __builtin_amdgcn_ballot_w64(sk != f0);
-                const unsigned so = (f / STEPS) * URF_TILE + tstar + urf_popc_below(psm);
-                const unsigned o4 = ons ? so * 4u : URF_OOB;
-                const float pr = urf_sqrt_rn_normal(rho2);   /* star_shaped_search.cpp:164: sqrtf(x * x + y * y) */
-                failed_m |= psm & ~(__builtin_amdgcn_ballot_w64(rho2 >= 0x1p-90f) & __builtin_amdgcn_ballot_w64(rho2 <= 0x1p126f));   /* (outside the shortcut's interval: the legacy kernels) */
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pr), bsr, o4, 0, URF_FRONT_NT);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(z), bsz, o4, 0, URF_FRONT_NT);
-                __builtin_amdgcn_raw_buffer_store_b16((short)((stp * L + lane) | (on ? 0u : URF_SLOT_OFF)), bss, ons ? so * 2u : URF_OOB, 0, URF_FRONT_NT);
-                if (STEPS <= 64u || stp < 64u) {   /* (uniform) */
-                    stepkey_v = lane == stp ? (int)f0 : stepkey_v;
-                    stepcnt_v = lane == stp ? (int)__popcll(psm) : stepcnt_v;
-                } else {
-                    stepkey_w = lane == stp - 64u ? (int)f0 : stepkey_w;
-                    stepcnt_w = lane == stp - 64u ? (int)__popcll(psm) : stepcnt_w;
-                }
-                tstar += (unsigned)__popcll(psm);
-            }
-            troi += (unsigned)__popcll(roim);
-        }
-        /* the lane's window moves on by its new ring point; what has become decidable is decided */
-        if (on) {
+        float rho2[NH], fi[NH];
+        unsigned sk[NH];
+        bool ons[NH];
+        unsigned long long psm[NH];
+#pragma unroll
+        for (unsigned h = 0; h < NH; h++) {
+            urf_front_ring<CP>& r = R[h];
+            const float x = X[h], y = Y[h], z = Z[h];
+            const unsigned i = f * L + h * 64u + lane;
+            rho2[h] = x * x + y * y;
+            const float u = -z * __builtin_amdgcn_rsqf(rho2[h]);   /* urf_fast_cot */
+            const bool fast = (rho2[h] >= URF_FAST_MIN2) & (rho2[h] <= URF_FAST_MAX2) & (__builtin_fabsf(u) <= URF_LUT_UMAX) & roi[h];
+            const bool on_f = fast & (u >= r.th.y) & (u <= r.th.z) & (u < r.th.below);
+            fi[h] = 0.f;
+            int fs = -1;
             if (PH == 1u) {
-                const double s2 = (double)x * (double)x + (double)y * (double)y;
-                maxs = s2 > maxs ? s2 : maxs;
-                pw |= 1u << (f & 31u);
+                fi[h] = urf_fast_polar(x, y);
+                if (STAR)
+                    fs = fast ? urf_fast_sector_ranged(fi[h], dp.Kfi, K, dp.sector_margin) : -1;
             }
-            econf = true;
-            win.template push<PH>(z, f - Fs);
+            on[h] = on_f;
+            const bool open = roi[h] && !(on_f && (PH != 1u || !STAR || fs >= 0));
+            /* (r6, vector-issue diet: a ballot of anything but a direct compare costs two vector instructions -- v_cndmask 0 / 1, v_cmp -- to
+             * mask it with exec; a plain divergent branch skips its block when no lane takes it for two SCALAR instructions.  Wave-level
+             * flags (failed, overflow) are OR-ed up as masks, per-lane state that only rare paths read (econf) likewise.) */
+            if (open) {   /* rare: the reference's exact sequence for the lanes that need it */
+                const unsigned o = urf_front_open(tab, nR, dp.p.interval, x, y, z, (PH == 1u && STAR) ? K : 0u, dp.Kfi, r.E, r.econf ? 1u : 0u);
+                on[h] = (o & 1u) != 0u;
+                fs = (int)((o >> 1) & 0x7ffu) - 1;
+                if (o & URF_FO_FAIL)
+                    failed = true;
+                if (PH == 1u && (o & URF_FO_NONE) && i >= upto)
+                    a.table_redo[s] = 1u;   /* the speculative ring table is incomplete (k_table_repair, legacy path) */
+                if (o & URF_FO_ADOPT) {   /* this laser sits on another table entry: learned from its first point */
+                    r.E = (o >> 12) & 0x7fu;
+                    r.th = urf_front_load_thr(a, s, C, r.E, nR);
+                }
+            }
+            sk[h] = (unsigned)fs;
+            ons[h] = false;
+            psm[h] = 0ull;
+            if (PH == 1u) {
+                /* the record, input order: ring | azimuth code (URF_REC_*; detector hits are OR-ed in by k_front_finish) */
+                const unsigned azc_v = urf_az_code(urf_fast_azimuth_of(fi[h]));   /* (unconditionally, then a select: a branch around eight instructions costs more) */
+                const unsigned azc = urf_fast_az_ok(x, y) ? azc_v : URF_REC_AZ_UNKNOWN;
+                __builtin_amdgcn_raw_buffer_store_b32((azc << URF_REC_AZ_SHIFT) | (on[h] ? r.E : LAY::RING_NONE), brec, mine ? i * 4u : URF_OOB, 0, URF_FRONT_NT);
+                if (STAR) {
+                    if (BEAM && roi[h] && !urf_in_beam(a.beams[fs < 0 ? 0 : fs], x, y))
+                        sk[h] = URF_SEC_NONE;
+                    /* (every lane is active here: the masks of direct compares need no exec) */
+                    psm[h] = roim[h] & __builtin_amdgcn_ballot_w64(sk[h] != URF_SEC_NONE) & __builtin_amdgcn_ballot_w64((int)sk[h] >= 0);
+                    ons[h] = roi[h] && sk[h] != URF_SEC_NONE && (int)sk[h] >= 0;
+                    /* (outside the interval of urf_sqrt_rn_normal's shortcut: the legacy kernels) */
+                    failed_m |= psm[h] & ~(__builtin_amdgcn_ballot_w64(rho2[h] >= 0x1p-90f) & __builtin_amdgcn_ballot_w64(rho2[h] <= 0x1p126f));
+                }
+            }
         }
-        if (PH == 0u)
-            return;
-        /* (straight-line: every lane computes, the lanes without a new point are masked out at the end -- branches around the
-         * tests put the four results through registers and selects) */
-        const bool full = win.full();
-        const bool c_in = win.c_in(on), p_in = win.p_in(on);
-        const bool hz = win.hz(curbH), hx = win.hx(curbH);
-        /* (lane masks combined as masks: `&` on bools mixed with the wave-uniform switches went through 0 / 1 integers in vector
-         * registers -- v_cndmask, v_and, v_cmp per term) */
-        bool zz = false, xz = false, ez = false, ex = false;
-        /* a window that began inside this march (a block border with a hole in the halo, a ring that has just entered the
-         * region of interest): positions unknown here, k_front_finish decides */
-        if (use_z) {   /* (uniform) */
-            zz = c_in && full && hz;
-            if (!from_start)
-                ez = c_in && !full;
+        if (PH == 1u) {
+            if (STAR) {
+                /* star-shaped search: the firing's participants -- of every half -- share one sector, the first participant's (half 0's, or
+                 * else half 1's), and their copies follow each other in input order: half 0's, then half 1's */
+                unsigned f0 = URF_SEC_NONE;
+#pragma unroll
+                for (unsigned h = NH; h-- > 0u;) {
+                    const unsigned src = psm[h] ? (unsigned)__ffsll((long long)psm[h]) - 1u : 0u;
+                    f0 = psm[h] ? (unsigned)__builtin_amdgcn_readlane((int)sk[h], (int)src) : f0;
+                }
+                unsigned np = 0;   /* participants of the halves in front */
+#pragma unroll
+                for (unsigned h = 0; h < NH; h++) {
+                    failed_m |= psm[h] & __builtin_amdgcn_ballot_w64(sk[h] != f0);
+                    const unsigned so = (f / STEPS) * URF_TILE + tstar + np + urf_popc_below(psm[h]);
+                    const unsigned o4 = ons[h] ? so * 4u : URF_OOB;
+                    const float pr = urf_sqrt_rn_normal(rho2[h]);   /* star_shaped_search.cpp:164: sqrtf(x * x + y * y) */
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pr), bsr, o4, 0, URF_FRONT_NT);
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(Z[h]), bsz, o4, 0, URF_FRONT_NT);
+                    __builtin_amdgcn_raw_buffer_store_b16((short)((stp * L + h * 64u + lane) | (on[h] ? 0u : URF_SLOT_OFF)), bss, ons[h] ? so * 2u : URF_OOB, 0,
+                                                          URF_FRONT_NT);
+                    np += (unsigned)__popcll(psm[h]);
+                }
+#pragma unroll
+                for (unsigned q = 0; q < NK; q++) {
+                    if (NK == 1u || stp / 64u == q) {   /* (uniform) */
+                        stepkey_v[q] = lane == stp - q * 64u ? (int)f0 : stepkey_v[q];
+                        stepcnt_v[q] = lane == stp - q * 64u ? (int)np : stepcnt_v[q];
+                    }
+                }
+                tstar += np;
+            }
+#pragma unroll
+            for (unsigned h = 0; h < NH; h++)
+                troi += (unsigned)__popcll(roim[h]);
         }
-        if (use_x) {
-            xz = p_in && full && hx;
-            if (!from_start)
-                ex = p_in && !full;
-        }
-        if (__ballot(zz | xz | ez | ex) != 0ull) {   /* (uniform) */
-            urf_front_push(cbuf, ncb, zz | ez, (win.centre_firing() + Fs) * L + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
-            urf_front_push(cbuf, ncb, xz | ex, (win.marked_firing() + Fs) * L + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
-            if (ncb > URF_FRONT_CBUF - 128u)
-                urf_front_flush(a, s, cbuf, ncb, overflow);
+        /* the lasers' windows move on by their new ring points; what has become decidable is decided */
+#pragma unroll
+        for (unsigned h = 0; h < NH; h++) {
+            urf_front_ring<CP>& r = R[h];
+            if (on[h]) {
+                if (PH == 1u) {
+                    const double s2 = (double)X[h] * (double)X[h] + (double)Y[h] * (double)Y[h];
+                    r.maxs = s2 > r.maxs ? s2 : r.maxs;
+                    r.pw |= 1u << (f & 31u);
+                }
+                r.econf = true;
+                r.win.template push<PH>(Z[h], f - Fs);
+            }
+            if (PH == 0u)
+                continue;
+            /* (straight-line: every lane computes, the lanes without a new point are masked out at the end -- branches around the
+             * tests put the four results through registers and selects) */
+            const bool full = r.win.full();
+            const bool c_in = r.win.c_in(on[h]), p_in = r.win.p_in(on[h]);
+            const bool hz = r.win.hz(curbH), hx = r.win.hx(curbH);
+            /* (lane masks combined as masks: `&` on bools mixed with the wave-uniform switches went through 0 / 1 integers in vector
+             * registers -- v_cndmask, v_and, v_cmp per term) */
+            bool zz = false, xz = false, ez = false, ex = false;
+            /* a window that began inside this march (a block border with a hole in the halo, a ring that has just entered the
+             * region of interest): positions unknown here, k_front_finish decides */
+            if (use_z) {   /* (uniform) */
+                zz = c_in && full && hz;
+                if (!from_start)
+                    ez = c_in && !full;
+            }
+            if (use_x) {
+                xz = p_in && full && hx;
+                if (!from_start)
+                    ex = p_in && !full;
+            }
+            if (__ballot(zz | xz | ez | ex) != 0ull) {   /* (uniform) */
+                urf_front_push(cbuf, ncb, zz | ez, (r.win.centre_firing() + Fs) * L + h * 64u + lane, zz ? URF_FC_ZZ : URF_FC_EDGE_Z);
+                urf_front_push(cbuf, ncb, xz | ex, (r.win.marked_firing() + Fs) * L + h * 64u + lane, xz ? URF_FC_XZ : URF_FC_EDGE_X);
+                if (ncb > URF_FRONT_CBUF - 128u)
+                    urf_front_flush(a, s, cbuf, ncb, overflow);
+            }
         }
     };
-    /* the presence words of 32 firings (L = 64: the tile's, tile_end) */
+    /* the presence words of 32 firings (64 lasers: a tile; 128: two) */
     auto pres_end = [&](const unsigned pt) {
-        if (lane < L)
-            a.front_pres[(size_t)s * a.tiles * 64u + (size_t)pt * L + lane] = pw;
-        pw = 0;
+#pragma unroll
+        for (unsigned h = 0; h < NH; h++) {
+            if (mine)
+                LAY::pres(a, s)[(size_t)pt * L + h * 64u + lane] = R[h].pw;
+            R[h].pw = 0;
+        }
     };
     auto tile_end = [&](const unsigned t) {
         const size_t row = (size_t)s * a.tiles + t;
-        if (L == 64u) {
-            a.front_pres[row * 64u + lane] = pw;
-            pw = 0;
-        }
         if (lane == 0)
             a.tile_roi[row] = troi;
-        if (STAR && STEPS > 32u) {
-            /* the same construction as below over 64 or 128 steps: a register per 64 of them, the running values carried from one to the
-             * next */
-            constexpr unsigned NH = STEPS > 64u ? 2u : 1u;
-            unsigned fk[NH], sbase_h[NH];
+        if (STAR) {
+            /* sector k starts with the first step whose sector is >= k (urf_split_holey's construction: the steps' keys with the empty
+             * steps filled in from the left must not fall; bisection over them).  A register per 64 steps, the running values carried from
+             * one to the next */
+            unsigned fk[NK], sbase_q[NK];
             unsigned carry = 0, total = 0;
 #pragma unroll
-            for (unsigned h = 0; h < NH; h++) {
-                const unsigned key = (unsigned)(h ? stepkey_w : stepkey_v), sc = (unsigned)(h ? stepcnt_w : stepcnt_v);
-                const unsigned k1 = key != URF_SEC_NONE ? key + 1u : 0u;
+            for (unsigned q = 0; q < NK; q++) {
+                const bool held = W == 64u || lane < W;   /* this lane holds a step */
+                const unsigned k1 = (held && (unsigned)stepkey_v[q] != URF_SEC_NONE) ? (unsigned)stepkey_v[q] + 1u : 0u;
                 unsigned m = urf_wave_scan_max(k1);
                 m = m > carry ? m : carry;
                 unsigned exc = (unsigned)__shfl_up((int)m, 1);
                 exc = lane == 0 ? carry : exc;
                 if (__ballot(k1 != 0u && k1 < exc) != 0ull)
-                    failed = true;   /* (uniform) the sectors fall inside the tile */
-                fk[h] = m;
+                    failed = true;   /* (uniform) the sectors fall inside the tile (the sweep's seam, an unorganised cloud) */
+                fk[q] = m;
                 carry = (unsigned)__builtin_amdgcn_readlane((int)m, 63);
+                const unsigned sc = held ? (unsigned)stepcnt_v[q] : 0u;
                 const unsigned sinc = urf_wave_scan_add(sc) + total;
-                sbase_h[h] = sinc - sc;
+                sbase_q[q] = sinc - sc;   /* lane j: participating points of the steps in front of step q * 64 + j; W < 64: lane W holds the tile's total */
                 total = (unsigned)__builtin_amdgcn_readlane((int)sinc, 63);
             }
             for (unsigned k0 = 0; k0 <= K; k0 += 64u) {
                 const unsigned k = k0 + lane;
                 unsigned cnt = 0;   /* number of steps whose filled-in key + 1 is < k + 1 (the keys do not fall: a count per register adds up) */
 #pragma unroll
-                for (unsigned h = 0; h < NH; h++) {
+                for (unsigned q = 0; q < NK; q++) {
                     unsigned lo = 0;
 #pragma unroll
-                    for (unsigned st = 32u; st > 0; st >>= 1) {
-                        const unsigned v = (unsigned)__shfl((int)fk[h], (int)(lo + st - 1u));
+                    for (unsigned st = W / 2u; st > 0; st >>= 1) {
+                        const unsigned v = (unsigned)__shfl((int)fk[q], (int)(lo + st - 1u));
                         lo += v < k + 1u ? st : 0u;
                     }
-                    const unsigned v = (unsigned)__shfl((int)fk[h], (int)lo);
-                    lo += (lo == 63u && v < k + 1u) ? 1u : 0u;
+                    const unsigned v = (unsigned)__shfl((int)fk[q], (int)lo);
+                    lo += (lo == W - 1u && v < k + 1u) ? 1u : 0u;
                     cnt += lo;
                 }
-                unsigned so = total;
+                unsigned so;
+                if constexpr (W < 64u) {
+                    so = (unsigned)__shfl((int)sbase_q[0], (int)cnt);   /* (lane W holds the tile's total) */
+                } else {
+                    so = total;
 #pragma unroll
-                for (unsigned h = 0; h < NH; h++) {
-                    const unsigned v = (unsigned)__shfl((int)sbase_h[h], (int)(cnt & 63u));
-                    so = (cnt >> 6) == h ? v : so;
+                    for (unsigned q = 0; q < NK; q++) {
+                        const unsigned v = (unsigned)__shfl((int)sbase_q[q], (int)(cnt & 63u));
+                        so = (cnt >> 6) == q ? v : so;
+                    }
                 }
-                if (k <= K)
-                    a.tsoff[row * (K + 1) + k] = (uint16_t)so;
-            }
-        }
-        if (STAR && STEPS == 32u) {
-            /* sector k starts with the first step whose sector is >= k (urf_split_holey's construction: the steps' keys
-             * with the empty steps filled in from the left must not fall; bisection over the 32 of them) */
-            const unsigned k1 = (lane < URF_FRONT_STEPS && (unsigned)stepkey_v != URF_SEC_NONE) ? (unsigned)stepkey_v + 1u : 0u;
-            const unsigned fk = urf_wave_scan_max(k1);
-            unsigned exc = (unsigned)__shfl_up((int)fk, 1);
-            exc = lane == 0 ? 0u : exc;
-            if (__ballot(k1 != 0u && k1 < exc) != 0ull)
-                failed = true;   /* (uniform) the sectors fall inside the tile (the sweep's seam, an unorganised cloud) */
-            const unsigned sc = lane < URF_FRONT_STEPS ? (unsigned)stepcnt_v : 0u;
-            const unsigned sinc = urf_wave_scan_add(sc);
-            const unsigned sbase_l = sinc - sc;   /* lane j: participating points of the steps in front of step j; lane 32: all */
-            for (unsigned k0 = 0; k0 <= K; k0 += 64u) {
-                const unsigned k = k0 + lane;
-                unsigned lo = 0;   /* number of steps whose filled-in key + 1 is < k + 1 */
-#pragma unroll
-                for (unsigned st = URF_FRONT_STEPS / 2; st > 0; st >>= 1) {
-                    const unsigned v = (unsigned)__shfl((int)fk, (int)(lo + st - 1u));
-                    lo += v < k + 1u ? st : 0u;
-                }
-                {
-                    const unsigned v = (unsigned)__shfl((int)fk, (int)lo);
-                    lo += (lo == URF_FRONT_STEPS - 1u && v < k + 1u) ? 1u : 0u;
-                }
-                const unsigned so = (unsigned)__shfl((int)sbase_l, (int)lo);   /* (lane 32 holds the tile's total) */
                 if (k <= K)
                     a.tsoff[row * (K + 1) + k] = (uint16_t)so;
             }
         }
         troi = 0;
         tstar = 0;
-        stepkey_v = (int)URF_SEC_NONE;
-        stepcnt_v = 0;
-        stepkey_w = (int)URF_SEC_NONE;
-        stepcnt_w = 0;
+#pragma unroll
+        for (unsigned q = 0; q < NK; q++) {
+            stepkey_v[q] = (int)URF_SEC_NONE;
+            stepcnt_v[q] = 0;
+        }
     };
 
-    /* The points arrive four firings ahead, in four register sets that are refilled as soon as they have been used: no
+    /* The points arrive four firings ahead, in four register sets (of NH halves) that are refilled as soon as they have been used: no
      * copies between sets (a copy waits for its source), every wait is for a load issued three firings ago. */
-    float px[4], py[4], pz[4];
+    float px[4][NH], py[4][NH], pz[4][NH];
     auto ld = [&](const unsigned j, const unsigned f) {
-        /* (a lane behind the scan's end, a lane without a laser: one point of the scan for all of them, never looked at) */
-        const unsigned i = f * L + lane, o = ((L == 64u || lane < L) && i < len) ? i : len - 1u;
-        px[j] = gx[o];
-        py[j] = gy[o];
-        pz[j] = gz[o];
+#pragma unroll
+        for (unsigned h = 0; h < NH; h++) {
+            /* (a lane behind the scan's end, a lane without a laser: one point of the scan for all of them, never looked at) */
+            const unsigned i = f * L + h * 64u + lane, o = i < mylen ? i : len - 1u;
+            px[j][h] = gx[o];
+            py[j][h] = gy[o];
+            pz[j][h] = gz[o];
+        }
     };
 #pragma unroll
     for (unsigned j = 0; j < 4; j++)
@@ -734,6 +805,11 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
             ld(j, f + j + 4u);
         }
     }
+    auto give_back = [&]() {
+        a.front_ok[s] = 0u;
+        if (ok == URF_FRONT_ROWS)
+            a.table_redo[s] = 1u;   /* (nobody has checked the rest of the scan against the rows' table) */
+    };
     for (unsigned f = F0; f < F1; f += 4) {
 #pragma unroll
         for (unsigned j = 0; j < 4; j++) {
@@ -741,14 +817,12 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
                 step(std::integral_constant<unsigned, 1u>{}, f + j, px[j], py[j], pz[j]);
             ld(j, f + j + 4u);
         }
-        if (L != 64u && (((f + 4u) & 31u) == 0u || f + 4u >= F1))   /* (uniform) */
+        if (((f + 4u) & 31u) == 0u || f + 4u >= F1)   /* (uniform) */
             pres_end(f >> 5);
         if (((f + 4u) % STEPS) == 0u || f + 4u >= F1) {   /* (uniform) the tile is complete */
             tile_end(f / STEPS);
             if (failed_m != 0ull || __ballot(failed | overflow) != 0ull) {   /* (uniform) */
-                a.front_ok[s] = 0u;
-                if (ok == URF_FRONT_ROWS)
-                    a.table_redo[s] = 1u;   /* (nobody has checked the rest of the scan against the rows' table) */
+                give_back();
                 return;
             }
         }
@@ -761,43 +835,53 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
             ld(j, f + j + 4u);
         }
     }
-    /* the block's last ring points of every lane: their windows reach behind the march */
-    if (!to_end) {
-        /* the CP newest, oldest first: none has been a centre, the CP - H newest have not been x_zero's marked point either */
-        auto tail = [&](auto bk) {
-            constexpr unsigned back = decltype(bk)::value;
-            const bool in = win.in_block(back);
-            const unsigned what = (use_z ? URF_FC_EDGE_Z : 0u) | ((use_x && back < CP - H) ? URF_FC_EDGE_X : 0u);
-            if (ncb > URF_FRONT_CBUF - 64u)
-                urf_front_flush(a, s, cbuf, ncb, overflow);
-            urf_front_push(cbuf, ncb, in && what != 0u, (win.firing(back) + Fs) * L + lane, what);
-        };
-        URF_FRONT_TAIL_CALLS(CP, tail)
+#pragma unroll
+    for (unsigned h = 0; h < NH; h++) {
+        urf_front_ring<CP>& r = R[h];
+        /* the block's last ring points of every laser: their windows reach behind the march */
+        if (!to_end) {
+            /* the CP newest, oldest first: none has been a centre, the CP - H newest have not been x_zero's marked point either */
+            auto tail = [&](auto bk) {
+                constexpr unsigned back = decltype(bk)::value;
+                const bool in = r.win.in_block(back);
+                const unsigned what = (use_z ? URF_FC_EDGE_Z : 0u) | ((use_x && back < CP - H) ? URF_FC_EDGE_X : 0u);
+                if (ncb > URF_FRONT_CBUF - 64u)
+                    urf_front_flush(a, s, cbuf, ncb, overflow);
+                urf_front_push(cbuf, ncb, in && what != 0u, (r.win.firing(back) + Fs) * L + h * 64u + lane, what);
+            };
+            URF_FRONT_TAIL_CALLS(CP, tail)
+        }
+        LAY::maxs_of_block(a, s, b)[h * 64u + lane] = (unsigned long long)__double_as_longlong(r.maxs);
+        /* one laser, one ring -- over the whole scan: the blocks agree through the scan's two tables */
+        if (r.econf) {
+            const unsigned o1 = atomicCAS(&LAY::lane_ring(a, s)[h * 64u + lane], 0xffffffffu, r.E);
+            const unsigned o2 = atomicCAS(&a.front_ring_lane[(size_t)s * C + r.E], 0xffffffffu, h * 64u + lane);
+            failed = failed | (o1 != 0xffffffffu && o1 != r.E) | (o2 != 0xffffffffu && o2 != h * 64u + lane);
+        }
     }
     urf_front_flush(a, s, cbuf, ncb, overflow);
-    a.front_maxs[((size_t)s * a.tiles + b) * 64u + lane] = (unsigned long long)__double_as_longlong(maxs);
-    /* one lane, one ring -- over the whole scan: the blocks agree through the scan's two tables */
-    if (econf) {
-        const unsigned o1 = atomicCAS(&a.front_lane_ring[(size_t)s * 64u + lane], 0xffffffffu, E);
-        const unsigned o2 = atomicCAS(&a.front_ring_lane[(size_t)s * C + E], 0xffffffffu, lane);
-        failed = failed | (o1 != 0xffffffffu && o1 != E) | (o2 != 0xffffffffu && o2 != lane);
-    }
-    if (failed_m != 0ull || __ballot(failed | overflow) != 0ull) {
-        a.front_ok[s] = 0u;
-        if (ok == URF_FRONT_ROWS)
-            a.table_redo[s] = 1u;
-    }
+    if (failed_m != 0ull || __ballot(failed | overflow) != 0ull)
+        give_back();
 }
 
 /* one kernel per laser count and per curbPoints, each under a name of its own (tools/kernel_resources.py lists kernels by their base
- * identifier) and with its own waves per SIMD.  The window is 2 * CP + 1 registers: 1..5 fit five waves per SIMD, 6..8 (13, 15, 17 heights
- * and a fourth / fifth register of firing numbers) get the next budget (four waves, 128 registers). */
+ * identifier) and with its own waves per SIMD.  The window is 2 * CP + 1 registers per laser.  64 / 32 / 16 lasers: 1..5 fit five waves per
+ * SIMD, 6..8 (13, 15, 17 heights and a fourth / fifth register of firing numbers) get the next budget (four waves, 128 registers).  128
+ * lasers, two windows and two sets of prefetched points: 1..7 hold three (168 registers; 7 fills them without a spill), 8 -- two windows of
+ * 17 heights and 2 x 5 registers of firing numbers -- gets two (256 registers). */
 #ifndef URF_FRONT_WAVES_WIDE
 #define URF_FRONT_WAVES_WIDE 4
 #endif
-#define URF_FRONT_WAVES_OF(CP) ((CP) <= 5 ? URF_FRONT_WAVES : URF_FRONT_WAVES_WIDE)
+#ifndef URF_FRONT128_WAVES
+#define URF_FRONT128_WAVES 3
+#endif
+#ifndef URF_FRONT128_WAVES_WIDE
+#define URF_FRONT128_WAVES_WIDE 2
+#endif
+#define URF_FRONT_WAVES_OF(L, CP) \
+    ((L) > 64u ? ((CP) <= 7 ? URF_FRONT128_WAVES : URF_FRONT128_WAVES_WIDE) : ((CP) <= 5 ? URF_FRONT_WAVES : URF_FRONT_WAVES_WIDE))
 #define URF_FRONT_KERNEL(name, L, CP)                                                                                                         \
-    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT_WAVES_OF(CP), URF_FRONT_WAVES_OF(CP))))                     \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT_WAVES_OF(L, CP), URF_FRONT_WAVES_OF(L, CP))))               \
     void name(urf_kargs a, urf_dev_params dp)                                                                                                 \
     {                                                                                                                                       \
         __shared__ urf_u2 cbuf[URF_FRONT_CBUF];                                                                                               \
@@ -808,15 +892,17 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
         else                                                                                                                                  \
             urf_front_body<true, true, L, CP>(a, dp, cbuf);                                                                                   \
     }
-/* curbPoints 5 in every front mode ... */
+/* curbPoints 5 in every front mode (128 lasers: with urf_set_front_lasers128 on) ... */
 URF_FRONT_KERNEL(k_front, 64u, 5)
 URF_FRONT_KERNEL(k_front32, 32u, 5)
 URF_FRONT_KERNEL(k_front16, 16u, 5)
-/* ... and 1..8 with urf_set_front_mode(ctx, 3) (64 lasers) and urf_set_front_curb_points(ctx, 1) (32, 16 and 128: urf_front128.hpp).  Nothing in
- * the body counts per wave what is counted per firing: the halos (HPRE, HPRE_WIDE, HPOST) are firings, and a lane meets at most one ring point per
- * firing whatever L is; fw[] holds firings relative to Fs (at most front_tpb * URF_TILE / 16 + 20 < 65536); candidate indices are (firing) * L +
- * lane.  The finish step is k_front_finish_cp*: it takes the laser count at run time (front_lsh). */
-#define URF_FRONT_CP_X(n) URF_FRONT_KERNEL(k_front_cp##n, 64u, n) URF_FRONT_KERNEL(k_front32_cp##n, 32u, n) URF_FRONT_KERNEL(k_front16_cp##n, 16u, n)
+URF_FRONT_KERNEL(k_front128, 128u, 5)
+/* ... and 1..8 with urf_set_front_mode(ctx, 3) (64 lasers) and urf_set_front_curb_points(ctx, 1) (32, 16 and 128).  Nothing in the body counts
+ * per wave what is counted per firing: the halos (HPRE, HPRE_WIDE, HPOST) are firings, and a laser meets at most one ring point per firing
+ * whatever L is; fw[] holds firings relative to Fs (at most front_tpb * URF_TILE / 16 + 20 < 65536); candidate indices are (firing) * L +
+ * laser slot.  The finish step is k_front_finish_cp* (k_front_finish128_cp*): it takes the laser count from its layout. */
+#define URF_FRONT_CP_X(n) \
+    URF_FRONT_KERNEL(k_front_cp##n, 64u, n) URF_FRONT_KERNEL(k_front32_cp##n, 32u, n) URF_FRONT_KERNEL(k_front16_cp##n, 16u, n) URF_FRONT_KERNEL(k_front128_cp##n, 128u, n)
 URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
 #undef URF_FRONT_CP_X
 

@@ -295,7 +295,7 @@ struct urf_kargs {
     uint32_t* front_ncand;      /* [S] */
     uint32_t* front_st;         /* [S][URF_FRONT_ST_WORDS] k_front_finish part 1 -> part 2 */
     uint32_t* front_list;       /* [S] URF_LIST_FRONT */
-    uint32_t  front_lsh;        /* log2 of the lasers per firing the fused kernels march with (4, 5, 6: params.channels = 16, 32, 64; 7: 128, urf_front128.hpp); point f * L + l is
+    uint32_t  front_lsh;        /* log2 of the lasers per firing the fused kernels march with (4, 5, 6: params.channels = 16, 32, 64; 7: 128, urf_set_front_lasers128); point f * L + l is
                                  * laser slot l of firing f, a tile holds URF_TILE / L firings */
     uint32_t  front_lists;      /* this call launches the legacy kernels list-driven (k_split_list, k_ring_list, k_label_list) */
     /* row-major organised sweeps (height = the sensor's L = 1 << front_lsh lasers, width = firings: point l * F + f): front_ok[s] == URF_FRONT_ROWS,
@@ -310,7 +310,7 @@ struct urf_kargs {
     float*    tx;               /* [S * sstride] firing-order copies (scratch stride) */
     float*    ty;
     float*    tz;
-    /* 128 lasers per firing (urf_set_front_lasers128, urf_front128.hpp; front_lsh == 7): what is sized for 64 lanes above, sized for 128.
+    /* 128 lasers per firing (urf_set_front_lasers128, urf_front.hpp; front_lsh == 7): what is sized for 64 lanes above, sized for 128.
      * NULL until the switch has been turned on.  tiles2 = tiles rounded up to an even number (a presence word covers 32 firings: two tiles). */
     uint32_t* front_pres128;      /* [S][tiles2 * 64] word (f >> 5) * 128 + l */
     unsigned long long* front_maxs128; /* [S][tiles2 * 64] per block (an even number of tiles) and laser slot */

@@ -1,6 +1,6 @@
 /*
- * urf_k_front_outputs.hpp -- the published order and the road_marker points of a scan that took the fused front end (urf_front.hpp,
- * urf_front128.hpp), straight from what that call left on the device (urf_set_front_outputs): siblings of urf_k_outputs.hpp's
+ * urf_k_front_outputs.hpp -- the published order and the road_marker points of a scan that took the fused front end (urf_front.hpp: any
+ * laser count), straight from what that call left on the device (urf_set_front_outputs): siblings of urf_k_outputs.hpp's
  * k_ring_order, k_marker_ring, k_marker_ring_literal and k_marker_bins under their own names.
  *
  * A fused scan keeps no ring-sorted copies.  Its ring r is one laser slot, its j-th point the j-th set bit of that slot's presence

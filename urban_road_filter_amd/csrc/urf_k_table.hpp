@@ -242,7 +242,7 @@ __device__ void urf_ring_table_scan(const urf_kargs& a, const urf_dev_params& dp
     urf_scan_range(a, s, off, len);
     const unsigned C = (unsigned)dp.p.channels;
     if (first_walk && a.front && a.front_lsh == 7u && tid < 128u)
-        a.front_lane_ring128[(size_t)s * 128u + tid] = 0xffffffffu;   /* (128 lasers per firing, urf_front128.hpp: the laser slots' rings, as k_ring_table does for 64) */
+        a.front_lane_ring128[(size_t)s * 128u + tid] = 0xffffffffu;   /* (128 lasers per firing, urf_front.hpp: the laser slots' rings, as k_ring_table does for 64) */
     if (tid == 0) {
         urf_scan_info in;
         in.status = URF_OK;      /* k_offsets turns it into URF_TOO_FEW_POINTS when piece < 30 */
