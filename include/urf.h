@@ -557,7 +557,22 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * above keeps its meaning with these instances: per-scan hand-back, identical labels and summaries, urf_front_scans, ragged batches,
  * row-major sightings and the callback path's row-major sweeps, urf_set_front_long_sweeps, urf_set_front_outputs, the dense entry
  * points.  curbPoints 9..30 keep the general kernels everywhere; with the switch off every call launches exactly what it launched
- * before the switch existed.  Opt-in: its times are in profiles/curb_points_lasers_bench.json. */
+ * before the switch existed.  Opt-in: its times are in profiles/curb_points_lasers_bench.json.
+ *
+ * Firings that span several star sectors (urf_set_front_multi_sector): the fused kernels want the points of a firing that take part in the
+ * star-shaped search to share one sector, and the sectors not to fall inside a tile of 2048 points.  No real spinning LiDAR delivers that:
+ * the unit turns while a firing is shot (VLP-16, HDL-32E), its lasers carry fixed azimuth offsets (VLP-32C, HDL-64E, a staggered Ouster
+ * cloud), and a sweep that does not start on a tile border has its seam (sector K - 1 -> 0) inside a tile.  With the switch off such a
+ * scan is handed back to the general kernels.  With it on, the star-shaped search on and curbPoints == 5, every front mode that takes a
+ * call launches the k_front*_ms instance of the march (16, 32, 64 lasers; 128 behind urf_set_front_lasers128), which accepts any sector
+ * per participant, and k_front_sectors behind it (urban_road_filter_amd/csrc/urf_k_front_sectors.hpp), which puts every tile's star records in
+ * sector order; everything downstream is unchanged, labels and summaries are identical.  Every OTHER rule of the shape still hands a scan
+ * back (one laser, one ring; ranges; a ring point on the sensor's axis; unorganised clouds).  curbPoints 1..4 and 6..8 (mode 3) keep
+ * their plain instances and with them today's hand-back of such scans; with the star-shaped search off sectors do not matter and the plain
+ * kernel is launched.  Firing order, row-major, ragged batches, the callback path's row-major sweeps, urf_set_front_long_sweeps,
+ * urf_set_front_outputs and the dense entry points keep their meaning.  With the switch off every call launches exactly what it launched
+ * before the switch existed.  Turning it on allocates two bytes per scratch element (URF_ERR_OOM: it stays off).  Opt-in: its times are in
+ * profiles/front_multi_sector_bench.json. */
 int urf_set_front_mode(urf_ctx* ctx, int mode);
 int urf_front_scans(urf_ctx* ctx, uint32_t* n_fused);
 /* 0 (default): as today.  1: with channels == 128 and curbPoints == 5, front modes 2 and 3 also send sweeps of 128 lasers per
@@ -573,6 +588,11 @@ int urf_set_front_long_sweeps(urf_ctx* ctx, int on);
  * 1..8 with channels == 16 or 32, and with channels == 128 when urf_set_front_lasers128 is on; modes 0, 1 and 2 never do.  Forgets
  * sightings / hand-backs like urf_set_front_mode.  Anything else: URF_ERR_INVALID_ARG. */
 int urf_set_front_curb_points(urf_ctx* ctx, int on);
+/* 0 (default): as today, a scan whose firings span several star sectors, or whose sectors fall inside a tile, is handed back to the
+ * general kernels.  1: with the star-shaped search on and curbPoints == 5 the fused front end keeps such a scan (k_front*_ms and
+ * k_front_sectors, above); other curbPoints keep the plain instances.  Forgets sightings / hand-backs like urf_set_front_mode.
+ * URF_ERR_OOM: the switch stays off.  Anything else: URF_ERR_INVALID_ARG. */
+int urf_set_front_multi_sector(urf_ctx* ctx, int on);
 /* 0 (default): after a call that took the fused front end, urf_ordered_indices*, urf_clouds_batch_* with
  * URF_ORDER_REFERENCE and urf_marker_points* first run that call again through the general kernels, and the context stays with those.
  * 1: these read-outs take a fused call's results as they are (urban_road_filter_amd/csrc/urf_k_front_outputs.hpp: the rings' points

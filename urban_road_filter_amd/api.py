@@ -178,6 +178,7 @@ def lib(hooks=False):
         "urf_set_front_lasers128": [vp, C.c_int],
         "urf_set_front_long_sweeps": [vp, C.c_int],
         "urf_set_front_curb_points": [vp, C.c_int],
+        "urf_set_front_multi_sector": [vp, C.c_int],
         "urf_set_front_outputs": [vp, C.c_int],
         "urf_callback_path_preset": [vp, C.c_uint32],
         "urf_classify_batch_soa_dense": [vp, fp, fp, fp, vp, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp],
@@ -415,6 +416,13 @@ class Context:
         set_front_lasers128 is on (modes 0, 1 and 2 never; 9..30 keep the general kernels; include/urf.h); 0 (default) keeps curb_points
         other than 5 to 64 lasers.  Opt-in."""
         self._check(self._lib.urf_set_front_curb_points(self._h, int(on)), "urf_set_front_curb_points")
+
+    def set_front_multi_sector(self, on):
+        """urf_set_front_multi_sector: 1 lets the fused front end keep scans whose firings span several star sectors, or whose sectors
+        fall inside a tile -- what every real spinning LiDAR delivers (rotation during a firing, azimuth offsets per laser, staggered
+        Ouster clouds, the sweep's seam) -- with the star-shaped search on and curb_points == 5 (other curb_points: the plain instances;
+        include/urf.h); 0 (default) hands such scans back to the general kernels.  Opt-in."""
+        self._check(self._lib.urf_set_front_multi_sector(self._h, int(on)), "urf_set_front_multi_sector")
 
     def set_front_outputs(self, on):
         """urf_set_front_outputs: 1 lets ordered_indices*, clouds_batch_* in the reference order and marker_points* take the results of a call

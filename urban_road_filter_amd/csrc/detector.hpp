@@ -124,6 +124,15 @@ public:
         if (rc != URF_OK)
             throw Error(rc, "urf_set_front_curb_points");
     }
+    /* urf_set_front_multi_sector: the fused front end keeps scans whose firings span several star sectors or whose sectors fall inside a
+     * tile (real sensors' azimuth offsets, rotation during a firing, the sweep's seam), with the star-shaped search on and curbPoints == 5.
+     * Off by default and opt-in. */
+    void setFrontMultiSector(bool on)
+    {
+        const int rc = urf_set_front_multi_sector(ctx_, on ? 1 : 0);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_set_front_multi_sector");
+    }
 
     /* Also build the "road_marker" MarkerArray (lidar_segmentation.cpp:295-351, 369-602, topic :59,601);
      * fixedFrame = params::fixedFrame (cfg:10).  Off by default: the polygon is a visualisation product. */
@@ -254,6 +263,15 @@ public:
         const int rc = urf_set_front_curb_points(ctx_, on ? 1 : 0);
         if (rc != URF_OK)
             throw Error(rc, "urf_set_front_curb_points");
+    }
+    /* urf_set_front_multi_sector: the fused front end keeps scans whose firings span several star sectors or whose sectors fall inside a
+     * tile (real sensors' azimuth offsets, rotation during a firing, the sweep's seam), with the star-shaped search on and curbPoints == 5.
+     * Off by default and opt-in. */
+    void setFrontMultiSector(bool on)
+    {
+        const int rc = urf_set_front_multi_sector(ctx_, on ? 1 : 0);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_set_front_multi_sector");
     }
 
     /* Dense messages (the driver dropped the non-returns) with a field named "ring" (UINT8 or UINT16, count 1) are put back into firing

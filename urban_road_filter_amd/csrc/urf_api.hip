@@ -24,6 +24,7 @@
 #include "urf_internal.hpp"
 #include "urf_kernels.hpp"
 #include "urf_front.hpp"
+#include "urf_k_front_sectors.hpp"
 #include "urf_k_front_outputs.hpp"
 
 #define URF_ASYNC_SLOTS 4
@@ -54,7 +55,8 @@ struct lazy_buf {
  * ring-count hint) have URF_ASYNC_SLOTS, one per sweep in flight, whatever max_batch is.  urf_create allocates SCANS and SLOTS;
  * CAPTURE comes with the first urf_enable_stage_capture, ROW_MAJOR (the firing-order copies of row-major organised sweeps) once
  * such a sweep has been sighted (rows_state_update), LASERS128 (what the fused front end sizes for 64 lanes, sized for 128: urf_front.hpp)
- * with the first urf_set_front_lasers128(ctx, 1).  sstride, max_tiles and front_cand_cap are the context's (scratch_walk). */
+ * with the first urf_set_front_lasers128(ctx, 1), MULTI_SECTOR (the star records' sectors, k_front*_ms -> k_front_sectors) with the first
+ * urf_set_front_multi_sector(ctx, 1).  sstride, max_tiles and front_cand_cap are the context's (scratch_walk). */
 #define URF_SCRATCH_SCANS(X)                                                                                                     \
     X(rx, sstride) X(ry, sstride) X(rz, sstride) X(rec, sstride)                                                                 \
     X(sr, sstride) X(sz, sstride) X(sslot, sstride) X(ssrt16, sstride) X(ssrt, sstride) X(wsg, sstride)                          \
@@ -85,7 +87,8 @@ struct lazy_buf {
     X(front_pres128, URF_FRONT128_TILES2(max_tiles) * 64) X(front_maxs128, URF_FRONT128_TILES2(max_tiles) * 64)                  \
     X(front_lane_ring128, URF_FRONT128_L) X(front_st128, URF_FRONT128_ST_WORDS) X(rows_v128, URF_FRONT128_L)                     \
     X(front_cand128, URF_FRONT128_CAND_CAP(max_points)) X(front_all128, URF_FRONT128_CAND_CAP(max_points))
-enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR, URF_SCR_LASERS128 };
+#define URF_SCRATCH_MULTI_SECTOR(X) X(front_skey, sstride)
+enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR, URF_SCR_LASERS128, URF_SCR_MULTI_SECTOR };
 
 
 /* curbPoints the fused front end has an instance for: 5 in every mode; with urf_set_front_mode(3) and 64 lasers per firing the values of
@@ -99,8 +102,10 @@ static bool front_curb_points_ok(int front_mode, bool cp_lasers, unsigned L, int
  * k_front16 / k_front128 and k_front_finish / k_front_finish128 in every mode */
 using urf_front_fn = void (*)(urf_kargs, urf_dev_params);
 using urf_front_finish_fn = void (*)(urf_kargs, urf_dev_params, unsigned);
-static urf_front_fn front_kernel(unsigned lsh, int cp)
+static urf_front_fn front_kernel(unsigned lsh, int cp, bool ms)
 {
+    if (ms && cp == 5)   /* urf_set_front_multi_sector with the star-shaped search on (urf_policy::plan: a.front_ms) */
+        return lsh == 7u ? k_front128_ms : lsh == 5u ? k_front32_ms : lsh == 4u ? k_front16_ms : k_front_ms;
     switch (cp) {
 #define URF_FRONT_CP_X(n) \
     case n: return lsh == 7u ? k_front128_cp##n : lsh == 5u ? k_front32_cp##n : lsh == 4u ? k_front16_cp##n : k_front_cp##n;
@@ -157,6 +162,9 @@ struct __attribute__((visibility("hidden"))) urf_policy {
     bool every_batch() const { return front_mode >= 2; }
     bool lasers128 = false;         /* urf_set_front_lasers128: modes 2 and 3 take sweeps of 128 lasers per firing too (k_front128*, urf_front.hpp; its scratch is there) */
     bool curb_points = false;       /* urf_set_front_curb_points: mode 3 takes curbPoints 1..8 at 16, 32 and (lasers128) 128 lasers per firing too (k_front32_cp*, k_front16_cp*, k_front128_cp*) */
+    /* urf_set_front_multi_sector: with the star-shaped search on and curbPoints 5 the march is a k_front*_ms instance and k_front_sectors follows it
+     * (urf_k_front_sectors.hpp): firings that span several sectors, sectors that fall inside a tile stay fused.  Other curbPoints: the plain instances. */
+    bool multi_sector = false;
     bool long_sweeps = false;       /* urf_set_front_long_sweeps: modes 2 and 3 take scans of up to URF_FRONT_LONG_MAX_TILES tiles (the finish kernels with more dynamic LDS) */
     uint32_t front_max_tiles() const { return long_sweeps && every_batch() ? URF_FRONT_LONG_MAX_TILES : URF_FRONT_MAX_TILES; }
     uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
@@ -243,6 +251,7 @@ struct __attribute__((visibility("hidden"))) urf_policy {
             a.front_tpb = a.front_tpb < 2u ? 2u : (a.front_tpb & ~1u);
         a.front_lists = (a.front && !front_direct && !slot) ? 1u : 0u;   /* (the callback path's sequence holds the general kernels as grids anyway) */
         a.front_rows = (a.front && front_rows) ? 1u : 0u;   /* (independent of the two other speculations: the repair kernels come with it) */
+        a.front_ms = (a.front && multi_sector && dp.p.star_shaped_method != 0 && dp.p.curbPoints == 5) ? 1u : 0u;
     }
 };
 
@@ -417,16 +426,19 @@ static void scratch_walk(const urf_ctx* c, urf_kargs& k, F&& f)
 #define URF_X_CAPTURE(field, n) f(URF_SCR_CAPTURE, k.field, (size_t)c->max_batch, (size_t)(n));
 #define URF_X_ROW_MAJOR(field, n) f(URF_SCR_ROW_MAJOR, k.field, (size_t)c->max_batch, (size_t)(n));
 #define URF_X_LASERS128(field, n) f(URF_SCR_LASERS128, k.field, (size_t)c->max_batch, (size_t)(n));
+#define URF_X_MULTI_SECTOR(field, n) f(URF_SCR_MULTI_SECTOR, k.field, (size_t)c->max_batch, (size_t)(n));
     URF_SCRATCH_SCANS(URF_X_SCANS)
     URF_SCRATCH_SLOTS(URF_X_SLOTS)
     URF_SCRATCH_CAPTURE(URF_X_CAPTURE)
     URF_SCRATCH_ROW_MAJOR(URF_X_ROW_MAJOR)
     URF_SCRATCH_LASERS128(URF_X_LASERS128)
+    URF_SCRATCH_MULTI_SECTOR(URF_X_MULTI_SECTOR)
 #undef URF_X_SCANS
 #undef URF_X_SLOTS
 #undef URF_X_CAPTURE
 #undef URF_X_ROW_MAJOR
 #undef URF_X_LASERS128
+#undef URF_X_MULTI_SECTOR
 }
 
 /* Allocates the arrays of `group` that are missing (URF_OK: all of them are there). */
@@ -835,6 +847,24 @@ extern "C" int urf_set_front_curb_points(urf_ctx* c, int on)
     return URF_OK;
 }
 
+extern "C" int urf_set_front_multi_sector(urf_ctx* c, int on)
+{
+    if (!c || (on != 0 && on != 1))
+        return URF_ERR_INVALID_ARG;
+    if (on) {   /* the star records' sectors, one per scratch element: allocated once, with the first call that turns the switch on */
+        URF_HIP(c, hipSetDevice(c->device));
+        const int rc = scratch_alloc(c, URF_SCR_MULTI_SECTOR);
+        if (rc != URF_OK)
+            return rc;
+    }
+    if ((on != 0) != c->pol.multi_sector)   /* (a new start) */
+        c->pol.forget_front();
+    c->pol.set(c->pol.multi_sector, on != 0);
+    if (on)
+        c->pol.set(c->pol.want_ring_sorted, false);
+    return URF_OK;
+}
+
 extern "C" int urf_set_front_outputs(urf_ctx* c, int on)
 {
     if (!c || (on != 0 && on != 1))
@@ -1068,7 +1098,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
         hipLaunchKernelGGL(k_transpose, g_tiles, dim3(256), 0, st, a);
     if (a.front) {   /* (a tile is URF_TILE points, whatever the laser count: URF_TILE / L firings) */
         const dim3 g_front((a.tiles + a.front_tpb - 1) / a.front_tpb, n_scans);
-        hipLaunchKernelGGL(front_kernel(a.front_lsh, dp.p.curbPoints), g_front, dim3(64), 0, st, a, dp);
+        hipLaunchKernelGGL(front_kernel(a.front_lsh, dp.p.curbPoints, a.front_ms != 0u), g_front, dim3(64), 0, st, a, dp);
     }
     if (a.front_lists) {   /* what k_front handed back (normally nothing) */
         hipLaunchKernelGGL(k_table_repair, g_scan, dim3(URF_TABLE_THREADS), 0, st, a, dp, 1u);
@@ -1080,6 +1110,9 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
         hipLaunchKernelGGL(k_table_repair, g_scan, dim3(URF_TABLE_THREADS), 0, st, a, dp, 0u);
         hipLaunchKernelGGL(k_split_repair, dim3(c->n_cus), dim3(URF_TILE_THREADS), urf_split_lds_bytes(C, K, star), st, a, dp);
     }
+    /* the tiles of the scans k_front*_ms kept: their star records by sector, their tsoff rows (a scan that was handed back: k_split's) */
+    if (a.front_ms)
+        hipLaunchKernelGGL(k_front_sectors, g_tiles, dim3(URF_FSEC_THREADS), 0, st, a, dp);
     mark();
     /* k_front_finish's first part (positions, the detectors' candidates and their marks) depends on nothing behind k_front: it goes to a
      * stream of its own and runs NEXT TO k_index, the star-shaped search's sort and walk -- it waits for scattered loads (0.18 ms on its

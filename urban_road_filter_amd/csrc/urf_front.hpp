@@ -36,6 +36,9 @@
  * sectors that fall inside a tile, a ring point on the sensor's axis, an incomplete speculative ring table) clears
  * front_ok[s] and takes the legacy kernels, which skip every scan whose flag is still set.  Labels are the same
  * either way, bit for bit: the arithmetic is the legacy path's (urf_device.hpp, urf_x_zero_angle, urf_z_zero_angle).
+ * With urf_set_front_multi_sector on, "a firing in two sectors" and "sectors that fall inside a tile" are no such reasons (curbPoints 5, the
+ * star-shaped search on): the march is a k_front*_ms instance (urf_front_body's MS) and k_front_sectors (urf_k_front_sectors.hpp) sorts
+ * each tile's star records by sector behind it.
  *
  * ONE body per kernel around the march, for every laser count.  k_front_finish*, k_transpose (here) and k_rows_probe (urf_k_table.hpp) each
  * exist as a named wrapper per family -- 64 / 32 / 16 lasers, the count read at run time, and 128 (k_front_finish128*, k_transpose128,
@@ -479,11 +482,18 @@ struct urf_front_ring {
  *
  * What the laser count decides besides NH is named here once: the arrays sized for 64 or for 128 lanes and the record's "on no ring"
  * (urf_front_lay<(L > 64)>), the width of a firing's region-of-interest word (step), which half the first star participant comes from and
- * how many there are in front of a half (step), how many registers hold a tile's steps (NK). */
-template <bool STAR, bool BEAM, unsigned L, unsigned CP>
+ * how many there are in front of a half (step), how many registers hold a tile's steps (NK).
+ *
+ * MS (urf_set_front_multi_sector; k_front*_ms, CP == 5, STAR only): a firing's participants may lie in SEVERAL sectors, and the sectors may
+ * fall inside a tile -- a real sensor's azimuth offsets per laser, its rotation during a firing, the sweep's seam.  The march then leaves
+ * the tile's star records compacted in INPUT order as ever (tile base + participants in front), each with its 16-bit sector in the same
+ * place of front_skey, and the tile's participant count in tsoff[row][K]; k_front_sectors (urf_k_front_sectors.hpp) sorts the tile's
+ * records by sector, stably, and writes the tile's tsoff row.  No one-sector test, no step keys, no bisection; every other rule stays. */
+template <bool STAR, bool BEAM, unsigned L, unsigned CP, bool MS = false>
 __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
 {
     static_assert(L == 128u || L == 64u || L == 32u || L == 16u, "a firing fills two waves, the wave, half of it or a quarter");
+    static_assert(!MS || (STAR && CP == 5u), "the multi-sector instances: star-shaped search on, curbPoints 5");
     using LAY = urf_front_lay<(L > 64u)>;
     constexpr unsigned NH = L > 64u ? 2u : 1u;    /* halves of a firing: lasers per lane */
     const unsigned s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
@@ -515,6 +525,7 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
     const __amdgpu_buffer_rsrc_t brec = urf_buf(a.rec + sb, len * 4u);
     const __amdgpu_buffer_rsrc_t bsr = urf_buf(a.sr + sb, a.tiles * URF_TILE * 4u), bsz = urf_buf(a.sz + sb, a.tiles * URF_TILE * 4u);
     const __amdgpu_buffer_rsrc_t bss = urf_buf(a.sslot + sb, a.tiles * URF_TILE * 2u);
+    const __amdgpu_buffer_rsrc_t bsk = MS ? urf_buf(a.front_skey + sb, a.tiles * URF_TILE * 2u) : bss;   /* (MS: the records' sectors, slot for slot) */
     const unsigned nR = a.info[s].n_rings;
     const unsigned upto_v = a.table_upto[s];
     /* (a row-major scan's table rests on EVERY point lying on its row's entry -- k_ring_table's third rule: a point on none asks for the long walk) */
@@ -633,15 +644,21 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
                 /* star-shaped search: the firing's participants -- of every half -- share one sector, the first participant's (half 0's, or
                  * else half 1's), and their copies follow each other in input order: half 0's, then half 1's */
                 unsigned f0 = URF_SEC_NONE;
+                if constexpr (!MS) {
 #pragma unroll
-                for (unsigned h = NH; h-- > 0u;) {
-                    const unsigned src = psm[h] ? (unsigned)__ffsll((long long)psm[h]) - 1u : 0u;
-                    f0 = psm[h] ? (unsigned)__builtin_amdgcn_readlane((int)sk[h], (int)src) : f0;
+                    for (unsigned h = NH; h-- > 0u;) {
+                        const unsigned src = psm[h] ? (unsigned)__ffsll((long long)psm[h]) - 1u : 0u;
+                        f0 = psm[h] ? (unsigned)__builtin_amdgcn_readlane((int)sk[h], (int)src) : f0;
+                    }
                 }
                 unsigned np = 0;   /* participants of the halves in front */
 #pragma unroll
                 for (unsigned h = 0; h < NH; h++) {
-                    failed_m |= psm[h] & __builtin_amdgcn_ballot_w64(sk[h] != f0);
+                    if constexpr (!MS)
+                        failed_m |= psm[h] & __builtin_amdgcn_ballot_w64(sk[h] != f0);
+                    else   /* any sector per participant: k_front_sectors puts the tile's records in order */
+                        __builtin_amdgcn_raw_buffer_store_b16((short)sk[h], bsk, ons[h] ? ((f / STEPS) * URF_TILE + tstar + np + urf_popc_below(psm[h])) * 2u : URF_OOB,
+                                                              0, URF_FRONT_NT);
                     const unsigned so = (f / STEPS) * URF_TILE + tstar + np + urf_popc_below(psm[h]);
                     const unsigned o4 = ons[h] ? so * 4u : URF_OOB;
                     const float pr = urf_sqrt_rn_normal(rho2[h]);   /* star_shaped_search.cpp:164: sqrtf(x * x + y * y) */
@@ -651,11 +668,13 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
                                                           URF_FRONT_NT);
                     np += (unsigned)__popcll(psm[h]);
                 }
+                if constexpr (!MS) {
 #pragma unroll
-                for (unsigned q = 0; q < NK; q++) {
-                    if (NK == 1u || stp / 64u == q) {   /* (uniform) */
-                        stepkey_v[q] = lane == stp - q * 64u ? (int)f0 : stepkey_v[q];
-                        stepcnt_v[q] = lane == stp - q * 64u ? (int)np : stepcnt_v[q];
+                    for (unsigned q = 0; q < NK; q++) {
+                        if (NK == 1u || stp / 64u == q) {   /* (uniform) */
+                            stepkey_v[q] = lane == stp - q * 64u ? (int)f0 : stepkey_v[q];
+                            stepcnt_v[q] = lane == stp - q * 64u ? (int)np : stepcnt_v[q];
+                        }
                     }
                 }
                 tstar += np;
@@ -720,7 +739,11 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
         const size_t row = (size_t)s * a.tiles + t;
         if (lane == 0)
             a.tile_roi[row] = troi;
-        if (STAR) {
+        if constexpr (MS) {
+            /* the tile's participants, where k_front_sectors finds them: it writes the whole row */
+            if (lane == 0)
+                a.tsoff[row * (K + 1) + K] = (uint16_t)tstar;
+        } else if (STAR) {
             /* sector k starts with the first step whose sector is >= k (urf_split_holey's construction: the steps' keys with the empty
              * steps filled in from the left must not fall; bisection over them).  A register per 64 steps, the running values carried from
              * one to the next */
@@ -905,6 +928,22 @@ URF_FRONT_KERNEL(k_front128, 128u, 5)
     URF_FRONT_KERNEL(k_front_cp##n, 64u, n) URF_FRONT_KERNEL(k_front32_cp##n, 32u, n) URF_FRONT_KERNEL(k_front16_cp##n, 16u, n) URF_FRONT_KERNEL(k_front128_cp##n, 128u, n)
 URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
 #undef URF_FRONT_CP_X
+/* ... and the multi-sector instances (urf_set_front_multi_sector; urf_front_body's MS): curbPoints 5, the two bodies of the star-shaped
+ * search -- with the search off sectors do not matter and the host launches the plain kernel.  The budgets of their plain siblings. */
+#define URF_FRONT_KERNEL_MS(name, L)                                                                                                          \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT_WAVES_OF(L, 5), URF_FRONT_WAVES_OF(L, 5))))                 \
+    void name(urf_kargs a, urf_dev_params dp)                                                                                                 \
+    {                                                                                                                                       \
+        __shared__ urf_u2 cbuf[URF_FRONT_CBUF];                                                                                               \
+        if (!dp.p.starbeam_filter)                                                                                                            \
+            urf_front_body<true, false, L, 5, true>(a, dp, cbuf);                                                                             \
+        else                                                                                                                                  \
+            urf_front_body<true, true, L, 5, true>(a, dp, cbuf);                                                                              \
+    }
+URF_FRONT_KERNEL_MS(k_front_ms, 64u)
+URF_FRONT_KERNEL_MS(k_front32_ms, 32u)
+URF_FRONT_KERNEL_MS(k_front16_ms, 16u)
+URF_FRONT_KERNEL_MS(k_front128_ms, 128u)
 
 /* ------------------------------------------------------------------------- */
 /* k_front_finish                                                              */

@@ -196,7 +196,7 @@ struct urf_kargs {
     uint32_t  front;            /* this call launches it (urf_api.hip decides: 64 / 32 / 16 channels, curbPoints 5 -- mode 3 and 64 channels: 1..8 --, no stage capture, a batch) */
     uint32_t  front_tpb;        /* tiles per block of k_front */
     uint32_t  front_cand_cap;   /* entries per scan of front_cand / front_all */
-    uint32_t  front_pad_;
+    uint32_t  front_ms;         /* urf_set_front_multi_sector, star-shaped search on, curbPoints 5: the march is a k_front*_ms instance, k_front_sectors follows it (urf_k_front_sectors.hpp) */
     /* output */
     uint8_t* labels;
     urf_scan_info* info;        /* context copy, [n_scans] */
@@ -319,6 +319,8 @@ struct urf_kargs {
     float*    rows_v128;          /* [S][128] k_rows_probe128 */
     urf_u2*   front_cand128;      /* [S][URF_FRONT128_CAND_CAP] front_cand / front_all of a call that takes these kernels (front_cand_cap likewise) */
     urf_u2*   front_all128;
+    /* firings that span several star sectors (urf_set_front_multi_sector, urf_k_front_sectors.hpp).  NULL until the switch has been turned on. */
+    uint16_t* front_skey;         /* [S * sstride] k_front*_ms -> k_front_sectors: the sector of the star record in the same place of sr / sz / sslot */
 };
 #define URF_FRONT_ROWS 2u
 
