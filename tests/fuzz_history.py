@@ -1,6 +1,6 @@
 """Scripts of calls for the call-history tests (tests/test_history_cpu.py, tests/test_gpu_history.py): what ONE long-lived context is asked to
 do -- settings, batch calls, sweeps of the callback path, read-outs -- in a random but reproducible order, the clouds and the parameter sets
-the steps draw from, and a shadow of urf_policy::plan's history-free part (urban_road_filter_amd/csrc/urf_api.hip) that says where the path
+the steps draw from, and a shadow of urf_policy::plan's history-free part (urban_road_filter_amd/csrc/urf_policy.hpp; tests/test_policy_table.py holds it to the real function) that says where the path
 of a call is certain.  Pure numpy; no GPU.
 
 A step is a dict of plain values (names of pool entries, tags of parameter sets), so that the steps so far print readably in an assertion

@@ -162,8 +162,7 @@ def test_the_symbol_is_declared_wrapped_and_exported():
     header = open(os.path.join(ROOT, "include", "urf.h")).read()
     assert re.search(r"\bint\s+urf_set_front_multi_sector\s*\(\s*urf_ctx\s*\*\s*ctx\s*,\s*int\s+on\s*\)\s*;", header)
     assert callable(getattr(u.Context, "set_front_multi_sector", None))
-    src = open(os.path.join(ROOT, "urban_road_filter_amd", "csrc", "detector.hpp")).read()
-    assert len(re.findall(r"void\s+setFrontMultiSector\s*\(\s*bool\s+on\s*\)", src)) == 2   # Detector and BatchDetector
+    # (both C++ adapters have its setter: tests/test_front_switches_api.py)
     lib = u.lib()
     assert hasattr(lib, "urf_set_front_multi_sector")
     assert lib.urf_set_front_multi_sector(None, 1) == -1   # (no context: URF_ERR_INVALID_ARG, before anything touches a device)

@@ -3,7 +3,7 @@ labels, summaries and read-outs against oracle B for the same input and the para
 
 (a) random histories (tests/fuzz_history.py: settings, batch calls through every entry point, groups of sweeps on the callback path,
 read-outs; tests/test_history_cpu.py pins what the scripts contain), with urf_front_scans asserted wherever urf_policy::plan
-(urban_road_filter_amd/csrc/urf_api.hip) decides without looking at the history; (b) directed histories: a walk through the laser counts,
+(urban_road_filter_amd/csrc/urf_policy.hpp) decides without looking at the history; (b) directed histories: a walk through the laser counts,
 a walk through the per-call tile stride, the row-major probation running out, the switches around the read-outs, the callback path through
 settings changes, stage capture in mid-life.
 

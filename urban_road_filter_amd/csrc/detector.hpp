@@ -83,7 +83,36 @@ struct PointCloud2 {
     bool is_dense = false;
 };
 
-class Detector {
+/* The switches of the fused front end, for both adapters: each setter forwards to the entry point of include/urf.h it is named after and
+ * throws Error(code, that entry point's name) when it fails.  All are off by default and opt-in. */
+class FrontSwitches {
+public:
+    /* urf_set_front_outputs: the reference order and road_marker of a sweep or batch that took the fused front end (a row-major organised
+     * stream) come from that run as it is, instead of a second one through the general kernels that keeps the context on them: with it,
+     * what takes the fused front end keeps taking it with setReferenceOrder(true) / enableRoadMarker(true). */
+    void setFrontOutputs(bool on) { set(urf_set_front_outputs, "urf_set_front_outputs", on); }
+    /* urf_set_front_lasers128 / urf_set_front_long_sweeps: front modes 2 and 3 also take sweeps of 128 lasers per firing (channels == 128,
+     * curbPoints == 5) / of 129..256 tiles of 2048 points (a 128 x 4096 sweep is 256). */
+    void setFrontLasers128(bool on) { set(urf_set_front_lasers128, "urf_set_front_lasers128", on); }
+    void setFrontLongSweeps(bool on) { set(urf_set_front_long_sweeps, "urf_set_front_long_sweeps", on); }
+    /* urf_set_front_curb_points: front mode 3 also takes curbPoints 1..8 with channels == 16 or 32, and with 128 when setFrontLasers128
+     * is on (otherwise 64 lasers only). */
+    void setFrontCurbPoints(bool on) { set(urf_set_front_curb_points, "urf_set_front_curb_points", on); }
+    /* urf_set_front_multi_sector: the fused front end keeps scans whose firings span several star sectors or whose sectors fall inside a
+     * tile (real sensors' azimuth offsets, rotation during a firing, the sweep's seam), with the star-shaped search on and curbPoints == 5. */
+    void setFrontMultiSector(bool on) { set(urf_set_front_multi_sector, "urf_set_front_multi_sector", on); }
+
+protected:
+    urf_ctx* ctx_ = nullptr;
+    void set(int (*entry)(urf_ctx*, int), const char* name, bool on)
+    {
+        const int rc = entry(ctx_, on ? 1 : 0);
+        if (rc != URF_OK)
+            throw Error(rc, name);
+    }
+};
+
+class Detector : public FrontSwitches {
 public:
     explicit Detector(int device = 0, uint32_t max_points = 1u << 20);
     ~Detector();
@@ -94,46 +123,6 @@ public:
      * azimuth inside a ring -- lidar_segmentation.cpp:289-291, 354-367) instead of input order.
      * Costs one extra per-ring sort on the GPU; roi is in input order either way. */
     void setReferenceOrder(bool on) { reference_order_ = on; }
-    /* urf_set_front_outputs: the reference order and road_marker of a sweep that took the fused front end (a row-major organised
-     * stream) come from that run as it is, instead of a second one through the general kernels that keeps the context on them. */
-    void setFrontOutputs(bool on)
-    {
-        const int rc = urf_set_front_outputs(ctx_, on ? 1 : 0);
-        if (rc != URF_OK)
-            throw Error(rc, "urf_set_front_outputs");
-    }
-    /* urf_set_front_lasers128 / urf_set_front_long_sweeps: front modes 2 and 3 also take sweeps of 128 lasers per firing (channels == 128,
-     * curbPoints == 5) / of 129..256 tiles of 2048 points (a 128 x 4096 sweep is 256).  Both are off by default and opt-in. */
-    void setFrontLasers128(bool on)
-    {
-        const int rc = urf_set_front_lasers128(ctx_, on ? 1 : 0);
-        if (rc != URF_OK)
-            throw Error(rc, "urf_set_front_lasers128");
-    }
-    void setFrontLongSweeps(bool on)
-    {
-        const int rc = urf_set_front_long_sweeps(ctx_, on ? 1 : 0);
-        if (rc != URF_OK)
-            throw Error(rc, "urf_set_front_long_sweeps");
-    }
-    /* urf_set_front_curb_points: front mode 3 also takes curbPoints 1..8 with channels == 16 or 32, and with 128 when setFrontLasers128
-     * is on (otherwise 64 lasers only).  Off by default and opt-in. */
-    void setFrontCurbPoints(bool on)
-    {
-        const int rc = urf_set_front_curb_points(ctx_, on ? 1 : 0);
-        if (rc != URF_OK)
-            throw Error(rc, "urf_set_front_curb_points");
-    }
-    /* urf_set_front_multi_sector: the fused front end keeps scans whose firings span several star sectors or whose sectors fall inside a
-     * tile (real sensors' azimuth offsets, rotation during a firing, the sweep's seam), with the star-shaped search on and curbPoints == 5.
-     * Off by default and opt-in. */
-    void setFrontMultiSector(bool on)
-    {
-        const int rc = urf_set_front_multi_sector(ctx_, on ? 1 : 0);
-        if (rc != URF_OK)
-            throw Error(rc, "urf_set_front_multi_sector");
-    }
-
     /* Also build the "road_marker" MarkerArray (lidar_segmentation.cpp:295-351, 369-602, topic :59,601);
      * fixedFrame = params::fixedFrame (cfg:10).  Off by default: the polygon is a visualisation product. */
     void enableRoadMarker(bool on, const std::string& fixed_frame = "left_os1/os1_lidar")
@@ -197,7 +186,6 @@ private:
     void split(const Pending& m);
     static void resolve(const PointCloud2& msg, uint32_t off[3], int64_t& off_intensity, uint64_t& n);
     friend class BatchDetector;
-    urf_ctx* ctx_ = nullptr;
     bool reference_order_ = false;
     bool marker_on_ = false, marker_published_ = false;
     MarkerBuilder marker_;
@@ -225,7 +213,7 @@ private:
  * sizes gives the MarkerArrays Detector gives for the same messages one by one.  Marker points and line strips are built on the
  * device (urf_marker_points_batch -> urf_marker_strips_batch) and come back in one copy; with the marker off, filtered()
  * launches nothing for it. */
-class BatchDetector {
+class BatchDetector : public FrontSwitches {
 public:
     BatchDetector(int device = 0, uint32_t max_points = 1u << 20, uint32_t max_batch = 64);
     ~BatchDetector();
@@ -235,45 +223,6 @@ public:
     void setParams(const urf_params& p);
     urf_params params() const;
     void setReferenceOrder(bool on) { reference_order_ = on; }
-    /* as Detector's: with it, batches that take the fused front end keep taking it with setReferenceOrder(true) / enableRoadMarker(true) */
-    void setFrontOutputs(bool on)
-    {
-        const int rc = urf_set_front_outputs(ctx_, on ? 1 : 0);
-        if (rc != URF_OK)
-            throw Error(rc, "urf_set_front_outputs");
-    }
-    /* urf_set_front_lasers128 / urf_set_front_long_sweeps: front modes 2 and 3 also take sweeps of 128 lasers per firing (channels == 128,
-     * curbPoints == 5) / of 129..256 tiles of 2048 points (a 128 x 4096 sweep is 256).  Both are off by default and opt-in. */
-    void setFrontLasers128(bool on)
-    {
-        const int rc = urf_set_front_lasers128(ctx_, on ? 1 : 0);
-        if (rc != URF_OK)
-            throw Error(rc, "urf_set_front_lasers128");
-    }
-    void setFrontLongSweeps(bool on)
-    {
-        const int rc = urf_set_front_long_sweeps(ctx_, on ? 1 : 0);
-        if (rc != URF_OK)
-            throw Error(rc, "urf_set_front_long_sweeps");
-    }
-    /* urf_set_front_curb_points: front mode 3 also takes curbPoints 1..8 with channels == 16 or 32, and with 128 when setFrontLasers128
-     * is on (otherwise 64 lasers only).  Off by default and opt-in. */
-    void setFrontCurbPoints(bool on)
-    {
-        const int rc = urf_set_front_curb_points(ctx_, on ? 1 : 0);
-        if (rc != URF_OK)
-            throw Error(rc, "urf_set_front_curb_points");
-    }
-    /* urf_set_front_multi_sector: the fused front end keeps scans whose firings span several star sectors or whose sectors fall inside a
-     * tile (real sensors' azimuth offsets, rotation during a firing, the sweep's seam), with the star-shaped search on and curbPoints == 5.
-     * Off by default and opt-in. */
-    void setFrontMultiSector(bool on)
-    {
-        const int rc = urf_set_front_multi_sector(ctx_, on ? 1 : 0);
-        if (rc != URF_OK)
-            throw Error(rc, "urf_set_front_multi_sector");
-    }
-
     /* Dense messages (the driver dropped the non-returns) with a field named "ring" (UINT8 or UINT16, count 1) are put back into firing
      * slots on the device and classified as organised sweeps (urf_classify_batch_pc2_dense, include/urf.h): max_firings = the sensor's
      * firings per revolution, slot_of_ring[ring] = the laser's position inside a firing (empty: the ring is the position).  Same clouds,
@@ -306,7 +255,6 @@ public:
 private:
     void check(int rc, const char* what) const;
     void* grow(void*& p, size_t& cap, size_t bytes);
-    urf_ctx* ctx_ = nullptr;
     void* stream_ = nullptr;
     uint32_t max_points_ = 0, max_batch_ = 0;
     bool reference_order_ = false;

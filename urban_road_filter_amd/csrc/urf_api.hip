@@ -22,6 +22,7 @@
 #include "urf_test_hooks.h"
 #endif
 #include "urf_internal.hpp"
+#include "urf_policy.hpp"
 #include "urf_kernels.hpp"
 #include "urf_front.hpp"
 #include "urf_k_front_sectors.hpp"
@@ -90,170 +91,56 @@ struct lazy_buf {
 #define URF_SCRATCH_MULTI_SECTOR(X) X(front_skey, sstride)
 enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR, URF_SCR_LASERS128, URF_SCR_MULTI_SECTOR };
 
-
-/* curbPoints the fused front end has an instance for: 5 in every mode; with urf_set_front_mode(3) and 64 lasers per firing the values of
- * URF_FRONT_CP_MASK (urf_front.hpp); with urf_set_front_curb_points on top of that (cp_lasers) the same values at 16, 32 and 128 lasers (whether
- * 128 lasers are taken at all is urf_set_front_lasers128's business: urf_policy::plan).  9..30 keep the general kernels everywhere. */
-static bool front_curb_points_ok(int front_mode, bool cp_lasers, unsigned L, int cp)
-{
-    return cp == 5 || (front_mode == 3 && (L == 64u || cp_lasers) && cp >= 1 && cp <= 8 && ((URF_FRONT_CP_MASK >> cp) & 1u) != 0u);
-}
-/* ... and the instances, chosen per call from the laser count (lsh: 4, 5, 6, 7) and the parameters in force: 5 is k_front / k_front32 /
- * k_front16 / k_front128 and k_front_finish / k_front_finish128 in every mode */
-using urf_front_fn = void (*)(urf_kargs, urf_dev_params);
-using urf_front_finish_fn = void (*)(urf_kargs, urf_dev_params, unsigned);
-static urf_front_fn front_kernel(unsigned lsh, int cp, bool ms)
-{
-    if (ms && cp == 5)   /* urf_set_front_multi_sector with the star-shaped search on (urf_policy::plan: a.front_ms) */
-        return lsh == 7u ? k_front128_ms : lsh == 5u ? k_front32_ms : lsh == 4u ? k_front16_ms : k_front_ms;
-    switch (cp) {
+/* The kernels of a call's fused family (urf_policy.hpp: urf_front_family), in one table.  An instance of the march and of the finish kernel
+ * exists per curbPoints (and, for 5, as the march of urf_set_front_multi_sector): the march per laser count -- 16, 32, 64, 128: the family's
+ * `lasers` --, the finish kernel per width, because 64, 32 and 16 lasers share one that reads the count at run time (front_lsh).  The probe,
+ * the transpose and the label kernel exist per width only. */
+struct front_kernels {
+    void (*probe)(urf_kargs, urf_dev_params);
+    void (*transpose)(urf_kargs);
+    void (*march)(urf_kargs, urf_dev_params);
+    void (*finish)(urf_kargs, urf_dev_params, unsigned);
+    void (*label)(urf_kargs, urf_dev_params);
+};
+static const struct {
+    int cp;
+    bool ms;
+    decltype(front_kernels::march) march[4];
+    decltype(front_kernels::finish) finish[2];
+} FRONT_INSTANCES[] = {
+    { 5, false, { k_front16, k_front32, k_front, k_front128 }, { k_front_finish, k_front_finish128 } },   /* the symbols of every front mode */
+    { 5, true, { k_front16_ms, k_front32_ms, k_front_ms, k_front128_ms }, { k_front_finish, k_front_finish128 } },
 #define URF_FRONT_CP_X(n) \
-    case n: return lsh == 7u ? k_front128_cp##n : lsh == 5u ? k_front32_cp##n : lsh == 4u ? k_front16_cp##n : k_front_cp##n;
-        URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
+    { n, false, { k_front16_cp##n, k_front32_cp##n, k_front_cp##n, k_front128_cp##n }, { k_front_finish_cp##n, k_front_finish128_cp##n } },
+    URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
 #undef URF_FRONT_CP_X
-    }
-    return lsh == 7u ? k_front128 : lsh == 5u ? k_front32 : lsh == 4u ? k_front16 : k_front;
-}
-static urf_front_finish_fn front_finish_kernel(unsigned lsh, int cp)
+};
+static front_kernels front_kernels_of(const urf_front_family& f)
 {
-    switch (cp) {   /* (64, 32 and 16 lasers: one kernel, the laser count at run time -- front_lsh) */
-#define URF_FRONT_CP_X(n) \
-    case n: return lsh == 7u ? k_front_finish128_cp##n : k_front_finish_cp##n;
-        URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
-#undef URF_FRONT_CP_X
+    const auto* in = &FRONT_INSTANCES[0];   /* (a call without the fused kernels launches none of them) */
+    for (const auto& i : FRONT_INSTANCES)
+        if (i.cp == f.cp && i.ms == (f.ms != 0))
+            in = &i;
+    return { f.wide ? k_rows_probe128 : k_rows_probe, f.wide ? k_transpose128 : k_transpose, in->march[f.lasers], in->finish[f.wide],
+             f.wide ? k_label_front128 : k_label_front };
+}
+/* ... and the one place where the 128-laser family's candidate lists (URF_FRONT128_CAND_CAP) take the place of the others' */
+static void front_family_args(const urf_front_family& f, uint32_t max_points, urf_kargs& a)
+{
+    if (f.wide) {
+        a.front_cand = a.front_cand128;
+        a.front_all = a.front_all128;
+        a.front_cand_cap = URF_FRONT128_CAND_CAP(max_points);
     }
-    return lsh == 7u ? k_front_finish128 : k_front_finish;
 }
 
-/* Scans of 129..256 tiles (urf_set_front_long_sweeps; 256 tiles: a 128 x 4096 sweep): the same finish kernels with the dynamic LDS their
- * layout needs for that many tiles -- a presence word and a 16-bit count per (tile, lane), 384 B per tile, and the chunk of the candidate
- * list: 108 KiB at 256 tiles, one workgroup per CU instead of four.  A call of at most URF_FRONT_MAX_TILES tiles asks for what it always
- * asked for.  Nothing else in the fused kernels counts tiles: the 16-bit counts hold a lane's ring points in the tiles before, at most
- * 255 x 2048 / 16 < 65536 (16 lasers per firing). */
-#define URF_FRONT_LONG_MAX_TILES 256u
+/* the finish kernels' dynamic LDS for `tiles` tiles (above URF_FRONT_MAX_TILES: urf_set_front_long_sweeps has asked the device) */
 static constexpr size_t urf_finish_lds_bytes(unsigned tiles)
 {
     return (size_t)tiles * 384 + 2 * URF_FINISH_CHUNK * sizeof(urf_u2);
 }
 static_assert(urf_finish_lds_bytes(URF_FRONT_LONG_MAX_TILES) + sizeof(urf_finish_shared_t<URF_FRONT128_L>) <= 160u * 1024u, "a CU's LDS");
 static_assert(URF_FRONT128_TILES2(URF_FRONT_LONG_MAX_TILES) == URF_FRONT_LONG_MAX_TILES, "an even number: k_front_finish128's layout is as large");
-
-/* The launch policy: which kernels a call launches, decided on the host from what the kernels of earlier calls reported through the
- * host-mapped flag words (enum urf_flag).  fold() is the only reader of the words: a batch call runs it in run_pipeline, a sweep of the
- * callback path in urf_classify_pc2_async, before either launches anything.  plan() turns the fields into a call's urf_kargs.  Every
- * change of what plan() reads bumps `epoch` (set()), the key of the callback path's captured sequences: a replayed sequence launches
- * what a fresh one would.  (Hidden: the library exports the C ABI, not this struct's functions.) */
-struct __attribute__((visibility("hidden"))) urf_policy {
-    uint32_t* flags = nullptr;      /* [URF_FLAG_WORDS] pinned, device-mapped (urf_kargs::flags) */
-    uint64_t epoch = 1;             /* bumped by everything a captured sequence depends on (the settings' entry points bump it too) */
-    /* k_ring_table speculates: it stops when no new ring has shown up for a while (speculate) and at the ring count of the row's previous
-     * call (use_hint).  k_split checks; a scan that proves a rule wrong is repaired in the same call and raises its flag word
-     * (URF_FLAG_LOOKAHEAD_FAILED / URF_FLAG_HINT_FAILED), and the context does without that rule from then on. */
-    bool speculate = true, use_hint = true;
-    /* the callback path's short sequence leaves out what normally finds nothing to do; a sweep that needed the kernels for the work lists
-     * of oversized star sectors (slot_lists), for rings with a point on the sensor's axis (slot_nan) or for equal planar ranges in a star
-     * sector (slot_ties: any real sensor's sweep) comes back with a URF_STATUS_REDO_* status and is run again with them, as are all later
-     * ones (on_redo) */
-    bool slot_lists = false, slot_nan = false, slot_ties = false;
-    /* the fused front end (urf_front.hpp, urf_set_front_mode): 0 never, 1 batches of at least URF_FRONT_MIN_SCANS scans (default), 2 every
-     * batch call it applies to, 3 as 2 and curbPoints 1..8 at 64 lasers (every_batch(): 2 or 3).  After a read-back of ring-sorted results the context keeps to the general kernels (want_ring_sorted,
-     * last_call). */
-    int front_mode = 1;
-    bool every_batch() const { return front_mode >= 2; }
-    bool lasers128 = false;         /* urf_set_front_lasers128: modes 2 and 3 take sweeps of 128 lasers per firing too (k_front128*, urf_front.hpp; its scratch is there) */
-    bool curb_points = false;       /* urf_set_front_curb_points: mode 3 takes curbPoints 1..8 at 16, 32 and (lasers128) 128 lasers per firing too (k_front32_cp*, k_front16_cp*, k_front128_cp*) */
-    /* urf_set_front_multi_sector: with the star-shaped search on and curbPoints 5 the march is a k_front*_ms instance and k_front_sectors follows it
-     * (urf_k_front_sectors.hpp): firings that span several sectors, sectors that fall inside a tile stay fused.  Other curbPoints: the plain instances. */
-    bool multi_sector = false;
-    bool long_sweeps = false;       /* urf_set_front_long_sweeps: modes 2 and 3 take scans of up to URF_FRONT_LONG_MAX_TILES tiles (the finish kernels with more dynamic LDS) */
-    uint32_t front_max_tiles() const { return long_sweeps && every_batch() ? URF_FRONT_LONG_MAX_TILES : URF_FRONT_MAX_TILES; }
-    uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
-    bool want_ring_sorted = false;
-    /* urf_set_front_outputs: the published order and the marker points of a fused call come from what it left on the device
-     * (urf_k_front_outputs.hpp) instead of a second run through the general kernels.  Decides no launch of a classify call: not part of
-     * the epoch. */
-    bool front_outputs = false;
-    /* k_front hands a scan without the shape back to the general kernels: launched list-driven until a call has done so
-     * (URF_FLAG_FRONT_HANDED_BACK: front_direct, full grids from then on); mode 1 stops trying once a whole batch has been handed back
-     * (URF_FLAG_FRONT_ALL_HANDED_BACK: front_off, unorganised clouds).  forget_front() starts over. */
-    bool front_direct = false, front_off = false;
-    /* row-major organised sweeps (k_ring_table's third rule): once one has been sighted (URF_FLAG_ROWS_SIGHTED) the firing-order copies are
-     * allocated and the sequences hold k_rows_probe and k_transpose (front_rows; rows_oom: the allocation failed).  Once a scan has taken
-     * the layout (URF_FLAG_ROWS_TAKEN: rows_used), or while the sighting is on probation, batches below mode 1's threshold and the
-     * callback path take the fused kernels too. */
-    bool front_rows = false, rows_oom = false, rows_used = false;
-    uint32_t rows_probation = 0;
-
-    template <class T>
-    void set(T& field, T value)
-    {
-        if (field != value) {
-            field = value;
-            epoch++;
-        }
-    }
-    /* urf_set_params with other parameters, urf_set_front_mode with another mode, the row-major sighting */
-    void forget_front()
-    {
-        set(front_direct, false);
-        set(front_off, false);
-        flags[URF_FLAG_FRONT_HANDED_BACK] = flags[URF_FLAG_FRONT_ALL_HANDED_BACK] = 0;
-    }
-    int fold(urf_ctx* c, hipStream_t st);
-    /* A sighting that no scan confirms (a sweep in firing order whose region of interest begins with a single laser) lapses after 16 calls
-     * that count: every submission on the callback path, whichever kernels it takes, but only those batch calls below mode 1's threshold
-     * that took the fused kernels on its strength. */
-    void probation_sweep() { lapse(front_rows); }
-    void probation_batch(const urf_kargs& a) { lapse(a.front && !every_batch() && a.n_scans < URF_FRONT_MIN_SCANS); }
-    void lapse(bool counts)
-    {
-        if (counts && !rows_used && rows_probation && --rows_probation == 0)
-            epoch++;
-    }
-    /* a sweep of the callback path that the short sequence voided: from now on the sequence holds what it needed (false: no such status) */
-    bool on_redo(int status)
-    {
-        switch (status) {
-        case URF_STATUS_REDO_TABLE: set(speculate, false); return true;
-        case URF_STATUS_REDO_HINT: set(use_hint, false); return true;
-        case URF_STATUS_REDO_LISTS: set(slot_lists, true); return true;
-        case URF_STATUS_REDO_NAN: set(slot_nan, true); return true;
-        case URF_STATUS_REDO_TIES: set(slot_ties, true); return true;
-        }
-        return false;
-    }
-    /* The launch decisions of one call (a.tiles, a.capture, a.n_scans set): slot, a sweep of the callback path; general_only, no fused
-     * kernels (last_call). */
-    void plan(urf_kargs& a, const urf_dev_params& dp, bool slot, bool general_only) const
-    {
-        a.table_lookahead = speculate ? URF_TABLE_LOOKAHEAD : 0u;
-        a.table_hint = (speculate && use_hint) ? 1u : 0u;
-        /* A sweep of the callback path is waited for by the host before anybody sees its result: the kernels that normally find nothing
-         * to do -- the two repair kernels behind the speculative ring table, the two for the work lists of oversized star sectors, 20 of a
-         * sweep's 200 microseconds -- are left out, k_index voids a sweep that needed them, and urf_classify_pc2_wait() runs it again. */
-        a.optimistic = slot ? ((speculate ? URF_OPT_NO_REPAIR : 0u) | (slot_lists ? 0u : URF_OPT_NO_LISTS) | (slot_nan ? 0u : URF_OPT_NO_NAN) |
-                               (slot_ties ? 0u : URF_OPT_NO_TIES)) : 0u;
-        /* The fused front end: a firing of 64, 32 or 16 lasers (params.channels) = the first lanes of a wave, the detectors' window of
-         * curbPoints == 5 (mode 3, 64 lasers -- with urf_set_front_curb_points every laser count --: 1..8, URF_FRONT_CP_MASK; the instance is chosen per call, front_kernel()) in registers, no stage capture (its values are the general kernels').  Row-major sweeps gain from it at any batch size (the general kernels need 0.64 ms for four such
-         * sweeps, the fused ones 0.26, tools/r6_min_scans.py --rows), sweeps in firing order only from 192 per call on, and not as single
-         * sweeps of the callback path (tools/r6_single_sweep.py). */
-        const unsigned L = (unsigned)dp.p.channels;
-        const bool lasers = L == 64u || L == 32u || L == 16u || (L == 128u && lasers128 && every_batch());
-        a.front_lsh = L == 16u ? 4u : (L == 32u ? 5u : (L == 128u ? 7u : 6u));
-        const bool shape = front_mode != 0 && !front_off && !general_only && !want_ring_sorted && a.capture == 0 &&
-                           lasers && front_curb_points_ok(front_mode, curb_points, L, dp.p.curbPoints) && a.tiles <= front_max_tiles();
-        /* (16 / 32 lasers: nothing below mode 2 until their crossover has been measured -- no batch size, no row-major sighting, no callback path) */
-        const bool small_ok = front_rows && (rows_used || rows_probation > 0) && (L == 64u || every_batch());
-        a.front = (shape && (slot ? small_ok : (every_batch() || small_ok || a.n_scans >= (L == 64u ? URF_FRONT_MIN_SCANS : (L == 32u ? URF_FRONT_MIN_SCANS_32 : URF_FRONT_MIN_SCANS_16))))) ? 1u : 0u;
-        a.front_sight = (shape && !a.front && !front_rows && !rows_oom && (L == 64u || every_batch())) ? 1u : 0u;
-        a.front_tpb = front_tpb ? front_tpb : (a.n_scans >= URF_FRONT_TPB_SCANS ? URF_FRONT_TPB_LARGE : (a.n_scans >= 16u ? URF_FRONT_TPB_SMALL : 1u));
-        if (a.front_lsh == 7u)   /* (a presence word of k_front128 covers two tiles: no block may end inside one) */
-            a.front_tpb = a.front_tpb < 2u ? 2u : (a.front_tpb & ~1u);
-        a.front_lists = (a.front && !front_direct && !slot) ? 1u : 0u;   /* (the callback path's sequence holds the general kernels as grids anyway) */
-        a.front_rows = (a.front && front_rows) ? 1u : 0u;   /* (independent of the two other speculations: the repair kernels come with it) */
-        a.front_ms = (a.front && multi_sector && dp.p.star_shaped_method != 0 && dp.p.curbPoints == 5) ? 1u : 0u;
-    }
-};
 
 /* "The last call", for the entry points that take their input from it (urf_read_stage, urf_ordered_indices, urf_marker_points,
  * urf_clouds_batch_*): publish_last() is the only writer of the whole record, last_call() the readers' way to it. */
@@ -455,7 +342,7 @@ static int scratch_alloc(urf_ctx* c, urf_scratch_group group)
 /* What the kernels of earlier calls reported, taken into the policy before a call's launches (never inside a stream capture: the first
  * row-major sighting lets the calls in flight on `st`, the stream the call launches on, finish -- what they handed back, possibly all
  * of their sweeps, says nothing about the calls to come -- and allocates the firing-order copies before the call takes its arguments). */
-int urf_policy::fold(urf_ctx* c, hipStream_t st)
+int urf_policy::fold(urf_ctx* c, hipStream_t st)   /* (hipStream_t: ihipStream_t*) */
 {
     if (front_mode != 0 && !front_rows && !rows_oom && flags[URF_FLAG_ROWS_SIGHTED]) {
         URF_HIP(c, hipStreamSynchronize(st));
@@ -792,77 +679,58 @@ extern "C" int urf_set_front_mode(urf_ctx* c, int mode)
     return URF_OK;
 }
 
-extern "C" int urf_set_front_lasers128(urf_ctx* c, int on)
+/* The on / off switches of the fused front end that plan() reads: `prepare` (may be null) runs when the switch is turned on, before anything
+ * changes, and may refuse; a change is a new start (forget_front); turning a switch on, like urf_set_front_mode, ends want_ring_sorted. */
+static int set_front_switch(urf_ctx* c, int on, bool urf_policy::*field, int (*prepare)(urf_ctx*))
 {
     if (!c || (on != 0 && on != 1))
         return URF_ERR_INVALID_ARG;
-    if (on) {   /* what the fused kernels size for 64 lanes, sized for 128: allocated once, with the first call that turns the switch on */
+    if (on && prepare) {
         URF_HIP(c, hipSetDevice(c->device));
-        const int rc = scratch_alloc(c, URF_SCR_LASERS128);
+        const int rc = prepare(c);
         if (rc != URF_OK)
             return rc;
     }
-    if ((on != 0) != c->pol.lasers128)   /* (a new start) */
+    if ((on != 0) != c->pol.*field)   /* (a new start) */
         c->pol.forget_front();
-    c->pol.set(c->pol.lasers128, on != 0);
+    c->pol.set(c->pol.*field, on != 0);
     if (on)
         c->pol.set(c->pol.want_ring_sorted, false);
     return URF_OK;
 }
 
+extern "C" int urf_set_front_lasers128(urf_ctx* c, int on)
+{   /* what the fused kernels size for 64 lanes, sized for 128: allocated once, with the first call that turns the switch on */
+    return set_front_switch(c, on, &urf_policy::lasers128, [](urf_ctx* x) { return scratch_alloc(x, URF_SCR_LASERS128); });
+}
+
+/* The finish kernels' dynamic LDS at URF_FRONT_LONG_MAX_TILES tiles: a device that does not grant a workgroup that much keeps the switch
+ * off.  Measured on the MI355X: the HIP runtime grants a workgroup the whole 160 KiB without being asked -- a launch
+ * with 110 592 B succeeds without hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize), and the call changes neither that nor
+ * the occupancy below 129 tiles -- so the attribute is not set: this limit is the only condition. */
+static int long_sweeps_lds(urf_ctx* c)
+{
+    int lds_max = 0;
+    URF_HIP(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    if ((size_t)lds_max < urf_finish_lds_bytes(URF_FRONT_LONG_MAX_TILES) + sizeof(urf_finish_shared_t<URF_FRONT128_L>)) {
+        c->last_error = "urf_set_front_long_sweeps: the device grants a workgroup " + std::to_string(lds_max) + " bytes of LDS";
+        return URF_ERR_OOM;
+    }
+    return URF_OK;
+}
 extern "C" int urf_set_front_long_sweeps(urf_ctx* c, int on)
 {
-    if (!c || (on != 0 && on != 1))
-        return URF_ERR_INVALID_ARG;
-    if (on) {
-        /* The finish kernels' dynamic LDS at URF_FRONT_LONG_MAX_TILES tiles: a device that does not grant a workgroup that much keeps the
-         * switch off.  Measured on the MI355X: the HIP runtime grants a workgroup the whole 160 KiB without being
-         * asked -- a launch with 110 592 B succeeds without hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize), and the call
-         * changes neither that nor the occupancy below 129 tiles -- so the attribute is not set: this limit is the only condition. */
-        URF_HIP(c, hipSetDevice(c->device));
-        int lds_max = 0;
-        URF_HIP(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
-        if ((size_t)lds_max < urf_finish_lds_bytes(URF_FRONT_LONG_MAX_TILES) + sizeof(urf_finish_shared_t<URF_FRONT128_L>)) {
-            c->last_error = "urf_set_front_long_sweeps: the device grants a workgroup " + std::to_string(lds_max) + " bytes of LDS";
-            return URF_ERR_OOM;
-        }
-    }
-    if ((on != 0) != c->pol.long_sweeps)   /* (a new start) */
-        c->pol.forget_front();
-    c->pol.set(c->pol.long_sweeps, on != 0);
-    if (on)
-        c->pol.set(c->pol.want_ring_sorted, false);
-    return URF_OK;
+    return set_front_switch(c, on, &urf_policy::long_sweeps, long_sweeps_lds);
 }
 
 extern "C" int urf_set_front_curb_points(urf_ctx* c, int on)
 {
-    if (!c || (on != 0 && on != 1))
-        return URF_ERR_INVALID_ARG;
-    if ((on != 0) != c->pol.curb_points)   /* (a new start) */
-        c->pol.forget_front();
-    c->pol.set(c->pol.curb_points, on != 0);
-    if (on)
-        c->pol.set(c->pol.want_ring_sorted, false);
-    return URF_OK;
+    return set_front_switch(c, on, &urf_policy::curb_points, nullptr);
 }
 
 extern "C" int urf_set_front_multi_sector(urf_ctx* c, int on)
-{
-    if (!c || (on != 0 && on != 1))
-        return URF_ERR_INVALID_ARG;
-    if (on) {   /* the star records' sectors, one per scratch element: allocated once, with the first call that turns the switch on */
-        URF_HIP(c, hipSetDevice(c->device));
-        const int rc = scratch_alloc(c, URF_SCR_MULTI_SECTOR);
-        if (rc != URF_OK)
-            return rc;
-    }
-    if ((on != 0) != c->pol.multi_sector)   /* (a new start) */
-        c->pol.forget_front();
-    c->pol.set(c->pol.multi_sector, on != 0);
-    if (on)
-        c->pol.set(c->pol.want_ring_sorted, false);
-    return URF_OK;
+{   /* the star records' sectors, one per scratch element: allocated once, with the first call that turns the switch on */
+    return set_front_switch(c, on, &urf_policy::multi_sector, [](urf_ctx* x) { return scratch_alloc(x, URF_SCR_MULTI_SECTOR); });
 }
 
 extern "C" int urf_set_front_outputs(urf_ctx* c, int on)
@@ -1080,25 +948,18 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
         stage++;
     };
     mark();
-    const bool l128 = a.front_lsh == 7u;   /* 128 lasers per firing: k_front128* and its siblings (urf_front.hpp) */
-    if (l128 && a.front) {   /* ... and their candidate lists (URF_FRONT128_CAND_CAP) */
-        a.front_cand = a.front_cand128;
-        a.front_all = a.front_all128;
-        a.front_cand_cap = URF_FRONT128_CAND_CAP(c->max_points);
-    }
-    if (a.front_rows && l128)
-        hipLaunchKernelGGL(k_rows_probe128, g_scan, dim3(256), 0, st, a, dp);
-    else if (a.front_rows)
-        hipLaunchKernelGGL(k_rows_probe, g_scan, dim3(256), 0, st, a, dp);
+    const urf_front_family fam = urf_front_family_of(a.front, a.front_lsh, a.front_rows, a.front_ms, a.tiles, dp.p.curbPoints);
+    const front_kernels fk = front_kernels_of(fam);
+    front_family_args(fam, c->max_points, a);
+    if (fam.rows)
+        hipLaunchKernelGGL(fk.probe, g_scan, dim3(256), 0, st, a, dp);
     hipLaunchKernelGGL(k_ring_table, g_scan, dim3(URF_TABLE_THREADS), 0, st, a, dp);
     mark();
-    if (a.front_rows && l128)
-        hipLaunchKernelGGL(k_transpose128, g_tiles, dim3(256), 0, st, a);
-    else if (a.front_rows)
-        hipLaunchKernelGGL(k_transpose, g_tiles, dim3(256), 0, st, a);
+    if (fam.rows)
+        hipLaunchKernelGGL(fk.transpose, g_tiles, dim3(256), 0, st, a);
     if (a.front) {   /* (a tile is URF_TILE points, whatever the laser count: URF_TILE / L firings) */
         const dim3 g_front((a.tiles + a.front_tpb - 1) / a.front_tpb, n_scans);
-        hipLaunchKernelGGL(front_kernel(a.front_lsh, dp.p.curbPoints, a.front_ms != 0u), g_front, dim3(64), 0, st, a, dp);
+        hipLaunchKernelGGL(fk.march, g_front, dim3(64), 0, st, a, dp);
     }
     if (a.front_lists) {   /* what k_front handed back (normally nothing) */
         hipLaunchKernelGGL(k_table_repair, g_scan, dim3(URF_TABLE_THREADS), 0, st, a, dp, 1u);
@@ -1119,10 +980,9 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
      * own), they are bound by vector issue.  With the per-kernel event brackets on (urf_enable_kernel_timing) everything stays on one
      * stream, so that the brackets add up to the step. */
     bool side = false, part1 = false;
-    const size_t finish_lds = urf_finish_lds_bytes(l128 ? URF_FRONT128_TILES2(a.tiles) : a.tiles);   /* (above URF_FRONT_MAX_TILES tiles: urf_set_front_long_sweeps has asked the device) */
-    const urf_front_finish_fn finish = front_finish_kernel(a.front_lsh, dp.p.curbPoints);
+    const size_t finish_lds = urf_finish_lds_bytes(fam.finish_tiles);
     if (a.front && !ev && !slot && side_fork(c, st)) {
-        hipLaunchKernelGGL(finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, c->side_stream, a, dp, 1u);
+        hipLaunchKernelGGL(fk.finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, c->side_stream, a, dp, 1u);
         part1 = true;
         side = hipEventRecord(c->ev_join, c->side_stream) == hipSuccess;
         if (!side)   /* (cannot be joined by an event: wait for it here) */
@@ -1175,7 +1035,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
     if (a.front) {
         if (side && hipStreamWaitEvent(st, c->ev_join, 0) != hipSuccess)
             (void)hipStreamSynchronize(c->side_stream);
-        hipLaunchKernelGGL(finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, st, a, dp, part1 ? 2u : 0u);   /* (2: the star-shaped hits, the hand-over to k_beams) */
+        hipLaunchKernelGGL(fk.finish, g_scan, dim3(URF_FINISH_THREADS), finish_lds, st, a, dp, part1 ? 2u : 0u);   /* (2: the star-shaped hits, the hand-over to k_beams) */
     }
     /* the rings that hold a point with a NaN azimuth (k_split listed them: normally none, the kernel returns at once) */
     if (!(a.optimistic & URF_OPT_NO_NAN))
@@ -1187,10 +1047,8 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
         hipLaunchKernelGGL(k_label_list, dim3(c->n_cus * 4), dim3(URF_LABEL_TILE_THREADS), 0, st, a, dp);
     else
         hipLaunchKernelGGL(k_label, g_tiles, dim3(URF_LABEL_TILE_THREADS), 0, st, a, dp);
-    if (a.front && l128)
-        hipLaunchKernelGGL(k_label_front128, g_tiles, dim3(URF_LABEL_TILE_THREADS), 0, st, a, dp);
-    else if (a.front)
-        hipLaunchKernelGGL(k_label_front, g_tiles, dim3(URF_LABEL_TILE_THREADS), 0, st, a, dp);
+    if (a.front)
+        hipLaunchKernelGGL(fk.label, g_tiles, dim3(URF_LABEL_TILE_THREADS), 0, st, a, dp);
     mark();
     URF_HIP(c, hipGetLastError());
     if (call.info)

@@ -61,6 +61,8 @@
 #ifndef URF_FRONT_HPP
 #define URF_FRONT_HPP
 
+#include "urf_policy.hpp"
+
 #define URF_FRONT_HPRE 8u      /* firings in front of a block: 7 fill a window without holes (x_zero's j >= 5 rule) */
 #ifndef URF_FRONT_HPRE_WIDE
 #define URF_FRONT_HPRE_WIDE 12u   /* ... for curbPoints 6..8 (mode 3): the point x_zero marks needs CP + CP / 2 = 9, 10, 12 ring points in front of it */
@@ -70,41 +72,20 @@
 #endif
 #define URF_FRONT_LANES 64u
 #define URF_FRONT_STEPS (URF_TILE / URF_FRONT_LANES)   /* firings per tile */
-#define URF_FRONT_MIN_SCANS 192u  /* below (mode 1): the general kernels.  A block of k_front is ONE wave marching 80-144 dependent steps, k_front_finish one
-                                   * workgroup per scan: with few scans the device is empty and the chains are the time (tools/r6_min_scans.py, general / fused ms per call:
-                                   * 32 sweeps 0.21 / 0.25-0.33, 64: 0.31 / 0.32-0.40, 128: 0.45 / 0.44-0.50, 256: 0.73 / 0.66-0.70, 1024: 2.44 / 2.1) */
-#define URF_FRONT_MIN_SCANS_32 0xffffffffu   /* 32 / 16 lasers per firing, mode 1: never (mode 2 only) */
-#define URF_FRONT_MIN_SCANS_16 0xffffffffu
-#define URF_FRONT_TPB_SMALL 2u    /* tiles per block of k_front for batches below URF_FRONT_TPB_SCANS scans (more, shorter chains), ... */
-#define URF_FRONT_TPB_LARGE 4u    /* ... and from there on (less halo): 256 sweeps 0.663 / 0.703 ms at 2 / 4, 1024 sweeps 0.829 / 0.820 */
-#define URF_FRONT_TPB_SCANS 512u
-#define URF_FRONT_CP_MASK 0x1feu   /* curbPoints with a fused instance at 64 lasers (bit cp; 5 in every mode, the others with urf_set_front_mode(3)) */
-/* ... and the values besides 5, for everything that exists once per value: the march at four laser counts (k_front*_cp<n>), the finish
- * kernels (k_front_finish*_cp<n>) and the host's choice among them (urf_api.hip) */
-#define URF_FRONT_CP_OTHERS(X) X(1) X(2) X(3) X(4) X(6) X(7) X(8)
-#define URF_FRONT_MAX_TILES 128u  /* k_front_finish keeps a presence word per (tile, lane) in LDS */
+/* (What only the host's decision reads -- batch thresholds, tiles per block, URF_FRONT_CP_OTHERS, tile limits, URF_FRONT128_TILES2 -- stands in urf_policy.hpp.) */
+#define URF_FRONT_CP_MASK 0x1feu   /* urf_policy.hpp's, repeated to the letter: tests/test_front_curb_points_resources.py reads it here */
 #define URF_FRONT_RING_NONE 0x7fu  /* ring field of an input-order record */
 #define URF_FRONT_ST_WORDS 72u   /* k_front_finish part 1 -> part 2: 64 list lengths, 4 quadrant values, the length of the list of marks, two counts */
 /* ... and of the 128-laser family (urf_set_front_lasers128), whose arrays are the siblings sized for 128 (urf_kargs::*128), allocated when
  * the switch is turned on.  What these kernels leave behind keeps the layout its readers know, indexed by f * 128 + l: region-of-interest bits
  * (two 64-bit words per firing), slots (stp * 128 + l < 2048), tsoff, candidate indices.  A tile is 16 firings and a presence word 32 of
  * them: word (f >> 5) * 128 + l covers two tiles, so the words per scan are counted for an even number of tiles (URF_FRONT128_TILES2), and a
- * block of the march holds an even number of tiles (front_tpb, urf_api.hip) -- no presence word is shared between two blocks. */
+ * block of the march holds an even number of tiles (front_tpb, urf_policy.hpp) -- no presence word is shared between two blocks. */
 #define URF_FRONT128_L 128u
 #define URF_FRONT128_LSH 7u
 #define URF_FRONT128_RING_MASK 0xffu   /* ring field of an input-order record of these kernels: table entry 127 is a ring, 0xff is "none" */
 #define URF_FRONT128_RING_NONE 0xffu
-#define URF_FRONT128_TILES2(tiles) (((tiles) + 1u) & ~1u)   /* a presence word covers 32 firings, two tiles of 128 lasers: words and block maxima are counted for an even number */
 #define URF_FRONT128_ST_WORDS 136u     /* k_front_finish128 part 1 -> part 2: 128 list lengths, 4 quadrant values, list length, two counts */
-/* Entries per scan of the candidate lists of these kernels.  The points that pass the march's height tests are counted per LASER, not per
- * column: a ring that crosses a curb hands on up to eleven centres (z_zero) and six marked points (x_zero) per crossing, a street has four
- * crossings per ring -- 128 x 68 = 8 704 for 128 lasers however short the sweep is (a 128 x 256 street of urf_synth_cloud: 5 200 - 5 600),
- * above the context's max(max_points / 8, 4096) for sweeps below 128 x 544.  Twice that for range noise; a list that overflows still only
- * hands its scan back.
- * curbPoints 1..8 (urf_set_front_curb_points): 2 * CP + 1 centres and CP + 1 marked points per crossing, at 8 that is 17 and 9 -- 4 x 26 = 104 per
- * laser: 128 x 104 = 13 312 here, below the cap as it is; 32 x 104 = 3 328 and 16 x 104 = 1 664 at 32 and 16 lasers, below the context's floor of
- * 4096 (a block's border adds at most 2 * CP edge items per laser: 16 more per block).  No cap grows for the new instances. */
-#define URF_FRONT128_CAND_CAP(max_points) ((max_points) / 8u > 16384u ? (max_points) / 8u : 16384u)
 /* candidate kinds */
 #define URF_FC_XZ 1u       /* passed x_zero's height tests as the marked point: angle test pending */
 #define URF_FC_ZZ 2u       /* passed z_zero's as the centre */
@@ -499,7 +480,7 @@ __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev
     const unsigned s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
     unsigned off, len;
     urf_scan_range(a, s, off, len);
-    const unsigned TPB = a.front_tpb;   /* (128 lasers: even, urf_api.hip -- no presence word is shared between two blocks) */
+    const unsigned TPB = a.front_tpb;   /* (128 lasers: even, urf_policy.hpp -- no presence word is shared between two blocks) */
     const unsigned t_first = b * TPB;
     if (t_first * URF_TILE >= len)
         return;

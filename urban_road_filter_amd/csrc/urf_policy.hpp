@@ -1,0 +1,208 @@
+/* urf_policy.hpp -- the launch policy of the host API: which kernels a call launches (urf_policy::plan) and which family of the fused
+ * front end they belong to (urf_front_family_of).  Host code without a HIP call: it compiles with a plain C++17 compiler, and
+ * tests/cpp/policy_table.cpp walks its decisions without a GPU. */
+#ifndef URF_POLICY_HPP
+#define URF_POLICY_HPP
+
+#include <cstdint>
+
+#include "urf_internal.hpp"
+
+struct urf_ctx;
+struct ihipStream_t;   /* (hipStream_t is a pointer to it: fold() is the one member that needs HIP, defined in urf_api.hip) */
+
+/* ---- what only the host's decision reads of the fused front end (the kernels: urf_front.hpp) ---- */
+#define URF_FRONT_MIN_SCANS 192u  /* below (mode 1): the general kernels.  A block of k_front is ONE wave marching 80-144 dependent steps, k_front_finish one
+                                   * workgroup per scan: with few scans the device is empty and the chains are the time (tools/r6_min_scans.py, general / fused ms per call:
+                                   * 32 sweeps 0.21 / 0.25-0.33, 64: 0.31 / 0.32-0.40, 128: 0.45 / 0.44-0.50, 256: 0.73 / 0.66-0.70, 1024: 2.44 / 2.1) */
+#define URF_FRONT_MIN_SCANS_32 0xffffffffu   /* 32 / 16 lasers per firing, mode 1: never (mode 2 only) */
+#define URF_FRONT_MIN_SCANS_16 0xffffffffu
+#define URF_FRONT_TPB_SMALL 2u    /* tiles per block of k_front for batches below URF_FRONT_TPB_SCANS scans (more, shorter chains), ... */
+#define URF_FRONT_TPB_LARGE 4u    /* ... and from there on (less halo): 256 sweeps 0.663 / 0.703 ms at 2 / 4, 1024 sweeps 0.829 / 0.820 */
+#define URF_FRONT_TPB_SCANS 512u
+#define URF_FRONT_CP_MASK 0x1feu   /* curbPoints with a fused instance at 64 lasers (bit cp; 5 in every mode, the others with urf_set_front_mode(3)) */
+/* ... and the values besides 5, for everything that exists once per value: the march at four laser counts (k_front*_cp<n>), the finish
+ * kernels (k_front_finish*_cp<n>) and the host's choice among them (urf_front_family_of, urf_api.hip: front_kernels) */
+#define URF_FRONT_CP_OTHERS(X) X(1) X(2) X(3) X(4) X(6) X(7) X(8)
+#define URF_FRONT_MAX_TILES 128u  /* k_front_finish keeps a presence word per (tile, lane) in LDS */
+#define URF_FRONT128_TILES2(tiles) (((tiles) + 1u) & ~1u)   /* a presence word covers 32 firings, two tiles of 128 lasers: words and block maxima are counted for an even number */
+/* Entries per scan of the candidate lists of these kernels.  The points that pass the march's height tests are counted per LASER, not per
+ * column: a ring that crosses a curb hands on up to eleven centres (z_zero) and six marked points (x_zero) per crossing, a street has four
+ * crossings per ring -- 128 x 68 = 8 704 for 128 lasers however short the sweep is (a 128 x 256 street of urf_synth_cloud: 5 200 - 5 600),
+ * above the context's max(max_points / 8, 4096) for sweeps below 128 x 544.  Twice that for range noise; a list that overflows still only
+ * hands its scan back.
+ * curbPoints 1..8 (urf_set_front_curb_points): 2 * CP + 1 centres and CP + 1 marked points per crossing, at 8 that is 17 and 9 -- 4 x 26 = 104 per
+ * laser: 128 x 104 = 13 312 here, below the cap as it is; 32 x 104 = 3 328 and 16 x 104 = 1 664 at 32 and 16 lasers, below the context's floor of
+ * 4096 (a block's border adds at most 2 * CP edge items per laser: 16 more per block).  No cap grows for the new instances. */
+#define URF_FRONT128_CAND_CAP(max_points) ((max_points) / 8u > 16384u ? (max_points) / 8u : 16384u)
+/* Scans of 129..256 tiles (urf_set_front_long_sweeps; 256 tiles: a 128 x 4096 sweep): the same finish kernels with the dynamic LDS their
+ * layout needs for that many tiles -- a presence word and a 16-bit count per (tile, lane), 384 B per tile, and the chunk of the candidate
+ * list: 108 KiB at 256 tiles, one workgroup per CU instead of four.  A call of at most URF_FRONT_MAX_TILES tiles asks for what it always
+ * asked for.  Nothing else in the fused kernels counts tiles: the 16-bit counts hold a lane's ring points in the tiles before, at most
+ * 255 x 2048 / 16 < 65536 (16 lasers per firing). */
+#define URF_FRONT_LONG_MAX_TILES 256u
+
+/* The launch policy: which kernels a call launches, decided on the host from what the kernels of earlier calls reported through the
+ * host-mapped flag words (enum urf_flag).  fold() is the only reader of the words: a batch call runs it in run_pipeline, a sweep of the
+ * callback path in urf_classify_pc2_async, before either launches anything.  plan() turns the fields into a call's urf_kargs.  Every
+ * change of what plan() reads bumps `epoch` (set()), the key of the callback path's captured sequences: a replayed sequence launches
+ * what a fresh one would.  (Hidden: the library exports the C ABI, not this struct's functions.) */
+struct __attribute__((visibility("hidden"))) urf_policy {
+    uint32_t* flags = nullptr;      /* [URF_FLAG_WORDS] pinned, device-mapped (urf_kargs::flags) */
+    uint64_t epoch = 1;             /* bumped by everything a captured sequence depends on (the settings' entry points bump it too) */
+    /* k_ring_table speculates: it stops when no new ring has shown up for a while (speculate) and at the ring count of the row's previous
+     * call (use_hint).  k_split checks; a scan that proves a rule wrong is repaired in the same call and raises its flag word
+     * (URF_FLAG_LOOKAHEAD_FAILED / URF_FLAG_HINT_FAILED), and the context does without that rule from then on. */
+    bool speculate = true, use_hint = true;
+    /* the callback path's short sequence leaves out what normally finds nothing to do; a sweep that needed the kernels for the work lists
+     * of oversized star sectors (slot_lists), for rings with a point on the sensor's axis (slot_nan) or for equal planar ranges in a star
+     * sector (slot_ties: any real sensor's sweep) comes back with a URF_STATUS_REDO_* status and is run again with them, as are all later
+     * ones (on_redo) */
+    bool slot_lists = false, slot_nan = false, slot_ties = false;
+    /* the fused front end (urf_front.hpp, urf_set_front_mode): 0 never, 1 batches of at least URF_FRONT_MIN_SCANS scans (default), 2 every
+     * batch call it applies to, 3 as 2 and curbPoints 1..8 at 64 lasers (every_batch(): 2 or 3).  After a read-back of ring-sorted results the
+     * context keeps to the general kernels (want_ring_sorted, last_call). */
+    int front_mode = 1;
+    bool every_batch() const { return front_mode >= 2; }
+    /* urf_set_front_lasers128: modes 2 and 3 take sweeps of 128 lasers per firing too (k_front128*, urf_front.hpp; its scratch is there) */
+    bool lasers128 = false;
+    /* urf_set_front_curb_points: mode 3 takes curbPoints 1..8 at 16, 32 and (lasers128) 128 lasers per firing too (k_front32_cp*,
+     * k_front16_cp*, k_front128_cp*) */
+    bool curb_points = false;
+    /* urf_set_front_multi_sector: with the star-shaped search on and curbPoints 5 the march is a k_front*_ms instance and k_front_sectors
+     * follows it (urf_k_front_sectors.hpp): firings that span several sectors, sectors that fall inside a tile stay fused.  Other
+     * curbPoints: the plain instances. */
+    bool multi_sector = false;
+    bool long_sweeps = false;       /* urf_set_front_long_sweeps: modes 2 and 3 take scans of up to URF_FRONT_LONG_MAX_TILES tiles */
+    uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
+    bool want_ring_sorted = false;
+    /* urf_set_front_outputs: the published order and the marker points of a fused call come from what it left on the device
+     * (urf_k_front_outputs.hpp) instead of a second run through the general kernels.  Decides no launch of a classify call: not part of
+     * the epoch. */
+    bool front_outputs = false;
+    /* k_front hands a scan without the shape back to the general kernels: launched list-driven until a call has done so
+     * (URF_FLAG_FRONT_HANDED_BACK: front_direct, full grids from then on); mode 1 stops trying once a whole batch has been handed back
+     * (URF_FLAG_FRONT_ALL_HANDED_BACK: front_off, unorganised clouds).  forget_front() starts over. */
+    bool front_direct = false, front_off = false;
+    /* row-major organised sweeps (k_ring_table's third rule): once one has been sighted (URF_FLAG_ROWS_SIGHTED) the firing-order copies are
+     * allocated and the sequences hold k_rows_probe and k_transpose (front_rows; rows_oom: the allocation failed).  Once a scan has taken
+     * the layout (URF_FLAG_ROWS_TAKEN: rows_used), or while the sighting is on probation, batches below mode 1's threshold and the
+     * callback path take the fused kernels too. */
+    bool front_rows = false, rows_oom = false, rows_used = false;
+    uint32_t rows_probation = 0;
+
+    template <class T>
+    void set(T& field, T value)
+    {
+        if (field != value) {
+            field = value;
+            epoch++;
+        }
+    }
+    /* urf_set_params with other parameters, urf_set_front_mode with another mode, the row-major sighting */
+    void forget_front()
+    {
+        set(front_direct, false);
+        set(front_off, false);
+        flags[URF_FLAG_FRONT_HANDED_BACK] = flags[URF_FLAG_FRONT_ALL_HANDED_BACK] = 0;
+    }
+    int fold(urf_ctx* c, ihipStream_t* st);
+    /* A sighting that no scan confirms (a sweep in firing order whose region of interest begins with a single laser) lapses after 16 calls
+     * that count: every submission on the callback path, whichever kernels it takes, but only those batch calls below mode 1's threshold
+     * that took the fused kernels on its strength. */
+    void probation_sweep() { lapse(front_rows); }
+    void probation_batch(const urf_kargs& a) { lapse(a.front && !every_batch() && a.n_scans < URF_FRONT_MIN_SCANS); }
+    void lapse(bool counts)
+    {
+        if (counts && !rows_used && rows_probation && --rows_probation == 0)
+            epoch++;
+    }
+    /* a sweep of the callback path that the short sequence voided: from now on the sequence holds what it needed (false: no such status) */
+    bool on_redo(int status)
+    {
+        switch (status) {
+        case URF_STATUS_REDO_TABLE: set(speculate, false); return true;
+        case URF_STATUS_REDO_HINT: set(use_hint, false); return true;
+        case URF_STATUS_REDO_LISTS: set(slot_lists, true); return true;
+        case URF_STATUS_REDO_NAN: set(slot_nan, true); return true;
+        case URF_STATUS_REDO_TIES: set(slot_ties, true); return true;
+        }
+        return false;
+    }
+    /* ---- what plan() asks of the settings, each question in one place ---- */
+    /* the lasers per firing the fused kernels take: 64, 32 and 16; 128 with urf_set_front_lasers128 in modes 2 and 3 */
+    bool lasers_ok(unsigned L) const { return L == 64u || L == 32u || L == 16u || (L == 128u && lasers128 && every_batch()); }
+    /* the curbPoints they have an instance for: 5 in every mode; with urf_set_front_mode(3) and 64 lasers per firing the values of
+     * URF_FRONT_CP_MASK; with urf_set_front_curb_points on top of that the same values at 16, 32 and 128 lasers (whether 128 lasers are
+     * taken at all is lasers_ok's business).  9..30 keep the general kernels everywhere. */
+    bool curb_points_ok(unsigned L, int cp) const { return cp == 5 || (front_mode == 3 && (L == 64u || curb_points) && cp >= 1 && cp <= 8 && ((URF_FRONT_CP_MASK >> cp) & 1u) != 0u); }
+    /* the tiles per scan: urf_set_front_long_sweeps raises the limit in modes 2 and 3 (the finish kernels with more dynamic LDS) */
+    uint32_t front_max_tiles() const { return long_sweeps && every_batch() ? URF_FRONT_LONG_MAX_TILES : URF_FRONT_MAX_TILES; }
+    /* mode 1: the scans per batch call from which sweeps in firing order gain (16 / 32 lasers: never, until their crossover has been measured) */
+    static uint32_t min_scans(unsigned L) { return L == 64u ? URF_FRONT_MIN_SCANS : (L == 32u ? URF_FRONT_MIN_SCANS_32 : URF_FRONT_MIN_SCANS_16); }
+    /* Row-major sweeps gain at any batch size (the general kernels need 0.64 ms for four such sweeps, the fused ones 0.26, tools/r6_min_scans.py
+     * --rows): once a scan has taken the layout, or while the sighting is on probation, batches below min_scans() and the callback path take the
+     * fused kernels too.  (16 / 32 / 128 lasers: nothing below mode 2 -- no batch size, no row-major sighting, no callback path.) */
+    bool small_ok(unsigned L) const { return front_rows && (rows_used || rows_probation > 0) && (L == 64u || every_batch()); }
+    /* tiles per block of k_front: what URF_FRONT_TPB says, else by batch size; 128 lasers (lsh 7): an even number, because a presence word
+     * of k_front128 covers two tiles and no block may end inside one */
+    uint32_t tiles_per_block(uint32_t n_scans, uint32_t lsh) const
+    {
+        const uint32_t tpb = front_tpb ? front_tpb : (n_scans >= URF_FRONT_TPB_SCANS ? URF_FRONT_TPB_LARGE : (n_scans >= 16u ? URF_FRONT_TPB_SMALL : 1u));
+        return lsh != 7u ? tpb : (tpb < 2u ? 2u : (tpb & ~1u));
+    }
+
+    /* The launch decisions of one call (a.tiles, a.capture, a.n_scans set): slot, a sweep of the callback path; general_only, no fused
+     * kernels (last_call). */
+    void plan(urf_kargs& a, const urf_dev_params& dp, bool slot, bool general_only) const
+    {
+        a.table_lookahead = speculate ? URF_TABLE_LOOKAHEAD : 0u;
+        a.table_hint = (speculate && use_hint) ? 1u : 0u;
+        /* A sweep of the callback path is waited for by the host before anybody sees its result: the kernels that normally find nothing
+         * to do -- the two repair kernels behind the speculative ring table, the two for the work lists of oversized star sectors, 20 of a
+         * sweep's 200 microseconds -- are left out, k_index voids a sweep that needed them, and urf_classify_pc2_wait() runs it again. */
+        a.optimistic = slot ? ((speculate ? URF_OPT_NO_REPAIR : 0u) | (slot_lists ? 0u : URF_OPT_NO_LISTS) | (slot_nan ? 0u : URF_OPT_NO_NAN) |
+                               (slot_ties ? 0u : URF_OPT_NO_TIES)) : 0u;
+        /* The fused front end: a firing of 64, 32 or 16 lasers (params.channels) = the first lanes of a wave (128: two per lane), the
+         * detectors' window of curbPoints points in registers (the instance is chosen per call: urf_front_family_of), no stage capture (its
+         * values are the general kernels').  Sweeps in firing order gain from 192 per call on, and not as single sweeps of the callback path
+         * (tools/r6_single_sweep.py); row-major ones always (small_ok). */
+        const unsigned L = (unsigned)dp.p.channels;
+        a.front_lsh = L == 16u ? 4u : (L == 32u ? 5u : (L == 128u ? 7u : 6u));
+        const bool shape = front_mode != 0 && !front_off && !general_only && !want_ring_sorted && a.capture == 0 && lasers_ok(L) &&
+                           curb_points_ok(L, dp.p.curbPoints) && a.tiles <= front_max_tiles();
+        const bool enough = slot ? small_ok(L) : (every_batch() || small_ok(L) || a.n_scans >= min_scans(L));
+        a.front = (shape && enough) ? 1u : 0u;
+        a.front_sight = (shape && !a.front && !front_rows && !rows_oom && (L == 64u || every_batch())) ? 1u : 0u;
+        a.front_tpb = tiles_per_block(a.n_scans, a.front_lsh);
+        a.front_lists = (a.front && !front_direct && !slot) ? 1u : 0u;   /* (the callback path's sequence holds the general kernels as grids anyway) */
+        a.front_rows = (a.front && front_rows) ? 1u : 0u;   /* (independent of the two other speculations: the repair kernels come with it) */
+        a.front_ms = (a.front && multi_sector && dp.p.star_shaped_method != 0 && dp.p.curbPoints == 5) ? 1u : 0u;
+    }
+};
+
+/* The family of the fused front end a call's kernels belong to, from what plan() decided (a.front, a.front_lsh, a.front_rows, a.front_ms,
+ * a.tiles) and the call's curbPoints.  urf_api.hip's table (front_kernels) turns it into the kernels; nothing else on the host knows
+ * what differs between the families.  A call without the fused kernels: all zero. */
+struct urf_front_family {
+    uint8_t fused;          /* a.front */
+    uint8_t lasers;         /* 0, 1, 2, 3: 16, 32, 64, 128 lasers per firing (the march: k_front16*, k_front32*, k_front*, k_front128*) */
+    uint8_t wide;           /* 128 lasers: probe, transpose, finish and label kernel are the *128 siblings, the candidate lists likewise */
+    uint8_t cp;             /* the march's and the finish kernel's instance: 5, or the call's curbPoints where it is one of URF_FRONT_CP_OTHERS */
+    uint8_t ms;             /* the march is the k_front*_ms instance (a.front_ms; cp is 5) */
+    uint8_t rows;           /* the probe and the transpose are launched (a.front_rows) */
+    uint32_t finish_tiles;  /* the tiles the finish kernel's dynamic LDS is sized for (128 lasers: an even number) */
+};
+static inline urf_front_family urf_front_family_of(uint32_t front, uint32_t front_lsh, uint32_t front_rows, uint32_t front_ms, uint32_t tiles, int cp)
+{
+    if (!front)
+        return urf_front_family{ 0, 0, 0, 0, 0, 0, 0u };
+#define URF_FRONT_CP_X(n) || cp == n
+    const bool other = false URF_FRONT_CP_OTHERS(URF_FRONT_CP_X);
+#undef URF_FRONT_CP_X
+    const bool wide = front_lsh == 7u;
+    return urf_front_family{ 1, (uint8_t)(front_lsh - 4u), wide, (uint8_t)(other ? cp : 5), front_ms != 0u, front_rows != 0u,
+                             wide ? URF_FRONT128_TILES2(tiles) : tiles };
+}
+
+#endif /* URF_POLICY_HPP */
