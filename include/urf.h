@@ -70,7 +70,8 @@ extern "C" {
  * urf_marker_strips_batch with struct urf_marker_strip, URF_MARKER_MAX_STRIPS, URF_MARKER_MAX_STRIP_POINTS (the line strips of
  * road_marker: one sweep on the host, a batch of sweeps on the device); urf_classify_batch_soa_dense / urf_classify_batch_pc2_dense with
  * urf_set_dense_slots and urf_dense_scans (dense sweeps put back into firing slots by laser id on the device, then classified as
- * organised ones); urf_set_front_curb_points (front mode 3's curbPoints 1..8 at 16, 32 and 128 lasers per firing as well).
+ * organised ones); urf_set_front_curb_points (front mode 3's curbPoints 1..8 at 16, 32 and 128 lasers per firing as well);
+ * urf_set_front_multi_sector_curb_points (urf_set_front_multi_sector at curbPoints 1..8 instead of 5 only).
  * WHICH std::sort (4 above): the one of libstdc++ as shipped with GCC 5 .. 13 (bits/stl_algo.h: __sort = __introsort_loop with
  * _S_threshold 16, __move_median_to_first on (first + 1, mid, last - 1), __unguarded_partition, depth limit 2 * floor(log2 n),
  * __partial_sort as the fallback, then __final_insertion_sort); tests/test_stdsort.py pins the restatement against the std::sort
@@ -568,11 +569,22 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * per participant, and k_front_sectors behind it (urban_road_filter_amd/csrc/urf_k_front_sectors.hpp), which puts every tile's star records in
  * sector order; everything downstream is unchanged, labels and summaries are identical.  Every OTHER rule of the shape still hands a scan
  * back (one laser, one ring; ranges; a ring point on the sensor's axis; unorganised clouds).  curbPoints 1..4 and 6..8 (mode 3) keep
- * their plain instances and with them today's hand-back of such scans; with the star-shaped search off sectors do not matter and the plain
+ * their plain instances and with them the hand-back of such scans unless urf_set_front_multi_sector_curb_points (below) is on as well;
+ * with the star-shaped search off sectors do not matter and the plain
  * kernel is launched.  Firing order, row-major, ragged batches, the callback path's row-major sweeps, urf_set_front_long_sweeps,
  * urf_set_front_outputs and the dense entry points keep their meaning.  With the switch off every call launches exactly what it launched
  * before the switch existed.  Turning it on allocates two bytes per scratch element (URF_ERR_OOM: it stays off).  Opt-in: its times are in
- * profiles/front_multi_sector_bench.json. */
+ * profiles/front_multi_sector_bench.json.
+ *
+ * ... at curbPoints 1..8 (urf_set_front_multi_sector_curb_points): the multi-sector march exists for curbPoints 5 only unless this switch
+ * is on.  With it on AND urf_set_front_multi_sector on, a call that takes the fused kernels with the star-shaped search on and curbPoints
+ * 1..4 or 6..8 launches the k_front*_ms_cp<n> instance of the march (the window of 2 * curbPoints + 1 heights of k_front*_cp<n>, any
+ * sector per participant) with k_front_sectors behind it; the finish step is the plain one of that curbPoints.  Whether such a call takes
+ * the fused kernels at all is decided as before: front mode 3 at 64 lasers, urf_set_front_curb_points on top of it at 16, 32 and 128,
+ * urf_set_front_lasers128 for 128.  The switch decides nothing with urf_set_front_multi_sector off, in front modes below 3, with the
+ * star-shaped search off, at curbPoints 5 and at curbPoints 9..30, and it allocates nothing.  Labels and summaries are identical; with the
+ * switch off every call launches exactly what it launched before the switch existed.  Opt-in: its times (64 lasers, curbPoints 3
+ * and 8) are in profiles/front_multi_sector_cp_bench.json. */
 int urf_set_front_mode(urf_ctx* ctx, int mode);
 int urf_front_scans(urf_ctx* ctx, uint32_t* n_fused);
 /* 0 (default): as today.  1: with channels == 128 and curbPoints == 5, front modes 2 and 3 also send sweeps of 128 lasers per
@@ -593,6 +605,11 @@ int urf_set_front_curb_points(urf_ctx* ctx, int on);
  * k_front_sectors, above); other curbPoints keep the plain instances.  Forgets sightings / hand-backs like urf_set_front_mode.
  * URF_ERR_OOM: the switch stays off.  Anything else: URF_ERR_INVALID_ARG. */
 int urf_set_front_multi_sector(urf_ctx* ctx, int on);
+/* 0 (default): as today, urf_set_front_multi_sector applies to curbPoints == 5 only.  1: it applies to every curbPoints the call's fused
+ * kernels have an instance for (1..8: front mode 3, urf_set_front_curb_points), through k_front*_ms_cp<n>; nothing changes while
+ * urf_set_front_multi_sector is off.  Allocates nothing.  Forgets sightings / hand-backs like urf_set_front_mode.  Anything else:
+ * URF_ERR_INVALID_ARG. */
+int urf_set_front_multi_sector_curb_points(urf_ctx* ctx, int on);
 /* 0 (default): after a call that took the fused front end, urf_ordered_indices*, urf_clouds_batch_* with
  * URF_ORDER_REFERENCE and urf_marker_points* first run that call again through the general kernels, and the context stays with those.
  * 1: these read-outs take a fused call's results as they are (urban_road_filter_amd/csrc/urf_k_front_outputs.hpp: the rings' points

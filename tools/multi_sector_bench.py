@@ -3,6 +3,8 @@
 Prints ONE JSON line; recorded under profiles/front_multi_sector_bench.json.
 
     timeout 900 python tools/multi_sector_bench.py [--scans 1024] [--steps 20] [--warmup 3] [--distinct 32]
+    timeout 900 python tools/multi_sector_bench.py --curb-points 3,8     (urf_set_front_multi_sector_curb_points on against off, see below;
+                                                                          recorded under profiles/front_multi_sector_cp_bench.json)
     rocprofv3 --kernel-trace --stats -- python tools/multi_sector_bench.py --trace-only   (k_front_sectors' own time: a run of its own)
 
 Workloads (tests/sensor_models.py), --scans resident sweeps each, --distinct distinct ones repeated:
@@ -13,7 +15,11 @@ Workloads (tests/sensor_models.py), --scans resident sweeps each, --distinct dis
 Behind a label gate against oracle B (tests/oracles.py) two contexts in front mode 2 -- the switch on, the switch off -- are timed with
 device events, interleaved call by call.  Per side: the 10th / 50th / 90th percentiles of ms per call, the per-pair ratio off / on,
 urf_front_scans (after the warm-up and after the timed calls) next to the number of scans tests/front_shape.py's predicate accepts; then, with urf_enable_kernel_timing, the context's per-stage event brackets of both (the bracket named k_split holds the
-march, k_front_sectors and the general split)."""
+march, k_front_sectors and the general split).
+
+--curb-points LIST (default: none, the run above, unchanged): per workload and per value of the list, curbPoints set to it, BOTH contexts in
+front mode 3 with urf_set_front_multi_sector on; urf_set_front_multi_sector_curb_points is on in one and off in the other, so that "off" is
+what that parameter gets without the new switch.  Same label gate, same interleaving, same figures per (workload, curbPoints)."""
 import argparse
 import json
 import os
@@ -37,6 +43,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--distinct", type=int, default=32, help="distinct sweeps the batch is built from")
     ap.add_argument("--workloads", default=",".join(w[0] for w in WORKLOADS))
+    ap.add_argument("--curb-points", default="", help="comma-separated curbPoints (1..4, 6..8): time urf_set_front_multi_sector_curb_points instead")
     ap.add_argument("--trace-only", action="store_true", help="five calls of the switch-on context per workload, for a kernel trace")
     args = ap.parse_args()
     import torch
@@ -48,17 +55,26 @@ def main():
         raise SystemExit("no GPU: nothing is measured here")
     dev = torch.device("cuda:0")
     S = args.scans
-    out = {"metric": "front_multi_sector_bench", "device": torch.cuda.get_device_name(0), "scans": S, "front_mode": 2,
-           "timing": "device events per call, off / on interleaved call by call in one process; ms", "results": []}
+    cps = [int(v) for v in args.curb_points.split(",") if v]
+    if any(cp not in (1, 2, 3, 4, 6, 7, 8) for cp in cps):
+        raise SystemExit("--curb-points: values of 1..4 and 6..8")
+    # (switch under test, front mode of both contexts): without --curb-points the run recorded in profiles/front_multi_sector_bench.json
+    mode = 3 if cps else 2
+    out = {"metric": "front_multi_sector_cp_bench" if cps else "front_multi_sector_bench", "device": torch.cuda.get_device_name(0), "scans": S,
+           "front_mode": mode, "timing": "device events per call, off / on interleaved call by call in one process; ms", "results": []}
+    if cps:
+        out["switch"] = "urf_set_front_multi_sector_curb_points (urf_set_front_multi_sector on in both contexts)"
     t0 = time.time()
     st = torch.cuda.Stream()
     pct = lambda v: [float(np.percentile(v, q)) for q in (10, 50, 90)]  # noqa: E731
     with torch.cuda.stream(st):
-        for name, model, W, layout in WORKLOADS:
+        for name, model, W, layout, cp in [w + (cp,) for w in WORKLOADS for cp in (cps or [None])]:
             if name not in args.workloads.split(","):
                 continue
             L = SM.lasers(model)
             p = SM.params_for(model, wide=True)
+            if cp is not None:
+                p.curbPoints = cp
             k_distinct = min(args.distinct, S)
             # (start 0: the seam on a tile border, so that the ideal twins are fused with the switch off)
             clouds = [SM.sweep(model, firings=W, world=k % 3, seed=700 + k, noise=model != "ideal64", layout=layout) for k in range(k_distinct)]
@@ -75,8 +91,9 @@ def main():
                 ctxs = {"on": on, "off": off}
                 for side, ctx in ctxs.items():
                     ctx.set_stream(st.cuda_stream)
-                    ctx.set_front_mode(2)
-                    ctx.set_front_multi_sector(1 if side == "on" else 0)
+                    ctx.set_front_mode(mode)
+                    ctx.set_front_multi_sector(1 if side == "on" or cps else 0)
+                    ctx.set_front_multi_sector_curb_points(1 if side == "on" and cps else 0)
                 calls = {side: (lambda c=ctx, lab=labs[side]: c.classify_batch_soa(dx, dy, dz, n, S, lab, None)) for side, ctx in ctxs.items()}
                 if args.trace_only:
                     for _ in range(5):
@@ -92,7 +109,7 @@ def main():
                     got = labs[side].cpu().numpy()
                     for k, lb in want.items():
                         if not np.array_equal(got[k * n:(k + 1) * n], lb):
-                            raise SystemExit("label gate: %s side %s scan %d differs from oracle B" % (name, side, k))
+                            raise SystemExit("label gate: %s%s side %s scan %d differs from oracle B" % (name, " curbPoints %d" % cp if cps else "", side, k))
                 ts = {"on": [], "off": []}
                 for _ in range(args.steps):
                     for side in ("off", "on"):
@@ -112,7 +129,7 @@ def main():
                     ms, n_calls = ctx.kernel_timing()
                     stages[side] = {k: v / max(n_calls, 1) for k, v in ms.items()}
                     ctx.enable_kernel_timing(False)
-                out["results"].append({"workload": name, "model": model, "lasers": L, "firings": W, "layout": layout, "points": S * n,
+                out["results"].append({"workload": name, **({"curbPoints": cp} if cps else {}), "model": model, "lasers": L, "firings": W, "layout": layout, "points": S * n,
                                        "front_scans": fused, "front_scans_after_timing": fused_after, "fusable_scans": fusable, "off_ms_p10_p50_p90": pct(ts["off"]), "on_ms_p10_p50_p90": pct(ts["on"]),
                                        "off_over_on_p10_p50_p90": pct([a / b for a, b in zip(ts["off"], ts["on"])]),
                                        "stage_brackets_ms_per_call": stages})

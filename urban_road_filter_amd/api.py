@@ -179,6 +179,7 @@ def lib(hooks=False):
         "urf_set_front_long_sweeps": [vp, C.c_int],
         "urf_set_front_curb_points": [vp, C.c_int],
         "urf_set_front_multi_sector": [vp, C.c_int],
+        "urf_set_front_multi_sector_curb_points": [vp, C.c_int],
         "urf_set_front_outputs": [vp, C.c_int],
         "urf_callback_path_preset": [vp, C.c_uint32],
         "urf_classify_batch_soa_dense": [vp, fp, fp, fp, vp, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp],
@@ -423,6 +424,13 @@ class Context:
         Ouster clouds, the sweep's seam) -- with the star-shaped search on and curb_points == 5 (other curb_points: the plain instances;
         include/urf.h); 0 (default) hands such scans back to the general kernels.  Opt-in."""
         self._check(self._lib.urf_set_front_multi_sector(self._h, int(on)), "urf_set_front_multi_sector")
+
+    def set_front_multi_sector_curb_points(self, on):
+        """urf_set_front_multi_sector_curb_points: 1 extends set_front_multi_sector from curb_points == 5 to every curb_points the fused
+        front end has an instance for (1..8: front mode 3, set_front_curb_points for 16 / 32 / 128 lasers); it decides nothing while
+        set_front_multi_sector is off, in front modes below 3 or with the star-shaped search off, and allocates nothing (include/urf.h);
+        0 (default) keeps the plain instances, and their hand-back of real sensors' sweeps, for those values.  Opt-in."""
+        self._check(self._lib.urf_set_front_multi_sector_curb_points(self._h, int(on)), "urf_set_front_multi_sector_curb_points")
 
     def set_front_outputs(self, on):
         """urf_set_front_outputs: 1 lets ordered_indices*, clouds_batch_* in the reference order and marker_points* take the results of a call

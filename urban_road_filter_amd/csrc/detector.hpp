@@ -99,8 +99,11 @@ public:
      * is on (otherwise 64 lasers only). */
     void setFrontCurbPoints(bool on) { set(urf_set_front_curb_points, "urf_set_front_curb_points", on); }
     /* urf_set_front_multi_sector: the fused front end keeps scans whose firings span several star sectors or whose sectors fall inside a
-     * tile (real sensors' azimuth offsets, rotation during a firing, the sweep's seam), with the star-shaped search on and curbPoints == 5. */
+     * tile (real sensors' azimuth offsets, rotation during a firing, the sweep's seam), with the star-shaped search on and curbPoints == 5 ... */
     void setFrontMultiSector(bool on) { set(urf_set_front_multi_sector, "urf_set_front_multi_sector", on); }
+    /* urf_set_front_multi_sector_curb_points: ... and, on top of setFrontMultiSector, with every curbPoints 1..8 that front mode 3 (and
+     * setFrontCurbPoints) sends through the fused front end.  Decides nothing while setFrontMultiSector is off.  Times: profiles/front_multi_sector_cp_bench.json. */
+    void setFrontMultiSectorCurbPoints(bool on) { set(urf_set_front_multi_sector_curb_points, "urf_set_front_multi_sector_curb_points", on); }
 
 protected:
     urf_ctx* ctx_ = nullptr;

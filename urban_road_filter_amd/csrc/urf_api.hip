@@ -92,7 +92,7 @@ struct lazy_buf {
 enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR, URF_SCR_LASERS128, URF_SCR_MULTI_SECTOR };
 
 /* The kernels of a call's fused family (urf_policy.hpp: urf_front_family), in one table.  An instance of the march and of the finish kernel
- * exists per curbPoints (and, for 5, as the march of urf_set_front_multi_sector): the march per laser count -- 16, 32, 64, 128: the family's
+ * exists per curbPoints (the march twice: plain, and as the march of urf_set_front_multi_sector): the march per laser count -- 16, 32, 64, 128: the family's
  * `lasers` --, the finish kernel per width, because 64, 32 and 16 lasers share one that reads the count at run time (front_lsh).  The probe,
  * the transpose and the label kernel exist per width only. */
 struct front_kernels {
@@ -113,6 +113,10 @@ static const struct {
 #define URF_FRONT_CP_X(n) \
     { n, false, { k_front16_cp##n, k_front32_cp##n, k_front_cp##n, k_front128_cp##n }, { k_front_finish_cp##n, k_front_finish128_cp##n } },
     URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
+#undef URF_FRONT_CP_X
+#define URF_FRONT_CP_X(n) \
+    { n, true, { k_front16_ms_cp##n, k_front32_ms_cp##n, k_front_ms_cp##n, k_front128_ms_cp##n }, { k_front_finish_cp##n, k_front_finish128_cp##n } },
+    URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)   /* (urf_set_front_multi_sector_curb_points) */
 #undef URF_FRONT_CP_X
 };
 static front_kernels front_kernels_of(const urf_front_family& f)
@@ -731,6 +735,11 @@ extern "C" int urf_set_front_curb_points(urf_ctx* c, int on)
 extern "C" int urf_set_front_multi_sector(urf_ctx* c, int on)
 {   /* the star records' sectors, one per scratch element: allocated once, with the first call that turns the switch on */
     return set_front_switch(c, on, &urf_policy::multi_sector, [](urf_ctx* x) { return scratch_alloc(x, URF_SCR_MULTI_SECTOR); });
+}
+
+extern "C" int urf_set_front_multi_sector_curb_points(urf_ctx* c, int on)
+{   /* (allocates nothing: front_skey comes with urf_set_front_multi_sector, without which this switch decides nothing) */
+    return set_front_switch(c, on, &urf_policy::multi_sector_cp, nullptr);
 }
 
 extern "C" int urf_set_front_outputs(urf_ctx* c, int on)

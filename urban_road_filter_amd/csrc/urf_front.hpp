@@ -36,9 +36,10 @@
  * sectors that fall inside a tile, a ring point on the sensor's axis, an incomplete speculative ring table) clears
  * front_ok[s] and takes the legacy kernels, which skip every scan whose flag is still set.  Labels are the same
  * either way, bit for bit: the arithmetic is the legacy path's (urf_device.hpp, urf_x_zero_angle, urf_z_zero_angle).
- * With urf_set_front_multi_sector on, "a firing in two sectors" and "sectors that fall inside a tile" are no such reasons (curbPoints 5, the
- * star-shaped search on): the march is a k_front*_ms instance (urf_front_body's MS) and k_front_sectors (urf_k_front_sectors.hpp) sorts
- * each tile's star records by sector behind it.
+ * With urf_set_front_multi_sector on, "a firing in two sectors" and "sectors that fall inside a tile" are no such reasons (the star-shaped
+ * search on; curbPoints 5, and 1..4 and 6..8 with urf_set_front_multi_sector_curb_points on top): the march is a k_front*_ms or
+ * k_front*_ms_cp<n> instance (urf_front_body's MS) and k_front_sectors (urf_k_front_sectors.hpp) sorts each tile's star records by sector
+ * behind it.
  *
  * ONE body per kernel around the march, for every laser count.  k_front_finish*, k_transpose (here) and k_rows_probe (urf_k_table.hpp) each
  * exist as a named wrapper per family -- 64 / 32 / 16 lasers, the count read at run time, and 128 (k_front_finish128*, k_transpose128,
@@ -465,7 +466,8 @@ struct urf_front_ring {
  * (urf_front_lay<(L > 64)>), the width of a firing's region-of-interest word (step), which half the first star participant comes from and
  * how many there are in front of a half (step), how many registers hold a tile's steps (NK).
  *
- * MS (urf_set_front_multi_sector; k_front*_ms, CP == 5, STAR only): a firing's participants may lie in SEVERAL sectors, and the sectors may
+ * MS (urf_set_front_multi_sector; k_front*_ms, and k_front*_ms_cp<n> behind urf_set_front_multi_sector_curb_points; STAR only, any CP -- nothing
+ * below that depends on MS reads the window): a firing's participants may lie in SEVERAL sectors, and the sectors may
  * fall inside a tile -- a real sensor's azimuth offsets per laser, its rotation during a firing, the sweep's seam.  The march then leaves
  * the tile's star records compacted in INPUT order as ever (tile base + participants in front), each with its 16-bit sector in the same
  * place of front_skey, and the tile's participant count in tsoff[row][K]; k_front_sectors (urf_k_front_sectors.hpp) sorts the tile's
@@ -474,7 +476,7 @@ template <bool STAR, bool BEAM, unsigned L, unsigned CP, bool MS = false>
 __device__ __forceinline__ void urf_front_body(const urf_kargs& a, const urf_dev_params& dp, urf_u2* cbuf)
 {
     static_assert(L == 128u || L == 64u || L == 32u || L == 16u, "a firing fills two waves, the wave, half of it or a quarter");
-    static_assert(!MS || (STAR && CP == 5u), "the multi-sector instances: star-shaped search on, curbPoints 5");
+    static_assert(!MS || STAR, "multi-sector needs the star-shaped search");
     using LAY = urf_front_lay<(L > 64u)>;
     constexpr unsigned NH = L > 64u ? 2u : 1u;    /* halves of a firing: lasers per lane */
     const unsigned s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
@@ -909,22 +911,29 @@ URF_FRONT_KERNEL(k_front128, 128u, 5)
     URF_FRONT_KERNEL(k_front_cp##n, 64u, n) URF_FRONT_KERNEL(k_front32_cp##n, 32u, n) URF_FRONT_KERNEL(k_front16_cp##n, 16u, n) URF_FRONT_KERNEL(k_front128_cp##n, 128u, n)
 URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
 #undef URF_FRONT_CP_X
-/* ... and the multi-sector instances (urf_set_front_multi_sector; urf_front_body's MS): curbPoints 5, the two bodies of the star-shaped
- * search -- with the search off sectors do not matter and the host launches the plain kernel.  The budgets of their plain siblings. */
-#define URF_FRONT_KERNEL_MS(name, L)                                                                                                          \
-    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT_WAVES_OF(L, 5), URF_FRONT_WAVES_OF(L, 5))))                 \
+/* ... and the multi-sector instances (urf_front_body's MS), the two bodies of the star-shaped search -- with the search off sectors do
+ * not matter and the host launches the plain kernel.  The budgets of their plain siblings.  curbPoints 5 (urf_set_front_multi_sector) ... */
+#define URF_FRONT_KERNEL_MS(name, L, CP)                                                                                                      \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(URF_FRONT_WAVES_OF(L, CP), URF_FRONT_WAVES_OF(L, CP))))               \
     void name(urf_kargs a, urf_dev_params dp)                                                                                                 \
     {                                                                                                                                       \
         __shared__ urf_u2 cbuf[URF_FRONT_CBUF];                                                                                               \
         if (!dp.p.starbeam_filter)                                                                                                            \
-            urf_front_body<true, false, L, 5, true>(a, dp, cbuf);                                                                             \
+            urf_front_body<true, false, L, CP, true>(a, dp, cbuf);                                                                            \
         else                                                                                                                                  \
-            urf_front_body<true, true, L, 5, true>(a, dp, cbuf);                                                                              \
+            urf_front_body<true, true, L, CP, true>(a, dp, cbuf);                                                                             \
     }
-URF_FRONT_KERNEL_MS(k_front_ms, 64u)
-URF_FRONT_KERNEL_MS(k_front32_ms, 32u)
-URF_FRONT_KERNEL_MS(k_front16_ms, 16u)
-URF_FRONT_KERNEL_MS(k_front128_ms, 128u)
+URF_FRONT_KERNEL_MS(k_front_ms, 64u, 5)
+URF_FRONT_KERNEL_MS(k_front32_ms, 32u, 5)
+URF_FRONT_KERNEL_MS(k_front16_ms, 16u, 5)
+URF_FRONT_KERNEL_MS(k_front128_ms, 128u, 5)
+/* ... and the others of 1..8 (urf_set_front_multi_sector_curb_points on top of it; which of them a call may take at all is the plain
+ * instances' rule: urf_policy::curb_points_ok) */
+#define URF_FRONT_CP_X(n)                                                                                                                     \
+    URF_FRONT_KERNEL_MS(k_front_ms_cp##n, 64u, n) URF_FRONT_KERNEL_MS(k_front32_ms_cp##n, 32u, n) URF_FRONT_KERNEL_MS(k_front16_ms_cp##n, 16u, n) \
+    URF_FRONT_KERNEL_MS(k_front128_ms_cp##n, 128u, n)
+URF_FRONT_CP_OTHERS(URF_FRONT_CP_X)
+#undef URF_FRONT_CP_X
 
 /* ------------------------------------------------------------------------- */
 /* k_front_finish                                                              */

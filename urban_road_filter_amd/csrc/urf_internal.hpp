@@ -196,7 +196,7 @@ struct urf_kargs {
     uint32_t  front;            /* this call launches it (urf_api.hip decides: 64 / 32 / 16 channels, curbPoints 5 -- mode 3 and 64 channels: 1..8 --, no stage capture, a batch) */
     uint32_t  front_tpb;        /* tiles per block of k_front */
     uint32_t  front_cand_cap;   /* entries per scan of front_cand / front_all */
-    uint32_t  front_ms;         /* urf_set_front_multi_sector, star-shaped search on, curbPoints 5: the march is a k_front*_ms instance, k_front_sectors follows it (urf_k_front_sectors.hpp) */
+    uint32_t  front_ms;         /* urf_set_front_multi_sector, star-shaped search on, curbPoints 5 (urf_set_front_multi_sector_curb_points: whatever value the call is fused with): the march is a k_front*_ms / k_front*_ms_cp<n> instance, k_front_sectors follows it (urf_k_front_sectors.hpp) */
     /* output */
     uint8_t* labels;
     urf_scan_info* info;        /* context copy, [n_scans] */

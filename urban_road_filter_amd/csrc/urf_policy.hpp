@@ -71,8 +71,11 @@ struct __attribute__((visibility("hidden"))) urf_policy {
     bool curb_points = false;
     /* urf_set_front_multi_sector: with the star-shaped search on and curbPoints 5 the march is a k_front*_ms instance and k_front_sectors
      * follows it (urf_k_front_sectors.hpp): firings that span several sectors, sectors that fall inside a tile stay fused.  Other
-     * curbPoints: the plain instances. */
+     * curbPoints: the plain instances ... */
     bool multi_sector = false;
+    /* ... unless urf_set_front_multi_sector_curb_points is on as well: then whatever curbPoints the call's fused kernels have an instance
+     * for (curb_points_ok: 1..8) has a multi-sector one (k_front*_ms_cp<n>).  Without multi_sector it decides nothing. */
+    bool multi_sector_cp = false;
     bool long_sweeps = false;       /* urf_set_front_long_sweeps: modes 2 and 3 take scans of up to URF_FRONT_LONG_MAX_TILES tiles */
     uint32_t front_tpb = 0;         /* tiles per block of k_front; 0: by batch size (URF_FRONT_TPB_*), else what URF_FRONT_TPB says */
     bool want_ring_sorted = false;
@@ -177,7 +180,7 @@ struct __attribute__((visibility("hidden"))) urf_policy {
         a.front_tpb = tiles_per_block(a.n_scans, a.front_lsh);
         a.front_lists = (a.front && !front_direct && !slot) ? 1u : 0u;   /* (the callback path's sequence holds the general kernels as grids anyway) */
         a.front_rows = (a.front && front_rows) ? 1u : 0u;   /* (independent of the two other speculations: the repair kernels come with it) */
-        a.front_ms = (a.front && multi_sector && dp.p.star_shaped_method != 0 && dp.p.curbPoints == 5) ? 1u : 0u;
+        a.front_ms = (a.front && multi_sector && dp.p.star_shaped_method != 0 && (dp.p.curbPoints == 5 || multi_sector_cp)) ? 1u : 0u;
     }
 };
 
@@ -189,7 +192,7 @@ struct urf_front_family {
     uint8_t lasers;         /* 0, 1, 2, 3: 16, 32, 64, 128 lasers per firing (the march: k_front16*, k_front32*, k_front*, k_front128*) */
     uint8_t wide;           /* 128 lasers: probe, transpose, finish and label kernel are the *128 siblings, the candidate lists likewise */
     uint8_t cp;             /* the march's and the finish kernel's instance: 5, or the call's curbPoints where it is one of URF_FRONT_CP_OTHERS */
-    uint8_t ms;             /* the march is the k_front*_ms instance (a.front_ms; cp is 5) */
+    uint8_t ms;             /* the march is the k_front*_ms instance (a.front_ms), k_front*_ms_cp<n> where cp is not 5 */
     uint8_t rows;           /* the probe and the transpose are launched (a.front_rows) */
     uint32_t finish_tiles;  /* the tiles the finish kernel's dynamic LDS is sized for (128 lasers: an even number) */
 };
