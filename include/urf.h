@@ -71,7 +71,8 @@ extern "C" {
  * road_marker: one sweep on the host, a batch of sweeps on the device); urf_classify_batch_soa_dense / urf_classify_batch_pc2_dense with
  * urf_set_dense_slots and urf_dense_scans (dense sweeps put back into firing slots by laser id on the device, then classified as
  * organised ones); urf_set_front_curb_points (front mode 3's curbPoints 1..8 at 16, 32 and 128 lasers per firing as well);
- * urf_set_front_multi_sector_curb_points (urf_set_front_multi_sector at curbPoints 1..8 instead of 5 only).
+ * urf_set_front_multi_sector_curb_points (urf_set_front_multi_sector at curbPoints 1..8 instead of 5 only); urf_set_dense_outputs
+ * (the reference-order read-outs after a dense call, in the caller's indices).
  * WHICH std::sort (4 above): the one of libstdc++ as shipped with GCC 5 .. 13 (bits/stl_algo.h: __sort = __introsort_loop with
  * _S_threshold 16, __move_median_to_first on (first + 1, mid, last - 1), __unguarded_partition, depth limit 2 * floor(log2 n),
  * __partial_sort as the fallback, then __final_insertion_sort); tests/test_stdsort.py pins the restatement against the std::sort
@@ -658,7 +659,25 @@ int urf_set_front_outputs(urf_ctx* ctx, int on);
  * alive; urf_clouds_batch_soa / urf_clouds_batch_pc2 with URF_ORDER_INPUT read the caller's dense labels and inputs (LIFETIME as
  * above) and give the records the ragged call gives.  urf_ordered_indices*, urf_clouds_batch_* with URF_ORDER_REFERENCE and
  * urf_read_stage would answer in padded indices: they return URF_ERR_INVALID_ARG (urf_last_error says why) and leave the context
- * as it was.  Mapping padded indices back to the dense ones is left to a later version.
+ * as it was -- unless urf_set_dense_outputs is on.
+ * urf_set_dense_outputs(ctx, 1): after a dense call urf_ordered_indices, urf_ordered_indices_batch and urf_clouds_batch_* with
+ * URF_ORDER_REFERENCE answer in the CALLER'S indices.  The padded scan holds the dense points in input order, so the reference's orders
+ * on it are the dense scan's with every index i replaced by its padded position; a device pass behind the list kernels
+ * (k_dense_inverse once per dense call, k_dense_unmap_lists per read-out) replaces them back.  The lists hold indices 0 .. len_s - 1
+ * into dense scan s in the reference's order, the counts are as ever; urf_ordered_indices' host buffers need room for the dense scan's
+ * length, urf_ordered_indices_batch's stride must be at least the dense call's max_len (not W * L; smaller: URF_ERR_INVALID_ARG).
+ * urf_clouds_batch_* give counts, offsets and records exactly as after urf_classify_batch_*_ragged on the same points (capacity
+ * 3 * n_scans * max_len of the dense call): `roi` from the dense labels in input order, the three ordered clouds gathered from the
+ * caller's dense inputs through the mapped lists.  LIFETIME: the ordered indices need nothing of the caller's; the reference-order
+ * clouds read the caller's dense labels and inputs, as the input-order clouds do.  Scans that were not aligned, empty,
+ * URF_TOO_FEW_POINTS or cut at max_len give what the ragged call gives.  Both positions of urf_set_front_outputs work: off, a fused
+ * dense call's padded batch is run again through the general kernels (every buffer the context's; the context stays with those), on,
+ * there is no second run.  The first such read-out allocates the inverse map (4 bytes per point of max_points * max_batch;
+ * URF_ERR_OOM from that read-out, the context keeps working).  The switch itself allocates and launches nothing, decides nothing about
+ * which kernels classify, forgets no sighting or hand-back, and decides nothing after a call that was not dense.  0 (default): the
+ * refusals above.  Anything else: URF_ERR_INVALID_ARG.
+ * urf_read_stage stays refused after a dense call in either position: stage values are defined per PADDED input point and are a
+ * parity tool, not a published output.
  * The kernels are urban_road_filter_amd/csrc/urf_k_dense.hpp; they run outside the timing brackets below. */
 int urf_classify_batch_soa_dense(urf_ctx* ctx, const float* d_x, const float* d_y, const float* d_z,
                                  const void* d_laser, uint32_t laser_bytes,
@@ -671,6 +690,7 @@ int urf_classify_batch_pc2_dense(urf_ctx* ctx, const uint8_t* d_data, const uint
                                  uint32_t max_firings, uint8_t* d_labels, urf_scan_info* d_info);
 int urf_set_dense_slots(urf_ctx* ctx, const uint8_t* slot_of_id, uint32_t n_ids);
 int urf_dense_scans(urf_ctx* ctx, uint32_t* n_aligned);
+int urf_set_dense_outputs(urf_ctx* ctx, int on);
 
 /* ---- per-kernel timing (benchmark) ------------------------------------------
  * With timing on, every classify call brackets each kernel of the pipeline

@@ -187,6 +187,7 @@ def lib(hooks=False):
                                          C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp],
         "urf_set_dense_slots": [vp, u8p, C.c_uint32],
         "urf_dense_scans": [vp, C.c_void_p],
+        "urf_set_dense_outputs": [vp, C.c_int],
     }
     for name, args in sig.items():
         if name in HOOK_SYMBOLS and not has_hooks:
@@ -572,6 +573,12 @@ class Context:
         n = C.c_uint32(0)
         self._check(self._lib.urf_dense_scans(self._h, C.addressof(n)), "urf_dense_scans")
         return n.value
+
+    def set_dense_outputs(self, on):
+        """urf_set_dense_outputs: 1 lets ordered_indices* and clouds_batch_* in the reference order answer after a dense call, in the
+        caller's dense indices (the padded positions mapped back on the device; include/urf.h); 0 (default) keeps them refused.
+        read_stage stays refused after a dense call either way."""
+        self._check(self._lib.urf_set_dense_outputs(self._h, int(on)), "urf_set_dense_outputs")
 
     def clouds_batch_soa(self, d_intensity, order, d_records, capacity, d_counts, d_offsets):
         """The four published clouds of every scan of the last (SoA) batch call as 32-byte records on the device:

@@ -531,9 +531,10 @@ size_t BatchDetector::filtered(const std::vector<PointCloud2>& msgs)
     if (hipMemcpyAsync(d_data, h_data_.data(), h_data_.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(d_offsets, offsets.data(), (S + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess)
         throw Error(URF_ERR_HIP, "BatchDetector: upload failed");
-    /* setDenseRealign: every message carries the same `ring` field, input order, and the sensor's padded sweep fits the context */
+    /* setDenseRealign: every message carries the same `ring` field, input order (or setDenseOutputs: the reference order comes back in the
+     * messages' indices), and the sensor's padded sweep fits the context */
     uint32_t ring_off = 0, ring_bytes = 0;
-    if (dense_firings_ != 0 && !reference_order_) {
+    if (dense_firings_ != 0 && (!reference_order_ || dense_outputs_)) {
         ringField(msgs[0], ring_off, ring_bytes);
         for (size_t i = 1; i < S && ring_bytes; i++) {
             uint32_t o = 0, b = 0;

@@ -230,9 +230,17 @@ public:
      * slots on the device and classified as organised sweeps (urf_classify_batch_pc2_dense, include/urf.h): max_firings = the sensor's
      * firings per revolution, slot_of_ring[ring] = the laser's position inside a firing (empty: the ring is the position).  Same clouds,
      * headers and road_marker either way; off by default, max_firings == 0 turns it off.  Messages without such a field, the reference
-     * order (setReferenceOrder) and a sensor whose max_firings * channels sweep does not fit max_points keep the ragged call. */
+     * order (setReferenceOrder) while setDenseOutputs is off, and a sensor whose max_firings * channels sweep does not fit max_points keep
+     * the ragged call. */
     void setDenseRealign(uint32_t max_firings, const std::vector<uint8_t>& slot_of_ring = {});
-    /* messages of the last filtered() call that were put back into firing slots (0 when it took the ragged call) */
+    /* urf_set_dense_outputs: the reference order after a dense call, in the messages' own indices.  On, setReferenceOrder(true) no longer
+     * keeps filtered() off the dense call: same clouds, in the reference's order.  Off (default): filtered() chooses as above. */
+    void setDenseOutputs(bool on)
+    {
+        set(urf_set_dense_outputs, "urf_set_dense_outputs", on);
+        dense_outputs_ = on;
+    }
+    /* messages of the last filtered() call that were put back into firing slots (0 when it took the ragged call), in either order */
     size_t denseAligned() const { return dense_aligned_; }
 
     /* As Detector's: also build "road_marker" for every message (off by default; the polygon parameters start from
@@ -262,6 +270,7 @@ private:
     uint32_t max_points_ = 0, max_batch_ = 0;
     bool reference_order_ = false;
     uint32_t dense_firings_ = 0;   /* setDenseRealign */
+    bool dense_outputs_ = false;   /* setDenseOutputs */
     size_t dense_aligned_ = 0;
     /* device buffers (grown on demand) */
     void* d_data_ = nullptr;

@@ -250,6 +250,12 @@ struct urf_ctx {
     lazy_buf<uint8_t> dn_labels;
     lazy_buf<uint32_t> dn_words;
     lazy_buf<uint8_t> dn_map;
+    /* urf_set_dense_outputs: the inverse of dn_pos ([max_batch][max_points], k_dense_inverse), grown by the first read-out that needs it
+     * and built once per dense call: dn_calls counts those (a rerun of the padded batch writes `last` and leaves dn_pos as it is), dn_inv_of
+     * is the one dn_inv holds (0: none) */
+    lazy_buf<uint32_t> dn_inv;
+    uint64_t dn_calls = 0, dn_inv_of = 0;
+    bool dense_outputs = false;
     uint8_t dense_map[256];         /* urf_set_dense_slots (urf_create: the identity); 0xff: no such id */
     bool dense_map_dirty = true;    /* ... not yet in dn_map */
     float* d_newY = nullptr;
@@ -613,6 +619,7 @@ extern "C" int urf_set_stream(urf_ctx* c, void* hip_stream)
     c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     c->pol.epoch++;
     c->fo_prep.seq = 0;   /* (what k_front_out_prep wrote on the stream before is not ordered in front of this one) */
+    c->dn_inv_of = 0;     /* (nor what k_dense_inverse wrote) */
     return URF_OK;
 }
 
@@ -1267,6 +1274,15 @@ static int classify_batch_dense(urf_ctx* c, int kind, urf_dense_args d, const ui
     c->last.dense.z = d.z;
     c->last.dense.labels = d_labels;
     c->last.dense.max_len = max_len;
+    c->dn_calls++;   /* (dn_pos is another call's now: dn_inv holds no inverse of it) */
+    return URF_OK;
+}
+
+extern "C" int urf_set_dense_outputs(urf_ctx* c, int on)
+{
+    if (!c || (on != 0 && on != 1))
+        return URF_ERR_INVALID_ARG;
+    c->dense_outputs = on != 0;   /* (dn_inv grows with the first read-out that needs it: dense_unmap) */
     return URF_OK;
 }
 
@@ -1664,10 +1680,11 @@ static const urf_last_call* last_valid(urf_ctx* c, uint32_t scan = 0, int kind =
 }
 
 /* After a dense call (urf_classify_batch_*_dense) the record is the PADDED batch: what answers in padded indices -- urf_ordered_indices*,
- * urf_clouds_batch_* in the reference order, urf_read_stage -- is refused (mapping them back is not built). */
-static bool refuse_dense(urf_ctx* c, const char* what)
+ * urf_clouds_batch_* in the reference order, urf_read_stage -- is refused, unless it is one of the lists (`mapped`) and
+ * urf_set_dense_outputs is on: launch_ordered then maps them back to the caller's indices (dense_unmap). */
+static bool refuse_dense(urf_ctx* c, const char* what, bool mapped = false)
 {
-    if (!c->last.dense.on)
+    if (!c->last.dense.on || (mapped && c->dense_outputs))
         return false;
     c->last_error = std::string(what) + ": not available after a dense call (urf_classify_batch_*_dense): its results index the padded sweeps";
     return true;
@@ -1770,6 +1787,34 @@ static int front_out_prepare(urf_ctx* c, const urf_last_call& l, uint32_t s0, ui
     return URF_OK;
 }
 
+/* The lists k_ordered_lists wrote for scans [s0, s0 + n) of a dense call, from padded positions to the caller's dense indices, in place
+ * (urf_k_dense.hpp).  The inverse of dn_pos is built by the first read-out behind a dense call and kept for the others. */
+static int dense_unmap(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t n, uint32_t* d_road, uint32_t* d_curb, uint32_t* d_r10,
+                       uint32_t stride, const uint32_t* d_counts)
+{
+    hipStream_t st = c->stream;
+    const bool regrow = (size_t)c->max_points * c->max_batch > c->dn_inv.cap;
+    if (regrow)
+        c->dn_inv_of = 0;
+    const int rc = grow(c, c->dn_inv, (size_t)c->max_points * c->max_batch, st);
+    if (rc != URF_OK)
+        return rc;
+    const uint32_t WL = l.a.max_len, max_len = l.dense.max_len;   /* (the padded call's scans are W * L points each) */
+    urf_dense_unmap_args u{ c->offsets_copy, max_len, WL, c->dn_pos.p, c->dn_inv.p };
+    if (c->dn_inv_of != c->dn_calls) {
+        c->dn_inv_of = 0;
+        const unsigned tiles = max_len ? (max_len + URF_TILE - 1) / URF_TILE : 1u;
+        hipLaunchKernelGGL(k_dense_inverse, dim3(tiles, l.scans), dim3(URF_DENSE_THREADS), 0, st, u);
+        URF_HIP(c, hipGetLastError());   /* (the mark only behind a launch that was accepted) */
+        c->dn_inv_of = c->dn_calls;
+    }
+    const uint32_t most = stride < max_len ? stride : max_len;   /* (a list holds points of the scan: at most its length) */
+    hipLaunchKernelGGL(k_dense_unmap_lists, dim3(most ? (most + URF_DENSE_THREADS - 1) / URF_DENSE_THREADS : 1u, n, 3), dim3(URF_DENSE_THREADS), 0,
+                       st, u, s0, d_road, d_curb, d_r10, stride, d_counts);
+    URF_HIP(c, hipGetLastError());
+    return URF_OK;
+}
+
 /* scans [s0, s0 + n) of the last classify call (l: from last_call), lists of `stride` entries per scan on the device */
 static int launch_ordered(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t n, uint32_t* d_road, uint32_t* d_curb, uint32_t* d_r10,
                           uint32_t stride, uint32_t* d_counts)
@@ -1790,15 +1835,15 @@ static int launch_ordered(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint3
     hipLaunchKernelGGL(k_ordered_lists, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, c->ord_pos.p, c->ord_cls.p, d_road,
                        d_curb, d_r10, stride, d_counts);
     URF_HIP(c, hipGetLastError());
-    return URF_OK;
+    return l.dense.on ? dense_unmap(c, l, s0, n, d_road, d_curb, d_r10, stride, d_counts) : URF_OK;   /* (refuse_dense: the switch is on) */
 }
 
 extern "C" int urf_ordered_indices_batch(urf_ctx* c, uint32_t* d_road, uint32_t* d_curb, uint32_t* d_ring10, uint32_t stride,
                                          uint32_t* d_counts)
 {
     const urf_last_call* l = c ? last_valid(c) : nullptr;
-    if (!l || !d_counts || stride < l->a.max_len || refuse_dense(c, "urf_ordered_indices_batch"))
-        return URF_ERR_INVALID_ARG;
+    if (!l || !d_counts || refuse_dense(c, "urf_ordered_indices_batch", true) || stride < (l->dense.on ? l->dense.max_len : l->a.max_len))
+        return URF_ERR_INVALID_ARG;   /* (a dense call's lists hold dense points: none is longer than its max_len) */
     const int rc = last_call(c, 0, l, URF_NEED_RING_ORDER);
     return rc != URF_OK ? rc : launch_ordered(c, *l, 0, l->scans, d_road, d_curb, d_ring10, stride, d_counts);
 }
@@ -1806,7 +1851,7 @@ extern "C" int urf_ordered_indices_batch(urf_ctx* c, uint32_t* d_road, uint32_t*
 extern "C" int urf_ordered_indices(urf_ctx* c, uint32_t scan, uint32_t* road, uint32_t* curb, uint32_t* ring10,
                                    uint32_t* counts)
 {
-    if (!c || !counts || refuse_dense(c, "urf_ordered_indices"))
+    if (!c || !counts || refuse_dense(c, "urf_ordered_indices", true))
         return URF_ERR_INVALID_ARG;
     const size_t mp = c->sstride;
     const urf_last_call* l;
@@ -1853,8 +1898,10 @@ static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, ur
     const urf_last_call* l;
     if (!d_counts || !d_offsets || (order != URF_ORDER_INPUT && order != URF_ORDER_REFERENCE) || !(l = last_valid(c, 0, kind)))
         return URF_ERR_INVALID_ARG;
-    const bool dense = l->dense.on;   /* input order: the caller's dense labels, inputs and offsets; the reference order is the padded batch's */
-    if (dense && order == URF_ORDER_REFERENCE && refuse_dense(c, "urf_clouds_batch_* with URF_ORDER_REFERENCE"))
+    /* a dense call: the caller's dense labels, inputs and offsets; the reference order is the padded batch's, mapped back by launch_ordered
+     * under urf_set_dense_outputs */
+    const bool dense = l->dense.on;
+    if (dense && order == URF_ORDER_REFERENCE && refuse_dense(c, "urf_clouds_batch_* with URF_ORDER_REFERENCE", true))
         return URF_ERR_INVALID_ARG;
     const uint32_t S = l->scans, max_len = dense ? l->dense.max_len : l->a.max_len, stride = max_len ? max_len : 1u;
     if (d_records && capacity < 3ull * S * max_len)

@@ -265,4 +265,70 @@ __global__ __launch_bounds__(URF_DENSE_THREADS) void k_dense_labels(urf_dense_ar
     }
 }
 
+/* ---- the way back: the reference-order lists of the padded batch in the caller's dense indices (urf_set_dense_outputs) -------------
+ * pos grows strictly with i inside a scan, so its inverse is a function on the positions that hold a point; the ordered lists
+ * (k_ordered_lists) hold only such positions, the holes being NaN and dropped before anything else.
+ *   k_dense_inverse      workgroup (tile, scan): inv[s * W * L + pos[i]] = i for the scan's points; the holes of inv are never written
+ *   k_dense_unmap_lists  workgroup (256 entries, scan, list): entries 0 .. count - 1 of road / curb / ring10 in place, p -> inv[p];
+ *                        every entry is checked against pos (a hole of inv holds anything), a miss stores URF_DENSE_NONE */
+#define URF_DENSE_NONE 0xffffffffu
+
+struct urf_dense_unmap_args {
+    const uint32_t* offsets;      /* [n_scans + 1] the context's copy of the dense call's */
+    uint32_t max_len, WL;         /* the dense call's; W * L: stride of pos and inv */
+    const uint32_t* pos;          /* [n_scans][W * L] */
+    uint32_t* inv;                /* [n_scans][W * L] */
+};
+
+__device__ __forceinline__ void urf_dense_unmap_range(const urf_dense_unmap_args& a, unsigned s, unsigned& len)
+{
+    len = a.offsets[s + 1] - a.offsets[s];   /* (urf_dense_range) */
+    len = len > a.max_len ? a.max_len : len;
+}
+
+__global__ __launch_bounds__(URF_DENSE_THREADS) void k_dense_inverse(urf_dense_unmap_args a)
+{
+    const unsigned t = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
+    unsigned len;
+    urf_dense_unmap_range(a, s, len);
+    const unsigned long long pbase = (unsigned long long)s * a.WL;
+#pragma unroll
+    for (unsigned j = 0; j < URF_DENSE_CHUNKS; j++) {
+        const unsigned i = t * URF_TILE + j * URF_DENSE_THREADS + tid;
+        if (i < len) {   /* (len <= max_len <= W * L: inside the scan's row of pos) */
+            const unsigned p = a.pos[pbase + i];
+            if (p < a.WL)
+                a.inv[pbase + p] = i;
+        }
+    }
+}
+
+/* scans [s0, s0 + gridDim.y) of the dense call; the lists and counts as k_ordered_lists wrote them (scan s0 first, a list may be NULL) */
+__global__ __launch_bounds__(URF_DENSE_THREADS) void k_dense_unmap_lists(urf_dense_unmap_args a, unsigned s0, unsigned* road_all,
+                                                                         unsigned* curb_all, unsigned* ring10_all, unsigned stride,
+                                                                         const unsigned* counts_all)
+{
+    const unsigned k = blockIdx.z, s = s0 + blockIdx.y;
+    const unsigned e = blockIdx.x * URF_DENSE_THREADS + threadIdx.x;
+    unsigned* const all = k == 0 ? road_all : k == 1 ? curb_all : ring10_all;
+    if (!all)
+        return;
+    unsigned n = counts_all[(size_t)blockIdx.y * 3 + k];
+    n = n > stride ? stride : n;
+    if (e >= n)
+        return;
+    unsigned len;
+    urf_dense_unmap_range(a, s, len);
+    const unsigned long long pbase = (unsigned long long)s * a.WL;
+    unsigned* const q = all + (size_t)blockIdx.y * stride + e;
+    const unsigned p = *q;
+    unsigned i = URF_DENSE_NONE;
+    if (p < a.WL) {
+        const unsigned j = a.inv[pbase + p];
+        if (j < len && a.pos[pbase + j] == p)
+            i = j;
+    }
+    *q = i;
+}
+
 #endif /* URF_K_DENSE_HPP */
