@@ -72,7 +72,9 @@ extern "C" {
  * urf_set_dense_slots and urf_dense_scans (dense sweeps put back into firing slots by laser id on the device, then classified as
  * organised ones); urf_set_front_curb_points (front mode 3's curbPoints 1..8 at 16, 32 and 128 lasers per firing as well);
  * urf_set_front_multi_sector_curb_points (urf_set_front_multi_sector at curbPoints 1..8 instead of 5 only); urf_set_dense_outputs
- * (the reference-order read-outs after a dense call, in the caller's indices).
+ * (the reference-order read-outs after a dense call, in the caller's indices); urf_set_dense_elevations with
+ * urf_classify_batch_soa_dense_elev / urf_classify_batch_pc2_dense_elev (the dense calls for clouds without a `ring` field: laser ids
+ * derived from the points' elevation on the device).
  * WHICH std::sort (4 above): the one of libstdc++ as shipped with GCC 5 .. 13 (bits/stl_algo.h: __sort = __introsort_loop with
  * _S_threshold 16, __move_median_to_first on (first + 1, mid, last - 1), __unguarded_partition, depth limit 2 * floor(log2 n),
  * __partial_sort as the fallback, then __final_insertion_sort); tests/test_stdsort.py pins the restatement against the std::sort
@@ -691,6 +693,42 @@ int urf_classify_batch_pc2_dense(urf_ctx* ctx, const uint8_t* d_data, const uint
 int urf_set_dense_slots(urf_ctx* ctx, const uint8_t* slot_of_id, uint32_t n_ids);
 int urf_dense_scans(urf_ctx* ctx, uint32_t* n_aligned);
 int urf_set_dense_outputs(urf_ctx* ctx, int on);
+
+/* ---- dense sweeps without a `ring` field: laser ids from elevation, on the device ---------
+ * The reference subscribes to pcl::PointXYZI -- x, y, z, intensity, no `ring` --, and a dense cloud of that kind has no id to hand to
+ * the calls above.  These calls derive one per point from its vertical angle and then run the dense calls unchanged.
+ * THE ID RULE.  The caller states once per context the elevation in degrees of the laser in every slot of a firing: elev_deg[l],
+ * l = 0 .. n-1, in firing order (the order urf_set_dense_slots maps to; the sensor's datasheet has the table).  On the host the slots
+ * are ranked by ascending elevation, the lower slot first among equals: e_0 <= ... <= e_{n-1}, slot_of_rank[n], and for k = 0 .. n-2
+ * T[k] = (float)tan((e_k + e_{k+1}) / 2 * pi / 180), computed in double.  On the device, per point: h = sqrtf(x * x + y * y); rank =
+ * the number of k with z > T[k] * h; id = slot_of_rank[rank].  T[k] * h does not decrease with k for h >= 0, so the rank is a binary
+ * search of at most 7 steps.
+ * EDGE POINTS get whatever the compares give: a point with a NaN field, a point at (0, 0, 0) or a point on the sensor's axis has rank
+ * 0, or n-1 for z > 0 on the axis (infinite fields: as IEEE multiplies and compares them); a point outside the sensor's fan takes the
+ * outermost laser's slot; two lasers of equal elevation cannot be told apart (the lower slot ranks first, the threshold between them
+ * is their own tangent, and their points fall to either side of it).  All of this costs speed only: by THE RULE above, labels and
+ * summaries are those of the ragged call for any ids whatever, and a scan whose derived ids do not line up is "not aligned" or handed
+ * back like any other.
+ * urf_set_dense_elevations: n = 1 .. 128 values, each finite and strictly inside (-90, 90); anything else: URF_ERR_INVALID_ARG, and
+ * the table set before stays.  NULL with n = 0 clears it.  The table is copied; the next elevation call takes it to the device.
+ * THE CALLS.  urf_classify_batch_soa_dense / urf_classify_batch_pc2_dense without d_laser / off_laser and laser_bytes: every argument
+ * rule, capacity rule, "not aligned" rule and everything under AFTER A DENSE CALL holds as written there (urf_dense_scans,
+ * urf_front_scans, urf_set_dense_outputs and the read-outs, urf_read_stage's refusal).  Added: no table set, or a table whose n is
+ * not the parameters' `channels` at the call: URF_ERR_INVALID_ARG, urf_last_error says which.  The derived ids are slots: the map of
+ * urf_set_dense_slots does not apply to them and is left as it is for the next call with ids of the caller's.  The first such call
+ * allocates one byte per point of max_points * max_batch for the ids (URF_ERR_OOM from that call), which are kept at the indices of
+ * the caller's arrays: urf_classify_batch_soa_dense_elev therefore wants d_offsets[n_scans] <= max_points * max_batch, as
+ * urf_classify_batch_pc2_dense_elev checks of n_total (the offsets live on the device, the call cannot answer URF_ERR_CAPACITY for
+ * them; ids beyond that are not written).  A context that never makes such a call allocates and launches nothing new.
+ * The kernels (k_dense_ids_soa / k_dense_ids_pc2, urf_k_dense.hpp) run in front of the dense calls', outside the timing brackets. */
+int urf_set_dense_elevations(urf_ctx* ctx, const float* elev_deg, uint32_t n);
+int urf_classify_batch_soa_dense_elev(urf_ctx* ctx, const float* d_x, const float* d_y, const float* d_z,
+                                      const uint32_t* d_offsets, uint32_t max_len, uint32_t n_scans,
+                                      uint32_t max_firings, uint8_t* d_labels, urf_scan_info* d_info);
+int urf_classify_batch_pc2_dense_elev(urf_ctx* ctx, const uint8_t* d_data, const uint32_t* d_offsets, uint64_t n_total,
+                                      uint32_t max_len, uint32_t n_scans, uint32_t point_step,
+                                      uint32_t off_x, uint32_t off_y, uint32_t off_z,
+                                      uint32_t max_firings, uint8_t* d_labels, urf_scan_info* d_info);
 
 /* ---- per-kernel timing (benchmark) ------------------------------------------
  * With timing on, every classify call brackets each kernel of the pipeline

@@ -57,6 +57,13 @@ int urf_selftest_fast(urf_ctx* ctx, uint64_t n_samples, float* err);
  * store their records with non-temporal stores (an A/B switch for tools/batch_clouds_bench.py: measured slower). */
 int urf_set_debug_flags(urf_ctx* ctx, uint32_t flags);
 
+/* The ids urf_classify_batch_*_dense_elev derived (include/urf.h): the first n bytes of the context's id buffer, indexed like the
+ * caller's arrays, after a synchronise.  n beyond the buffer (no such call yet: any n > 0): URF_ERR_INVALID_ARG. */
+int urf_test_dense_ids(urf_ctx* ctx, uint8_t* host, uint64_t n);
+/* Benchmark helper: the id kernel of the last such call launched `reps` times again on the context's stream between two events (the
+ * caller's inputs must still be alive); *ms = milliseconds per launch.  Synchronous.  No such call yet: URF_ERR_INVALID_ARG. */
+int urf_test_dense_ids_ms(urf_ctx* ctx, uint32_t reps, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,8 +10,17 @@ Per sensor model (hdl64e-like with range noise, ideal64; tests/sensor_models.py)
   a  classify_batch_soa_ragged on the dense points   (context A: the baseline -- that entry point's code is the parent commit's)
   b  classify_batch_soa_dense                        (context B)
   c  classify_batch_soa on the organised twin        (context B: the padded sweeps built on the host, the bound)
-Per side: the 10th / 50th / 90th percentiles of ms per call, the per-pair ratio a / b, urf_front_scans, urf_dense_scans."""
+Per side: the 10th / 50th / 90th percentiles of ms per call, the per-pair ratio a / b, urf_front_scans, urf_dense_scans.
+
+    timeout 900 python tools/dense_bench.py --elev ... > profiles/dense_elev_bench.json
+
+--elev adds a fourth arm, interleaved with the others (their keys and calls stay as they are):
+  d  classify_batch_soa_dense_elev                   (context D, the library with the test hooks: no ids handed in, derived on the
+                                                      device from the points' elevation and the model's table, urf_set_dense_elevations)
+with its percentiles, the per-pair ratios a / d and b / d, the share of derived ids that are the true slots, and the id kernel's own
+bracket (urf_test_dense_ids_ms: k_dense_ids_soa of the last call launched again, ms per launch)."""
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -32,6 +41,7 @@ def main():
     ap.add_argument("--distinct", type=int, default=32, help="distinct sweeps the batch is built from")
     ap.add_argument("--firings", type=int, default=2048)
     ap.add_argument("--models", default="hdl64e,ideal64")
+    ap.add_argument("--elev", action="store_true", help="add arm d: the dense call with ids derived from elevation")
     args = ap.parse_args()
     import torch
     import urban_road_filter_amd as u
@@ -42,7 +52,7 @@ def main():
         raise SystemExit("no GPU: nothing is measured here")
     dev = torch.device("cuda:0")
     S, W = args.scans, args.firings
-    out = {"metric": "dense_bench", "device": torch.cuda.get_device_name(0), "scans": S, "firings": W, "front_mode": 2,
+    out = {"metric": "dense_elev_bench" if args.elev else "dense_bench", "device": torch.cuda.get_device_name(0), "scans": S, "firings": W, "front_mode": 2,
            "timing": "device events per call, a / b / c interleaved call by call in one process; ms", "results": []}
     t0 = time.time()
     st = torch.cuda.Stream()
@@ -74,32 +84,43 @@ def main():
             lab_a = torch.empty(n_total, dtype=torch.uint8, device=dev)
             lab_b = torch.empty(n_total, dtype=torch.uint8, device=dev)
             lab_c = torch.empty(S * n, dtype=torch.uint8, device=dev)
+            lab_d = torch.empty(n_total if args.elev else 1, dtype=torch.uint8, device=dev)
+            arms = ("a", "b", "c", "d") if args.elev else ("a", "b", "c")
             gate = sorted({0, 1, S - 1})
             want = {k: O.run_b(*dense[order[k]], p)[0] for k in gate}
-            with u.Context(n, S, params=p) as A, u.Context(n, S, params=p) as B:
-                for ctx in (A, B):
+            with contextlib.ExitStack() as stack:
+                A, B = stack.enter_context(u.Context(n, S, params=p)), stack.enter_context(u.Context(n, S, params=p))
+                Dx = stack.enter_context(u.Context(n, S, params=p, hooks=True)) if args.elev else None
+                for ctx in (A, B, Dx) if args.elev else (A, B):
                     ctx.set_stream(st.cuda_stream)
                     ctx.set_front_mode(2)
+                if args.elev:
+                    Dx.set_dense_elevations(SM.MODELS[model]["elev"])
                 calls = {"a": lambda: A.classify_batch_soa_ragged(dx, dy, dz, doff, max_len, S, lab_a, None),
                          "b": lambda: B.classify_batch_soa_dense(dx, dy, dz, did, 2, doff, max_len, S, W, lab_b, None),
-                         "c": lambda: B.classify_batch_soa(tx, ty, tz, n, S, lab_c, None)}
-                fused, aligned_scans = {}, None
-                for name in ("a", "b", "c"):   # the label gate and the warm-up
+                         "c": lambda: B.classify_batch_soa(tx, ty, tz, n, S, lab_c, None),
+                         "d": lambda: Dx.classify_batch_soa_dense_elev(dx, dy, dz, doff, max_len, S, W, lab_d, None)}
+                fused, aligned_scans, elev_info = {}, None, {}
+                for name in arms:   # the label gate and the warm-up
                     for _ in range(max(2, args.warmup)):
                         calls[name]()
                     torch.cuda.synchronize()
-                    ctx = A if name == "a" else B
+                    ctx = A if name == "a" else Dx if name == "d" else B
                     fused[name] = int(ctx.front_scans())
                     if name == "b":
                         aligned_scans = int(B.dense_scans())
+                    if name == "d":
+                        true_slots = np.concatenate([slots[k] for k in order]).astype(np.uint8)
+                        elev_info = {"dense_scans_d": int(Dx.dense_scans()),
+                                     "derived_ids_equal_true_slots": float((Dx.dense_ids(n_total) == true_slots).mean())}
                     if name != "c":
-                        got = (lab_a if name == "a" else lab_b).cpu().numpy()
+                        got = (lab_a if name == "a" else lab_d if name == "d" else lab_b).cpu().numpy()
                         for k, lb in want.items():
                             if not np.array_equal(got[offs[k]:offs[k + 1]], lb):
                                 raise SystemExit("label gate: %s side %s scan %d differs from oracle B" % (model, name, k))
-                ts = {"a": [], "b": [], "c": []}
+                ts = {name: [] for name in arms}
                 for _ in range(args.steps):
-                    for name in ("a", "b", "c"):
+                    for name in arms:
                         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         e0.record()
                         calls[name]()
@@ -111,7 +132,15 @@ def main():
                                        "a_ragged_ms_p10_p50_p90": pct(ts["a"]), "b_dense_ms_p10_p50_p90": pct(ts["b"]),
                                        "c_twin_ms_p10_p50_p90": pct(ts["c"]),
                                        "a_over_b_p10_p50_p90": pct([a / b for a, b in zip(ts["a"], ts["b"])])})
-            del dx, dy, dz, tx, ty, tz, did, lab_a, lab_b, lab_c
+                if args.elev:
+                    calls["d"]()   # (the id kernel's bracket launches the last elevation call's again)
+                    torch.cuda.synchronize()
+                    ids_ms = [Dx.dense_ids_ms(5) for _ in range(args.steps)]
+                    out["results"][-1].update(elev_info, d_dense_elev_ms_p10_p50_p90=pct(ts["d"]),
+                                              a_over_d_p10_p50_p90=pct([a / d for a, d in zip(ts["a"], ts["d"])]),
+                                              b_over_d_p10_p50_p90=pct([b / d for b, d in zip(ts["b"], ts["d"])]),
+                                              k_dense_ids_soa_ms_p10_p50_p90=pct(ids_ms))
+            del dx, dy, dz, tx, ty, tz, did, lab_a, lab_b, lab_c, lab_d
             torch.cuda.empty_cache()
     out["wall_s"] = time.time() - t0
     print(json.dumps(out))

@@ -103,7 +103,8 @@ PARAM_BOOL, PARAM_INT, PARAM_DOUBLE, PARAM_STR = range(4)
 
 _LIBS = {}
 
-HOOK_SYMBOLS = ("urf_set_debug_flags", "urf_selftest", "urf_selftest_fast", "urf_synth_cloud", "urf_bench_callback_stream")
+HOOK_SYMBOLS = ("urf_set_debug_flags", "urf_selftest", "urf_selftest_fast", "urf_synth_cloud", "urf_bench_callback_stream",
+                "urf_test_dense_ids", "urf_test_dense_ids_ms")
 
 
 def lib_path(hooks=False):
@@ -188,6 +189,12 @@ def lib(hooks=False):
         "urf_set_dense_slots": [vp, u8p, C.c_uint32],
         "urf_dense_scans": [vp, C.c_void_p],
         "urf_set_dense_outputs": [vp, C.c_int],
+        "urf_set_dense_elevations": [vp, fp, C.c_uint32],
+        "urf_classify_batch_soa_dense_elev": [vp, fp, fp, fp, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp],
+        "urf_classify_batch_pc2_dense_elev": [vp, u8p, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.c_uint32, C.c_uint32, u8p, vp],
+        "urf_test_dense_ids": [vp, u8p, C.c_uint64],
+        "urf_test_dense_ids_ms": [vp, C.c_uint32, C.POINTER(C.c_float)],
     }
     for name, args in sig.items():
         if name in HOOK_SYMBOLS and not has_hooks:
@@ -579,6 +586,44 @@ class Context:
         caller's dense indices (the padded positions mapped back on the device; include/urf.h); 0 (default) keeps them refused.
         read_stage stays refused after a dense call either way."""
         self._check(self._lib.urf_set_dense_outputs(self._h, int(on)), "urf_set_dense_outputs")
+
+    # -- ... without a `ring` field: the laser ids derived from the points' elevation on the device ----
+    def set_dense_elevations(self, elev):
+        """urf_set_dense_elevations: elev[l] = elevation in degrees of the laser in slot l of a firing (1..128 values, each strictly
+        inside (-90, 90)); None clears the table.  Its size must equal the parameters' channels when an elevation call is made."""
+        if elev is None:
+            self._check(self._lib.urf_set_dense_elevations(self._h, None, 0), "urf_set_dense_elevations")
+            return
+        e = np.ascontiguousarray(elev, np.float32).reshape(-1)
+        self._check(self._lib.urf_set_dense_elevations(self._h, e.ctypes.data, e.size), "urf_set_dense_elevations")
+
+    def classify_batch_soa_dense_elev(self, d_x, d_y, d_z, d_offsets, max_len, n_scans, max_firings, d_labels, d_info=None):
+        """urf_classify_batch_soa_dense_elev: classify_batch_soa_dense without d_laser: the ids come from the points' elevation and
+        the table of set_dense_elevations; same labels and infos (include/urf.h)."""
+        self._check(self._lib.urf_classify_batch_soa_dense_elev(self._h, _ptr(d_x), _ptr(d_y), _ptr(d_z), _ptr(d_offsets), max_len, n_scans,
+                                                                max_firings, _ptr(d_labels), _ptr(d_info)),
+                    "urf_classify_batch_soa_dense_elev")
+
+    def classify_batch_pc2_dense_elev(self, d_data, d_offsets, n_total, max_len, n_scans, point_step, off_x, off_y, off_z, max_firings,
+                                      d_labels, d_info=None):
+        """urf_classify_batch_pc2_dense_elev: classify_batch_pc2_dense for records without a laser id."""
+        self._check(self._lib.urf_classify_batch_pc2_dense_elev(self._h, _ptr(d_data), _ptr(d_offsets), n_total, max_len, n_scans,
+                                                                point_step, off_x, off_y, off_z, max_firings, _ptr(d_labels),
+                                                                _ptr(d_info)), "urf_classify_batch_pc2_dense_elev")
+
+    def dense_ids(self, n):
+        """Test hook: the first n derived ids of the last elevation call, indexed like its inputs (uint8 array)."""
+        self._need_hooks("urf_test_dense_ids")
+        out = np.zeros(max(int(n), 1), np.uint8)
+        self._check(self._lib.urf_test_dense_ids(self._h, out.ctypes.data, int(n)), "urf_test_dense_ids")
+        return out[:int(n)]
+
+    def dense_ids_ms(self, reps=10):
+        """Benchmark hook: milliseconds per launch of the last elevation call's id kernel, run `reps` times again."""
+        self._need_hooks("urf_test_dense_ids_ms")
+        ms = C.c_float(0)
+        self._check(self._lib.urf_test_dense_ids_ms(self._h, int(reps), C.byref(ms)), "urf_test_dense_ids_ms")
+        return float(ms.value)
 
     def clouds_batch_soa(self, d_intensity, order, d_records, capacity, d_counts, d_offsets):
         """The four published clouds of every scan of the last (SoA) batch call as 32-byte records on the device:

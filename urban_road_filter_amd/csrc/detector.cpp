@@ -447,6 +447,12 @@ void BatchDetector::setDenseRealign(uint32_t max_firings, const std::vector<uint
     dense_firings_ = max_firings;
 }
 
+void BatchDetector::setDenseElevations(const std::vector<float>& elev_deg)
+{
+    check(urf_set_dense_elevations(ctx_, elev_deg.empty() ? nullptr : elev_deg.data(), (uint32_t)elev_deg.size()), "urf_set_dense_elevations");
+    dense_elev_n_ = elev_deg.size();
+}
+
 /* the `ring` field of a record layout: UINT8 or UINT16, count 1, inside the record; bytes = 0: none */
 static void ringField(const PointCloud2& m, uint32_t& off, uint32_t& bytes)
 {
@@ -531,22 +537,32 @@ size_t BatchDetector::filtered(const std::vector<PointCloud2>& msgs)
     if (hipMemcpyAsync(d_data, h_data_.data(), h_data_.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(d_offsets, offsets.data(), (S + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess)
         throw Error(URF_ERR_HIP, "BatchDetector: upload failed");
-    /* setDenseRealign: every message carries the same `ring` field, input order (or setDenseOutputs: the reference order comes back in the
+    /* setDenseRealign: every message carries the same `ring` field (or none does: setDenseElevations), input order (or setDenseOutputs: the reference order comes back in the
      * messages' indices), and the sensor's padded sweep fits the context */
     uint32_t ring_off = 0, ring_bytes = 0;
+    bool by_elevation = false;   /* setDenseElevations: no message carries the field, and the table fits the parameters */
     if (dense_firings_ != 0 && (!reference_order_ || dense_outputs_)) {
         ringField(msgs[0], ring_off, ring_bytes);
-        for (size_t i = 1; i < S && ring_bytes; i++) {
+        by_elevation = ring_bytes == 0 && dense_elev_n_ != 0 && dense_elev_n_ == (size_t)params().channels;
+        for (size_t i = 1; i < S && (ring_bytes || by_elevation); i++) {
             uint32_t o = 0, b = 0;
             ringField(msgs[i], o, b);
             if (o != ring_off || b != ring_bytes)
                 ring_bytes = 0;
+            if (b != 0)
+                by_elevation = false;
         }
         const uint64_t padded = (uint64_t)dense_firings_ * (uint32_t)params().channels;
-        if (padded > max_points_ || max_len > padded)
+        if (padded > max_points_ || max_len > padded) {
             ring_bytes = 0;
+            by_elevation = false;
+        }
     }
-    if (ring_bytes) {
+    if (by_elevation) {
+        check(urf_classify_batch_pc2_dense_elev(ctx_, d_data, d_offsets, total, max_len, (uint32_t)S, step, off[0], off[1], off[2], dense_firings_,
+                                                d_labels, d_info),
+              "urf_classify_batch_pc2_dense_elev");
+    } else if (ring_bytes) {
         check(urf_classify_batch_pc2_dense(ctx_, d_data, d_offsets, total, max_len, (uint32_t)S, step, off[0], off[1], off[2], ring_off, ring_bytes,
                                            dense_firings_, d_labels, d_info),
               "urf_classify_batch_pc2_dense");
@@ -570,7 +586,7 @@ size_t BatchDetector::filtered(const std::vector<PointCloud2>& msgs)
     if (n_rec && (hipMemcpyAsync(h_records_.data(), d_rec, n_rec * sizeof(urf_point_xyzi), hipMemcpyDeviceToHost, st) != hipSuccess ||
                   hipStreamSynchronize(st) != hipSuccess))
         throw Error(URF_ERR_HIP, "BatchDetector: read-back failed");
-    if (ring_bytes) {
+    if (ring_bytes || by_elevation) {
         uint32_t n_aligned = 0;
         check(urf_dense_scans(ctx_, &n_aligned), "urf_dense_scans");
         dense_aligned_ = n_aligned;

@@ -229,10 +229,16 @@ public:
     /* Dense messages (the driver dropped the non-returns) with a field named "ring" (UINT8 or UINT16, count 1) are put back into firing
      * slots on the device and classified as organised sweeps (urf_classify_batch_pc2_dense, include/urf.h): max_firings = the sensor's
      * firings per revolution, slot_of_ring[ring] = the laser's position inside a firing (empty: the ring is the position).  Same clouds,
-     * headers and road_marker either way; off by default, max_firings == 0 turns it off.  Messages without such a field, the reference
-     * order (setReferenceOrder) while setDenseOutputs is off, and a sensor whose max_firings * channels sweep does not fit max_points keep
-     * the ragged call. */
+     * headers and road_marker either way; off by default, max_firings == 0 turns it off.  Messages without such a field (but see
+     * setDenseElevations), the reference order (setReferenceOrder) while setDenseOutputs is off, and a sensor whose max_firings *
+     * channels sweep does not fit max_points keep the ragged call. */
     void setDenseRealign(uint32_t max_firings, const std::vector<uint8_t>& slot_of_ring = {});
+    /* urf_set_dense_elevations: elev_deg[l] = the elevation in degrees of the laser in slot l of a firing (the sensor's datasheet).  With
+     * setDenseRealign on, messages WITHOUT a `ring` field (pcl::PointXYZI, what the reference subscribes to) then take
+     * urf_classify_batch_pc2_dense_elev -- the ids derived from the points' elevation on the device -- when the table's size is the
+     * parameters' channels; otherwise, and without this call, they keep the ragged call.  Messages with the field are not affected.  An
+     * empty vector clears the table. */
+    void setDenseElevations(const std::vector<float>& elev_deg);
     /* urf_set_dense_outputs: the reference order after a dense call, in the messages' own indices.  On, setReferenceOrder(true) no longer
      * keeps filtered() off the dense call: same clouds, in the reference's order.  Off (default): filtered() chooses as above. */
     void setDenseOutputs(bool on)
@@ -270,6 +276,7 @@ private:
     uint32_t max_points_ = 0, max_batch_ = 0;
     bool reference_order_ = false;
     uint32_t dense_firings_ = 0;   /* setDenseRealign */
+    size_t dense_elev_n_ = 0;      /* setDenseElevations */
     bool dense_outputs_ = false;   /* setDenseOutputs */
     size_t dense_aligned_ = 0;
     /* device buffers (grown on demand) */

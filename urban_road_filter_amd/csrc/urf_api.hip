@@ -5,6 +5,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -250,6 +251,14 @@ struct urf_ctx {
     lazy_buf<uint8_t> dn_labels;
     lazy_buf<uint32_t> dn_words;
     lazy_buf<uint8_t> dn_map;
+    /* urf_classify_batch_*_dense_elev: the ids derived from the points' elevation ([max_batch][max_points] bytes, indexed like the
+     * caller's arrays) and the device copy of dense_elev, both grown by the first such call */
+    lazy_buf<uint8_t> dn_ids;
+    lazy_buf<urf_dense_elev_table> dn_elev;
+    urf_dense_elev_table dense_elev;   /* urf_set_dense_elevations, for dense_elev_n slots (0: none) */
+    uint32_t dense_elev_n = 0;
+    bool dense_elev_dirty = true;      /* ... not yet in dn_elev */
+    struct { urf_dense_args d; urf_dense_ids_args e; uint32_t kind = URF_LAST_NONE; } dn_ids_call;   /* the last id launch (urf_test_dense_ids_ms) */
     /* urf_set_dense_outputs: the inverse of dn_pos ([max_batch][max_points], k_dense_inverse), grown by the first read-out that needs it
      * and built once per dense call: dn_calls counts those (a rerun of the padded batch writes `last` and leaves dn_pos as it is), dn_inv_of
      * is the one dn_inv holds (0: none) */
@@ -474,7 +483,8 @@ extern "C" int urf_create(urf_ctx** out, int device_id, uint32_t max_points, uin
     c->max_tiles = (uint32_t)max_tiles;
     c->sstride = (uint32_t)sstride;
     for (unsigned i = 0; i < 256; i++)
-        c->dense_map[i] = (uint8_t)i;
+        c->dense_map[i] = c->dense_elev.identity[i] = (uint8_t)i;
+    (void)urf_set_dense_elevations(c, nullptr, 0);   /* (no table: the rest of dense_elev) */
     int rc = URF_OK;
     auto fail = [&](int code) {
         urf_destroy(c);
@@ -1204,7 +1214,7 @@ extern "C" int urf_dense_scans(urf_ctx* c, uint32_t* n_aligned)
 /* d: where ids and points come from (id*, x / y / z or data and its layout; the rest is filled in here).  The padded batch -- n_scans
  * scans of W * L points in the SoA staging, NaN wherever no point landed -- is a plain batch call to everything behind the scatter. */
 static int classify_batch_dense(urf_ctx* c, int kind, urf_dense_args d, const uint32_t* d_offsets, uint32_t max_len, uint32_t n_scans,
-                                uint32_t max_firings, uint8_t* d_labels, urf_scan_info* d_info)
+                                uint32_t max_firings, uint8_t* d_labels, urf_scan_info* d_info, bool elev = false)
 {
     const uint64_t WL = (uint64_t)max_firings * (uint32_t)c->params.channels;
     if (WL > c->max_points || max_len > WL || n_scans > c->max_batch)
@@ -1219,6 +1229,8 @@ static int classify_batch_dense(urf_ctx* c, int kind, urf_dense_args d, const ui
     if ((rc = ensure_soa_staging(c)) != URF_OK || (rc = grow(c, c->dn_pos, n_all)) != URF_OK || (rc = grow(c, c->dn_labels, n_all)) != URF_OK ||
         (rc = grow(c, c->dn_words, 2 * per_tile + c->max_batch + 1)) != URF_OK || (rc = grow(c, c->dn_map, 256)) != URF_OK)
         return rc;
+    if (elev && ((rc = grow(c, c->dn_ids, n_all)) != URF_OK || (rc = grow(c, c->dn_elev, 1)) != URF_OK))
+        return rc;
     if ((rc = order_after_slots(c)) != URF_OK)   /* the staging arrays are shared with the callback path */
         return rc;
     hipStream_t st = c->stream;
@@ -1226,6 +1238,11 @@ static int classify_batch_dense(urf_ctx* c, int kind, urf_dense_args d, const ui
         URF_HIP(c, hipStreamSynchronize(st));
         URF_HIP(c, hipMemcpy(c->dn_map.p, c->dense_map, sizeof(c->dense_map), hipMemcpyHostToDevice));
         c->dense_map_dirty = false;
+    }
+    if (elev && c->dense_elev_dirty) {   /* (as rare, and as far outside every captured sequence) */
+        URF_HIP(c, hipStreamSynchronize(st));
+        URF_HIP(c, hipMemcpy(c->dn_elev.p, &c->dense_elev, sizeof(c->dense_elev), hipMemcpyHostToDevice));
+        c->dense_elev_dirty = false;
     }
     d.offsets = d_offsets;
     d.max_len = max_len;
@@ -1236,6 +1253,11 @@ static int classify_batch_dense(urf_ctx* c, int kind, urf_dense_args d, const ui
     d.L = (uint32_t)c->params.channels;
     d.W = max_firings;
     d.slot_of_id = c->dn_map.p;
+    if (elev) {   /* derived ids are slots already: the table's identity, not urf_set_dense_slots' map */
+        d.id = c->dn_ids.p;
+        d.id_stride = d.id_bytes = 1u;
+        d.slot_of_id = c->dn_elev.p->identity;
+    }
     d.tile_cnt = dense_word(c, 0);
     d.tile_base = dense_word(c, 1);
     d.aligned = dense_word(c, 2);
@@ -1253,6 +1275,16 @@ static int classify_batch_dense(urf_ctx* c, int kind, urf_dense_args d, const ui
     URF_HIP(c, hipMemsetAsync(c->sz.p, 0xff, fill, st));
     URF_HIP(c, hipMemsetAsync(d.n_aligned, 0, sizeof(uint32_t), st));
     const dim3 g_tiles(d.tiles, n_scans);
+    if (elev) {
+        const urf_dense_ids_args e{ c->dn_elev.p, c->dn_ids.p, (unsigned long long)c->dn_ids.cap };
+        if (kind == URF_LAST_PC2)
+            hipLaunchKernelGGL(k_dense_ids_pc2, g_tiles, dim3(URF_DENSE_THREADS), 0, st, d, e);
+        else
+            hipLaunchKernelGGL(k_dense_ids_soa, g_tiles, dim3(URF_DENSE_THREADS), 0, st, d, e);
+        c->dn_ids_call.d = d;
+        c->dn_ids_call.e = e;
+        c->dn_ids_call.kind = (uint32_t)kind;
+    }
     hipLaunchKernelGGL(k_dense_count, g_tiles, dim3(URF_DENSE_THREADS), 0, st, d);
     hipLaunchKernelGGL(k_dense_scan, dim3(n_scans), dim3(URF_DENSE_THREADS), 0, st, d);
     if (kind == URF_LAST_PC2)
@@ -1300,6 +1332,72 @@ extern "C" int urf_classify_batch_soa_dense(urf_ctx* c, const float* d_x, const 
     d.y = d_y;
     d.z = d_z;
     return classify_batch_dense(c, URF_LAST_SOA, d, d_offsets, max_len, n_scans, max_firings, d_labels, d_info);
+}
+
+/* ---- ... by ids derived from the points' elevation: clouds without a `ring` field ------------------------------- */
+extern "C" int urf_set_dense_elevations(urf_ctx* c, const float* elev_deg, uint32_t n)
+{
+    if (!c || (!elev_deg && n != 0) || (elev_deg && (n == 0 || n > URF_DENSE_ELEV_MAX)))
+        return URF_ERR_INVALID_ARG;
+    for (uint32_t l = 0; l < n; l++)
+        if (!(elev_deg[l] > -90.f && elev_deg[l] < 90.f))   /* (NaN fails both) */
+            return URF_ERR_INVALID_ARG;
+    /* slots by ascending elevation, the lower slot first among equals; thresholds at the tangents of the midpoints, in double */
+    uint8_t rank_slot[URF_DENSE_ELEV_MAX];
+    for (uint32_t l = 0; l < n; l++)
+        rank_slot[l] = (uint8_t)l;
+    std::stable_sort(rank_slot, rank_slot + n, [&](uint8_t a, uint8_t b) { return elev_deg[a] < elev_deg[b]; });
+    urf_dense_elev_table& t = c->dense_elev;
+    for (uint32_t k = 0; k < URF_DENSE_ELEV_MAX; k++) {
+        t.thr[k] = INFINITY;
+        t.slot_of_rank[k] = k < n ? rank_slot[k] : (uint8_t)0xff;
+        if (k + 1 < n)
+            t.thr[k] = (float)std::tan(((double)elev_deg[rank_slot[k]] + (double)elev_deg[rank_slot[k + 1]]) / 2.0 * 3.14159265358979323846 / 180.0);
+    }
+    c->dense_elev_n = n;
+    c->dense_elev_dirty = true;   /* (a copy; the device gets it with the next elevation call) */
+    return URF_OK;
+}
+
+/* the refusal the elevation calls add to the dense calls' */
+static bool refuse_elev(urf_ctx* c, const char* what)
+{
+    if (c->dense_elev_n != 0 && c->dense_elev_n == (uint32_t)c->params.channels)
+        return false;
+    c->last_error = std::string(what) + (c->dense_elev_n == 0 ? ": no elevation table (urf_set_dense_elevations)"
+                                                               : ": the elevation table's size is not the parameters' channels");
+    return true;
+}
+
+extern "C" int urf_classify_batch_soa_dense_elev(urf_ctx* c, const float* d_x, const float* d_y, const float* d_z, const uint32_t* d_offsets,
+                                                 uint32_t max_len, uint32_t n_scans, uint32_t max_firings, uint8_t* d_labels,
+                                                 urf_scan_info* d_info)
+{
+    if (!c || !d_x || !d_y || !d_z || !d_offsets || !d_labels || refuse_elev(c, "urf_classify_batch_soa_dense_elev"))
+        return URF_ERR_INVALID_ARG;
+    urf_dense_args d{};
+    d.x = d_x;
+    d.y = d_y;
+    d.z = d_z;
+    return classify_batch_dense(c, URF_LAST_SOA, d, d_offsets, max_len, n_scans, max_firings, d_labels, d_info, true);
+}
+
+extern "C" int urf_classify_batch_pc2_dense_elev(urf_ctx* c, const uint8_t* d_data, const uint32_t* d_offsets, uint64_t n_total,
+                                                 uint32_t max_len, uint32_t n_scans, uint32_t point_step, uint32_t off_x, uint32_t off_y,
+                                                 uint32_t off_z, uint32_t max_firings, uint8_t* d_labels, urf_scan_info* d_info)
+{
+    if (!c || !d_data || !d_offsets || !d_labels || !pc2_layout_ok(point_step, off_x, off_y, off_z) ||
+        refuse_elev(c, "urf_classify_batch_pc2_dense_elev"))
+        return URF_ERR_INVALID_ARG;
+    if (n_total > (uint64_t)c->max_points * c->max_batch)
+        return URF_ERR_CAPACITY;
+    urf_dense_args d{};
+    d.data = d_data;
+    d.step = point_step;
+    d.ox = off_x;
+    d.oy = off_y;
+    d.oz = off_z;
+    return classify_batch_dense(c, URF_LAST_PC2, d, d_offsets, max_len, n_scans, max_firings, d_labels, d_info, true);
 }
 
 extern "C" int urf_classify_batch_pc2_dense(urf_ctx* c, const uint8_t* d_data, const uint32_t* d_offsets, uint64_t n_total, uint32_t max_len,
@@ -2357,6 +2455,49 @@ extern "C" int urf_bench_callback_stream(urf_ctx* c, const uint8_t* const* msgs,
                 1e6 * c->ht[3] / n_sweeps, 1e6 * c->ht[4] / n_sweeps, 1e6 * c->ht[5] / n_sweeps);
         c->ht_on = false;
     }
+    return URF_OK;
+}
+
+/* the first n bytes of dn_ids as the last elevation call left them */
+extern "C" int urf_test_dense_ids(urf_ctx* c, uint8_t* host, uint64_t n)
+{
+    if (!c || !host || n > c->dn_ids.cap)
+        return URF_ERR_INVALID_ARG;
+    URF_HIP(c, hipSetDevice(c->device));
+    URF_HIP(c, hipStreamSynchronize(c->stream));
+    if (n)
+        URF_HIP(c, hipMemcpy(host, c->dn_ids.p, n, hipMemcpyDeviceToHost));
+    return URF_OK;
+}
+
+/* the id kernel of the last elevation call launched `reps` times again between two events: *ms = the mean of one launch */
+extern "C" int urf_test_dense_ids_ms(urf_ctx* c, uint32_t reps, float* ms)
+{
+    if (!c || !ms || reps == 0 || c->dn_ids_call.kind == URF_LAST_NONE)
+        return URF_ERR_INVALID_ARG;
+    URF_HIP(c, hipSetDevice(c->device));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    URF_HIP(c, hipEventCreate(&e0));
+    hipError_t err = hipEventCreate(&e1);
+    if (err == hipSuccess) {
+        const urf_dense_args& d = c->dn_ids_call.d;
+        const dim3 g_tiles(d.tiles, d.n_scans);
+        (void)hipEventRecord(e0, c->stream);
+        for (uint32_t r = 0; r < reps; r++) {
+            if (c->dn_ids_call.kind == URF_LAST_PC2)
+                hipLaunchKernelGGL(k_dense_ids_pc2, g_tiles, dim3(URF_DENSE_THREADS), 0, c->stream, d, c->dn_ids_call.e);
+            else
+                hipLaunchKernelGGL(k_dense_ids_soa, g_tiles, dim3(URF_DENSE_THREADS), 0, c->stream, d, c->dn_ids_call.e);
+        }
+        (void)hipEventRecord(e1, c->stream);
+        err = hipEventSynchronize(e1);
+        if (err == hipSuccess)
+            err = hipEventElapsedTime(ms, e0, e1);
+        (void)hipEventDestroy(e1);
+    }
+    (void)hipEventDestroy(e0);
+    URF_HIP(c, err);
+    *ms /= (float)reps;
     return URF_OK;
 }
 

@@ -15,6 +15,7 @@
  *                        through LDS) on top of the tile's base; x / y / z to the padded staging, the position to the per-point map
  *                        (_pc2 reads the records itself: it stands in for k_pc2_to_soa)
  *   k_dense_labels       d_labels[off[s] + i] = padded labels[s * W * L + pos[i]]
+ *   k_dense_ids_*        (urf_classify_batch_*_dense_elev only, in front of the others) the ids themselves, from the points' elevation
  * Positions come from counts and prefixes only.  Point indices inside a scan are 32 bit, everything multiplied by a scan number 64.
  */
 #ifndef URF_K_DENSE_HPP
@@ -330,5 +331,86 @@ __global__ __launch_bounds__(URF_DENSE_THREADS) void k_dense_unmap_lists(urf_den
     }
     *q = i;
 }
+
+/* ---- laser ids from elevation, for clouds without a `ring` field (urf_classify_batch_*_dense_elev, include/urf.h) -------------------
+ * The caller's table of elevations per firing slot, ranked on the host (urf_set_dense_elevations): thr[k] = the tangent of the midpoint
+ * between the k-th and the (k+1)-th ranked elevation, slot_of_rank[r] = the slot of rank r.  Per point h = sqrtf(x * x + y * y), rank =
+ * the number of k with z > thr[k] * h, id = slot_of_rank[rank].  thr[k] * h does not decrease with k (thr does not, h >= 0, and a
+ * rounded product keeps the order), so the compares are true up to the rank and false from there on: a binary search, 7 steps over the
+ * 127 entries of a table padded with +Inf (z > Inf * h is false for every z and h, NaN included).  What the compares give for
+ * non-finite points, (0, 0, 0) and points on the axis is the rule; nothing downstream depends on an id being right.
+ *   k_dense_ids_*        workgroup (tile, scan): one id byte per point to ids[offsets[s] + i], indexed like the caller's arrays -- where
+ *                        k_dense_count and k_dense_scatter_* then read them (id_stride 1, id_bytes 1, the identity map of the table) */
+#define URF_DENSE_ELEV_MAX 128
+
+/* what urf_set_dense_elevations builds and the elevation calls copy to the device (dn_elev), as it lies there */
+struct urf_dense_elev_table {
+    float thr[URF_DENSE_ELEV_MAX];                 /* [n - 1] ascending, +Inf behind them */
+    uint8_t slot_of_rank[URF_DENSE_ELEV_MAX];      /* [n] */
+    uint8_t identity[256];                         /* the slot map of derived ids: urf_set_dense_slots' does not apply to them */
+};
+
+struct urf_dense_ids_args {
+    const urf_dense_elev_table* table;
+    uint8_t* ids;                 /* [cap] */
+    unsigned long long cap;       /* bytes of ids: a point at or beyond it (offsets the context was not made for) is not written */
+};
+
+template <bool PC2>
+__device__ __forceinline__ void urf_dense_ids(const urf_dense_args& a, const urf_dense_ids_args& e)
+{
+    __shared__ float thr[URF_DENSE_ELEV_MAX];
+    __shared__ uint8_t sor[URF_DENSE_ELEV_MAX];
+    const unsigned t = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
+    unsigned off, len;
+    urf_dense_range(a, s, off, len);
+    if (t * URF_TILE >= len)   /* (uniform: nothing of this tile exists) */
+        return;
+    if (tid < URF_DENSE_ELEV_MAX) {
+        thr[tid] = e.table->thr[tid];
+        sor[tid] = e.table->slot_of_rank[tid];
+    }
+    __syncthreads();
+#pragma unroll
+    for (unsigned j = 0; j < URF_DENSE_CHUNKS; j++) {
+        const unsigned i = t * URF_TILE + j * URF_DENSE_THREADS + tid;
+        const unsigned long long g = (unsigned long long)off + i;
+        if (i >= len || g >= e.cap)
+            continue;
+        float fx, fy, fz;
+        if (PC2) {   /* (k_dense_scatter_pc2's two ways to a record) */
+            const uint8_t* r = a.data + g * a.step;
+            if ((((unsigned long long)(r + a.ox) | (unsigned long long)(r + a.oy) | (unsigned long long)(r + a.oz)) & 3ull) == 0) {
+                fx = *(const float*)(r + a.ox);
+                fy = *(const float*)(r + a.oy);
+                fz = *(const float*)(r + a.oz);
+            } else {
+                unsigned bx = 0, by = 0, bz = 0;
+                for (int b = 3; b >= 0; b--) {
+                    bx = (bx << 8) | r[a.ox + b];
+                    by = (by << 8) | r[a.oy + b];
+                    bz = (bz << 8) | r[a.oz + b];
+                }
+                fx = __uint_as_float(bx);
+                fy = __uint_as_float(by);
+                fz = __uint_as_float(bz);
+            }
+        } else {
+            fx = a.x[g];
+            fy = a.y[g];
+            fz = a.z[g];
+        }
+        const float h = sqrtf(fx * fx + fy * fy);
+        unsigned rank = 0;
+#pragma unroll
+        for (unsigned step = URF_DENSE_ELEV_MAX / 2; step > 0; step >>= 1)   /* thr[rank + step - 1] <= thr[126] */
+            if (fz > thr[rank + step - 1u] * h)
+                rank += step;
+        e.ids[g] = sor[rank];   /* (rank <= n - 1: the padding compares false) */
+    }
+}
+
+__global__ __launch_bounds__(URF_DENSE_THREADS) void k_dense_ids_soa(urf_dense_args a, urf_dense_ids_args e) { urf_dense_ids<false>(a, e); }
+__global__ __launch_bounds__(URF_DENSE_THREADS) void k_dense_ids_pc2(urf_dense_args a, urf_dense_ids_args e) { urf_dense_ids<true>(a, e); }
 
 #endif /* URF_K_DENSE_HPP */
