@@ -3,8 +3,8 @@ points (urf_marker_points*) of a call that took the fused front end, read from w
 (urban_road_filter_amd/csrc/urf_k_front_outputs.hpp) -- no second run through the general kernels, the context stays fused, the caller's
 labels are only read.  Every list and every marker point against oracle B (road_order, curb_order, ring10_order, marker_pts), exact:
 firing order and row-major, batches and the callback path, batches that mix fused and handed-back scans, rings with bit-equal azimuths
-(the literal quicksort), 16 / 32 / 64 / 128 lasers, other curbPoints in mode 3, partial tiles, rings longer than 2048 points, drop-outs
-in every encoding, empty rings; the switch off; the error codes."""
+(the literal quicksort), 16 / 32 / 64 / 128 lasers, other curbPoints in mode 3, partial tiles, rings longer than 2048 points (with bit-equal azimuths too: general
+and fused kernels), drop-outs in every encoding, empty rings; the switch off; the error codes."""
 import numpy as np
 import pytest
 
@@ -237,10 +237,10 @@ def test_mixed_batch():
 
 
 # ---- 6. equal azimuths: the literal quicksort ----
-def repeated_firings(cloud, every):
+def repeated_firings(cloud, every, lasers=64):
     out = tuple(a.copy() for a in cloud)
     for A in out:
-        R = A.reshape(-1, 64)
+        R = A.reshape(-1, lasers)
         R[every::every] = R[every - 1::every][:len(R[every::every])]
     return out
 
@@ -254,14 +254,14 @@ def equal_azimuth_pairs(st):
     return int((counts - 1).sum())
 
 
-def nudged(cloud, every, st):
+def nudged(cloud, every, st, lasers=64):
     """repeated_firings, and of every pair one of which is a marker point (st: oracle B on the repeated cloud) one point's z a float step
     up, the first and the second of the pair in turn: the two keep azimuth and planar distance, bit for bit, and differ in z -- WHICH of
     them the marker pass takes shows in the marker point.  (Every repeated firing moved that way leaves no road point.)"""
-    out = repeated_firings(cloud, every)
+    out = repeated_firings(cloud, every, lasers)
     x, y, z = out
     mk = {(m[0].tobytes(), m[1].tobytes(), m[2].tobytes()) for m in st["marker_pts"]}
-    R = np.arange(len(x)).reshape(-1, 64)
+    R = np.arange(len(x)).reshape(-1, lasers)
     k = 0
     for fr in range(every, R.shape[0], every):
         for i, j in zip(R[fr - 1], R[fr]):
@@ -358,6 +358,44 @@ def test_small_and_awkward_shapes(name):
         check_labels(b, refs)
         check_readouts(ctx, refs, stride, what=name)
         assert ctx.front_scans() == len(scans)
+
+
+# ---- 7b. rings longer than 2048 points WITH bit-equal azimuths: the sort in global memory, then the literal pass on that array ----
+@pytest.mark.parametrize("variant", ["repeated", "nudged"])
+def test_long_rings_with_equal_azimuths(variant):
+    """16 x 2176 (17 tiles: the smallest sweep whose rings pass 2048 points), every 8th firing a copy of the one before.  The general
+    kernels (front mode 0) and the fused read-outs (front mode 2, urf_set_front_outputs) against oracle B, every list and marker point."""
+    p = lasers_params(16)
+    key, cloud = ("16x2176", 1, "repeated8"), repeated_firings(u.synth_cloud(16, 2176, 1, 5), 8, 16)
+    if variant == "nudged":
+        key, cloud = ("16x2176", 1, "nudged8"), nudged(u.synth_cloud(16, 2176, 1, 5), 8, ref(key, cloud, p)[2], 16)
+    r = ref(key, cloud, p)
+    n = len(cloud[0])
+    assert n == 16 * 2176 and r[1]["status"] == 0 and r[1]["n_rings"] == 16
+    lens = np.bincount(r[2]["ring"][r[2]["ring"] >= 0])
+    assert len(lens) == 16 and min(lens) == max(lens) == 2176                      # every ring: sorted in global memory
+    assert equal_azimuth_pairs(r[2]) > 1000, equal_azimuth_pairs(r[2])
+    if variant == "repeated":
+        assert equal_azimuth_pairs(r[2]) == 4336
+        assert (len(r[2]["road_order"]), len(r[2]["curb_order"]), len(r[2]["marker_pts"])) == (8164, 220, 260)
+    else:
+        assert (len(r[2]["road_order"]), len(r[2]["marker_pts"])) == (7527, 185)
+        assert order_decides(cloud, r[2]) >= 4 and r[1]["n_road"] > 5000
+    b = Soa([cloud])
+    with u.Context(n, 1, params=p) as ctx:                                         # arm 1: the general kernels
+        ctx.set_front_mode(0)
+        b.classify(ctx)
+        assert ctx.front_scans() == 0
+        check_labels(b, [r])
+        check_readouts(ctx, [r], n, what=("long rings, general", variant))
+    with u.Context(n, 1, params=p) as ctx:                                         # arm 2: the fused call's read-outs
+        ctx.set_front_mode(2)
+        ctx.set_front_outputs(1)
+        b.classify(ctx)
+        assert ctx.front_scans() == 1
+        check_labels(b, [r])
+        check_readouts(ctx, [r], n, what=("long rings, fused", variant))
+        assert ctx.front_scans() == 1
 
 
 # ---- 8. errors ----

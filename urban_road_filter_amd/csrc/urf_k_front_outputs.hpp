@@ -19,15 +19,16 @@
  *                      the published order and the marker tables.  The per-ring kernels read contiguous memory.
  *   k_ring_order_front, k_marker_ring_front, k_marker_ring_literal_front, k_marker_bins_front
  *                      launched on the grids of their general counterparts, which return at once for a fused scan (urf_scan_fused) as
- *                      these do for every other; the rules -- ties, the literal quicksort, (d, first in ring order) -- are theirs,
- *                      word for word.
+ *                      these do for every other.  They hold no rule of their own: ties, the literal quicksort, (d, first in ring order)
+ *                      live once in urf_k_readouts.hpp, templated on a ring view, and a kernel here is its launch shape, its early
+ *                      returns and the view urf_ring_fused over the pre-pass's arrays.  (The one place that states those rules a second
+ *                      time is on the other side: k_marker_ring's register-resident path for rings of up to 2048 points.)
  *
- * Precondition: k_front hands back every scan with a ring point on the sensor's axis, so a fused scan has no NaN azimuth.
+ * Precondition: k_front hands back every scan with a ring point on the sensor's axis, so a fused scan has no NaN azimuth
+ * (urf_ring_fused::MAY_NAN).
  */
 #ifndef URF_K_FRONT_OUTPUTS_HPP
 #define URF_K_FRONT_OUTPUTS_HPP
-
-#define URF_FOUT_SRC_MASK 0x3fffffffu   /* entry = input index (relative to the scan) | class << 30 */
 
 /* out[i] = in[0] + .. + in[i - 1] for i = 0 .. n (n <= 128), by the workgroup's first wave: two elements per lane */
 __device__ __forceinline__ void urf_fout_excl_scan(const unsigned* in, unsigned* out, unsigned n, unsigned tid)
@@ -156,8 +157,17 @@ __global__ __launch_bounds__(256) void k_front_out_prep(urf_kargs a, urf_dev_par
     }
 }
 
-/* k_ring_order for a fused scan: the azimuth bits of the ring's points lie contiguous in az_all (k_front_out_prep), the key of position i
- * is (bits, i).  Rings beyond 2048 points are sorted in the ring's stretch of wsg. */
+/* The ring of a fused scan as the shared bodies reach it (urf_ring_fused): its stretch of k_front_out_prep's arrays.  d_all: where distances
+ * are read (the marker kernels). */
+__device__ __forceinline__ urf_ring_fused urf_fout_ring(const urf_kargs& a, unsigned s, unsigned C, unsigned c, unsigned scan_of_launch,
+                                                        const unsigned* az_all, const unsigned* ent_all, const float* d_all)
+{
+    const size_t ro = (size_t)scan_of_launch * a.sstride + a.ring_off[(size_t)s * (C + 1) + c];
+    return urf_ring_fused{ az_all + ro, ent_all + ro, d_all ? d_all + ro : nullptr };
+}
+
+/* k_ring_order for a fused scan: the key of position i is (az[i], i).  Rings beyond 2048 points are sorted in the ring's stretch of wsg, which
+ * is the array of the literal pass as well. */
 __global__ __launch_bounds__(256) void k_ring_order_front(urf_kargs a, urf_dev_params dp, unsigned s0, const unsigned* az_all,
                                                           const unsigned* ent_all, unsigned* rord_all, unsigned* rcls_all)
 {
@@ -171,7 +181,6 @@ __global__ __launch_bounds__(256) void k_ring_order_front(urf_kargs a, urf_dev_p
     const urf_scan_info in = a.info[s];
     if (!urf_scan_fused(a, s, in))
         return;
-    unsigned* rord = rord_all + (size_t)blockIdx.y * a.sstride;
     unsigned* rcls = rcls_all + ((size_t)blockIdx.y * URF_MAX_CHANNELS + c) * 2;
     if (c >= in.n_rings) {
         if (tid < 2)
@@ -181,105 +190,43 @@ __global__ __launch_bounds__(256) void k_ring_order_front(urf_kargs a, urf_dev_p
     const unsigned C = (unsigned)dp.p.channels;
     const unsigned n = a.ring_cnt[(size_t)s * C + c];
     const unsigned rel = a.ring_off[(size_t)s * (C + 1) + c];
-    const unsigned sb = urf_sbase(a, s);
-    const unsigned* const az = az_all + (size_t)blockIdx.y * a.sstride + rel;
-    const unsigned* const ent = ent_all + (size_t)blockIdx.y * a.sstride + rel;
-    auto key_of = [&](unsigned i) { return ((unsigned long long)az[i] << 32) | i; };
+    unsigned* const rord = rord_all + (size_t)blockIdx.y * a.sstride + rel;
+    const urf_ring_fused v = urf_fout_ring(a, s, C, c, blockIdx.y, az_all, ent_all, nullptr);
     if (tid < 2)
         ncls[tid] = 0;
     if (tid == 0)
         sh_tie = 0;
     __syncthreads();
-    /* equal azimuths: k_ring_order's literal_order (the keys in bucket order are the keys by position; SORTED may be LIT itself: it is
-     * read before the barrier and written behind it) */
-    volatile unsigned long long* const LIT = (volatile unsigned long long*)(a.wsg + sb + rel);
-    auto literal_order = [&](const unsigned long long* SORTED) -> bool {
-        for (unsigned j = tid; j + 1 < n; j += NT)
-            if ((unsigned)(SORTED[j] >> 32) == (unsigned)(SORTED[j + 1] >> 32))
-                sh_tie = 1u;
-        __syncthreads();
-        if (!sh_tie)
-            return false;   /* (uniform) */
-        for (unsigned j = tid; j < n; j += NT)
-            LIT[j] = key_of(j);
-        __threadfence_block();
-        __syncthreads();
-        if (tid < 64)
-            urf_lomuto_sort(LIT, n, lom_stk);
-        __threadfence_block();
-        __syncthreads();
-        return true;
-    };
+    unsigned long long* const G = (unsigned long long*)(a.wsg + urf_sbase(a, s) + rel);
+    volatile unsigned long long* const LIT = G;
     unsigned my_road = 0, my_curb = 0;
-    auto publish = [&](unsigned j, unsigned pos) {
-        const unsigned e = ent[pos], cls = e >> 30;
-        rord[rel + j] = e;
-        my_road += cls == URF_LABEL_ROAD;
-        my_curb += cls == URF_LABEL_CURB;
-    };
     if (n <= CAP) {
         unsigned long long key[EPT];
 #pragma unroll
         for (unsigned e = 0; e < EPT; e++) {
             const unsigned i = tid + e * NT;
-            key[e] = i < n ? key_of(i) : ~0ull;
+            key[e] = i < n ? urf_ring_key(v, i) : ~0ull;
         }
         urf_block_sort_keys<NT, EPT, NB>(key, n, A, cnt, &ssh, false);
-        const bool lit = literal_order(A);
+        const bool lit = urf_ring_literal_order<NT>(v, n, A, LIT, &sh_tie, lom_stk, tid);
 #pragma unroll
         for (unsigned e = 0; e < EPT; e++) {
             const unsigned j = tid + e * NT;
             if (j < n)
-                publish(j, lit ? (unsigned)LIT[j] : (unsigned)A[j]);
+                urf_ring_publish(v, lit ? (unsigned)LIT[j] : (unsigned)A[j], &rord[j], my_road, my_curb);
         }
-    } else {
-        unsigned long long* const G = (unsigned long long*)(a.wsg + sb + rel);
-        for (unsigned i = tid; i < n; i += NT)
-            G[i] = key_of(i);
-        __threadfence_block();
-        __syncthreads();
-        unsigned P = 1;
-        while (P < n)
-            P <<= 1;
-        for (unsigned kk = 2; kk <= P; kk <<= 1)
-            for (unsigned j = kk >> 1; j > 0; j >>= 1) {
-                const bool flip = (j == (kk >> 1));
-                for (unsigned tt = tid; tt < (P >> 1); tt += NT) {
-                    const unsigned lo = ((tt & ~(j - 1)) << 1) | (tt & (j - 1));
-                    const unsigned hi = flip ? ((lo & ~(kk - 1)) + (kk - 1) - (lo & (kk - 1))) : lo + j;
-                    if (hi < n) {
-                        const unsigned long long ka = G[lo], kb = G[hi];
-                        if (ka > kb) {
-                            G[lo] = kb;
-                            G[hi] = ka;
-                        }
-                    }
-                }
-                __threadfence_block();
-                __syncthreads();
-            }
-        const bool lit = literal_order(G);
-        for (unsigned j = tid; j < n; j += NT)
-            publish(j, lit ? (unsigned)LIT[j] : (unsigned)G[j]);
-    }
-    if (my_road)
-        atomicAdd(&ncls[0], my_road);
-    if (my_curb)
-        atomicAdd(&ncls[1], my_curb);
-    __syncthreads();
-    if (tid < 2)
-        rcls[tid] = ncls[tid];
+    } else
+        urf_ring_order_long<NT>(v, n, G, LIT, &sh_tie, lom_stk, rord, my_road, my_curb, tid);
+    urf_ring_publish_counts(my_road, my_curb, ncls, rcls, tid);
 }
 
-/* k_marker_ring for a fused scan: azimuth bits, class and planar distance of the ring's points lie contiguous (k_front_out_prep,
- * azimuth bits by position).  m_pos holds the marker point's input index, relative to the scan (k_marker_bins_front). */
+/* k_marker_ring for a fused scan: every ring pass by pass (its points lie contiguous: nothing to keep in registers).  m_pos holds the marker
+ * point's input index, relative to the scan (urf_ring_fused::marker_id). */
 __global__ __launch_bounds__(256) void k_marker_ring_front(urf_kargs a, urf_dev_params dp, unsigned s0, const unsigned* az_all,
                                                            const unsigned* ent_all, const float* d_all, float* m_d_all, unsigned* m_pos_all,
                                                            uint8_t* m_red_all, uint8_t* m_lit_all)
 {
-    __shared__ int nrmin[URF_DEG_CELLS];
-    __shared__ unsigned long long best[URF_DEG_CELLS];
-    __shared__ unsigned bestpos[URF_DEG_CELLS];
+    __shared__ urf_marker_tabs T;
     __shared__ unsigned need_lit;
     const unsigned c = blockIdx.x, s = s0 + blockIdx.y, tid = threadIdx.x;
     const urf_scan_info in = a.info[s];
@@ -291,64 +238,16 @@ __global__ __launch_bounds__(256) void k_marker_ring_front(urf_kargs a, urf_dev_
         return;
     }
     const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;
-    float* m_d = m_d_all + blockIdx.y * cells;
-    unsigned* m_pos = m_pos_all + blockIdx.y * cells;
-    uint8_t* m_red = m_red_all + blockIdx.y * cells;
     const unsigned C = (unsigned)dp.p.channels;
-    const unsigned n = a.ring_cnt[(size_t)s * C + c];
-    const size_t ro = (size_t)blockIdx.y * a.sstride + a.ring_off[(size_t)s * (C + 1) + c];
-    const unsigned* const az = az_all + ro;
-    const unsigned* const ent = ent_all + ro;
-    const float* const dist = d_all + ro;
-    for (unsigned i = tid; i < URF_DEG_CELLS; i += 256) {
-        nrmin[i] = URF_INT_NONE_MIN;
-        best[i] = 0;
-        bestpos[i] = 0xffffffffu;
-    }
+    const urf_ring_fused v = urf_fout_ring(a, s, C, c, blockIdx.y, az_all, ent_all, d_all);
+    T.init(tid);
     if (tid == 0)
         need_lit = 0;
     __syncthreads();
-    auto bin_of = [](float az) {
-        const int b = (int)__builtin_floorf(az);
-        return b < 0 ? 0 : (b > 360 ? 360 : b);
-    };
-    /* pass 1: where does the scan of this ring stop in each degree (:318) */
-    for (unsigned p = tid; p < n; p += 256) {
-        const unsigned ab = az[p];
-        if ((ent[p] >> 30) != URF_LABEL_ROAD)
-            atomicMin(&nrmin[bin_of(__uint_as_float(ab))], (int)ab);
-    }
-    __syncthreads();
-    /* pass 2: farthest road point in front of it (:325-335); key = (d, first in azimuth order) */
-    for (int pass = 0; pass < 2; pass++) {
-        for (unsigned p = tid; p < n; p += 256) {
-            const unsigned ab = az[p];
-            if ((ent[p] >> 30) != URF_LABEL_ROAD)
-                continue;
-            const int bin = bin_of(__uint_as_float(ab));
-            if ((int)ab == nrmin[bin])
-                need_lit = 1u;   /* the very azimuth of the degree's first non-road point: in front of it or behind? */
-            if ((int)ab < nrmin[bin]) {
-                const float d = dist[p];
-                if (d > 0.0f) {   /* "d > maxDistanceRoad" with maxDistanceRoad starting at 0 */
-                    const unsigned long long k = ((unsigned long long)urf_fbits(d) << 32) | (0xffffffffu - ab);
-                    if (pass == 0)
-                        atomicMax(&best[bin], k);
-                    else if (k == best[bin] && atomicMin(&bestpos[bin], p) != 0xffffffffu)
-                        need_lit = 1u;   /* two road points with this distance AND azimuth: which comes first? */
-                }
-            }
-        }
-        __syncthreads();
-    }
+    urf_marker_passes(v, a.ring_cnt[(size_t)s * C + c], T, &need_lit, tid);
     if (tid == 0)
         m_lit_all[(size_t)blockIdx.y * URF_MAX_CHANNELS + c] = (uint8_t)need_lit;
-    for (unsigned i = tid; i < URF_DEG_CELLS; i += 256) {
-        const size_t o = (size_t)c * URF_DEG_CELLS + i;
-        m_d[o] = __uint_as_float((unsigned)(best[i] >> 32));
-        m_pos[o] = bestpos[i] == 0xffffffffu ? 0xffffffffu : ent[bestpos[i]] & URF_FOUT_SRC_MASK;
-        m_red[o] = nrmin[i] != URF_INT_NONE_MIN;
-    }
+    T.store(v, c, m_d_all + blockIdx.y * cells, m_pos_all + blockIdx.y * cells, m_red_all + blockIdx.y * cells, tid);
 }
 
 /* k_marker_ring_literal for a fused scan: the rings k_marker_ring_front flagged, sorted literally in the ring's stretch of wsg. */
@@ -360,65 +259,14 @@ __global__ __launch_bounds__(256) void k_marker_ring_literal_front(urf_kargs a, 
     const urf_scan_info in = a.info[s];
     if (!urf_scan_fused(a, s, in) || !m_lit_all[(size_t)blockIdx.y * URF_MAX_CHANNELS + c])
         return;
-    __shared__ int nrmin[URF_DEG_CELLS];
-    __shared__ unsigned long long best[URF_DEG_CELLS];
-    __shared__ unsigned bestpos[URF_DEG_CELLS];
+    __shared__ urf_marker_tabs T;
     __shared__ int stk[2 * 64];
     const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;
-    float* m_d = m_d_all + blockIdx.y * cells;
-    unsigned* m_pos = m_pos_all + blockIdx.y * cells;
-    uint8_t* m_red = m_red_all + blockIdx.y * cells;
     const unsigned C = (unsigned)dp.p.channels;
-    const unsigned n = a.ring_cnt[(size_t)s * C + c];
+    const urf_ring_fused v = urf_fout_ring(a, s, C, c, blockIdx.y, az_all, ent_all, d_all);
     const unsigned rel = a.ring_off[(size_t)s * (C + 1) + c];
-    const size_t ro = (size_t)blockIdx.y * a.sstride + rel;
-    const unsigned* const az = az_all + ro;
-    const unsigned* const ent = ent_all + ro;
-    const float* const dist = d_all + ro;
-    volatile unsigned long long* const LIT = (volatile unsigned long long*)(a.wsg + urf_sbase(a, s) + rel);
-    for (unsigned i = tid; i < URF_DEG_CELLS; i += 256) {
-        nrmin[i] = URF_INT_NONE_MIN;
-        best[i] = 0;
-        bestpos[i] = 0xffffffffu;
-    }
-    for (unsigned p = tid; p < n; p += 256)
-        LIT[p] = ((unsigned long long)az[p] << 32) | p;   /* (azimuth bits, position), in ring order */
-    __threadfence_block();
-    __syncthreads();
-    if (tid < 64 && n >= 2)
-        urf_lomuto_sort(LIT, n, stk);
-    __threadfence_block();
-    __syncthreads();
-    for (int pass = 0; pass < 3; pass++) {
-        for (unsigned j = tid; j < n; j += 256) {
-            const unsigned long long e = LIT[j];
-            const float az = urf_pair_alpha(e);
-            const unsigned p = (unsigned)e;
-            const unsigned lab = ent[p] >> 30;
-            int bin = (int)__builtin_floorf(az);
-            bin = bin < 0 ? 0 : (bin > 360 ? 360 : bin);
-            if (pass == 0) {
-                if (lab != URF_LABEL_ROAD)
-                    atomicMin(&nrmin[bin], (int)j);   /* :318 the scan of this ring stops here */
-            } else if (lab == URF_LABEL_ROAD && (int)j < nrmin[bin]) {
-                const float d = dist[p];
-                if (d > 0.0f) {
-                    const unsigned long long k = ((unsigned long long)urf_fbits(d) << 32) | (0xffffffffu - j);   /* (d, first in the ring's order) */
-                    if (pass == 1)
-                        atomicMax(&best[bin], k);
-                    else if (k == best[bin])
-                        bestpos[bin] = p;
-                }
-            }
-        }
-        __syncthreads();
-    }
-    for (unsigned i = tid; i < URF_DEG_CELLS; i += 256) {
-        const size_t o = (size_t)c * URF_DEG_CELLS + i;
-        m_d[o] = __uint_as_float((unsigned)(best[i] >> 32));
-        m_pos[o] = bestpos[i] == 0xffffffffu ? 0xffffffffu : ent[bestpos[i]] & URF_FOUT_SRC_MASK;
-        m_red[o] = nrmin[i] != URF_INT_NONE_MIN;
-    }
+    urf_marker_literal(v, a.ring_cnt[(size_t)s * C + c], (volatile unsigned long long*)(a.wsg + urf_sbase(a, s) + rel), T, stk, tid);
+    T.store(v, c, m_d_all + blockIdx.y * cells, m_pos_all + blockIdx.y * cells, m_red_all + blockIdx.y * cells, tid);
 }
 
 /* k_marker_bins for a fused scan: m_pos holds input indices, the point comes from the call's input arrays. */
@@ -432,47 +280,10 @@ __global__ __launch_bounds__(384) void k_marker_bins_front(urf_kargs a, urf_dev_
     if (!urf_scan_fused(a, s, in))
         return;
     const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;
-    const float* m_d = m_d_all + blockIdx.x * cells;
-    const unsigned* m_pos = m_pos_all + blockIdx.x * cells;
-    const uint8_t* m_red = m_red_all + blockIdx.x * cells;
-    float* out = out_all + (size_t)blockIdx.x * URF_DEG_CELLS * 4;
-    unsigned* count = count_all + blockIdx.x;
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned off, len;
     urf_scan_range(a, s, off, len);
-    const unsigned nR = in.n_rings;
-    unsigned id = 0xffffffffu;
-    float red = 0.f;
-    if (tid <= 360) {
-        float maxd = 0.f;
-        for (unsigned j = 0; j < nR; j++) {
-            const size_t o = (size_t)j * URF_DEG_CELLS + tid;
-            if (m_pos[o] != 0xffffffffu && m_d[o] > maxd) {   /* :329 */
-                maxd = m_d[o];
-                id = m_pos[o];
-            }
-            if (m_red[o]) {                                  /* :318-321, 338-339 */
-                red = 1.f;
-                break;
-            }
-        }
-    }
-    const bool valid = id != 0xffffffffu;                    /* :343 */
-    const unsigned long long m = __ballot(valid);
-    if (lane == 0)
-        wsum[wave] = __popcll(m);
-    __syncthreads();
-    unsigned pre = __popcll(m & ((1ull << lane) - 1ull));
-    for (unsigned w = 0; w < wave; w++)
-        pre += wsum[w];
-    if (valid) {
-        out[4 * pre + 0] = a.x[(size_t)off + id];
-        out[4 * pre + 1] = a.y[(size_t)off + id];
-        out[4 * pre + 2] = a.z[(size_t)off + id];
-        out[4 * pre + 3] = red;
-    }
-    if (tid == 0)
-        *count = wsum[0] + wsum[1] + wsum[2] + wsum[3] + wsum[4] + wsum[5];
+    urf_marker_bins<urf_ring_fused>(a, off, in.n_rings, m_d_all + blockIdx.x * cells, m_pos_all + blockIdx.x * cells,
+                                    m_red_all + blockIdx.x * cells, out_all + (size_t)blockIdx.x * URF_DEG_CELLS * 4, count_all + blockIdx.x, wsum);
 }
 
 #endif /* URF_K_FRONT_OUTPUTS_HPP */

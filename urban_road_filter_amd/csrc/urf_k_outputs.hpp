@@ -164,48 +164,15 @@ __global__ __launch_bounds__(256) void k_ring_order(urf_kargs a, urf_dev_params 
         sh_tie = 0;
     __syncthreads();
     const urf_ring_map map = { mapP, mapA, ntiles, (float)ntiles / (float)(n > 0 ? n : 1) };
-    /* Two points of the ring with bit-identical azimuths: their order is the one the reference's Lomuto quicksort
-     * (lidar_segmentation.cpp:70-93; deterministic, not stable) leaves.  SORTED = the (azimuth, position) keys in
-     * ascending order; if two neighbours share their azimuth the keys go back into bucket order (the ring's stretch of wsg,
-     * which nobody reads after k_star_walk), one wave runs the quicksort literally (urf_lomuto_sort, as k_nan_rings does for
-     * rings with NaN azimuths) and the ring is published in that order. */
+    const urf_ring_sorted v = { a, s, C, c, ntiles, sb, off, &map };
+    /* bit-equal azimuths (urf_ring_literal_order): the keys go back into bucket order in the ring's stretch of wsg */
     volatile unsigned long long* const LIT = (volatile unsigned long long*)(a.wsg + sb + rel);
-    auto literal_order = [&](const unsigned long long* SORTED) -> bool {
-        for (unsigned j = tid; j + 1 < n; j += NT)
-            if ((unsigned)(SORTED[j] >> 32) == (unsigned)(SORTED[j + 1] >> 32))
-                sh_tie = 1u;
-        __syncthreads();
-        if (!sh_tie)
-            return false;   /* (uniform) */
-        for (unsigned j = tid; j < n; j += NT) {
-            const unsigned long long k = SORTED[j];
-            LIT[(unsigned)k] = k;
-        }
-        __threadfence_block();
-        __syncthreads();
-        if (tid < 64)
-            urf_lomuto_sort(LIT, n, lom_stk);
-        __threadfence_block();
-        __syncthreads();
-        return true;
-    };
-    /* what is published for position i of the ring: the point's input index | its class << 30 */
-    auto entry_of = [&](unsigned i, unsigned& cls) {
-        const unsigned slot = map.at(i);
-        const unsigned src = (slot & ~(URF_TILE - 1u)) + (a.rec[sb + slot] & URF_REC_SRC_MASK);
-        cls = a.labels[off + src] & URF_LABEL_MASK;
-        return src | (cls << 30);
-    };
     unsigned my_road = 0, my_curb = 0;
     if ((a.nan_mask[(size_t)s * 4 + (c >> 5)] >> (c & 31u)) & 1u) {
         /* (uniform) a ring with NaN azimuths: k_nan_rings ran the reference's quicksort literally and left the ring in
          * its final order -- where a NaN lands is no function of the azimuths */
-        for (unsigned j = tid; j < n; j += NT) {
-            unsigned cls;
-            rord[rel + j] = entry_of(a.ssrt[sb + rel + j], cls);
-            my_road += cls == URF_LABEL_ROAD;
-            my_curb += cls == URF_LABEL_CURB;
-        }
+        for (unsigned j = tid; j < n; j += NT)
+            urf_ring_publish(v, a.ssrt[sb + rel + j], &rord[rel + j], my_road, my_curb);
     } else if (n <= CAP) {
         unsigned long long key[EPT];
         unsigned slot[EPT];
@@ -227,58 +194,16 @@ __global__ __launch_bounds__(256) void k_ring_order(urf_kargs a, urf_dev_params 
             }
         }
         urf_block_sort_keys<NT, EPT, NB>(key, n, A, cnt, &ssh, false);
-        const bool lit = literal_order(A);
+        const bool lit = urf_ring_literal_order<NT>(v, n, A, LIT, &sh_tie, lom_stk, tid);
 #pragma unroll
         for (unsigned e = 0; e < EPT; e++) {
             const unsigned j = tid + e * NT;
-            if (j < n) {
-                unsigned cls;
-                rord[rel + j] = entry_of(lit ? (unsigned)LIT[j] : (unsigned)A[j], cls);
-                my_road += cls == URF_LABEL_ROAD;
-                my_curb += cls == URF_LABEL_CURB;
-            }
+            if (j < n)
+                urf_ring_publish(v, lit ? (unsigned)LIT[j] : (unsigned)A[j], &rord[rel + j], my_road, my_curb);
         }
-    } else {
-        unsigned long long* G = gkeys + rel;
-        for (unsigned i = tid; i < n; i += NT)
-            G[i] = ((unsigned long long)urf_fbits(urf_exact_az(a, sb + map.at(i))) << 32) | i;
-        __threadfence_block();
-        __syncthreads();
-        unsigned P = 1;
-        while (P < n)
-            P <<= 1;
-        for (unsigned kk = 2; kk <= P; kk <<= 1)
-            for (unsigned j = kk >> 1; j > 0; j >>= 1) {
-                const bool flip = (j == (kk >> 1));
-                for (unsigned tt = tid; tt < (P >> 1); tt += NT) {
-                    const unsigned lo = ((tt & ~(j - 1)) << 1) | (tt & (j - 1));
-                    const unsigned hi = flip ? ((lo & ~(kk - 1)) + (kk - 1) - (lo & (kk - 1))) : lo + j;
-                    if (hi < n) {
-                        const unsigned long long ka = G[lo], kb = G[hi];
-                        if (ka > kb) {
-                            G[lo] = kb;
-                            G[hi] = ka;
-                        }
-                    }
-                }
-                __threadfence_block();
-                __syncthreads();
-            }
-        const bool lit = literal_order(G);
-        for (unsigned j = tid; j < n; j += NT) {
-            unsigned cls;
-            rord[rel + j] = entry_of(lit ? (unsigned)LIT[j] : (unsigned)G[j], cls);
-            my_road += cls == URF_LABEL_ROAD;
-            my_curb += cls == URF_LABEL_CURB;
-        }
-    }
-    if (my_road)
-        atomicAdd(&ncls[0], my_road);
-    if (my_curb)
-        atomicAdd(&ncls[1], my_curb);
-    __syncthreads();
-    if (tid < 2)
-        rcls[tid] = ncls[tid];
+    } else
+        urf_ring_order_long<NT>(v, n, gkeys + rel, LIT, &sh_tie, lom_stk, rord + rel, my_road, my_curb, tid);
+    urf_ring_publish_counts(my_road, my_curb, ncls, rcls, tid);
 }
 
 /* The lists of one scan = its rings in order, every ring in azimuth order (k_ring_order left, per ring
@@ -365,13 +290,11 @@ __global__ __launch_bounds__(256) void k_ordered_lists(urf_kargs a, urf_dev_para
  * of that degree that is not road.  Per ring and degree that is: the smallest azimuth of a non-road
  * point (where the scan of this ring stops, and with it the whole scan), and the farthest road point
  * in front of it (ties: the first in azimuth order).  k_marker_ring builds these two tables per ring
- * in LDS (no sort needed), k_marker_bins walks the rings per degree. */
+ * in LDS (urf_marker_tabs; no sort needed), k_marker_bins walks the rings per degree. */
 __global__ __launch_bounds__(256) void k_marker_ring(urf_kargs a, urf_dev_params dp, unsigned s0,
                                                      float* m_d_all, unsigned* m_pos_all, uint8_t* m_red_all, uint8_t* m_lit_all)
 {
-    __shared__ int nrmin[URF_DEG_CELLS];
-    __shared__ unsigned long long best[URF_DEG_CELLS];
-    __shared__ unsigned bestpos[URF_DEG_CELLS];
+    __shared__ urf_marker_tabs T;
     __shared__ unsigned need_lit;   /* the ring's order decides (k_marker_ring_literal) */
     const unsigned c = blockIdx.x, s = s0 + blockIdx.y, tid = threadIdx.x;
     const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;   /* per scan of the launch */
@@ -392,13 +315,7 @@ __global__ __launch_bounds__(256) void k_marker_ring(urf_kargs a, urf_dev_params
     const unsigned n = a.ring_cnt[(size_t)s * C + c];
     const unsigned sb = urf_sbase(a, s);
     const unsigned ntiles = (len + URF_TILE - 1) / URF_TILE;
-    /* input index of the point in ring-sorted slot `slot` (relative to the scan) */
-    auto src_of = [&](unsigned slot) { return (slot & ~(URF_TILE - 1u)) + (a.rec[sb + slot] & URF_REC_SRC_MASK); };
-    for (unsigned i = tid; i < URF_DEG_CELLS; i += 256) {
-        nrmin[i] = URF_INT_NONE_MIN;
-        best[i] = 0;
-        bestpos[i] = 0xffffffffu;
-    }
+    T.init(tid);
     if (tid == 0)
         need_lit = 0;
     constexpr unsigned EPT = 8;
@@ -408,7 +325,8 @@ __global__ __launch_bounds__(256) void k_marker_ring(urf_kargs a, urf_dev_params
          * then labels, eight points per thread in flight at a time -- and azimuth, label and slot stay
          * in registers for the three passes.  (Pass by pass, with seven dependent loads per point and
          * the exact azimuth worked out three times, this kernel took longer than the whole
-         * classification: 3.9 ms per 1024 sweeps.) */
+         * classification: 3.9 ms per 1024 sweeps.)  The one deliberate specialisation of the rules of
+         * urf_marker_passes (urf_k_readouts.hpp): a change there is a change here. */
         extern __shared__ unsigned sh_mark_tab[];   /* P[tiles + 1], radd[tiles] (urf_ring_map) */
         unsigned* const mapP = sh_mark_tab;
         unsigned* const mapA = sh_mark_tab + a.tiles + 1;
@@ -449,10 +367,9 @@ __global__ __launch_bounds__(256) void k_marker_ring(urf_kargs a, urf_dev_params
         int bin[EPT];
 #pragma unroll
         for (unsigned e = 0; e < EPT; e++) {
-            const int b = (int)__builtin_floorf(az[e]);
-            bin[e] = b < 0 ? 0 : (b > 360 ? 360 : b);
+            bin[e] = urf_deg_bin(az[e]);
             if (tid + e * 256 < n && az[e] == az[e] && ((labs >> (2 * e)) & 3u) != URF_LABEL_ROAD)
-                atomicMin(&nrmin[bin[e]], (int)urf_fbits(az[e]));
+                atomicMin(&T.nrmin[bin[e]], (int)urf_fbits(az[e]));
         }
         __syncthreads();
         /* pass 2: farthest road point in front of it (:325-335); key = (d, first in azimuth order) */
@@ -461,89 +378,39 @@ __global__ __launch_bounds__(256) void k_marker_ring(urf_kargs a, urf_dev_params
         for (unsigned e = 0; e < EPT; e++) {
             key[e] = 0;
             const bool road = tid + e * 256 < n && az[e] == az[e] && ((labs >> (2 * e)) & 3u) == URF_LABEL_ROAD;
-            if (road && (int)urf_fbits(az[e]) == nrmin[bin[e]])
+            if (road && (int)urf_fbits(az[e]) == T.nrmin[bin[e]])
                 need_lit = 1u;   /* the very azimuth of the degree's first non-road point: in front of it or behind? */
-            if (road && (int)urf_fbits(az[e]) < nrmin[bin[e]]) {
+            if (road && (int)urf_fbits(az[e]) < T.nrmin[bin[e]]) {
                 const float x = px[e], y = py[e];
                 const float d = (float)__builtin_sqrt((double)(0.f - x) * (double)(0.f - x) + (double)(0.f - y) * (double)(0.f - y));
                 if (d > 0.0f) {   /* "d > maxDistanceRoad" with maxDistanceRoad starting at 0 */
                     key[e] = ((unsigned long long)urf_fbits(d) << 32) | (0xffffffffu - urf_fbits(az[e]));
-                    atomicMax(&best[bin[e]], key[e]);
+                    atomicMax(&T.best[bin[e]], key[e]);
                 }
             }
         }
         __syncthreads();
 #pragma unroll
         for (unsigned e = 0; e < EPT; e++)
-            if (key[e] != 0 && key[e] == best[bin[e]])
-                if (atomicMin(&bestpos[bin[e]], tid + e * 256) != 0xffffffffu)
+            if (key[e] != 0 && key[e] == T.best[bin[e]])
+                if (atomicMin(&T.bestpos[bin[e]], tid + e * 256) != 0xffffffffu)
                     need_lit = 1u;   /* two road points with this distance AND azimuth: which comes first? */
         __syncthreads();
         if (tid == 0)
             m_lit_all[(size_t)blockIdx.y * URF_MAX_CHANNELS + c] = (uint8_t)need_lit;
-        for (unsigned i = tid; i < URF_DEG_CELLS; i += 256) {
-            const size_t o = (size_t)c * URF_DEG_CELLS + i;
-            m_d[o] = __uint_as_float((unsigned)(best[i] >> 32));
-            m_pos[o] = bestpos[i] == 0xffffffffu ? 0xffffffffu : sb + map.at(bestpos[i]);
-            m_red[o] = nrmin[i] != URF_INT_NONE_MIN;
-        }
+        T.store(urf_ring_sorted{ a, s, C, c, ntiles, sb, off, &map }, c, m_d, m_pos, m_red, tid);
         return;
     }
     __syncthreads();
-    /* pass 1: where does the scan of this ring stop in each degree (:318) */
-    for (unsigned p = tid; p < n; p += 256) {
-        const unsigned slot = urf_ring_slot(a, s, C, c, ntiles, p);
-        const float az = urf_exact_az(a, sb + slot);
-        const unsigned lab = a.labels[off + src_of(slot)] & URF_LABEL_MASK;
-        if (az == az && lab != URF_LABEL_ROAD) {
-            int bin = (int)__builtin_floorf(az);
-            bin = bin < 0 ? 0 : (bin > 360 ? 360 : bin);
-            atomicMin(&nrmin[bin], (int)urf_fbits(az));
-        }
-    }
-    __syncthreads();
-    /* pass 2: farthest road point in front of it (:325-335); key = (d, first in azimuth order) */
-    for (int pass = 0; pass < 2; pass++) {
-        for (unsigned p = tid; p < n; p += 256) {
-            const unsigned slot = urf_ring_slot(a, s, C, c, ntiles, p);
-            const float az = urf_exact_az(a, sb + slot);
-            const unsigned lab = a.labels[off + src_of(slot)] & URF_LABEL_MASK;
-            if (az == az && lab == URF_LABEL_ROAD) {
-                int bin = (int)__builtin_floorf(az);
-                bin = bin < 0 ? 0 : (bin > 360 ? 360 : bin);
-                if ((int)urf_fbits(az) == nrmin[bin])
-                    need_lit = 1u;
-                if ((int)urf_fbits(az) < nrmin[bin]) {
-                    const float x = a.rx[sb + slot], y = a.ry[sb + slot];
-                    const float d = (float)__builtin_sqrt((double)(0.f - x) * (double)(0.f - x) + (double)(0.f - y) * (double)(0.f - y));
-                    if (d > 0.0f) {   /* "d > maxDistanceRoad" with maxDistanceRoad starting at 0 */
-                        const unsigned long long key = ((unsigned long long)urf_fbits(d) << 32) | (0xffffffffu - urf_fbits(az));
-                        if (pass == 0)
-                            atomicMax(&best[bin], key);
-                        else if (key == best[bin] && atomicMin(&bestpos[bin], p) != 0xffffffffu)
-                            need_lit = 1u;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
+    const urf_ring_sorted v = { a, s, C, c, ntiles, sb, off, nullptr };
+    urf_marker_passes(v, n, T, &need_lit, tid);
     if (tid == 0)
         m_lit_all[(size_t)blockIdx.y * URF_MAX_CHANNELS + c] = (uint8_t)need_lit;
-    for (unsigned i = tid; i < URF_DEG_CELLS; i += 256) {
-        const size_t o = (size_t)c * URF_DEG_CELLS + i;
-        m_d[o] = __uint_as_float((unsigned)(best[i] >> 32));
-        m_pos[o] = bestpos[i] == 0xffffffffu ? 0xffffffffu : sb + urf_ring_slot(a, s, C, c, ntiles, bestpos[i]);
-        m_red[o] = nrmin[i] != URF_INT_NONE_MIN;
-    }
+    T.store(v, c, m_d, m_pos, m_red, tid);
 }
 
-/* The same tables when the ring's ORDER decides -- a road point shares its azimuth, bit for bit, with the first non-road
- * point of its degree, or two road points share azimuth and distance: which comes first is what the reference's Lomuto
- * quicksort (lidar_segmentation.cpp:70-93) leaves.  k_marker_ring flags such a ring (m_lit); this kernel, launched behind
- * it on the same grid, returns at once for every other ring.  The ring is sorted literally (urf_lomuto_sort on (azimuth,
- * position) pairs in the ring's stretch of wsg, as k_nan_rings / k_ring_order do) and the three passes compare places in
- * that order instead of azimuths.  Rare: never on a spinning sensor's sweep. */
+/* The same tables when the ring's ORDER decides (urf_marker_literal).  k_marker_ring flags such a ring (m_lit); this kernel, launched
+ * behind it on the same grid, returns at once for every other ring. */
 __global__ __launch_bounds__(256) void k_marker_ring_literal(urf_kargs a, urf_dev_params dp, unsigned s0, const uint8_t* m_lit_all,
                                                              float* m_d_all, unsigned* m_pos_all, uint8_t* m_red_all)
 {
@@ -552,68 +419,18 @@ __global__ __launch_bounds__(256) void k_marker_ring_literal(urf_kargs a, urf_de
         return;   /* (uniform) k_marker_ring_literal_front's; its flag is not written yet */
     if (!m_lit_all[(size_t)blockIdx.y * URF_MAX_CHANNELS + c])
         return;
-    __shared__ int nrmin[URF_DEG_CELLS];
-    __shared__ unsigned long long best[URF_DEG_CELLS];
-    __shared__ unsigned bestpos[URF_DEG_CELLS];
+    __shared__ urf_marker_tabs T;
     __shared__ int stk[2 * 64];
     const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;
-    float* m_d = m_d_all + blockIdx.y * cells;
-    unsigned* m_pos = m_pos_all + blockIdx.y * cells;
-    uint8_t* m_red = m_red_all + blockIdx.y * cells;
     unsigned off, len;
     urf_scan_range(a, s, off, len);
     const unsigned C = (unsigned)dp.p.channels;
     const unsigned n = a.ring_cnt[(size_t)s * C + c];
     const unsigned sb = urf_sbase(a, s);
-    const unsigned ntiles = (len + URF_TILE - 1) / URF_TILE;
     const unsigned rel = a.ring_off[(size_t)s * (C + 1) + c];
-    volatile unsigned long long* const LIT = (volatile unsigned long long*)(a.wsg + sb + rel);
-    for (unsigned i = tid; i < URF_DEG_CELLS; i += 256) {
-        nrmin[i] = URF_INT_NONE_MIN;
-        best[i] = 0;
-        bestpos[i] = 0xffffffffu;
-    }
-    for (unsigned p = tid; p < n; p += 256)
-        LIT[p] = ((unsigned long long)urf_fbits(urf_exact_az(a, sb + urf_ring_slot(a, s, C, c, ntiles, p))) << 32) | p;
-    __threadfence_block();
-    __syncthreads();
-    if (tid < 64 && n >= 2)
-        urf_lomuto_sort(LIT, n, stk);
-    __threadfence_block();
-    __syncthreads();
-    for (int pass = 0; pass < 3; pass++) {
-        for (unsigned j = tid; j < n; j += 256) {
-            const unsigned long long e = LIT[j];
-            const float az = urf_pair_alpha(e);
-            const unsigned p = (unsigned)e, slot = urf_ring_slot(a, s, C, c, ntiles, p);
-            const unsigned lab = a.labels[off + (slot & ~(URF_TILE - 1u)) + (a.rec[sb + slot] & URF_REC_SRC_MASK)] & URF_LABEL_MASK;
-            if (!(az == az))
-                continue;
-            int bin = (int)__builtin_floorf(az);
-            bin = bin < 0 ? 0 : (bin > 360 ? 360 : bin);
-            if (pass == 0) {
-                if (lab != URF_LABEL_ROAD)
-                    atomicMin(&nrmin[bin], (int)j);   /* :318 the scan of this ring stops here */
-            } else if (lab == URF_LABEL_ROAD && (int)j < nrmin[bin]) {
-                const float x = a.rx[sb + slot], y = a.ry[sb + slot];
-                const float d = (float)__builtin_sqrt((double)(0.f - x) * (double)(0.f - x) + (double)(0.f - y) * (double)(0.f - y));
-                if (d > 0.0f) {
-                    const unsigned long long key = ((unsigned long long)urf_fbits(d) << 32) | (0xffffffffu - j);   /* (d, first in the ring's order) */
-                    if (pass == 1)
-                        atomicMax(&best[bin], key);
-                    else if (key == best[bin])
-                        bestpos[bin] = p;
-                }
-            }
-        }
-        __syncthreads();
-    }
-    for (unsigned i = tid; i < URF_DEG_CELLS; i += 256) {
-        const size_t o = (size_t)c * URF_DEG_CELLS + i;
-        m_d[o] = __uint_as_float((unsigned)(best[i] >> 32));
-        m_pos[o] = bestpos[i] == 0xffffffffu ? 0xffffffffu : sb + urf_ring_slot(a, s, C, c, ntiles, bestpos[i]);
-        m_red[o] = nrmin[i] != URF_INT_NONE_MIN;
-    }
+    const urf_ring_sorted v = { a, s, C, c, (len + URF_TILE - 1) / URF_TILE, sb, off, nullptr };
+    urf_marker_literal(v, n, (volatile unsigned long long*)(a.wsg + sb + rel), T, stk, tid);
+    T.store(v, c, m_d_all + blockIdx.y * cells, m_pos_all + blockIdx.y * cells, m_red_all + blockIdx.y * cells, tid);
 }
 
 __global__ __launch_bounds__(384) void k_marker_bins(urf_kargs a, urf_dev_params dp, unsigned s0, const float* m_d_all,
@@ -623,48 +440,12 @@ __global__ __launch_bounds__(384) void k_marker_bins(urf_kargs a, urf_dev_params
     __shared__ unsigned wsum[6];
     const unsigned s = s0 + blockIdx.x;
     const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;
-    const float* m_d = m_d_all + blockIdx.x * cells;
-    const unsigned* m_pos = m_pos_all + blockIdx.x * cells;
-    const uint8_t* m_red = m_red_all + blockIdx.x * cells;
-    float* out = out_all + (size_t)blockIdx.x * URF_DEG_CELLS * 4;
-    unsigned* count = count_all + blockIdx.x;
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const urf_scan_info in = a.info[s];
     if (urf_scan_fused(a, s, in))
         return;   /* (uniform) k_marker_bins_front's */
-    const unsigned nR = in.status == URF_OK ? in.n_rings : 0;
-    unsigned id = 0xffffffffu;
-    float red = 0.f;
-    if (tid <= 360) {
-        float maxd = 0.f;
-        for (unsigned j = 0; j < nR; j++) {
-            const size_t o = (size_t)j * URF_DEG_CELLS + tid;
-            if (m_pos[o] != 0xffffffffu && m_d[o] > maxd) {   /* :329 */
-                maxd = m_d[o];
-                id = m_pos[o];
-            }
-            if (m_red[o]) {                                  /* :318-321, 338-339 */
-                red = 1.f;
-                break;
-            }
-        }
-    }
-    const bool valid = id != 0xffffffffu;                    /* :343 */
-    const unsigned long long m = __ballot(valid);
-    if (lane == 0)
-        wsum[wave] = __popcll(m);
-    __syncthreads();
-    unsigned pre = __popcll(m & ((1ull << lane) - 1ull));
-    for (unsigned w = 0; w < wave; w++)
-        pre += wsum[w];
-    if (valid) {
-        out[4 * pre + 0] = a.rx[id];
-        out[4 * pre + 1] = a.ry[id];
-        out[4 * pre + 2] = a.rz[id];
-        out[4 * pre + 3] = red;
-    }
-    if (tid == 0)
-        *count = wsum[0] + wsum[1] + wsum[2] + wsum[3] + wsum[4] + wsum[5];
+    urf_marker_bins<urf_ring_sorted>(a, 0u, in.status == URF_OK ? in.n_rings : 0, m_d_all + blockIdx.x * cells, m_pos_all + blockIdx.x * cells,
+                                     m_red_all + blockIdx.x * cells, out_all + (size_t)blockIdx.x * URF_DEG_CELLS * 4, count_all + blockIdx.x,
+                                     wsum);
 }
 
 #ifdef URF_ENABLE_TEST_HOOKS   /* liburf_hip_test.so only (include/urf_test_hooks.h) */

@@ -21,7 +21,7 @@
  *   k_label        road acceptance per point, label bytes       blind_spots.cpp:124-130,164-170, lidar_segmentation.cpp:354-367
  *
  * The kernels live in one header per family (r6), included below in this order: urf_k_table.hpp, urf_k_split.hpp,
- * urf_k_star.hpp, urf_k_ring.hpp, urf_k_beams_label.hpp, urf_k_outputs.hpp, urf_k_clouds.hpp (the
+ * urf_k_star.hpp, urf_k_ring.hpp, urf_k_beams_label.hpp, urf_k_readouts.hpp (ring views and the rules of the read-outs), urf_k_outputs.hpp, urf_k_clouds.hpp (the
  * published clouds of a batch as records), urf_k_markers.hpp (road_marker's line strips for a batch), urf_k_dense.hpp (dense sweeps put back
  * into firing slots by laser id, in front of the pipeline).  A batch of sweeps in firing order takes the
  * fused front end of urf_front.hpp (k_front, k_front_finish, k_label_front) instead of k_split / k_ring / k_label.
@@ -61,6 +61,7 @@
 #include "urf_k_star.hpp"
 #include "urf_k_ring.hpp"
 #include "urf_k_beams_label.hpp"
+#include "urf_k_readouts.hpp"
 #include "urf_k_outputs.hpp"
 #include "urf_k_clouds.hpp"
 #include "urf_k_markers.hpp"
