@@ -215,7 +215,20 @@ typedef struct urf_ctx urf_ctx;
 int urf_create(urf_ctx** ctx, int device_id, uint32_t max_points, uint32_t max_batch);
 int urf_destroy(urf_ctx* ctx);
 
-/* Replaces paramsCallback (src/main.cpp:4-34): may be called between scans. */
+/* Replaces paramsCallback (src/main.cpp:4-34): may be called between scans.
+ * THE PARAMETER BOX.  Every value the node's dynamic_reconfigure server can deliver -- each row of urf_param_table() anywhere in
+ * its [min, max], one at its end or all of them at theirs (interval 0.01 and 10, curbHeight 0.5, curbPoints 1 and 30, beamZone 10
+ * and 100, angleFilter1 / 2 / 3 at 0 and 180, a region of interest that is empty or inverted: URF_TOO_FEW_POINTS for every scan) --
+ * is followed bit for bit by every entry point: labels, summaries, published order and marker points are the reference's
+ * (tests/test_gpu_param_edges.py against oracle B, tests/test_param_edges_cpu.py oracle B against the reference's own sources).
+ * Outside the box the reference stays defined, and urf_set_params takes and follows in the same way: interval 0, above 10 and
+ * +Inf (every point on one ring); beamZone anywhere in (0, 360]; any angleFilter1 / 2 / 3, negative, above 180 and NaN included;
+ * any curbHeight, kdev_param, kdist_param (0, negative, NaN) and dmin_param; region-of-interest bounds beyond +-200, infinite or
+ * NaN (a NaN bound keeps no point); any beam_width.  It refuses, with URF_ERR_PARAMS and the parameters in force unchanged:
+ * channels outside 1..128, sectors outside 1..1022, curbPoints outside 1..30, xDirection outside 0..2,
+ * beamZone <= 0, above 360 or NaN, interval negative or NaN.
+ * Which kernels run does depend on the values (urf_set_front_mode below: curbPoints 9..30 and an interval that merges two lasers
+ * into one ring keep the general kernels); the results do not. */
 int urf_set_params(urf_ctx* ctx, const urf_params* p);
 int urf_get_params(const urf_ctx* ctx, urf_params* p);
 
@@ -533,6 +546,11 @@ int urf_enable_stage_capture(urf_ctx* ctx, int mode);
  * urf_set_front_mode with another mode forget both.  urf_front_scans: how many scans of the last batch call took the
  * fused front end (synchronises); a scan that kept its flag but has no result -- fewer than 30 points in the region of interest: nothing
  * is published for it by either kind of kernel -- is counted.
+ * One rule of capacity next to the rules of shape: the points whose detector decision is still open after the march wait in a list of
+ * max_points / 8 entries per scan (at least 4096; max_points as given to urf_create), which sweeps of a thousand firings and more
+ * never fill.  A sweep of a few hundred firings, whose neighbours on a ring lie more than a degree apart, leaves a quarter of its points
+ * and more there: in a context created for just its size the list overflows and the scan is handed back (same labels); a context
+ * created for sixteen times the points has room for every one.
  *
  * 128 lasers per firing (urf_set_front_lasers128, k_front128* in urban_road_filter_amd/csrc/urf_front.hpp): with the switch on, channels == 128 and
  * curbPoints == 5, modes 2 and 3 -- never modes 0 and 1 -- also take sweeps of 128 lasers per firing, in firing order (point f * 128 + l)

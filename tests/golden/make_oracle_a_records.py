@@ -12,7 +12,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-TESTS = ["tests/test_fuzz_cpu.py", "tests/test_markers.py", "tests/test_oracle.py", "tests/test_sensor_models_cpu.py"]
+TESTS = ["tests/test_fuzz_cpu.py", "tests/test_markers.py", "tests/test_oracle.py", "tests/test_param_edges_cpu.py",
+         "tests/test_sensor_models_cpu.py"]
 
 if __name__ == "__main__":
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
