@@ -643,6 +643,84 @@ int urf_set_front_multi_sector_curb_points(urf_ctx* ctx, int on);
  * hand-back.  The read-outs' scratch grows with their first use (URF_ERR_OOM from that call).  Anything else: URF_ERR_INVALID_ARG. */
 int urf_set_front_outputs(urf_ctx* ctx, int on);
 
+/* ---- urf_front_explain: why a scan of the last call left the fused front end, and what keeps it -----------------
+ * Labels are the same on either path, so nothing else tells a caller that a stream of sweeps runs on the slower kernels.  The function
+ * reads "the last call" like the other read-outs -- a batch call: n = its scans; a sweep of the callback path that has been waited for:
+ * n = 1, URF_ERR_BUSY once its scratch row has been resubmitted; a dense call: the PADDED batch, firing order -- and writes one record per
+ * scan to `out` (host memory).  layout: how the caller's sweeps are organised, 0 firing order (point f * channels + l), 1 row-major (point
+ * l * F + f).  It synchronises.  LIFETIME: the call's input arrays must still be alive and unmodified, as for urf_ordered_indices*.
+ * No call yet, n other than the call's scans, a layout other than 0 / 1, a null pointer: URF_ERR_INVALID_ARG -- except out == NULL with
+ * n == 0, which asks how many records the last call has: the function returns that number (0: no call yet) and does nothing else.
+ *
+ * It changes nothing in the context: no second run, no hand-back or sighting forgotten, the context does not turn to the general kernels
+ * (unlike the read-outs above), the next classify call launches exactly what it would have launched.  Its scratch grows with its first use
+ * (URF_ERR_OOM from that call); a context that never calls it allocates and launches nothing for it.
+ *
+ *   fused   1: the scan's flag is still set -- what urf_front_scans counts.
+ *   call    URF_WHY_CALL_*: the terms of the CALL's decision (the same for every scan) that were false; 0 exactly when the call
+ *           launched the fused kernels.
+ *   scan    URF_WHY_SCAN_*: the rules of the march this scan breaks under the call's settings, whether or not the call launched the fused
+ *           kernels.  k_front_explain (urf_k_front_explain.hpp) decides per point what the march decides -- region of interest, ring by the
+ *           reference's exact sequence against the scan's final ring table, star sector and participation (beam filter included) -- and
+ *           counts; the counters are always reported (star-shaped search off: the three sector counters are 0).  MULTI_SECTOR and
+ *           SECTORS_FALL are set only when the call ran, or would have run, without urf_set_front_multi_sector's march; CANDIDATES is
+ *           observed (the scan filed more entries than the list holds) and only set when the call ran the march.  A scan with
+ *           URF_TOO_FEW_POINTS, or an empty one: scan = 0 and the counters 0.
+ *           OTHER: the scan was handed back, the call's decision and every rule above are clean.  Then a speculation of the call was
+ *           repaired -- the ring table's look-ahead, the ring-count hint, the rows' table: the repair leaves no word behind, and the next
+ *           call does without that speculation -- or the scan broke a rule this function does not know.
+ *   advice  URF_ADVICE_*: the smallest change of settings that makes every false term of `call` true, plus what the scan's bits ask for
+ *           (MULTI_SECTOR / SECTORS_FALL: urf_set_front_multi_sector, and urf_set_front_multi_sector_curb_points when curbPoints != 5;
+ *           CANDIDATES: CAPACITY; ROWS_SIGHTING, OTHER: CALL_AGAIN; the four shape bits and ROWS_LENGTH: NEVER).  With NEVER no setting
+ *           helps -- channels not 16 / 32 / 64 / 128, curbPoints 9..30, more than 256 tiles per scan, a sweep that is not organised as
+ *           `layout` says (look at params.channels and params.interval) --; the other bits still name what else was missing.
+ *   The function cannot tell hand-backs apart that leave nothing behind (OTHER), and it does not see the sticky general context as a
+ *   property of the scan: READOUT in `call` says that a read-out turned the context to the general kernels (RESET: urf_set_front_mode
+ *   again; FRONT_OUTPUTS: urf_set_front_outputs keeps it from happening again). */
+#define URF_WHY_CALL_MODE_OFF     0x001u   /* urf_set_front_mode(ctx, 0) */
+#define URF_WHY_CALL_STOPPED      0x002u   /* mode 1 stopped trying after a whole batch was handed back */
+#define URF_WHY_CALL_READOUT      0x004u   /* a read-out of ring-sorted results: the context stays with the general kernels */
+#define URF_WHY_CALL_CAPTURE      0x008u   /* stage capture is on */
+#define URF_WHY_CALL_LASERS       0x010u   /* params.channels has no fused kernels under the settings */
+#define URF_WHY_CALL_CURB_POINTS  0x020u   /* params.curbPoints has no fused instance under the settings */
+#define URF_WHY_CALL_TILES        0x040u   /* the call's longest scan has more tiles of 2048 points than the settings take */
+#define URF_WHY_CALL_FEW_SCANS    0x080u   /* a batch call below mode 1's threshold */
+#define URF_WHY_CALL_CALLBACK     0x100u   /* a sweep of the callback path in firing order */
+#define URF_WHY_SCAN_LANE_TWO_RINGS 0x001u
+#define URF_WHY_SCAN_RING_TWO_LANES 0x002u
+#define URF_WHY_SCAN_AXIS           0x004u
+#define URF_WHY_SCAN_RANGE          0x008u
+#define URF_WHY_SCAN_ROWS_LENGTH    0x010u   /* layout 1 and the scan's length is not `channels` whole rows */
+#define URF_WHY_SCAN_MULTI_SECTOR   0x020u
+#define URF_WHY_SCAN_SECTORS_FALL   0x040u
+#define URF_WHY_SCAN_CANDIDATES     0x080u
+#define URF_WHY_SCAN_ROWS_SIGHTING  0x100u   /* layout 1 and the call's sequence had no probe / transpose: the first call only sights */
+#define URF_WHY_SCAN_OTHER          0x200u
+#define URF_ADVICE_MODE_2          0x0001u   /* urf_set_front_mode(ctx, 2) */
+#define URF_ADVICE_MODE_3          0x0002u   /* urf_set_front_mode(ctx, 3) */
+#define URF_ADVICE_LASERS128       0x0004u   /* urf_set_front_lasers128 */
+#define URF_ADVICE_LONG_SWEEPS     0x0008u   /* urf_set_front_long_sweeps */
+#define URF_ADVICE_CURB_POINTS     0x0010u   /* urf_set_front_curb_points */
+#define URF_ADVICE_MULTI_SECTOR    0x0020u   /* urf_set_front_multi_sector */
+#define URF_ADVICE_MULTI_SECTOR_CP 0x0040u   /* urf_set_front_multi_sector_curb_points */
+#define URF_ADVICE_FRONT_OUTPUTS   0x0080u   /* urf_set_front_outputs: read-outs without the second run */
+#define URF_ADVICE_RESET           0x0100u   /* call urf_set_front_mode again: it forgets hand-backs and the sticky read-out */
+#define URF_ADVICE_CAPTURE_OFF     0x0200u   /* urf_enable_stage_capture(ctx, 0) */
+#define URF_ADVICE_BATCH           0x0400u   /* the callback path in firing order: use a batch call */
+#define URF_ADVICE_NEVER           0x0800u   /* no setting helps */
+#define URF_ADVICE_CAPACITY        0x1000u   /* a context created for more points per scan has a longer candidate list */
+#define URF_ADVICE_CALL_AGAIN      0x2000u   /* the next call of the same kind does without what this one tried first */
+typedef struct urf_front_why {
+    uint32_t fused;                  /* 1: the scan's flag is still set (what urf_front_scans counts) */
+    uint32_t call, scan, advice;     /* URF_WHY_CALL_*, URF_WHY_SCAN_*, URF_ADVICE_* */
+    uint32_t lanes_two_rings, rings_two_lanes, axis_points, range_points;   /* laser slots that meet two rings; rings fed by two slots; ring points
+                                                                              * on the sensor's axis; star participants outside [2^-45, 2^63] */
+    uint32_t multi_sector_firings, max_sectors_per_firing, tiles_sectors_fall;
+    uint32_t candidates, candidate_cap;   /* entries the scan filed in the march's candidate list (0: no march), the list's length */
+    uint32_t reserved[3];
+} urf_front_why;                      /* 64 bytes */
+int urf_front_explain(urf_ctx* ctx, int layout /* 0 firing order, 1 row-major */, urf_front_why* out /* host */, uint32_t n);
+
 /* ---- dense sweeps: put back into firing slots by laser id, on the device ---------
  * The fused front end above wants point f * L + l to be laser slot l of firing f (L = channels), non-returns left in place as holes.  A
  * driver that DROPS non-returns (velodyne_pointcloud's default mode, any is_dense cloud) publishes firings of unequal length back to

@@ -86,6 +86,16 @@ class MarkerStrip(C.Structure):
                 ("first_point", C.c_uint32), ("n_points", C.c_uint32)]
 
 
+# urf_front_explain (include/urf.h: urf_front_why, URF_WHY_CALL_*, URF_WHY_SCAN_*, URF_ADVICE_*)
+FRONT_WHY_DTYPE = np.dtype([(name, "<u4") for name in ("fused", "call", "scan", "advice", "lanes_two_rings", "rings_two_lanes", "axis_points",
+                                                       "range_points", "multi_sector_firings", "max_sectors_per_firing", "tiles_sectors_fall",
+                                                       "candidates", "candidate_cap")] + [("reserved", "<u4", (3,))])
+WHY_CALL = {name: 1 << k for k, name in enumerate(("MODE_OFF", "STOPPED", "READOUT", "CAPTURE", "LASERS", "CURB_POINTS", "TILES", "FEW_SCANS", "CALLBACK"))}
+WHY_SCAN = {name: 1 << k for k, name in enumerate(("LANE_TWO_RINGS", "RING_TWO_LANES", "AXIS", "RANGE", "ROWS_LENGTH", "MULTI_SECTOR", "SECTORS_FALL",
+                                                   "CANDIDATES", "ROWS_SIGHTING", "OTHER"))}
+ADVICE = {name: 1 << k for k, name in enumerate(("MODE_2", "MODE_3", "LASERS128", "LONG_SWEEPS", "CURB_POINTS", "MULTI_SECTOR", "MULTI_SECTOR_CP",
+                                                 "FRONT_OUTPUTS", "RESET", "CAPTURE_OFF", "BATCH", "NEVER", "CAPACITY", "CALL_AGAIN"))}
+
 MARKER_ADD, MARKER_DELETE = 0, 2
 MARKER_MAX_POINTS, MARKER_MAX_STRIPS, MARKER_MAX_STRIP_POINTS = 361, 180, 540   # include/urf.h
 MARKER_STRIP_DTYPE = np.dtype([("id", "<i4"), ("action", "<i4"), ("r", "<f4"), ("g", "<f4"), ("b", "<f4"), ("a", "<f4"),
@@ -182,6 +192,7 @@ def lib(hooks=False):
         "urf_set_front_multi_sector": [vp, C.c_int],
         "urf_set_front_multi_sector_curb_points": [vp, C.c_int],
         "urf_set_front_outputs": [vp, C.c_int],
+        "urf_front_explain": [vp, C.c_int, vp, C.c_uint32],
         "urf_callback_path_preset": [vp, C.c_uint32],
         "urf_classify_batch_soa_dense": [vp, fp, fp, fp, vp, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp],
         "urf_classify_batch_pc2_dense": [vp, u8p, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -455,6 +466,17 @@ class Context:
         n = C.c_uint32(0)
         self._check(self._lib.urf_front_scans(self._h, C.addressof(n)), "urf_front_scans")
         return n.value
+
+    def front_explain(self, layout=0):
+        """urf_front_explain: one FRONT_WHY_DTYPE record per scan of the last call -- `fused`, the terms of the call's decision that were
+        false (`call`, WHY_CALL), the rules of the march the scan breaks (`scan`, WHY_SCAN) with their counters, and the settings that
+        keep it fused (`advice`, ADVICE).  layout: 0 firing order, 1 row-major organised.  Synchronises; the call's inputs must still be
+        alive; changes nothing about the calls to come (include/urf.h)."""
+        n = self._check(self._lib.urf_front_explain(self._h, int(layout), None, 0), "urf_front_explain")
+        out = np.zeros(n, FRONT_WHY_DTYPE)
+        if n:
+            self._check(self._lib.urf_front_explain(self._h, int(layout), out.ctypes.data, n), "urf_front_explain")
+        return out
 
     def enable_kernel_timing(self, on=True):
         self._check(self._lib.urf_enable_kernel_timing(self._h, int(on)), "urf_enable_kernel_timing")

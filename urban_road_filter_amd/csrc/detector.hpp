@@ -105,6 +105,65 @@ public:
      * setFrontCurbPoints) sends through the fused front end.  Decides nothing while setFrontMultiSector is off.  Times: profiles/front_multi_sector_cp_bench.json. */
     void setFrontMultiSectorCurbPoints(bool on) { set(urf_set_front_multi_sector_curb_points, "urf_set_front_multi_sector_curb_points", on); }
 
+    /* urf_front_explain: why each scan of the last call (Detector: the sweep waited for last; BatchDetector: the messages of the last
+     * filtered()) left the fused front end, and which of the setters above keeps it.  layout: 0 firing order, 1 row-major organised.
+     * Changes nothing about the calls to come. */
+    std::vector<urf_front_why> frontExplain(int layout)
+    {
+        const int n = urf_front_explain(ctx_, layout, nullptr, 0);   /* (the last call's scans) */
+        if (n < 0)
+            throw Error(n, "urf_front_explain");
+        std::vector<urf_front_why> why((size_t)n);
+        const int rc = n ? urf_front_explain(ctx_, layout, why.data(), (uint32_t)n) : URF_OK;
+        if (rc != URF_OK)
+            throw Error(rc, "urf_front_explain");
+        return why;
+    }
+    /* one English line per bit that is set and per setter the record advises, by its name */
+    static std::string describe(const urf_front_why& w)
+    {
+        static const struct { uint32_t urf_front_why::*word; uint32_t bit; const char* text; } LINES[] = {
+            { &urf_front_why::call, URF_WHY_CALL_MODE_OFF, "call: the fused front end is off (urf_set_front_mode 0)" },
+            { &urf_front_why::call, URF_WHY_CALL_STOPPED, "call: front mode 1 stopped trying after a whole batch was handed back" },
+            { &urf_front_why::call, URF_WHY_CALL_READOUT, "call: a read-out of ring-sorted results turned the context to the general kernels" },
+            { &urf_front_why::call, URF_WHY_CALL_CAPTURE, "call: stage capture is on" },
+            { &urf_front_why::call, URF_WHY_CALL_LASERS, "call: no fused kernels for this params.channels under the settings" },
+            { &urf_front_why::call, URF_WHY_CALL_CURB_POINTS, "call: no fused kernels for this params.curbPoints under the settings" },
+            { &urf_front_why::call, URF_WHY_CALL_TILES, "call: the longest scan has more tiles of 2048 points than the settings take" },
+            { &urf_front_why::call, URF_WHY_CALL_FEW_SCANS, "call: fewer scans than front mode 1 takes" },
+            { &urf_front_why::call, URF_WHY_CALL_CALLBACK, "call: a sweep of the callback path in firing order" },
+            { &urf_front_why::scan, URF_WHY_SCAN_LANE_TWO_RINGS, "scan: a laser slot meets two rings" },
+            { &urf_front_why::scan, URF_WHY_SCAN_RING_TWO_LANES, "scan: a ring is fed by two laser slots" },
+            { &urf_front_why::scan, URF_WHY_SCAN_AXIS, "scan: a ring point lies on the sensor's axis" },
+            { &urf_front_why::scan, URF_WHY_SCAN_RANGE, "scan: a planar range outside [2^-45, 2^63]" },
+            { &urf_front_why::scan, URF_WHY_SCAN_ROWS_LENGTH, "scan: row-major, but its length is not params.channels whole rows" },
+            { &urf_front_why::scan, URF_WHY_SCAN_MULTI_SECTOR, "scan: a firing spans several star sectors" },
+            { &urf_front_why::scan, URF_WHY_SCAN_SECTORS_FALL, "scan: the star sectors fall inside a tile" },
+            { &urf_front_why::scan, URF_WHY_SCAN_CANDIDATES, "scan: the candidate list was full" },
+            { &urf_front_why::scan, URF_WHY_SCAN_ROWS_SIGHTING, "scan: row-major, and this call could only sight the layout" },
+            { &urf_front_why::scan, URF_WHY_SCAN_OTHER, "scan: handed back for no rule known here: a repaired speculation (look-ahead table, ring-count hint, the rows' table), which leaves no word behind" },
+            { &urf_front_why::advice, URF_ADVICE_MODE_2, "advice: urf_set_front_mode(ctx, 2)" },
+            { &urf_front_why::advice, URF_ADVICE_MODE_3, "advice: urf_set_front_mode(ctx, 3)" },
+            { &urf_front_why::advice, URF_ADVICE_LASERS128, "advice: urf_set_front_lasers128(ctx, 1)" },
+            { &urf_front_why::advice, URF_ADVICE_LONG_SWEEPS, "advice: urf_set_front_long_sweeps(ctx, 1)" },
+            { &urf_front_why::advice, URF_ADVICE_CURB_POINTS, "advice: urf_set_front_curb_points(ctx, 1)" },
+            { &urf_front_why::advice, URF_ADVICE_MULTI_SECTOR, "advice: urf_set_front_multi_sector(ctx, 1)" },
+            { &urf_front_why::advice, URF_ADVICE_MULTI_SECTOR_CP, "advice: urf_set_front_multi_sector_curb_points(ctx, 1)" },
+            { &urf_front_why::advice, URF_ADVICE_FRONT_OUTPUTS, "advice: urf_set_front_outputs(ctx, 1), so that read-outs leave the context fused" },
+            { &urf_front_why::advice, URF_ADVICE_RESET, "advice: call urf_set_front_mode again: it forgets the hand-backs and the read-out" },
+            { &urf_front_why::advice, URF_ADVICE_CAPTURE_OFF, "advice: urf_enable_stage_capture(ctx, 0)" },
+            { &urf_front_why::advice, URF_ADVICE_BATCH, "advice: classify the sweeps with a batch call (urf_classify_batch_*)" },
+            { &urf_front_why::advice, URF_ADVICE_NEVER, "advice: no setting helps; check params.channels and params.interval against the sensor" },
+            { &urf_front_why::advice, URF_ADVICE_CAPACITY, "advice: create the context for more points per scan (urf_create: max_points), its candidate list grows with them" },
+            { &urf_front_why::advice, URF_ADVICE_CALL_AGAIN, "advice: make the call again: the next one does without what this one tried first" },
+        };
+        std::string text;
+        for (const auto& l : LINES)
+            if (w.*(l.word) & l.bit)
+                text += std::string(l.text) + "\n";
+        return text;
+    }
+
 protected:
     urf_ctx* ctx_ = nullptr;
     void set(int (*entry)(urf_ctx*, int), const char* name, bool on)

@@ -28,6 +28,7 @@
 #include "urf_front.hpp"
 #include "urf_k_front_sectors.hpp"
 #include "urf_k_front_outputs.hpp"
+#include "urf_k_front_explain.hpp"
 
 #define URF_ASYNC_SLOTS 4
 static_assert(URF_ASYNC_SLOTS == URF_MAX_IN_FLIGHT, "include/urf.h documents the number of sweeps in flight");
@@ -150,6 +151,12 @@ static_assert(URF_FRONT128_TILES2(URF_FRONT_LONG_MAX_TILES) == URF_FRONT_LONG_MA
 /* "The last call", for the entry points that take their input from it (urf_read_stage, urf_ordered_indices, urf_marker_points,
  * urf_clouds_batch_*): publish_last() is the only writer of the whole record, last_call() the readers' way to it. */
 enum urf_last_kind { URF_LAST_NONE, URF_LAST_SOA, URF_LAST_PC2, URF_LAST_SWEEP };   /* no call yet | the batch entry point | a sweep waited for */
+/* plan()'s decision about a call in words, kept for urf_front_explain: the terms that were false and the advice (urf_policy::why), and
+ * whether the march was, or would have been, the multi-sector one (ms_ok) */
+struct urf_planned {
+    urf_policy::reasons call = { 0u, 0u };
+    bool ms = false;
+};
 struct urf_last_call {
     int kind = URF_LAST_NONE;
     uint32_t scans = 0;
@@ -157,6 +164,7 @@ struct urf_last_call {
     urf_dev_params dp;
     uint32_t row = 0;               /* the scratch row of a.* (a batch call: 0) */
     uint64_t gen = 0;               /* a sweep: the row's submission number it was (urf_ctx::row_gen) */
+    urf_planned planned;            /* what the policy said about the call when it planned it (urf_front_explain) */
     /* a dense call (urf_classify_batch_*_dense): `a` is the padded batch -- staging, padded labels, all the context's own --, and
      * this is what the caller handed in, for urf_clouds_batch_* in input order (offsets: the context's copy) */
     struct {
@@ -198,6 +206,7 @@ struct urf_ctx {
         uint64_t key[3] = { 0, 0, 0 };  /* what the captured sequence was built for */
         urf_kargs cap_a;                /* ... and the kernel arguments / parameters it runs with */
         urf_dev_params cap_dp;
+        urf_planned cap_planned;        /* ... and what the policy said when it planned them */
         bool pending = false, used = false;
         uint64_t gen = 0;               /* the row's submission number of the sweep in this slot */
         uint32_t n_points = 0, ticket = 0;
@@ -279,6 +288,9 @@ struct urf_ctx {
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     urf_last_call last;
+    urf_planned planned;            /* run_pipeline: the call it planned last (its callers keep it with the call's arguments) */
+    /* urf_front_explain: k_front_explain's per-scan records ([scans][URF_FX_WORDS]), grown by its first call */
+    lazy_buf<uint32_t> fx_rec;
     std::string last_error;
     /* host-side cost of the callback path, phase by phase (only the build with the test hooks fills them:
      * URF_HOST_TIMES=1, printed by its benchmark loop; the context's layout is the same in both builds) */
@@ -955,6 +967,7 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
     const bool star = dp.p.star_shaped_method != 0;
     const dim3 g_tiles(a.tiles, n_scans), g_scan(n_scans);
     c->pol.plan(a, dp, slot, call.general_only);
+    c->planned = urf_planned{ c->pol.why(a, dp, slot, call.general_only), c->pol.ms_ok(dp) };   /* (host words for urf_front_explain: decides nothing) */
     if (!slot)
         c->pol.probation_batch(a);
 
@@ -1084,9 +1097,10 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
     return URF_OK;
 }
 
-static void publish_last(urf_ctx* c, int kind, uint32_t scans, const urf_kargs& a, const urf_dev_params& dp, uint32_t row = 0, uint64_t gen = 0)
+static void publish_last(urf_ctx* c, int kind, uint32_t scans, const urf_kargs& a, const urf_dev_params& dp, const urf_planned& planned, uint32_t row = 0,
+                         uint64_t gen = 0)
 {
-    c->last = urf_last_call{ kind, scans, a, dp, row, gen };
+    c->last = urf_last_call{ kind, scans, a, dp, row, gen, planned };
     c->last_seq++;
 }
 
@@ -1097,7 +1111,7 @@ static int classify_batch(urf_ctx* c, int kind, const urf_call& call)
     urf_dev_params dp;
     const int rc = run_pipeline(c, call, a, dp);
     if (rc == URF_OK && call.n_scans)
-        publish_last(c, kind, call.n_scans, a, dp);
+        publish_last(c, kind, call.n_scans, a, dp, c->planned);
     return rc;
 }
 
@@ -1551,6 +1565,7 @@ static int slot_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t n_points, uint3
                                 sl.cap_a, sl.cap_dp);
     if (rc != URF_OK)
         return rc;
+    sl.cap_planned = c->planned;
     URF_HIP(c, hipMemcpyAsync(sl.h_labels.p, sl.d_labels.p, n_points, hipMemcpyDeviceToHost, st));
     URF_HIP(c, hipMemcpyAsync(sl.h_info.p, kargs_row(c, row).info, sizeof(urf_scan_info), hipMemcpyDeviceToHost, st));
     return URF_OK;
@@ -1719,7 +1734,7 @@ extern "C" int urf_classify_pc2_wait(urf_ctx* c, uint32_t ticket, uint8_t* label
         }
     }
     /* only now is the sweep "the last call": its scratch row stays untouched until the row (or a batch call) is used again */
-    publish_last(c, URF_LAST_SWEEP, 1, sl.cap_a, sl.cap_dp, slot_row(c, sl), sl.gen);
+    publish_last(c, URF_LAST_SWEEP, 1, sl.cap_a, sl.cap_dp, sl.cap_planned, slot_row(c, sl), sl.gen);
     if (labels_out)
         std::memcpy(labels_out, sl.h_labels.p, sl.n_points);
     if (info)
@@ -1815,9 +1830,99 @@ static int last_call(urf_ctx* c, uint32_t scan, const urf_last_call*& out, urf_l
         c->pol.set(c->pol.want_ring_sorted, true);
         rc = run_pipeline(c, urf_call{ l.a.x, l.a.y, l.a.z, l.a.offsets, l.a.n_per_scan, l.a.max_len, l.a.n_scans, l.a.labels, nullptr, l.row,
                                        nullptr, &l.dp, (int)l.a.capture, true }, l.a, l.dp);
+        if (rc == URF_OK)
+            l.planned = c->planned;
         c->last_seq++;
     }
     return rc != URF_OK ? rc : order_after_slots(c);
+}
+
+/* ---- urf_front_explain (include/urf.h) ------------------------------------------------------ */
+/* The last call's record without last_call()'s second run: the function reads what the call left behind -- front_ok, front_ncand, the
+ * summaries, the final ring tables -- and the call's own points, launches k_front_explain on the context's stream and touches nothing a
+ * classify call reads (no want_ring_sorted, no epoch, no flag word). */
+extern "C" int urf_front_explain(urf_ctx* c, int layout, urf_front_why* out, uint32_t n)
+{
+    if (c && !out && n == 0 && (layout == 0 || layout == 1))   /* (the adapters' question: how many records) */
+        return last_valid(c) ? (int)c->last.scans : 0;
+    const urf_last_call* lp = c ? last_valid(c) : nullptr;
+    if (!lp || !out || (layout != 0 && layout != 1) || n != lp->scans)
+        return URF_ERR_INVALID_ARG;
+    const urf_last_call& l = *lp;
+    URF_HIP(c, hipSetDevice(c->device));
+    if (l.kind == URF_LAST_SWEEP && c->row_gen[l.row] != l.gen) {
+        c->last_error = "urf_front_explain: the scratch row of the sweep waited for last has been resubmitted";
+        return URF_ERR_BUSY;
+    }
+    int rc = grow(c, c->fx_rec, (size_t)n * URF_FX_WORDS, c->stream);
+    if (rc != URF_OK || (rc = order_after_slots(c)) != URF_OK)
+        return rc;
+    const urf_kargs& a = l.a;
+    const urf_dev_params& dp = l.dp;
+    const unsigned L = (unsigned)dp.p.channels;
+    const bool rows = layout == 1 && !l.dense.on;   /* (a dense call: the padded batch, firing order) */
+    const bool lasers = L == 16u || L == 32u || L == 64u || L == 128u;   /* (other counts: no laser slots to speak of, the counters stay 0) */
+    hipStream_t st = c->stream;
+    std::vector<uint32_t> rec((size_t)n * URF_FX_WORDS, 0u), ok(n), ncand(n), lens(n, a.n_per_scan);
+    std::vector<urf_scan_info> info(n);
+    if (lasers) {
+        URF_HIP(c, hipMemsetAsync(c->fx_rec.p, 0, rec.size() * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(k_front_explain, dim3(a.tiles, n), dim3(64), 0, st, a, dp, rows ? 1u : 0u, c->fx_rec.p);
+        URF_HIP(c, hipGetLastError());
+        URF_HIP(c, hipMemcpyAsync(rec.data(), c->fx_rec.p, rec.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    URF_HIP(c, hipMemcpyAsync(ok.data(), a.front_ok, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    URF_HIP(c, hipMemcpyAsync(ncand.data(), a.front_ncand, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    URF_HIP(c, hipMemcpyAsync(info.data(), a.info, n * sizeof(urf_scan_info), hipMemcpyDeviceToHost, st));
+    if (a.offsets) {
+        std::vector<uint32_t> offs((size_t)n + 1);
+        URF_HIP(c, hipMemcpyAsync(offs.data(), a.offsets, offs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        URF_HIP(c, hipStreamSynchronize(st));
+        for (uint32_t s = 0; s < n; s++)
+            lens[s] = std::min(offs[s + 1] - offs[s], a.max_len);
+    }
+    URF_HIP(c, hipStreamSynchronize(st));
+    const auto bits = [](const uint32_t* m) { return (uint32_t)(__builtin_popcount(m[0]) + __builtin_popcount(m[1]) + __builtin_popcount(m[2]) + __builtin_popcount(m[3])); };
+    for (uint32_t s = 0; s < n; s++) {
+        const uint32_t* r = &rec[(size_t)s * URF_FX_WORDS];
+        urf_front_why w;
+        std::memset(&w, 0, sizeof w);
+        w.fused = (a.front && ok[s]) ? 1u : 0u;
+        w.call = l.planned.call.why;
+        w.advice = l.planned.call.advice;
+        w.candidates = ncand[s];
+        w.candidate_cap = a.front_cand_cap;
+        if (info[s].status == URF_OK && lens[s] != 0u) {
+            w.lanes_two_rings = bits(r + URF_FX_LANE_MASK);
+            w.rings_two_lanes = bits(r + URF_FX_RING_MASK);
+            w.axis_points = r[URF_FX_AXIS];
+            w.range_points = r[URF_FX_RANGE];
+            w.multi_sector_firings = r[URF_FX_MULTI];
+            w.max_sectors_per_firing = r[URF_FX_MAX_SECTORS];
+            w.tiles_sectors_fall = r[URF_FX_FALL];
+            uint32_t scan = (w.lanes_two_rings ? URF_WHY_SCAN_LANE_TWO_RINGS : 0u) | (w.rings_two_lanes ? URF_WHY_SCAN_RING_TWO_LANES : 0u) |
+                            (w.axis_points ? URF_WHY_SCAN_AXIS : 0u) | (w.range_points ? URF_WHY_SCAN_RANGE : 0u);
+            if (rows && lasers && lens[s] % L != 0u)
+                scan |= URF_WHY_SCAN_ROWS_LENGTH;
+            if (scan)
+                w.advice |= URF_ADVICE_NEVER;
+            if (!l.planned.ms) {
+                const uint32_t ms = (w.multi_sector_firings ? URF_WHY_SCAN_MULTI_SECTOR : 0u) | (w.tiles_sectors_fall ? URF_WHY_SCAN_SECTORS_FALL : 0u);
+                if (ms)
+                    w.advice |= URF_ADVICE_MULTI_SECTOR | (dp.p.curbPoints != 5 ? URF_ADVICE_MULTI_SECTOR_CP : 0u);
+                scan |= ms;
+            }
+            if (a.front && ncand[s] > a.front_cand_cap)
+                scan |= URF_WHY_SCAN_CANDIDATES, w.advice |= URF_ADVICE_CAPACITY;
+            if (rows && a.front_rows == 0u)
+                scan |= URF_WHY_SCAN_ROWS_SIGHTING, w.advice |= URF_ADVICE_CALL_AGAIN;
+            if (!w.fused && !w.call && !scan)
+                scan = URF_WHY_SCAN_OTHER, w.advice |= URF_ADVICE_CALL_AGAIN;
+            w.scan = scan;
+        }
+        out[s] = w;
+    }
+    return URF_OK;
 }
 
 /* ---- index-set and marker outputs: every scan of a batch in one launch sequence ------------- */

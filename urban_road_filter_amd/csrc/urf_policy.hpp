@@ -155,6 +155,9 @@ struct __attribute__((visibility("hidden"))) urf_policy {
         return lsh != 7u ? tpb : (tpb < 2u ? 2u : (tpb & ~1u));
     }
 
+    /* the march of a fused call is, or would be, the multi-sector one (plan(): a.front_ms of a call that is fused) */
+    bool ms_ok(const urf_dev_params& dp) const { return multi_sector && dp.p.star_shaped_method != 0 && (dp.p.curbPoints == 5 || multi_sector_cp); }
+
     /* The launch decisions of one call (a.tiles, a.capture, a.n_scans set): slot, a sweep of the callback path; general_only, no fused
      * kernels (last_call). */
     void plan(urf_kargs& a, const urf_dev_params& dp, bool slot, bool general_only) const
@@ -181,6 +184,81 @@ struct __attribute__((visibility("hidden"))) urf_policy {
         a.front_lists = (a.front && !front_direct && !slot) ? 1u : 0u;   /* (the callback path's sequence holds the general kernels as grids anyway) */
         a.front_rows = (a.front && front_rows) ? 1u : 0u;   /* (independent of the two other speculations: the repair kernels come with it) */
         a.front_ms = (a.front && multi_sector && dp.p.star_shaped_method != 0 && (dp.p.curbPoints == 5 || multi_sector_cp)) ? 1u : 0u;
+    }
+
+    /* Why plan() gave a call the general kernels, and what would give it the fused ones (urf_front_explain; a.tiles, a.capture, a.n_scans
+     * set, as for plan()).  why: one URF_WHY_CALL_* bit per term of plan()'s `shape` and `enough` that is false, 0 exactly when plan() sets
+     * a.front.  advice: the smallest set of URF_ADVICE_* that makes every one of them true -- the mode to raise to, the switches to turn
+     * on, RESET (urf_set_front_mode again: forget_front and want_ring_sorted; a general_only run is the read-out's own and ends with it),
+     * CAPTURE_OFF, BATCH (a sweep of the callback path as a batch call, which then is large enough: 512 scans) --; NEVER where no setting
+     * helps, with the other bits still naming what else was missing.  FRONT_OUTPUTS goes with a sticky read-out: it does not undo it
+     * (RESET does) but keeps the next read-out from doing it again.  Asks plan()'s questions, decides no launch. */
+    struct reasons { uint32_t why, advice; };
+    reasons why(const urf_kargs& a, const urf_dev_params& dp, bool slot, bool general_only) const
+    {
+        const unsigned L = (unsigned)dp.p.channels;
+        const int cp = dp.p.curbPoints;
+        uint32_t w = 0, adv = 0;
+        int mode = front_mode;   /* the mode the advice raises to */
+        if (front_mode == 0)
+            w |= URF_WHY_CALL_MODE_OFF, mode = 2;   /* (no bit says 1: mode 2 takes every batch call mode 1 takes) */
+        if (front_off)
+            w |= URF_WHY_CALL_STOPPED, adv |= URF_ADVICE_RESET;
+        if (general_only || want_ring_sorted) {
+            w |= URF_WHY_CALL_READOUT, adv |= URF_ADVICE_RESET;
+            if (!front_outputs)
+                adv |= URF_ADVICE_FRONT_OUTPUTS;
+        }
+        if (a.capture != 0)
+            w |= URF_WHY_CALL_CAPTURE, adv |= URF_ADVICE_CAPTURE_OFF;
+        const bool known = L == 128u || L == 64u || L == 32u || L == 16u;
+        if (!known)
+            adv |= URF_ADVICE_NEVER;
+        if (!lasers_ok(L)) {
+            w |= URF_WHY_CALL_LASERS;
+            if (L == 128u) {
+                mode = mode < 2 ? 2 : mode;
+                if (!lasers128)
+                    adv |= URF_ADVICE_LASERS128;
+            }
+        }
+        const bool cp_known = cp >= 1 && cp <= 8 && ((URF_FRONT_CP_MASK >> cp) & 1u) != 0u;
+        if (!curb_points_ok(L, cp))
+            w |= URF_WHY_CALL_CURB_POINTS;
+        if (cp != 5 && cp_known) {   /* (asked of the mode the advice raises to: a call that lacks the mode for other reasons lacks it here too) */
+            mode = 3;
+            if (L != 64u && !curb_points)
+                adv |= URF_ADVICE_CURB_POINTS;
+            if (L == 128u && !lasers128)
+                adv |= URF_ADVICE_LASERS128;
+        } else if (cp != 5) {
+            adv |= URF_ADVICE_NEVER;
+        }
+        if (a.tiles > front_max_tiles())
+            w |= URF_WHY_CALL_TILES;
+        if (a.tiles > URF_FRONT_LONG_MAX_TILES) {
+            adv |= URF_ADVICE_NEVER;
+        } else if (a.tiles > URF_FRONT_MAX_TILES) {
+            mode = mode < 2 ? 2 : mode;
+            if (!long_sweeps)
+                adv |= URF_ADVICE_LONG_SWEEPS;
+        }
+        /* `enough`, asked of the mode so far: a mode raised for the shape's sake takes every batch call, and with a row-major sighting
+         * the callback path as well */
+        const bool sighted = front_rows && (rows_used || rows_probation > 0);
+        if (!(slot ? small_ok(L) : (every_batch() || small_ok(L) || a.n_scans >= min_scans(L)))) {
+            w |= slot ? URF_WHY_CALL_CALLBACK : URF_WHY_CALL_FEW_SCANS;
+            if (!slot || sighted) {   /* (with the sighting all a sweep lacks is the mode: small_ok) */
+                mode = mode < 2 ? 2 : mode;
+            } else {
+                adv |= URF_ADVICE_BATCH;
+                if (mode < 2 && 512u < min_scans(L))
+                    mode = 2;
+            }
+        }
+        if (mode != front_mode)
+            adv |= mode == 3 ? URF_ADVICE_MODE_3 : URF_ADVICE_MODE_2;
+        return reasons{ w, w ? adv : 0u };
     }
 };
 
