@@ -74,7 +74,8 @@ extern "C" {
  * urf_set_front_multi_sector_curb_points (urf_set_front_multi_sector at curbPoints 1..8 instead of 5 only); urf_set_dense_outputs
  * (the reference-order read-outs after a dense call, in the caller's indices); urf_set_dense_elevations with
  * urf_classify_batch_soa_dense_elev / urf_classify_batch_pc2_dense_elev (the dense calls for clouds without a `ring` field: laser ids
- * derived from the points' elevation on the device).
+ * derived from the points' elevation on the device); urf_set_sweep_outputs with urf_result_marker_points / urf_result_ordered_indices
+ * and URF_SWEEP_OUT_* (a sweep of the callback path brings its marker points and ordered lists along, read per ticket).
  * WHICH std::sort (4 above): the one of libstdc++ as shipped with GCC 5 .. 13 (bits/stl_algo.h: __sort = __introsort_loop with
  * _S_threshold 16, __move_median_to_first on (first + 1, mid, last - 1), __unguarded_partition, depth limit 2 * floor(log2 n),
  * __partial_sort as the fallback, then __final_insertion_sort); tests/test_stdsort.py pins the restatement against the std::sort
@@ -287,6 +288,33 @@ int urf_classify_pc2_async(urf_ctx* ctx, const uint8_t* data, uint32_t n_points,
 int urf_classify_pc2_wait(urf_ctx* ctx, uint32_t ticket, uint8_t* labels_out, urf_scan_info* info);
 int urf_result_labels(urf_ctx* ctx, uint32_t ticket, const uint8_t** labels);
 int urf_pinned_input(urf_ctx* ctx, size_t bytes, uint8_t** ptr);
+
+/* Marker points and the reference's order travelling WITH the sweep (opt-in; additive under ABI 5).  urf_marker_points and
+ * urf_ordered_indices read the scratch row of the sweep waited for last on the context's stream: they wait for every sweep in flight,
+ * launch their kernels behind them, synchronise, and answer URF_ERR_BUSY once the row has been resubmitted.  With a bit set here the
+ * captured sequence of every sweep submitted afterwards also produces that product on the sweep's own row and stream and copies it to a
+ * pinned result buffer of the sweep's slot, as labels and summary are; after urf_classify_pc2_wait it is read per ticket with no further
+ * GPU work, for any number of sweeps in flight up to URF_MAX_IN_FLIGHT and any max_batch -- no URF_ERR_BUSY, no second run of a fused
+ * row-major sweep, and the context stays fused (independent of urf_set_front_outputs).
+ *   urf_set_sweep_outputs   bits: URF_SWEEP_OUT_MARKER_POINTS | URF_SWEEP_OUT_ORDER, 0 (default) = off; other bits URF_ERR_INVALID_ARG.
+ *                           Allocates everything the sequences need (per scratch row the read-outs' scratch, per slot a device and a
+ *                           pinned result buffer of 1448 + 3 * max_points words): URF_ERR_OOM comes from here and leaves the switch as
+ *                           it was.  URF_ERR_BUSY while a sweep is in flight.  A change makes every slot capture its sequence again.  A
+ *                           context that never turns a bit on allocates and launches nothing.  Labels, summaries, urf_front_scans,
+ *                           urf_callback_path_state and batch calls are what they are without it.
+ *   urf_result_marker_points    *pts = the ticket's marker points (x, y, z, red per point, as urf_marker_points writes them), *count of them.
+ *   urf_result_ordered_indices  *road / *curb / *ring10 = the ticket's lists as urf_ordered_indices writes them (a pointer that is not
+ *                           wanted may be NULL), counts[3] their lengths.
+ * Both follow urf_result_labels: pointers into the slot's pinned buffer, valid until the slot is used again; a ticket never issued or
+ * overtaken URF_ERR_INVALID_ARG, one still in flight URF_ERR_BUSY; a sweep submitted while the product's bit was off
+ * URF_ERR_INVALID_ARG (urf_last_error names the switch); a sweep whose status is not URF_OK: count 0, counts {0, 0, 0}.
+ * urf_marker_points / urf_ordered_indices / urf_read_stage / urf_front_explain keep working next to them, BUSY rule included. */
+#define URF_SWEEP_OUT_MARKER_POINTS 1u
+#define URF_SWEEP_OUT_ORDER         2u
+int urf_set_sweep_outputs(urf_ctx* ctx, uint32_t bits);
+int urf_result_marker_points(urf_ctx* ctx, uint32_t ticket, const float** pts, uint32_t* count);
+int urf_result_ordered_indices(urf_ctx* ctx, uint32_t ticket, const uint32_t** road, const uint32_t** curb,
+                               const uint32_t** ring10, uint32_t counts[3]);
 
 /* ---- batch of scans, device-resident ---------------------------------------
  * n_scans independent scans of n_per_scan points each; scan s owns elements

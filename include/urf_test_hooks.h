@@ -54,7 +54,9 @@ int urf_selftest(urf_ctx* ctx, uint64_t* n_mismatches);
 int urf_selftest_fast(urf_ctx* ctx, uint64_t n_samples, float* err);
 /* Test hook: bit 2 (value 4) forces the general (comparison network) path of the star-shaped sort
  * for every sector; 0 in production.  Takes effect with the next classify call.  Bit 4 (value 16): urf_clouds_batch_*
- * store their records with non-temporal stores (an A/B switch for tools/batch_clouds_bench.py: measured slower). */
+ * store their records with non-temporal stores (an A/B switch for tools/batch_clouds_bench.py: measured slower).  Bit 5 (value 32):
+ * with both bits of urf_set_sweep_outputs set, a sweep's sequence launches the kernels of the two products one by one instead of
+ * k_sweep_rings / k_sweep_lists (an A/B switch for tools/sweep_outputs_bench.py). */
 int urf_set_debug_flags(urf_ctx* ctx, uint32_t flags);
 
 /* The ids urf_classify_batch_*_dense_elev derived (include/urf.h): the first n bytes of the context's id buffer, indexed like the

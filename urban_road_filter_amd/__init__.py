@@ -26,6 +26,7 @@ from .api import (  # noqa: F401
     synth_cloud,
     pc2_to_planes,
     ORDER_INPUT, ORDER_REFERENCE,
+    SWEEP_OUT_MARKER_POINTS, SWEEP_OUT_ORDER,
     FRONT_WHY_DTYPE, WHY_CALL, WHY_SCAN, ADVICE,
     LABEL_MASK, LABEL_ROAD, LABEL_CURB, FLAG_ROI, FLAG_RING, FLAG_RING10,
     STAGE_VALPHA, STAGE_RING, STAGE_AZIMUTH, STAGE_RANGE2D, STAGE_DETECT, STAGE_SECTOR,

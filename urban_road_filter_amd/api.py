@@ -96,6 +96,8 @@ WHY_SCAN = {name: 1 << k for k, name in enumerate(("LANE_TWO_RINGS", "RING_TWO_L
 ADVICE = {name: 1 << k for k, name in enumerate(("MODE_2", "MODE_3", "LASERS128", "LONG_SWEEPS", "CURB_POINTS", "MULTI_SECTOR", "MULTI_SECTOR_CP",
                                                  "FRONT_OUTPUTS", "RESET", "CAPTURE_OFF", "BATCH", "NEVER", "CAPACITY", "CALL_AGAIN"))}
 
+SWEEP_OUT_MARKER_POINTS, SWEEP_OUT_ORDER = 1, 2   # urf_set_sweep_outputs (include/urf.h: URF_SWEEP_OUT_*)
+
 MARKER_ADD, MARKER_DELETE = 0, 2
 MARKER_MAX_POINTS, MARKER_MAX_STRIPS, MARKER_MAX_STRIP_POINTS = 361, 180, 540   # include/urf.h
 MARKER_STRIP_DTYPE = np.dtype([("id", "<i4"), ("action", "<i4"), ("r", "<f4"), ("g", "<f4"), ("b", "<f4"), ("a", "<f4"),
@@ -204,6 +206,9 @@ def lib(hooks=False):
         "urf_classify_batch_soa_dense_elev": [vp, fp, fp, fp, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp],
         "urf_classify_batch_pc2_dense_elev": [vp, u8p, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                               C.c_uint32, C.c_uint32, u8p, vp],
+        "urf_set_sweep_outputs": [vp, C.c_uint32],
+        "urf_result_marker_points": [vp, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)],
+        "urf_result_ordered_indices": [vp, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u32p],
         "urf_test_dense_ids": [vp, u8p, C.c_uint64],
         "urf_test_dense_ids_ms": [vp, C.c_uint32, C.POINTER(C.c_float)],
     }
@@ -529,6 +534,31 @@ class Context:
         p = C.c_void_p()
         self._check(self._lib.urf_result_labels(self._h, ticket, C.byref(p)), "urf_result_labels")
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n_points,))
+
+    def set_sweep_outputs(self, bits):
+        """urf_set_sweep_outputs: SWEEP_OUT_MARKER_POINTS | SWEEP_OUT_ORDER -- every sweep submitted afterwards brings that product
+        along (result_marker_points / result_ordered_indices per ticket, no GPU work after the wait, any number of sweeps in flight
+        on any max_batch); 0 (default) off.  Allocates what the sequences need (UrfError -5 comes from here); -6 while a sweep is in
+        flight (include/urf.h)."""
+        self._check(self._lib.urf_set_sweep_outputs(self._h, int(bits)), "urf_set_sweep_outputs")
+
+    def result_marker_points(self, ticket):
+        """The marker points of a ticket that has been waited for, float32 [k, 4] = x, y, z, red (a copy of the slot's pinned buffer)."""
+        p, n = C.c_void_p(), C.c_uint32(0)
+        self._check(self._lib.urf_result_marker_points(self._h, ticket, C.byref(p), C.byref(n)), "urf_result_marker_points")
+        if n.value == 0:
+            return np.zeros((0, 4), np.float32)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n.value, 4)).copy()
+
+    def result_ordered_indices(self, ticket):
+        """Input indices of the road / curb / road_probably clouds of a ticket that has been waited for, in the order the reference
+        publishes them: three uint32 arrays (copies of the slot's pinned buffer)."""
+        ptrs = [C.c_void_p() for _ in range(3)]
+        cnt = (C.c_uint32 * 3)()
+        self._check(self._lib.urf_result_ordered_indices(self._h, ticket, C.byref(ptrs[0]), C.byref(ptrs[1]), C.byref(ptrs[2]), cnt),
+                    "urf_result_ordered_indices")
+        return tuple(np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(int(k),)).copy() if k else np.zeros(0, np.uint32)
+                     for p, k in zip(ptrs, cnt))
 
     # -- single scan, host, PointCloud2 layout ------------------------------------
     def classify_pc2(self, data, n_points, point_step, off_x, off_y, off_z):

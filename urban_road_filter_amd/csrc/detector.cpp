@@ -27,6 +27,15 @@ void Detector::check(int rc, const char* what) const
         throw Error(rc, std::string(what) + ": " + urf_strerror(rc) + " " + urf_last_error(ctx_));
 }
 
+void Detector::applySweepOutputs(bool sweep, bool marker, bool order)
+{
+    const uint32_t bits = sweep ? (marker ? URF_SWEEP_OUT_MARKER_POINTS : 0u) | (order ? URF_SWEEP_OUT_ORDER : 0u) : 0u;
+    if (bits == sweep_bits_)
+        return;   /* (a detector that never turns the switch on never calls the entry point) */
+    check(urf_set_sweep_outputs(ctx_, bits), "urf_set_sweep_outputs");
+    sweep_bits_ = bits;
+}
+
 void Detector::setParams(const urf_params& p) { check(urf_set_params(ctx_, &p), "urf_set_params"); }
 
 urf_params Detector::params() const
@@ -176,20 +185,31 @@ void Detector::split(const Pending& m)
                          road_probably_.points);
     if (!ok)
         throw Error(URF_ERR_HIP, "label bytes and summary counters disagree");
-    if (marker_on_) {
+    if (marker_on_ && sweep_outputs_) {   /* the sweep brought them along (urf_set_sweep_outputs): the slot's pinned result buffer */
+        const float* mp = nullptr;
+        uint32_t k = 0;
+        check(urf_result_marker_points(ctx_, m.ticket, &mp, &k), "urf_result_marker_points");
+        marker_published_ = marker_.build(mp, k, markers_);
+    } else if (marker_on_) {
         float mp[361 * 4];
         uint32_t k = 0;
         check(urf_marker_points(ctx_, 0, mp, &k), "urf_marker_points");
         marker_published_ = marker_.build(mp, k, markers_);
     }
     if (reference_order_) {
-        if (ord_.size() < 3 * (size_t)max_points_)
-            ord_.resize(3 * (size_t)max_points_);   /* once */
-        uint32_t* ro = ord_.data();
-        uint32_t* co = ro + max_points_;
-        uint32_t* po = co + max_points_;
+        const uint32_t *ro = nullptr, *co = nullptr, *po = nullptr;
         uint32_t cnt[3] = { 0, 0, 0 };
-        check(urf_ordered_indices(ctx_, 0, ro, co, po, cnt), "urf_ordered_indices");
+        if (sweep_outputs_) {
+            check(urf_result_ordered_indices(ctx_, m.ticket, &ro, &co, &po, cnt), "urf_result_ordered_indices");
+        } else {
+            if (ord_.size() < 3 * (size_t)max_points_)
+                ord_.resize(3 * (size_t)max_points_);   /* once */
+            uint32_t* const wr = ord_.data();
+            check(urf_ordered_indices(ctx_, 0, wr, wr + max_points_, wr + 2 * (size_t)max_points_, cnt), "urf_ordered_indices");
+            ro = wr;
+            co = wr + max_points_;
+            po = wr + 2 * (size_t)max_points_;
+        }
         const RecordsAny rec{ m.data, m.step, m.ox, m.oy, m.oz, m.oi };
         const RecordsXYZI recx{ m.data };
         PointXYZI q;

@@ -149,7 +149,7 @@ public:
             { &urf_front_why::advice, URF_ADVICE_CURB_POINTS, "advice: urf_set_front_curb_points(ctx, 1)" },
             { &urf_front_why::advice, URF_ADVICE_MULTI_SECTOR, "advice: urf_set_front_multi_sector(ctx, 1)" },
             { &urf_front_why::advice, URF_ADVICE_MULTI_SECTOR_CP, "advice: urf_set_front_multi_sector_curb_points(ctx, 1)" },
-            { &urf_front_why::advice, URF_ADVICE_FRONT_OUTPUTS, "advice: urf_set_front_outputs(ctx, 1), so that read-outs leave the context fused" },
+            { &urf_front_why::advice, URF_ADVICE_FRONT_OUTPUTS, "advice: urf_set_front_outputs(ctx, 1), so that read-outs leave the context fused (callback path: urf_set_sweep_outputs / Detector::setSweepOutputs, whose sweeps need no read-out)" },
             { &urf_front_why::advice, URF_ADVICE_RESET, "advice: call urf_set_front_mode again: it forgets the hand-backs and the read-out" },
             { &urf_front_why::advice, URF_ADVICE_CAPTURE_OFF, "advice: urf_enable_stage_capture(ctx, 0)" },
             { &urf_front_why::advice, URF_ADVICE_BATCH, "advice: classify the sweeps with a batch call (urf_classify_batch_*)" },
@@ -184,13 +184,29 @@ public:
     /* Emit road / curb / road_probably in the reference's own order (ring by ring, ascending
      * azimuth inside a ring -- lidar_segmentation.cpp:289-291, 354-367) instead of input order.
      * Costs one extra per-ring sort on the GPU; roi is in input order either way. */
-    void setReferenceOrder(bool on) { reference_order_ = on; }
+    void setReferenceOrder(bool on)
+    {
+        applySweepOutputs(sweep_outputs_, marker_on_, on);   /* (throws before anything changes) */
+        reference_order_ = on;
+    }
     /* Also build the "road_marker" MarkerArray (lidar_segmentation.cpp:295-351, 369-602, topic :59,601);
      * fixedFrame = params::fixedFrame (cfg:10).  Off by default: the polygon is a visualisation product. */
     void enableRoadMarker(bool on, const std::string& fixed_frame = "left_os1/os1_lidar")
     {
+        applySweepOutputs(sweep_outputs_, on, reference_order_);
         marker_on_ = on;
         marker_.setFixedFrame(fixed_frame);
+    }
+    /* urf_set_sweep_outputs: with it on, the marker points (enableRoadMarker) and the index lists of the reference order
+     * (setReferenceOrder) are produced by the sweep's own launch sequence and travel with its ticket -- collect() reads them from the
+     * ticket's result buffers instead of calling urf_marker_points / urf_ordered_indices, which wait for every sweep in flight and need
+     * one scratch row per sweep in flight.  With submit() / collect() and several sweeps in flight this keeps the pipelining; the clouds
+     * and the MarkerArray are the same byte for byte.  Off (default): the two synchronous calls, as before.  Like the two setters
+     * above it is callable between sweeps only: with a sweep in flight it throws Error(URF_ERR_BUSY). */
+    void setSweepOutputs(bool on)
+    {
+        applySweepOutputs(on, marker_on_, reference_order_);
+        sweep_outputs_ = on;
     }
     void setMarkerParams(const urf_marker_params& p) { marker_.setParams(p); }
     /* nullptr when the reference would not publish a MarkerArray for the last sweep */
@@ -248,8 +264,11 @@ private:
     void split(const Pending& m);
     static void resolve(const PointCloud2& msg, uint32_t off[3], int64_t& off_intensity, uint64_t& n);
     friend class BatchDetector;
+    void applySweepOutputs(bool sweep, bool marker, bool order);   /* urf_set_sweep_outputs with the bits the three settings add up to */
     bool reference_order_ = false;
     bool marker_on_ = false, marker_published_ = false;
+    bool sweep_outputs_ = false;
+    uint32_t sweep_bits_ = 0;   /* what the context has been told (0: never asked for, nothing allocated) */
     MarkerBuilder marker_;
     MarkerArray markers_;
     Pending pending_[URF_MAX_IN_FLIGHT];

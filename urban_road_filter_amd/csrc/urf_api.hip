@@ -212,7 +212,25 @@ struct urf_ctx {
         uint32_t n_points = 0, ticket = 0;
         uint32_t point_step = 0, off_x = 0, off_y = 0, off_z = 0;   /* layout of the message in d_raw */
         bool planes = false;            /* d_raw holds x[n] y[n] z[n] (a staged message) instead of the records */
+        /* urf_set_sweep_outputs: the sweep's marker points and ordered lists (sweep_out_words: URF_SWEEP_HDR words, then three
+         * lists of n_points entries), device and pinned; out_bits: the bits the sweep in this slot was submitted with */
+        lazy_buf<uint32_t> d_out;
+        lazy_buf<uint32_t, true> h_out;
+        uint32_t out_bits = 0;
     } slots[URF_ASYNC_SLOTS];
+    /* urf_set_sweep_outputs: what launch_markers / launch_ordered / front_out_prepare keep as context-wide lazy buffers, once per scratch
+     * row of the callback path (row r starts r * elements into each: sweep_row) -- a sweep's captured sequence produces its read-outs on
+     * its own row.  Allocated by the first call that turns a bit on; empty in a context that never does. */
+    struct sweep_scratch_t {
+        lazy_buf<float> mk_d;               /* [rows][URF_MAX_CHANNELS * URF_DEG_CELLS] */
+        lazy_buf<uint32_t> mk_pos;
+        lazy_buf<uint8_t> mk_red;           /* ... + URF_MAX_CHANNELS literal flags (mk_lit) behind the cells of a row */
+        lazy_buf<unsigned long long> ord_keys;   /* [rows][sstride] */
+        lazy_buf<uint32_t> ord_pos;
+        lazy_buf<uint32_t> ord_cls;         /* [rows][URF_MAX_CHANNELS * 2] */
+        lazy_buf<uint32_t> fo_az, fo_ent;   /* [rows][sstride] */
+        lazy_buf<float> fo_d;
+    } sweep;
     bool streams_made = false;
     urf_policy pol;                 /* which kernels a call launches */
     uint32_t n_rerun = 0;           /* sweeps urf_classify_pc2_wait had to run again */
@@ -776,6 +794,64 @@ extern "C" int urf_set_front_outputs(urf_ctx* c, int on)
     if (!c || (on != 0 && on != 1))
         return URF_ERR_INVALID_ARG;
     c->pol.front_outputs = on != 0;   /* (the read-outs' scratch grows with their first use: front_out_prepare) */
+    return URF_OK;
+}
+
+/* ---- urf_set_sweep_outputs (include/urf.h) ---------------------------------------------------- */
+/* A slot's result buffer, in 32-bit words: the marker points (URF_DEG_CELLS x 4 floats), their count, the three list counts -- one small
+ * copy --, then the road, curb and ring-10 lists at a stride of the sweep's n_points (one copy of 3 x n_points words, sized at capture). */
+#define URF_SWEEP_HDR_MCOUNT (URF_DEG_CELLS * 4u)
+#define URF_SWEEP_HDR_LCOUNTS (URF_SWEEP_HDR_MCOUNT + 1u)
+#define URF_SWEEP_HDR (URF_SWEEP_HDR_LCOUNTS + 3u)
+#define URF_DBG_SWEEP_OLD_KERNELS 32u   /* test hook (urf_set_debug_flags): with both bits set the sequence launches the kernels of the two
+                                           products one by one instead of k_sweep_rings / k_sweep_lists (A/B, tools/sweep_outputs_bench.py) */
+static uint32_t sweep_rows(const urf_ctx* c) { return c->max_batch < URF_ASYNC_SLOTS ? c->max_batch : URF_ASYNC_SLOTS; }
+
+/* Everything the sequences will need, before any of them is captured: nothing may be allocated inside a stream capture.  The buffers are
+ * of fixed size (rows, sstride, max_points): a second call finds them there. */
+static int sweep_outputs_alloc(urf_ctx* c)
+{
+    const size_t rows = sweep_rows(c), cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS, ss = c->sstride;
+    urf_ctx::sweep_scratch_t& w = c->sweep;
+    int rc;
+    if ((rc = grow(c, w.mk_d, rows * cells)) != URF_OK || (rc = grow(c, w.mk_pos, rows * cells)) != URF_OK ||
+        (rc = grow(c, w.mk_red, rows * (cells + URF_MAX_CHANNELS))) != URF_OK || (rc = grow(c, w.ord_keys, rows * ss)) != URF_OK ||
+        (rc = grow(c, w.ord_pos, rows * ss)) != URF_OK || (rc = grow(c, w.ord_cls, rows * URF_MAX_CHANNELS * 2)) != URF_OK ||
+        (rc = grow(c, w.fo_az, rows * ss)) != URF_OK || (rc = grow(c, w.fo_ent, rows * ss)) != URF_OK || (rc = grow(c, w.fo_d, rows * ss)) != URF_OK)
+        return rc;
+    const size_t words = URF_SWEEP_HDR + 3 * (size_t)c->max_points;
+    for (auto& sl : c->slots) {
+        const bool fresh = sl.d_out.cap < words;
+        if ((rc = grow(c, sl.d_out, words)) != URF_OK || (rc = grow(c, sl.h_out, words)) != URF_OK)
+            return rc;
+        if (fresh) {   /* (a sweep with one bit set copies the whole header) */
+            URF_HIP(c, hipMemset(sl.d_out.p, 0, URF_SWEEP_HDR * sizeof(uint32_t)));
+            std::memset(sl.h_out.p, 0, URF_SWEEP_HDR * sizeof(uint32_t));
+        }
+    }
+    return URF_OK;
+}
+
+extern "C" int urf_set_sweep_outputs(urf_ctx* c, uint32_t bits)
+{
+    if (!c)
+        return URF_ERR_INVALID_ARG;
+    if (bits & ~(URF_SWEEP_OUT_MARKER_POINTS | URF_SWEEP_OUT_ORDER)) {
+        c->last_error = "urf_set_sweep_outputs: bits other than URF_SWEEP_OUT_MARKER_POINTS | URF_SWEEP_OUT_ORDER";
+        return URF_ERR_INVALID_ARG;
+    }
+    for (const auto& sl : c->slots)
+        if (sl.pending) {
+            c->last_error = "urf_set_sweep_outputs: a sweep is in flight (urf_classify_pc2_wait it first)";
+            return URF_ERR_BUSY;
+        }
+    if (bits) {
+        URF_HIP(c, hipSetDevice(c->device));
+        const int rc = sweep_outputs_alloc(c);
+        if (rc != URF_OK)
+            return rc;   /* (the switch stays as it was) */
+    }
+    c->pol.set(c->pol.sweep_outputs, bits);   /* (every slot captures its sequence again) */
     return URF_OK;
 }
 
@@ -1541,6 +1617,81 @@ extern "C" int urf_pc2_to_planes(const uint8_t* data, uint32_t n_points, uint32_
     return URF_OK;
 }
 
+/* urf_set_sweep_outputs: the read-outs of the sweep run_pipeline has just launched on `st`, behind it on the same stream -- one linear
+ * chain, separate launches as the only synchronisation -- with the sweep's own arguments and parameters (sl.cap_a: its scratch row, scan
+ * 0), the row's read-out scratch and the slot's result buffers; then the copies to the slot's pinned buffer.  The kernels are
+ * launch_markers' / launch_ordered's: a fused sequence (cap_a.front) holds the pre-pass and the *_front siblings as well and the scan
+ * decides on the device which of each pair works; a sweep the short sequence voided leaves empty results (every kernel returns for a
+ * status that is not URF_OK) and gets the right ones from its rerun.  With both bits set the per-ring work of the two products is one
+ * launch (k_sweep_rings), lists and marker points another (k_sweep_lists).  c->fo_prep and want_ring_sorted are none of its business. */
+static int sweep_outputs_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t row, hipStream_t st, uint32_t n_points)
+{
+    const uint32_t bits = c->pol.sweep_outputs;
+    if (!bits)
+        return URF_OK;
+    const urf_kargs& a = sl.cap_a;
+    const urf_dev_params& dp = sl.cap_dp;
+    const bool mark = (bits & URF_SWEEP_OUT_MARKER_POINTS) != 0, order = (bits & URF_SWEEP_OUT_ORDER) != 0, fused = a.front != 0;
+    const bool merged = mark && order && !(c->debug_flags & URF_DBG_SWEEP_OLD_KERNELS);
+    const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS, ss = c->sstride;
+    urf_ctx::sweep_scratch_t& w = c->sweep;
+    float* const mk_d = w.mk_d.p + row * cells;
+    uint32_t* const mk_pos = w.mk_pos.p + row * cells;
+    uint8_t* const mk_red = w.mk_red.p + row * (cells + URF_MAX_CHANNELS);
+    uint8_t* const mk_lit = mk_red + cells;
+    unsigned long long* const ord_keys = w.ord_keys.p + row * ss;
+    uint32_t* const ord_pos = w.ord_pos.p + row * ss;
+    uint32_t* const ord_cls = w.ord_cls.p + (size_t)row * URF_MAX_CHANNELS * 2;
+    uint32_t* const fo_az = w.fo_az.p + row * ss;
+    uint32_t* const fo_ent = w.fo_ent.p + row * ss;
+    float* const fo_d = w.fo_d.p + row * ss;
+    uint32_t* const out = sl.d_out.p;
+    float* const d_pts = (float*)out;
+    uint32_t* const d_mcount = out + URF_SWEEP_HDR_MCOUNT;
+    uint32_t* const d_lcounts = out + URF_SWEEP_HDR_LCOUNTS;
+    uint32_t* const d_road = out + URF_SWEEP_HDR;
+    uint32_t* const d_curb = d_road + n_points;
+    uint32_t* const d_r10 = d_curb + n_points;
+    const dim3 g_ring((unsigned)dp.p.channels, 1), b256(256);
+    const size_t map_lds = (2 * (size_t)a.tiles + 1) * sizeof(unsigned);
+    if (fused)
+        hipLaunchKernelGGL(k_front_out_prep, dim3(a.tiles, 1), b256, 0, st, a, dp, 0u, fo_az, fo_ent, fo_d);
+    if (merged) {
+        hipLaunchKernelGGL(k_sweep_rings, g_ring, b256, map_lds, st, a, dp, urf_ring_outs{ ord_keys, ord_pos, ord_cls, mk_d, mk_pos, mk_red, mk_lit });
+    } else {
+        if (order)
+            hipLaunchKernelGGL(k_ring_order, g_ring, b256, map_lds, st, a, dp, 0u, ord_keys, ord_pos, ord_cls);
+        if (mark)
+            hipLaunchKernelGGL(k_marker_ring, g_ring, b256, map_lds, st, a, dp, 0u, mk_d, mk_pos, mk_red, mk_lit);
+    }
+    if (fused && order)
+        hipLaunchKernelGGL(k_ring_order_front, g_ring, b256, 0, st, a, dp, 0u, fo_az, fo_ent, ord_pos, ord_cls);
+    if (fused && mark)
+        hipLaunchKernelGGL(k_marker_ring_front, g_ring, b256, 0, st, a, dp, 0u, fo_az, fo_ent, fo_d, mk_d, mk_pos, mk_red, mk_lit);
+    if (mark) {   /* rings in which the ORDER of equal azimuths decides a marker point (normally none: every workgroup returns at once) */
+        hipLaunchKernelGGL(k_marker_ring_literal, g_ring, b256, 0, st, a, dp, 0u, mk_lit, mk_d, mk_pos, mk_red);
+        if (fused)
+            hipLaunchKernelGGL(k_marker_ring_literal_front, g_ring, b256, 0, st, a, dp, 0u, mk_lit, fo_az, fo_ent, fo_d, mk_d, mk_pos, mk_red);
+    }
+    if (merged) {
+        hipLaunchKernelGGL(k_sweep_lists, dim3((unsigned)dp.p.channels + 1u, 1), dim3(384), 0, st, a, dp,
+                           urf_sweep_lists_args{ ord_pos, ord_cls, d_road, d_curb, d_r10, d_lcounts, n_points, mk_d, mk_pos, mk_red, d_pts, d_mcount });
+    } else {
+        if (order)
+            hipLaunchKernelGGL(k_ordered_lists, g_ring, b256, 0, st, a, dp, 0u, ord_pos, ord_cls, d_road, d_curb, d_r10, n_points, d_lcounts);
+        if (mark) {
+            hipLaunchKernelGGL(k_marker_bins, dim3(1), dim3(384), 0, st, a, dp, 0u, mk_d, mk_pos, mk_red, d_pts, d_mcount);
+            if (fused)
+                hipLaunchKernelGGL(k_marker_bins_front, dim3(1), dim3(384), 0, st, a, dp, 0u, mk_d, mk_pos, mk_red, d_pts, d_mcount);
+        }
+    }
+    URF_HIP(c, hipGetLastError());
+    URF_HIP(c, hipMemcpyAsync(sl.h_out.p, out, URF_SWEEP_HDR * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (order)
+        URF_HIP(c, hipMemcpyAsync(sl.h_out.p + URF_SWEEP_HDR, d_road, 3 * (size_t)n_points * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return URF_OK;
+}
+
 /* what one sweep of the callback path launches on the compute stream: records -> SoA (unless the message was
  * staged as planes), the pipeline, results to the pinned host buffers */
 static int slot_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t n_points, uint32_t point_step, uint32_t off_x,
@@ -1568,7 +1719,7 @@ static int slot_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t n_points, uint3
     sl.cap_planned = c->planned;
     URF_HIP(c, hipMemcpyAsync(sl.h_labels.p, sl.d_labels.p, n_points, hipMemcpyDeviceToHost, st));
     URF_HIP(c, hipMemcpyAsync(sl.h_info.p, kargs_row(c, row).info, sizeof(urf_scan_info), hipMemcpyDeviceToHost, st));
-    return URF_OK;
+    return sweep_outputs_launch(c, sl, row, st, n_points);   /* (urf_set_sweep_outputs; off: nothing) */
 }
 
 extern "C" int urf_pinned_input(urf_ctx* c, size_t bytes, uint8_t** ptr)
@@ -1692,6 +1843,7 @@ extern "C" int urf_classify_pc2_async(urf_ctx* c, const uint8_t* data, uint32_t 
     sl.off_y = off_y;
     sl.off_z = off_z;
     sl.ticket = c->next_ticket;
+    sl.out_bits = c->pol.sweep_outputs;   /* (it cannot change while the sweep is pending) */
     sl.gen = ++c->row_gen[slot_row(c, sl)];
     *ticket = c->next_ticket++;
     return URF_OK;
@@ -1755,6 +1907,74 @@ extern "C" int urf_result_labels(urf_ctx* c, uint32_t ticket, const uint8_t** la
     if (sl.pending)
         return URF_ERR_BUSY;          /* not waited for yet: the buffer is still being written */
     *labels = sl.h_labels.p;
+    return URF_OK;
+}
+
+/* the ticket's slot for urf_result_marker_points / urf_result_ordered_indices: urf_result_labels' rules, and the sweep was submitted with `bit` */
+static int sweep_result_slot(urf_ctx* c, uint32_t ticket, uint32_t bit, const char* what, const urf_ctx::slot_t*& out)
+{
+    const urf_ctx::slot_t& sl = c->slots[ticket % URF_ASYNC_SLOTS];
+    if (!sl.used || sl.ticket != ticket)
+        return URF_ERR_INVALID_ARG;   /* never issued, or its slot has been used again since */
+    if (sl.pending)
+        return URF_ERR_BUSY;          /* not waited for yet: the buffer is still being written */
+    if (!(sl.out_bits & bit) || !sl.h_out.p) {
+        c->last_error = std::string(what) + ": the sweep was submitted without " +
+                        (bit == URF_SWEEP_OUT_ORDER ? "URF_SWEEP_OUT_ORDER" : "URF_SWEEP_OUT_MARKER_POINTS") + " (urf_set_sweep_outputs)";
+        return URF_ERR_INVALID_ARG;
+    }
+    out = &sl;
+    return URF_OK;
+}
+
+extern "C" int urf_result_marker_points(urf_ctx* c, uint32_t ticket, const float** pts, uint32_t* count)
+{
+    if (!c || !pts || !count)
+        return URF_ERR_INVALID_ARG;
+    *pts = nullptr;
+    *count = 0;
+    const urf_ctx::slot_t* sl = nullptr;
+    const int rc = sweep_result_slot(c, ticket, URF_SWEEP_OUT_MARKER_POINTS, "urf_result_marker_points", sl);
+    if (rc != URF_OK)
+        return rc;
+    *pts = (const float*)sl->h_out.p;
+    if (sl->h_info.p->status != URF_OK)
+        return URF_OK;   /* nothing is published for such a sweep */
+    const uint32_t n = sl->h_out.p[URF_SWEEP_HDR_MCOUNT];
+    if (n > URF_DEG_CELLS)
+        return URF_ERR_HIP;
+    *count = n;
+    return URF_OK;
+}
+
+extern "C" int urf_result_ordered_indices(urf_ctx* c, uint32_t ticket, const uint32_t** road, const uint32_t** curb, const uint32_t** ring10,
+                                          uint32_t counts[3])
+{
+    if (!c || !counts)
+        return URF_ERR_INVALID_ARG;
+    counts[0] = counts[1] = counts[2] = 0;
+    for (const uint32_t** p : { road, curb, ring10 })
+        if (p)
+            *p = nullptr;
+    const urf_ctx::slot_t* sl = nullptr;
+    const int rc = sweep_result_slot(c, ticket, URF_SWEEP_OUT_ORDER, "urf_result_ordered_indices", sl);
+    if (rc != URF_OK)
+        return rc;
+    const uint32_t* lists = sl->h_out.p + URF_SWEEP_HDR;   /* three lists at a stride of the sweep's n_points */
+    if (road)
+        *road = lists;
+    if (curb)
+        *curb = lists + sl->n_points;
+    if (ring10)
+        *ring10 = lists + 2 * (size_t)sl->n_points;
+    if (sl->h_info.p->status != URF_OK)
+        return URF_OK;
+    const uint32_t* h = sl->h_out.p + URF_SWEEP_HDR_LCOUNTS;
+    if (h[0] > sl->n_points || h[1] > sl->n_points || h[2] > sl->n_points)
+        return URF_ERR_HIP;
+    counts[0] = h[0];
+    counts[1] = h[1];
+    counts[2] = h[2];
     return URF_OK;
 }
 

@@ -115,40 +115,83 @@ __global__ __launch_bounds__(URF_COMPACT_THREADS) void k_compact_write(const uin
  * which two points share their azimuth bit for bit is then sorted AGAIN, literally as the
  * reference's Lomuto quicksort does it, whose order of equal azimuths is what gets published
  * (r5).  Rings of up to 2048 points sort in LDS, longer ones in global memory. */
-__global__ __launch_bounds__(256) void k_ring_order(urf_kargs a, urf_dev_params dp, unsigned s0,
-                                                    unsigned long long* gkeys_all, unsigned* rord_all, unsigned* rcls_all)
+/* What the per-ring read-out kernels write, per scan of the launch (blockIdx.y): the published order (sstride keys and entries, the ring's
+ * road / curb counts) and the marker tables (URF_MAX_CHANNELS x URF_DEG_CELLS cells, one literal flag per ring).  A kernel that does not
+ * produce a product leaves its pointers null. */
+struct urf_ring_outs {
+    unsigned long long* gkeys_all;
+    unsigned* rord_all;
+    unsigned* rcls_all;
+    float* m_d_all;
+    unsigned* m_pos_all;
+    uint8_t* m_red_all;
+    uint8_t* m_lit_all;
+};
+
+/* What is published for the ring's points, by position, staged in LDS by the instance that has label and source index of every point in
+ * registers anyway (k_sweep_rings): urf_ring_publish reads it instead of two dependent loads per point. */
+struct urf_ring_staged {
+    const unsigned* ent;
+    __device__ __forceinline__ unsigned at(unsigned i) const { return i; }
+    __device__ __forceinline__ unsigned entry(unsigned i, unsigned& cls) const
+    {
+        const unsigned e = ent[i];
+        cls = e >> 30;
+        return e;
+    }
+};
+
+/* One workgroup (256 threads) per ring of a scan with ring-sorted copies, for either product or both: ORDER, the ring's published order
+ * (k_ring_order); MARK, its two marker tables (k_marker_ring); both, k_sweep_rings -- the ring's run table goes into LDS once, every
+ * point's slot, coordinates, source index, label and exact azimuth are fetched and worked out once.
+ *
+ * The usual ring (at most 2048 points): every point is looked at ONCE -- its slot through the ring's run table in LDS (k_ring's map)
+ * instead of a bisection in global memory, slot records, then labels, eight points per thread in flight at a time -- and azimuth, label
+ * and slot stay in registers for the three marker passes and the sort's keys.  (Pass by pass, with seven dependent loads per point and
+ * the exact azimuth worked out three times, k_marker_ring took longer than the whole classification: 3.9 ms per 1024 sweeps.)  The
+ * marker passes here are the one deliberate specialisation of the rules of urf_marker_passes (urf_k_readouts.hpp): a change there is a
+ * change here.  Longer rings, and for the published order rings with NaN azimuths, take the shared bodies of urf_k_readouts.hpp. */
+template <bool ORDER, bool MARK>
+__device__ __forceinline__ void urf_ring_readout(const urf_kargs& a, const urf_dev_params& dp, unsigned s0, const urf_ring_outs& o)
 {
     constexpr unsigned NT = 256, NB = 2048, EPT = 8, CAP = NT * EPT;
-    __shared__ unsigned long long A[CAP];
-    __shared__ unsigned cnt[URF_BLOCK_CNT(NB, NT)];
+    constexpr bool BOTH = ORDER && MARK;
+    __shared__ unsigned long long A[ORDER ? CAP : 1];
+    __shared__ unsigned cnt[ORDER ? URF_BLOCK_CNT(NB, NT) : 1];
     __shared__ urf_sort_shared ssh;
     __shared__ unsigned ncls[2], sh_tie;
-    __shared__ int lom_stk[2 * 64];
-    extern __shared__ unsigned sh_ord_tab[];   /* P[tiles + 1], radd[tiles] (urf_ring_map) */
+    __shared__ int lom_stk[ORDER ? 2 * 64 : 1];
+    __shared__ urf_marker_tabs T;
+    __shared__ unsigned need_lit;   /* the ring's order decides (k_marker_ring_literal) */
+    __shared__ unsigned staged[BOTH ? CAP : 1];
+    extern __shared__ unsigned sh_ring_tab[];   /* P[tiles + 1], radd[tiles] (urf_ring_map) */
     const unsigned c = blockIdx.x, s = s0 + blockIdx.y, tid = threadIdx.x;
-    unsigned long long* gkeys = gkeys_all + (size_t)blockIdx.y * a.sstride;   /* per scan of the launch: sstride entries */
-    unsigned* rord = rord_all + (size_t)blockIdx.y * a.sstride;
-    unsigned* rcls = rcls_all + ((size_t)blockIdx.y * URF_MAX_CHANNELS + c) * 2;   /* road / curb points of the ring */
+    const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;   /* per scan of the launch */
+    unsigned* const rcls = ORDER ? o.rcls_all + ((size_t)blockIdx.y * URF_MAX_CHANNELS + c) * 2 : nullptr;   /* road / curb points of the ring */
+    uint8_t* const m_lit = MARK ? o.m_lit_all + (size_t)blockIdx.y * URF_MAX_CHANNELS + c : nullptr;
     const urf_scan_info in = a.info[s];
     if (urf_scan_fused(a, s, in))
-        return;   /* (uniform) k_ring_order_front's */
+        return;   /* (uniform) k_ring_order_front's, k_marker_ring_front's */
     if (in.status != URF_OK || c >= in.n_rings) {
-        if (tid < 2)
+        if (ORDER && tid < 2)
             rcls[tid] = 0;
+        if (MARK && tid == 0)
+            *m_lit = 0;
         return;
     }
     unsigned off, len;
     urf_scan_range(a, s, off, len);
     const unsigned C = (unsigned)dp.p.channels;
     const unsigned n = a.ring_cnt[(size_t)s * C + c];
-    const unsigned rel = a.ring_off[(size_t)s * (C + 1) + c];   /* scan-relative start of the ring */
+    const unsigned rel = ORDER ? a.ring_off[(size_t)s * (C + 1) + c] : 0u;   /* scan-relative start of the ring */
     const unsigned sb = urf_sbase(a, s);
     const unsigned ntiles = (len + URF_TILE - 1) / URF_TILE;
-    /* the ring's run table in LDS (k_ring's map): position in the ring -> ring-sorted slot without a
-     * bisection in global memory */
-    unsigned* const mapP = sh_ord_tab;
-    unsigned* const mapA = sh_ord_tab + a.tiles + 1;
-    {
+    const bool in_lds = n <= CAP;
+    /* the ring's run table in LDS (k_ring's map): position in the ring -> ring-sorted slot without a bisection in global memory
+     * (k_marker_ring alone keeps that bisection for its long rings) */
+    unsigned* const mapP = sh_ring_tab;
+    unsigned* const mapA = sh_ring_tab + a.tiles + 1;
+    if (ORDER || in_lds) {
         const unsigned* gp = a.rpre + ((size_t)s * C + c) * (a.tiles + 1);
         const uint16_t* gs = a.rstart + ((size_t)s * C + c) * a.tiles;
         for (unsigned t = tid; t <= ntiles; t += NT) {
@@ -158,52 +201,147 @@ __global__ __launch_bounds__(256) void k_ring_order(urf_kargs a, urf_dev_params 
                 mapA[t] = t * URF_TILE + gs[t] - pt;   /* relative to the scan's scratch base */
         }
     }
-    if (tid < 2)
-        ncls[tid] = 0;
-    if (tid == 0)
-        sh_tie = 0;
+    if constexpr (ORDER) {
+        if (tid < 2)
+            ncls[tid] = 0;
+        if (tid == 0)
+            sh_tie = 0;
+    }
+    if constexpr (MARK) {
+        T.init(tid);
+        if (tid == 0)
+            need_lit = 0;
+    }
     __syncthreads();
     const urf_ring_map map = { mapP, mapA, ntiles, (float)ntiles / (float)(n > 0 ? n : 1) };
     const urf_ring_sorted v = { a, s, C, c, ntiles, sb, off, &map };
     /* bit-equal azimuths (urf_ring_literal_order): the keys go back into bucket order in the ring's stretch of wsg */
     volatile unsigned long long* const LIT = (volatile unsigned long long*)(a.wsg + sb + rel);
+    /* (uniform) a ring with NaN azimuths: k_nan_rings ran the reference's quicksort literally and left the ring in its final order --
+     * where a NaN lands is no function of the azimuths */
+    const bool nan_ring = ORDER && ((a.nan_mask[(size_t)s * 4 + (c >> 5)] >> (c & 31u)) & 1u) != 0u;
     unsigned my_road = 0, my_curb = 0;
-    if ((a.nan_mask[(size_t)s * 4 + (c >> 5)] >> (c & 31u)) & 1u) {
-        /* (uniform) a ring with NaN azimuths: k_nan_rings ran the reference's quicksort literally and left the ring in
-         * its final order -- where a NaN lands is no function of the azimuths */
-        for (unsigned j = tid; j < n; j += NT)
-            urf_ring_publish(v, a.ssrt[sb + rel + j], &rord[rel + j], my_road, my_curb);
-    } else if (n <= CAP) {
-        unsigned long long key[EPT];
-        unsigned slot[EPT];
-        float px[EPT], py[EPT];
+    if (in_lds && !nan_ring) {
+        unsigned slot[EPT], sr[EPT];
+        float az[EPT], px[EPT], py[EPT];
 #pragma unroll
         for (unsigned e = 0; e < EPT; e++) {   /* coordinates of the thread's eight points in flight together */
-            const unsigned i = tid + e * NT;
-            slot[e] = i < n ? map.at(i) : 0u;
+            const unsigned p = tid + e * NT;
+            slot[e] = p < n ? map.at(p) : 0u;
+            if constexpr (MARK)
+                sr[e] = a.rec[sb + slot[e]] & URF_REC_SRC_MASK;
             px[e] = a.rx[sb + slot[e]];
             py[e] = a.ry[sb + slot[e]];
         }
+        unsigned labs = 0;   /* two bits per point */
+        if constexpr (MARK) {
 #pragma unroll
-        for (unsigned e = 0; e < EPT; e++) {
-            const unsigned i = tid + e * NT;
-            key[e] = ~0ull;
-            if (i < n) {
-                float d2;   /* the slot's record holds an approximation: the published order is that of the exact azimuth */
-                key[e] = ((unsigned long long)urf_fbits(urf_azimuth(px[e], py[e], &d2)) << 32) | i;
+            for (unsigned e = 0; e < EPT; e++) {
+                const unsigned src = (slot[e] & ~(URF_TILE - 1u)) + sr[e];
+                const unsigned lab = a.labels[off + src] & URF_LABEL_MASK;
+                labs |= lab << (2 * e);
+                if (BOTH && tid + e * NT < n)
+                    staged[tid + e * NT] = src | (lab << 30);   /* (urf_ring_sorted::entry) */
             }
         }
-        urf_block_sort_keys<NT, EPT, NB>(key, n, A, cnt, &ssh, false);
-        const bool lit = urf_ring_literal_order<NT>(v, n, A, LIT, &sh_tie, lom_stk, tid);
 #pragma unroll
-        for (unsigned e = 0; e < EPT; e++) {
-            const unsigned j = tid + e * NT;
-            if (j < n)
-                urf_ring_publish(v, lit ? (unsigned)LIT[j] : (unsigned)A[j], &rord[rel + j], my_road, my_curb);
+        for (unsigned e = 0; e < EPT; e++) {   /* (the slot's record holds an approximation of the azimuth: the published order and the tables are those of the exact one) */
+            float d2;
+            az[e] = urf_azimuth(px[e], py[e], &d2);
         }
-    } else
-        urf_ring_order_long<NT>(v, n, gkeys + rel, LIT, &sh_tie, lom_stk, rord + rel, my_road, my_curb, tid);
-    urf_ring_publish_counts(my_road, my_curb, ncls, rcls, tid);
+        if constexpr (MARK) {
+            /* pass 1: where does the scan of this ring stop in each degree (:318) */
+            int bin[EPT];
+#pragma unroll
+            for (unsigned e = 0; e < EPT; e++) {
+                bin[e] = urf_deg_bin(az[e]);
+                if (tid + e * NT < n && az[e] == az[e] && ((labs >> (2 * e)) & 3u) != URF_LABEL_ROAD)
+                    atomicMin(&T.nrmin[bin[e]], (int)urf_fbits(az[e]));
+            }
+            __syncthreads();
+            /* pass 2: farthest road point in front of it (:325-335); key = (d, first in azimuth order) */
+            unsigned long long mkey[EPT];
+#pragma unroll
+            for (unsigned e = 0; e < EPT; e++) {
+                mkey[e] = 0;
+                const bool road = tid + e * NT < n && az[e] == az[e] && ((labs >> (2 * e)) & 3u) == URF_LABEL_ROAD;
+                if (road && (int)urf_fbits(az[e]) == T.nrmin[bin[e]])
+                    need_lit = 1u;   /* the very azimuth of the degree's first non-road point: in front of it or behind? */
+                if (road && (int)urf_fbits(az[e]) < T.nrmin[bin[e]]) {
+                    const float x = px[e], y = py[e];
+                    const float d = (float)__builtin_sqrt((double)(0.f - x) * (double)(0.f - x) + (double)(0.f - y) * (double)(0.f - y));
+                    if (d > 0.0f) {   /* "d > maxDistanceRoad" with maxDistanceRoad starting at 0 */
+                        mkey[e] = ((unsigned long long)urf_fbits(d) << 32) | (0xffffffffu - urf_fbits(az[e]));
+                        atomicMax(&T.best[bin[e]], mkey[e]);
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (unsigned e = 0; e < EPT; e++)
+                if (mkey[e] != 0 && mkey[e] == T.best[bin[e]])
+                    if (atomicMin(&T.bestpos[bin[e]], tid + e * NT) != 0xffffffffu)
+                        need_lit = 1u;   /* two road points with this distance AND azimuth: which comes first? */
+            __syncthreads();
+            if (tid == 0)
+                *m_lit = (uint8_t)need_lit;
+            T.store(v, c, o.m_d_all + blockIdx.y * cells, o.m_pos_all + blockIdx.y * cells, o.m_red_all + blockIdx.y * cells, tid);
+        }
+        if constexpr (ORDER) {
+            unsigned* const rord = o.rord_all + (size_t)blockIdx.y * a.sstride;   /* per scan of the launch: sstride entries */
+            unsigned long long key[EPT];
+#pragma unroll
+            for (unsigned e = 0; e < EPT; e++) {
+                const unsigned i = tid + e * NT;
+                key[e] = i < n ? ((unsigned long long)urf_fbits(az[e]) << 32) | i : ~0ull;
+            }
+            urf_block_sort_keys<NT, EPT, NB>(key, n, A, cnt, &ssh, false);
+            const bool lit = urf_ring_literal_order<NT>(v, n, A, LIT, &sh_tie, lom_stk, tid);
+#pragma unroll
+            for (unsigned e = 0; e < EPT; e++) {
+                const unsigned j = tid + e * NT;
+                if (j < n) {
+                    const unsigned pos = lit ? (unsigned)LIT[j] : (unsigned)A[j];
+                    if constexpr (BOTH)
+                        urf_ring_publish(urf_ring_staged{ staged }, pos, &rord[rel + j], my_road, my_curb);
+                    else
+                        urf_ring_publish(v, pos, &rord[rel + j], my_road, my_curb);
+                }
+            }
+        }
+    } else {
+        if constexpr (ORDER) {
+            unsigned long long* const gkeys = o.gkeys_all + (size_t)blockIdx.y * a.sstride;
+            unsigned* const rord = o.rord_all + (size_t)blockIdx.y * a.sstride;
+            if (nan_ring) {
+                for (unsigned j = tid; j < n; j += NT)
+                    urf_ring_publish(v, a.ssrt[sb + rel + j], &rord[rel + j], my_road, my_curb);
+            } else
+                urf_ring_order_long<NT>(v, n, gkeys + rel, LIT, &sh_tie, lom_stk, rord + rel, my_road, my_curb, tid);
+        }
+        if constexpr (MARK) {
+            if constexpr (ORDER) {
+                urf_marker_passes(v, n, T, &need_lit, tid);
+                if (tid == 0)
+                    *m_lit = (uint8_t)need_lit;
+                T.store(v, c, o.m_d_all + blockIdx.y * cells, o.m_pos_all + blockIdx.y * cells, o.m_red_all + blockIdx.y * cells, tid);
+            } else {
+                const urf_ring_sorted vg = { a, s, C, c, ntiles, sb, off, nullptr };
+                urf_marker_passes(vg, n, T, &need_lit, tid);
+                if (tid == 0)
+                    *m_lit = (uint8_t)need_lit;
+                T.store(vg, c, o.m_d_all + blockIdx.y * cells, o.m_pos_all + blockIdx.y * cells, o.m_red_all + blockIdx.y * cells, tid);
+            }
+        }
+    }
+    if constexpr (ORDER)
+        urf_ring_publish_counts(my_road, my_curb, ncls, rcls, tid);
+}
+
+__global__ __launch_bounds__(256) void k_ring_order(urf_kargs a, urf_dev_params dp, unsigned s0,
+                                                    unsigned long long* gkeys_all, unsigned* rord_all, unsigned* rcls_all)
+{
+    urf_ring_readout<true, false>(a, dp, s0, urf_ring_outs{ gkeys_all, rord_all, rcls_all, nullptr, nullptr, nullptr, nullptr });
 }
 
 /* The lists of one scan = its rings in order, every ring in azimuth order (k_ring_order left, per ring
@@ -211,9 +349,10 @@ __global__ __launch_bounds__(256) void k_ring_order(urf_kargs a, urf_dev_params 
  * (ring, scan) finds where its ring starts in each list (the counts of the rings in front of it) and
  * appends its points in order -- ballot + prefix per 256 entries.  (One workgroup per SCAN walking all
  * ring points with three barriers per 1024 of them took 1.5 ms per 1024 sweeps.) */
-__global__ __launch_bounds__(256) void k_ordered_lists(urf_kargs a, urf_dev_params dp, unsigned s0, const unsigned* rord_all,
-                                                       const unsigned* rcls_all, unsigned* road_all, unsigned* curb_all,
-                                                       unsigned* ring10_all, unsigned stride, unsigned* counts_all)
+template <unsigned NT>   /* threads of the workgroup */
+__device__ __forceinline__ void urf_ordered_lists(const urf_kargs& a, const urf_dev_params& dp, unsigned s0, const unsigned* rord_all,
+                                                  const unsigned* rcls_all, unsigned* road_all, unsigned* curb_all, unsigned* ring10_all,
+                                                  unsigned stride, unsigned* counts_all)
 {
     const unsigned c = blockIdx.x, s = s0 + blockIdx.y;
     const unsigned* rord = rord_all + (size_t)blockIdx.y * a.sstride;
@@ -222,7 +361,7 @@ __global__ __launch_bounds__(256) void k_ordered_lists(urf_kargs a, urf_dev_para
     unsigned* curb = curb_all ? curb_all + (size_t)blockIdx.y * stride : nullptr;
     unsigned* ring10 = ring10_all ? ring10_all + (size_t)blockIdx.y * stride : nullptr;
     unsigned* counts = counts_all + (size_t)blockIdx.y * 3;
-    __shared__ unsigned wsum[2][4];
+    __shared__ unsigned wsum[2][NT / 64];
     __shared__ unsigned base[2];
     const unsigned tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const urf_scan_info in = a.info[s];
@@ -244,7 +383,7 @@ __global__ __launch_bounds__(256) void k_ordered_lists(urf_kargs a, urf_dev_para
     unsigned run0 = base[0], run1 = base[1];
     const unsigned n = a.ring_cnt[(size_t)s * C + c];
     const unsigned rel = a.ring_off[(size_t)s * (C + 1) + c];
-    for (unsigned j0 = 0; j0 < n; j0 += 256) {
+    for (unsigned j0 = 0; j0 < n; j0 += NT) {
         const unsigned j = j0 + tid;
         const unsigned ent = j < n ? rord[rel + j] : 0u;
         const unsigned src = ent & 0x3fffffffu, cls = j < n ? ent >> 30 : 0u;
@@ -256,7 +395,7 @@ __global__ __launch_bounds__(256) void k_ordered_lists(urf_kargs a, urf_dev_para
         __syncthreads();
         unsigned p0 = run0 + urf_popc_below(m0), p1 = run1 + urf_popc_below(m1);
 #pragma unroll
-        for (unsigned w = 0; w < 4; w++) {
+        for (unsigned w = 0; w < NT / 64; w++) {
             p0 += w < wave ? wsum[0][w] : 0u;
             p1 += w < wave ? wsum[1][w] : 0u;
             run0 += wsum[0][w];
@@ -281,6 +420,12 @@ __global__ __launch_bounds__(256) void k_ordered_lists(urf_kargs a, urf_dev_para
             counts[2] = n;
     }
 }
+__global__ __launch_bounds__(256) void k_ordered_lists(urf_kargs a, urf_dev_params dp, unsigned s0, const unsigned* rord_all,
+                                                       const unsigned* rcls_all, unsigned* road_all, unsigned* curb_all,
+                                                       unsigned* ring10_all, unsigned stride, unsigned* counts_all)
+{
+    urf_ordered_lists<256>(a, dp, s0, rord_all, rcls_all, road_all, curb_all, ring10_all, stride, counts_all);
+}
 
 /* ------------------------------------------------------------------------- */
 /* road_marker: marker points                                                  */
@@ -294,119 +439,14 @@ __global__ __launch_bounds__(256) void k_ordered_lists(urf_kargs a, urf_dev_para
 __global__ __launch_bounds__(256) void k_marker_ring(urf_kargs a, urf_dev_params dp, unsigned s0,
                                                      float* m_d_all, unsigned* m_pos_all, uint8_t* m_red_all, uint8_t* m_lit_all)
 {
-    __shared__ urf_marker_tabs T;
-    __shared__ unsigned need_lit;   /* the ring's order decides (k_marker_ring_literal) */
-    const unsigned c = blockIdx.x, s = s0 + blockIdx.y, tid = threadIdx.x;
-    const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;   /* per scan of the launch */
-    float* m_d = m_d_all + blockIdx.y * cells;
-    unsigned* m_pos = m_pos_all + blockIdx.y * cells;
-    uint8_t* m_red = m_red_all + blockIdx.y * cells;
-    const urf_scan_info in = a.info[s];
-    if (urf_scan_fused(a, s, in))
-        return;   /* (uniform) k_marker_ring_front's */
-    if (in.status != URF_OK || c >= in.n_rings) {
-        if (tid == 0)
-            m_lit_all[(size_t)blockIdx.y * URF_MAX_CHANNELS + c] = 0;
-        return;
-    }
-    unsigned off, len;
-    urf_scan_range(a, s, off, len);
-    const unsigned C = (unsigned)dp.p.channels;
-    const unsigned n = a.ring_cnt[(size_t)s * C + c];
-    const unsigned sb = urf_sbase(a, s);
-    const unsigned ntiles = (len + URF_TILE - 1) / URF_TILE;
-    T.init(tid);
-    if (tid == 0)
-        need_lit = 0;
-    constexpr unsigned EPT = 8;
-    if (n <= 256 * EPT) {
-        /* The usual ring (at most 2048 points): every point is looked at ONCE -- its slot through the
-         * ring's run table in LDS (k_ring's map) instead of a bisection in global memory, slot records,
-         * then labels, eight points per thread in flight at a time -- and azimuth, label and slot stay
-         * in registers for the three passes.  (Pass by pass, with seven dependent loads per point and
-         * the exact azimuth worked out three times, this kernel took longer than the whole
-         * classification: 3.9 ms per 1024 sweeps.)  The one deliberate specialisation of the rules of
-         * urf_marker_passes (urf_k_readouts.hpp): a change there is a change here. */
-        extern __shared__ unsigned sh_mark_tab[];   /* P[tiles + 1], radd[tiles] (urf_ring_map) */
-        unsigned* const mapP = sh_mark_tab;
-        unsigned* const mapA = sh_mark_tab + a.tiles + 1;
-        {
-            const unsigned* gp = a.rpre + ((size_t)s * C + c) * (a.tiles + 1);
-            const uint16_t* gs = a.rstart + ((size_t)s * C + c) * a.tiles;
-            for (unsigned t = tid; t <= ntiles; t += 256) {
-                const unsigned pt = gp[t];
-                mapP[t] = pt;
-                if (t < ntiles)
-                    mapA[t] = t * URF_TILE + gs[t] - pt;   /* relative to the scan's scratch base */
-            }
-        }
-        __syncthreads();
-        const urf_ring_map map = { mapP, mapA, ntiles, (float)ntiles / (float)(n > 0 ? n : 1) };
-        unsigned slot[EPT], sr[EPT];
-        float az[EPT], px[EPT], py[EPT];
-#pragma unroll
-        for (unsigned e = 0; e < EPT; e++) {
-            const unsigned p = tid + e * 256;
-            slot[e] = p < n ? map.at(p) : 0u;
-            sr[e] = a.rec[sb + slot[e]] & URF_REC_SRC_MASK;
-            px[e] = a.rx[sb + slot[e]];
-            py[e] = a.ry[sb + slot[e]];
-        }
-        unsigned labs = 0;   /* two bits per point */
-#pragma unroll
-        for (unsigned e = 0; e < EPT; e++) {
-            const unsigned lab = a.labels[off + (slot[e] & ~(URF_TILE - 1u)) + sr[e]] & URF_LABEL_MASK;
-            labs |= lab << (2 * e);
-        }
-#pragma unroll
-        for (unsigned e = 0; e < EPT; e++) {   /* (the slot's record holds an approximation of the azimuth) */
-            float d2;
-            az[e] = urf_azimuth(px[e], py[e], &d2);
-        }
-        /* pass 1: where does the scan of this ring stop in each degree (:318) */
-        int bin[EPT];
-#pragma unroll
-        for (unsigned e = 0; e < EPT; e++) {
-            bin[e] = urf_deg_bin(az[e]);
-            if (tid + e * 256 < n && az[e] == az[e] && ((labs >> (2 * e)) & 3u) != URF_LABEL_ROAD)
-                atomicMin(&T.nrmin[bin[e]], (int)urf_fbits(az[e]));
-        }
-        __syncthreads();
-        /* pass 2: farthest road point in front of it (:325-335); key = (d, first in azimuth order) */
-        unsigned long long key[EPT];
-#pragma unroll
-        for (unsigned e = 0; e < EPT; e++) {
-            key[e] = 0;
-            const bool road = tid + e * 256 < n && az[e] == az[e] && ((labs >> (2 * e)) & 3u) == URF_LABEL_ROAD;
-            if (road && (int)urf_fbits(az[e]) == T.nrmin[bin[e]])
-                need_lit = 1u;   /* the very azimuth of the degree's first non-road point: in front of it or behind? */
-            if (road && (int)urf_fbits(az[e]) < T.nrmin[bin[e]]) {
-                const float x = px[e], y = py[e];
-                const float d = (float)__builtin_sqrt((double)(0.f - x) * (double)(0.f - x) + (double)(0.f - y) * (double)(0.f - y));
-                if (d > 0.0f) {   /* "d > maxDistanceRoad" with maxDistanceRoad starting at 0 */
-                    key[e] = ((unsigned long long)urf_fbits(d) << 32) | (0xffffffffu - urf_fbits(az[e]));
-                    atomicMax(&T.best[bin[e]], key[e]);
-                }
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (unsigned e = 0; e < EPT; e++)
-            if (key[e] != 0 && key[e] == T.best[bin[e]])
-                if (atomicMin(&T.bestpos[bin[e]], tid + e * 256) != 0xffffffffu)
-                    need_lit = 1u;   /* two road points with this distance AND azimuth: which comes first? */
-        __syncthreads();
-        if (tid == 0)
-            m_lit_all[(size_t)blockIdx.y * URF_MAX_CHANNELS + c] = (uint8_t)need_lit;
-        T.store(urf_ring_sorted{ a, s, C, c, ntiles, sb, off, &map }, c, m_d, m_pos, m_red, tid);
-        return;
-    }
-    __syncthreads();
-    const urf_ring_sorted v = { a, s, C, c, ntiles, sb, off, nullptr };
-    urf_marker_passes(v, n, T, &need_lit, tid);
-    if (tid == 0)
-        m_lit_all[(size_t)blockIdx.y * URF_MAX_CHANNELS + c] = (uint8_t)need_lit;
-    T.store(v, c, m_d, m_pos, m_red, tid);
+    urf_ring_readout<false, true>(a, dp, s0, urf_ring_outs{ nullptr, nullptr, nullptr, m_d_all, m_pos_all, m_red_all, m_lit_all });
+}
+
+/* Both products of a sweep of the callback path in one launch (urf_set_sweep_outputs with both bits): grid (channels, 1).  k_marker_ring_literal
+ * follows it as it follows k_marker_ring. */
+__global__ __launch_bounds__(256) void k_sweep_rings(urf_kargs a, urf_dev_params dp, urf_ring_outs o)
+{
+    urf_ring_readout<true, true>(a, dp, 0u, o);
 }
 
 /* The same tables when the ring's ORDER decides (urf_marker_literal).  k_marker_ring flags such a ring (m_lit); this kernel, launched
@@ -446,6 +486,35 @@ __global__ __launch_bounds__(384) void k_marker_bins(urf_kargs a, urf_dev_params
     urf_marker_bins<urf_ring_sorted>(a, 0u, in.status == URF_OK ? in.n_rings : 0, m_d_all + blockIdx.x * cells, m_pos_all + blockIdx.x * cells,
                                      m_red_all + blockIdx.x * cells, out_all + (size_t)blockIdx.x * URF_DEG_CELLS * 4, count_all + blockIdx.x,
                                      wsum);
+}
+
+/* k_ordered_lists and k_marker_bins depend on nothing of each other: for ONE sweep of the callback path (urf_set_sweep_outputs with both
+ * bits) they are one launch, grid (channels + 1, 1) x 384 threads -- workgroups 0 .. channels - 1 append their ring to the lists,
+ * workgroup `channels` walks the rings' marker tables per degree, for a scan of either kind (urf_scan_fused: k_marker_bins_front's view). */
+struct urf_sweep_lists_args {
+    const unsigned *rord, *rcls;
+    unsigned *road, *curb, *ring10, *list_counts;   /* lists of `stride` entries, 3 counts */
+    unsigned stride;
+    const float* m_d;
+    const unsigned* m_pos;
+    const uint8_t* m_red;
+    float* pts;            /* URF_DEG_CELLS x 4 */
+    unsigned* pts_count;
+};
+__global__ __launch_bounds__(384) void k_sweep_lists(urf_kargs a, urf_dev_params dp, urf_sweep_lists_args o)
+{
+    if (blockIdx.x < (unsigned)dp.p.channels) {   /* (uniform) */
+        urf_ordered_lists<384>(a, dp, 0u, o.rord, o.rcls, o.road, o.curb, o.ring10, o.stride, o.list_counts);
+        return;
+    }
+    __shared__ unsigned wsum[6];
+    const urf_scan_info in = a.info[0];
+    if (urf_scan_fused(a, 0u, in)) {
+        unsigned off, len;
+        urf_scan_range(a, 0u, off, len);
+        urf_marker_bins<urf_ring_fused>(a, off, in.n_rings, o.m_d, o.m_pos, o.m_red, o.pts, o.pts_count, wsum);
+    } else
+        urf_marker_bins<urf_ring_sorted>(a, 0u, in.status == URF_OK ? in.n_rings : 0, o.m_d, o.m_pos, o.m_red, o.pts, o.pts_count, wsum);
 }
 
 #ifdef URF_ENABLE_TEST_HOOKS   /* liburf_hip_test.so only (include/urf_test_hooks.h) */

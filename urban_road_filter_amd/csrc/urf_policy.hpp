@@ -83,6 +83,9 @@ struct __attribute__((visibility("hidden"))) urf_policy {
      * (urf_k_front_outputs.hpp) instead of a second run through the general kernels.  Decides no launch of a classify call: not part of
      * the epoch. */
     bool front_outputs = false;
+    /* urf_set_sweep_outputs (URF_SWEEP_OUT_*): a sweep's captured sequence also produces its marker points and / or ordered lists.  Part
+     * of the epoch -- the slots capture again -- but not read by plan(): it decides no launch of the classification. */
+    uint32_t sweep_outputs = 0;
     /* k_front hands a scan without the shape back to the general kernels: launched list-driven until a call has done so
      * (URF_FLAG_FRONT_HANDED_BACK: front_direct, full grids from then on); mode 1 stops trying once a whole batch has been handed back
      * (URF_FLAG_FRONT_ALL_HANDED_BACK: front_off, unorganised clouds).  forget_front() starts over. */
