@@ -75,7 +75,9 @@ extern "C" {
  * (the reference-order read-outs after a dense call, in the caller's indices); urf_set_dense_elevations with
  * urf_classify_batch_soa_dense_elev / urf_classify_batch_pc2_dense_elev (the dense calls for clouds without a `ring` field: laser ids
  * derived from the points' elevation on the device); urf_set_sweep_outputs with urf_result_marker_points / urf_result_ordered_indices
- * and URF_SWEEP_OUT_* (a sweep of the callback path brings its marker points and ordered lists along, read per ticket).
+ * and URF_SWEEP_OUT_* (a sweep of the callback path brings its marker points and ordered lists along, read per ticket);
+ * urf_set_sweep_quantum with urf_callback_path_captures and URF_SWEEP_SEQS (sweeps of varying length on the callback path: padded to a
+ * quantum of points, one captured sequence per padded length).
  * WHICH std::sort (4 above): the one of libstdc++ as shipped with GCC 5 .. 13 (bits/stl_algo.h: __sort = __introsort_loop with
  * _S_threshold 16, __move_median_to_first on (first + 1, mid, last - 1), __unguarded_partition, depth limit 2 * floor(log2 n),
  * __partial_sort as the fallback, then __final_insertion_sort); tests/test_stdsort.py pins the restatement against the std::sort
@@ -315,6 +317,37 @@ int urf_set_sweep_outputs(urf_ctx* ctx, uint32_t bits);
 int urf_result_marker_points(urf_ctx* ctx, uint32_t ticket, const float** pts, uint32_t* count);
 int urf_result_ordered_indices(urf_ctx* ctx, uint32_t ticket, const uint32_t** road, const uint32_t** curb,
                                const uint32_t** ring10, uint32_t counts[3]);
+
+/* One captured sequence for sweeps of varying length (opt-in; additive under ABI 5).  The sequence a slot replays is keyed by the
+ * sweep's number of points: a stream whose sweeps differ in length -- velodyne_pointcloud's default mode, any is_dense cloud, anything a
+ * driver-side filter has touched -- captures and instantiates a sequence per sweep.  The reference drops non-finite points before
+ * anything else (lidar_segmentation.cpp:100-117) and never looks at an input index, so (NaN, NaN, NaN) points behind a sweep change no
+ * label and no summary: with a quantum set, a sweep of n points on the callback path (urf_classify_pc2_async and urf_classify_pc2) runs
+ * as n' points, n' the next multiple of the quantum, the last n' - n of them NaN, and every sweep of that n' replays one sequence.
+ *   urf_set_sweep_quantum   points: 0 (default) = off, every call launches, copies and captures what it does without the switch; else a
+ *                           multiple of 2048 (a tile) and at most the context's max_points, anything else URF_ERR_INVALID_ARG.
+ *                           URF_ERR_BUSY while a sweep is in flight; URF_ERR_OOM leaves the switch as it was.  A change forgets every
+ *                           captured sequence.  A sweep whose n' exceeds max_points runs unpadded under its own key, as without the
+ *                           switch.  Each slot keeps up to URF_SWEEP_SEQS sequences, the least recently used one making room for a
+ *                           ninth; whatever invalidates a sequence (parameters, settings, a larger message buffer) drops all of them.
+ *                           (8 is a design constant, not a measurement: a sensor's dense sweeps differ by a few tiles, and a larger
+ *                           quantum is the caller's lever.)  Off: one sequence per slot.
+ * A staged message gets its pad from the host, into the pinned planes; a message a producer wrote into urf_pinned_input's buffer is
+ * gathered by a kernel that reads the sweep's own length from a device word of the slot and stores NaN behind it -- the bytes of the
+ * pinned buffer behind the n records are never read.  A slot's message buffers grow to the largest message seen, and a new buffer
+ * forgets the slot's sequences: with a quantum set they grow to twice the padded length at once (at most max_points), and a producer
+ * asks urf_pinned_input for its largest message, not for each one's size.
+ * Everything the caller sees is in terms of its own n: urf_classify_pc2_wait copies n label bytes, urf_result_labels promises n bytes,
+ * urf_result_ordered_indices and urf_result_marker_points name only indices < n (a NaN point lies on no ring and in no cloud), and
+ * urf_read_stage, urf_ordered_indices, urf_marker_points, urf_compact_indices and urf_front_explain after such a sweep accept the byte
+ * counts and capacities they accept for the unpadded sweep and answer for its n points.  A sweep the short sequence voided is run again
+ * inside urf_classify_pc2_wait as the padded sweep it was.
+ *   urf_callback_path_captures   *n_captured = launch sequences captured so far over all slots, for any cause, switch on or off;
+ *                           *n_resident = the sequences a sweep submitted now could replay (those of an earlier epoch are released by
+ *                           their slot's next submission and not counted).  Either pointer may be NULL. */
+#define URF_SWEEP_SEQS 8
+int urf_set_sweep_quantum(urf_ctx* ctx, uint32_t points);
+int urf_callback_path_captures(const urf_ctx* ctx, uint32_t* n_captured, uint32_t* n_resident);
 
 /* ---- batch of scans, device-resident ---------------------------------------
  * n_scans independent scans of n_per_scan points each; scan s owns elements

@@ -209,6 +209,8 @@ def lib(hooks=False):
         "urf_set_sweep_outputs": [vp, C.c_uint32],
         "urf_result_marker_points": [vp, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)],
         "urf_result_ordered_indices": [vp, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u32p],
+        "urf_set_sweep_quantum": [vp, C.c_uint32],
+        "urf_callback_path_captures": [vp, u32p, u32p],
         "urf_test_dense_ids": [vp, u8p, C.c_uint64],
         "urf_test_dense_ids_ms": [vp, C.c_uint32, C.POINTER(C.c_float)],
     }
@@ -541,6 +543,19 @@ class Context:
         on any max_batch); 0 (default) off.  Allocates what the sequences need (UrfError -5 comes from here); -6 while a sweep is in
         flight (include/urf.h)."""
         self._check(self._lib.urf_set_sweep_outputs(self._h, int(bits)), "urf_set_sweep_outputs")
+
+    def set_sweep_quantum(self, points):
+        """urf_set_sweep_quantum: a sweep of the callback path runs as the next multiple of `points` points (a multiple of 2048, at most
+        max_points), NaN behind its own, so that sweeps of varying length replay one captured sequence per padded length; 0 (default)
+        off.  Results are in terms of the caller's points.  UrfError -1 for another value, -6 while a sweep is in flight
+        (include/urf.h)."""
+        self._check(self._lib.urf_set_sweep_quantum(self._h, int(points)), "urf_set_sweep_quantum")
+
+    def callback_path_captures(self):
+        """urf_callback_path_captures: (launch sequences captured so far over all slots, sequences held now)."""
+        n, r = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.urf_callback_path_captures(self._h, C.byref(n), C.byref(r)), "urf_callback_path_captures")
+        return n.value, r.value
 
     def result_marker_points(self, ticket):
         """The marker points of a ticket that has been waited for, float32 [k, 4] = x, y, z, red (a copy of the slot's pinned buffer)."""

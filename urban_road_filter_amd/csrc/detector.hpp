@@ -208,6 +208,11 @@ public:
         applySweepOutputs(on, marker_on_, reference_order_);
         sweep_outputs_ = on;
     }
+    /* urf_set_sweep_quantum: for streams whose messages differ in length (velodyne_pointcloud's default mode, any is_dense cloud).  A
+     * sweep runs as the next multiple of `points` points (a multiple of 2048, at most max_points), NaN behind its own, so that one
+     * captured launch sequence per padded length is replayed instead of a new one per message; clouds, labels and MarkerArray are the
+     * same byte for byte.  0 (default): off.  Between sweeps only: with a sweep in flight it throws Error(URF_ERR_BUSY). */
+    void setSweepQuantum(uint32_t points);
     void setMarkerParams(const urf_marker_params& p) { marker_.setParams(p); }
     /* nullptr when the reference would not publish a MarkerArray for the last sweep */
     const MarkerArray* road_marker() const { return marker_published_ ? &markers_ : nullptr; }

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <limits>
 #include <string>
 #include <vector>
 #if defined(__SSE2__)
@@ -165,6 +166,7 @@ struct urf_last_call {
     uint32_t row = 0;               /* the scratch row of a.* (a batch call: 0) */
     uint64_t gen = 0;               /* a sweep: the row's submission number it was (urf_ctx::row_gen) */
     urf_planned planned;            /* what the policy said about the call when it planned it (urf_front_explain) */
+    uint32_t sweep_n = 0;           /* a sweep: the caller's number of points (urf_set_sweep_quantum: a.n_per_scan is the padded length) */
     /* a dense call (urf_classify_batch_*_dense): `a` is the padded batch -- staging, padded labels, all the context's own --, and
      * this is what the caller handed in, for urf_clouds_batch_* in input order (offsets: the context's copy) */
     struct {
@@ -201,15 +203,28 @@ struct urf_ctx {
         lazy_buf<uint8_t> d_labels;     /* max_points */
         lazy_buf<urf_scan_info, true> h_info;
         hipEvent_t ev_done = nullptr;
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        uint64_t key[3] = { 0, 0, 0 };  /* what the captured sequence was built for */
-        urf_kargs cap_a;                /* ... and the kernel arguments / parameters it runs with */
+        /* the captured launch sequences: one, or with urf_set_sweep_quantum up to URF_SWEEP_SEQS, one per padded length (seq_find) */
+        struct seq_t {
+            hipGraph_t graph = nullptr;
+            hipGraphExec_t exec = nullptr;
+            uint64_t key[3] = { 0, 0, 0 };  /* what the captured sequence was built for */
+            urf_kargs cap_a;                /* ... and the kernel arguments / parameters it runs with */
+            urf_dev_params cap_dp;
+            urf_planned cap_planned;        /* ... and what the policy said when it planned them */
+            uint64_t used = 0;              /* urf_ctx::seq_clock of its last launch: the least recently used one makes room */
+        } seqs[URF_SWEEP_SEQS];
+        urf_kargs cap_a;                /* the arguments / parameters / plan of the sweep in this slot (its sequence's, or its direct launches') */
         urf_dev_params cap_dp;
-        urf_planned cap_planned;        /* ... and what the policy said when it planned them */
+        urf_planned cap_planned;
         bool pending = false, used = false;
         uint64_t gen = 0;               /* the row's submission number of the sweep in this slot */
         uint32_t n_points = 0, ticket = 0;
+        /* urf_set_sweep_quantum: the points the sweep runs as (n_points rounded up to the quantum, NaN behind the caller's; off: n_points),
+         * whether its sequence is a padded one, and the sweep's own length for k_pc2_to_soa_pad: a pinned word and its device copy */
+        uint32_t n_run = 0;
+        bool pad = false;
+        lazy_buf<uint32_t, true> h_n;
+        lazy_buf<uint32_t> d_n;
         uint32_t point_step = 0, off_x = 0, off_y = 0, off_z = 0;   /* layout of the message in d_raw */
         bool planes = false;            /* d_raw holds x[n] y[n] z[n] (a staged message) instead of the records */
         /* urf_set_sweep_outputs: the sweep's marker points and ordered lists (sweep_out_words: URF_SWEEP_HDR words, then three
@@ -234,6 +249,8 @@ struct urf_ctx {
     bool streams_made = false;
     urf_policy pol;                 /* which kernels a call launches */
     uint32_t n_rerun = 0;           /* sweeps urf_classify_pc2_wait had to run again */
+    uint32_t n_captured = 0;        /* launch sequences captured so far, all slots (urf_callback_path_captures) */
+    uint64_t seq_clock = 0;         /* launches of captured sequences so far (slot_t::seq_t::used) */
     /* Slot i works on scratch row i % rows, rows = min(max_batch, URF_ASYNC_SLOTS); row 0 runs on the
      * context's stream, every other row on a stream of its own (slots that share a row share its
      * stream: they are serialised).  Everything else the context launches runs on `stream`; the two
@@ -324,6 +341,23 @@ struct urf_ctx {
             return e_ == hipErrorOutOfMemory ? URF_ERR_OOM : URF_ERR_HIP;               \
         }                                                                               \
     } while (0)
+
+/* a slot's captured sequences: released one by one (seq_drop) or all of them (slot_forget); never while the slot's sweep is in flight */
+static void seq_drop(urf_ctx::slot_t::seq_t& q)
+{
+    if (q.exec)
+        (void)hipGraphExecDestroy(q.exec);
+    if (q.graph)
+        (void)hipGraphDestroy(q.graph);
+    q.exec = nullptr;
+    q.graph = nullptr;
+    q.key[0] = 0;
+}
+static void slot_forget(urf_ctx::slot_t& sl)
+{
+    for (auto& q : sl.seqs)
+        seq_drop(q);
+}
 
 template <class T>
 static int dev_alloc(urf_ctx* c, T** p, size_t count)
@@ -605,10 +639,7 @@ extern "C" int urf_destroy(urf_ctx* c)
     if (c->pol.flags)
         (void)hipHostFree(c->pol.flags);
     for (auto& sl : c->slots) {
-        if (sl.exec)
-            (void)hipGraphExecDestroy(sl.exec);
-        if (sl.graph)
-            (void)hipGraphDestroy(sl.graph);
+        slot_forget(sl);
         if (sl.ev_done)
             (void)hipEventDestroy(sl.ev_done);
     }
@@ -852,6 +883,47 @@ extern "C" int urf_set_sweep_outputs(urf_ctx* c, uint32_t bits)
             return rc;   /* (the switch stays as it was) */
     }
     c->pol.set(c->pol.sweep_outputs, bits);   /* (every slot captures its sequence again) */
+    return URF_OK;
+}
+
+/* ---- urf_set_sweep_quantum, urf_callback_path_captures (include/urf.h) ------------------------- */
+extern "C" int urf_set_sweep_quantum(urf_ctx* c, uint32_t points)
+{
+    if (!c)
+        return URF_ERR_INVALID_ARG;
+    if (points % URF_TILE != 0u || points > c->max_points) {
+        c->last_error = "urf_set_sweep_quantum: not a multiple of URF_TILE (2048) points, or more than the context's max_points";
+        return URF_ERR_INVALID_ARG;
+    }
+    for (const auto& sl : c->slots)
+        if (sl.pending) {
+            c->last_error = "urf_set_sweep_quantum: a sweep is in flight (urf_classify_pc2_wait it first)";
+            return URF_ERR_BUSY;
+        }
+    if (points) {   /* the slots' length words, before any sequence is captured */
+        URF_HIP(c, hipSetDevice(c->device));
+        for (auto& sl : c->slots) {
+            int rc;
+            if ((rc = grow(c, sl.h_n, 1)) != URF_OK || (rc = grow(c, sl.d_n, 1)) != URF_OK)
+                return rc;   /* (the switch stays as it was) */
+        }
+    }
+    c->pol.set(c->pol.sweep_quantum, points);   /* (a change: every slot forgets its sequences with its next sweep) */
+    return URF_OK;
+}
+
+extern "C" int urf_callback_path_captures(const urf_ctx* c, uint32_t* n_captured, uint32_t* n_resident)
+{
+    if (!c)
+        return URF_ERR_INVALID_ARG;
+    if (n_captured)
+        *n_captured = c->n_captured;
+    if (n_resident) {   /* (a sequence of an earlier epoch is no sweep's any more: its slot's next submission releases it) */
+        *n_resident = 0;
+        for (const auto& sl : c->slots)
+            for (const auto& q : sl.seqs)
+                *n_resident += (q.exec && q.key[0] == c->pol.epoch) ? 1u : 0u;
+    }
     return URF_OK;
 }
 
@@ -1541,8 +1613,9 @@ static int slot_prepare(urf_ctx* c, urf_ctx::slot_t& sl, size_t bytes)
     if ((rc = grow(c, sl.h_labels, c->max_points)) != URF_OK || (rc = grow(c, sl.h_info, 1)) != URF_OK ||
         (rc = grow(c, sl.d_labels, c->max_points)) != URF_OK)
         return rc;
-    if (bytes > sl.h_in.cap || bytes > sl.d_raw.cap) {   /* grows to the largest message seen (a new buffer invalidates the captured sequence) */
-        sl.key[0] = 0;
+    if (bytes > sl.h_in.cap || bytes > sl.d_raw.cap) {   /* grows to the largest message seen (a new buffer invalidates the captured sequences) */
+        for (auto& q : sl.seqs)
+            q.key[0] = 0;
         const hipStream_t st = slot_stream(c, sl);   /* the slot's last sweep may still read d_raw */
         if ((rc = grow(c, sl.h_in, bytes, st)) != URF_OK || (rc = grow(c, sl.d_raw, bytes, st)) != URF_OK)
             return rc;
@@ -1709,8 +1782,12 @@ static int slot_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t n_points, uint3
         sx = c->sx.p + (size_t)row * c->max_points;   /* (ensure_soa_staging: the caller) */
         sy = c->sy.p + (size_t)row * c->max_points;
         sz = c->sz.p + (size_t)row * c->max_points;
-        hipLaunchKernelGGL(k_pc2_to_soa, dim3((n_points + 255) / 256), dim3(256), 0, st, sl.d_raw.p, (unsigned long long)n_points,
-                           point_step, off_x, off_y, off_z, sx, sy, sz);
+        if (sl.pad)   /* (urf_set_sweep_quantum: n_points is the padded length, the sweep's own stands in the slot's device word) */
+            hipLaunchKernelGGL(k_pc2_to_soa_pad, dim3((n_points + 255) / 256), dim3(256), 0, st, sl.d_raw.p, sl.d_n.p, n_points, point_step,
+                               off_x, off_y, off_z, sx, sy, sz);
+        else
+            hipLaunchKernelGGL(k_pc2_to_soa, dim3((n_points + 255) / 256), dim3(256), 0, st, sl.d_raw.p, (unsigned long long)n_points,
+                               point_step, off_x, off_y, off_z, sx, sy, sz);
     }
     const int rc = run_pipeline(c, urf_call{ sx, sy, sz, nullptr, n_points, n_points, 1, sl.d_labels.p, nullptr, row, st, dp_in, capture_in },
                                 sl.cap_a, sl.cap_dp);
@@ -1755,9 +1832,28 @@ extern "C" int urf_classify_pc2_async(urf_ctx* c, const uint8_t* data, uint32_t 
     if (sl.h_in.p && data >= sl.h_in.p && data < sl.h_in.p + sl.h_in.cap && (data != sl.h_in.p || bytes > sl.h_in.cap))
         return URF_ERR_INVALID_ARG;
     const bool planes = data != sl.h_in.p;   /* (a producer that filled the pinned buffer itself wrote records) */
-    const size_t n4 = ((size_t)n_points + 3) & ~(size_t)3;
+    /* urf_set_sweep_quantum: the sweep runs as the next multiple of the quantum, (NaN, NaN, NaN) behind its own points -- the reference
+     * drops non-finite points before anything else, so labels and summary are those of the unpadded sweep -- and every sweep of that
+     * padded length replays one captured sequence.  A padded length beyond max_points: unpadded, under its own key. */
+    uint32_t n_run = n_points;
+    bool pad = false;
+    if (const uint32_t q = c->pol.sweep_quantum) {
+        const uint64_t up = ((uint64_t)n_points + q - 1) / q * q;
+        if (up <= c->max_points) {
+            n_run = (uint32_t)up;
+            pad = true;   /* (a multiple of the quantum too: it shares the padded sequence of its length) */
+        }
+    }
+    const size_t n4 = ((size_t)n_run + 3) & ~(size_t)3;
     const size_t plane_bytes = 3 * sizeof(float) * n4;
-    int rc = slot_prepare(c, sl, planes && plane_bytes > bytes ? plane_bytes : bytes);
+    size_t want = planes && plane_bytes > bytes ? plane_bytes : bytes;
+    if (pad && (want > sl.h_in.cap || want > sl.d_raw.cap)) {
+        /* a new buffer forgets the slot's sequences, and the messages of such a stream keep growing by a few points: room for twice the
+         * padded length (at most max_points), so that the lengths to come fit the buffer this one gets */
+        const size_t room = std::min<size_t>(2 * (size_t)n_run, c->max_points);
+        want = std::max(want, ((room + 3) & ~(size_t)3) * std::max<size_t>(point_step, 3 * sizeof(float)));
+    }
+    int rc = slot_prepare(c, sl, want);
     if (rc == URF_OK && !planes)
         rc = ensure_soa_staging(c);   /* where the device gathers the records' x / y / z */
     if (rc != URF_OK)
@@ -1776,19 +1872,32 @@ extern "C" int urf_classify_pc2_async(urf_ctx* c, const uint8_t* data, uint32_t 
          * second one is gathered (one 2-D copy per half: its columns of the three planes; 35 us for the whole, 22 per
          * half).  (urf_pinned_input() lets a producer write its records into the pinned buffer directly: no staging.) */
         float* X = (float*)sl.h_in.p;
-        const uint32_t mid = n_points >= 32768 ? (uint32_t)((n4 / 2) & ~(size_t)3) : 0u;
+        const size_t real4 = ((size_t)n_points + 3) & ~(size_t)3;   /* (the halves are halves of the sweep's own points; no pad: n4) */
+        const uint32_t mid = n_points >= 32768 ? (uint32_t)((real4 / 2) & ~(size_t)3) : 0u;
         const uint32_t cut[3] = { 0u, mid, n_points };
         for (int h = mid ? 0 : 1; h < 2; h++) {
             pc2_to_planes(data, cut[h], cut[h + 1], point_step, off_x, off_y, off_z, X, X + n4, X + 2 * n4);
+            if (h == 1 && n_run != n_points) {   /* the pad: the planes' tails, which the second copy's columns [mid, n_run) carry */
+                const float nan = std::numeric_limits<float>::quiet_NaN();
+                for (float* P : { X, X + n4, X + 2 * n4 })
+                    std::fill(P + n_points, P + n_run, nan);
+            }
             const size_t w = (h == 1 ? n4 - cut[1] : cut[1]) * sizeof(float), o = cut[h] * sizeof(float);
             URF_HIP(c, hipMemcpy2DAsync(sl.d_raw.p + o, n4 * sizeof(float), sl.h_in.p + o, n4 * sizeof(float), w, 3, hipMemcpyHostToDevice, st));
         }
     } else {
         URF_HIP(c, hipMemcpyAsync(sl.d_raw.p, sl.h_in.p, bytes, hipMemcpyHostToDevice, st));
+        if (pad) {   /* the sweep's own length for k_pc2_to_soa_pad: a word of the slot, copied in front of every launch of the sequence */
+            *sl.h_n.p = n_points;
+            URF_HIP(c, hipMemcpyAsync(sl.d_n.p, sl.h_n.p, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        }
     }
     if (planes != sl.planes)
-        sl.key[0] = 0;   /* the captured sequence reads the other format */
+        for (auto& q : sl.seqs)
+            q.key[0] = 0;   /* the captured sequences read the other format */
     sl.planes = planes;
+    sl.n_run = n_run;
+    sl.pad = pad;
     HT(0, ht0);   /* staging + H2D enqueue */
     /* what earlier calls reported, for this sweep and the replayed sequences (outside the stream capture: fold may synchronise) */
     rc = c->pol.fold(c, st);
@@ -1797,38 +1906,62 @@ extern "C" int urf_classify_pc2_async(urf_ctx* c, const uint8_t* data, uint32_t 
     c->pol.probation_sweep();
     /* the launch sequence of a sweep of this shape is captured once and replayed (one graph launch
      * instead of a dozen kernel launches per callback); anything it depends on bumps the epoch */
-    const uint64_t key[3] = { c->pol.epoch,((uint64_t)n_points << 32) | point_step,
+    const uint64_t key[3] = { c->pol.epoch,((uint64_t)n_run << 32) | point_step,
                               ((uint64_t)off_x << 42) ^ ((uint64_t)off_y << 21) ^ off_z };
     const bool use_graph = !c->timing && !(c->debug_flags & 8u);
     HT(1, ht0);   /* event record, ordering, stream wait */
-    if (use_graph && (sl.key[0] != key[0] || sl.key[1] != key[1] || sl.key[2] != key[2] || !sl.exec)) {
-        if (sl.exec)
-            (void)hipGraphExecDestroy(sl.exec);
-        if (sl.graph)
-            (void)hipGraphDestroy(sl.graph);
-        sl.exec = nullptr;
-        sl.graph = nullptr;
-        URF_HIP(c, hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-        rc = slot_launch(c, sl, n_points, point_step, off_x, off_y, off_z);
-        hipGraph_t g = nullptr;
-        const hipError_t e = hipStreamEndCapture(st, &g);
-        if (rc != URF_OK || e != hipSuccess) {
-            if (g)
-                (void)hipGraphDestroy(g);
-            if (rc == URF_OK)
-                URF_HIP(c, e);
-            return rc;
-        }
-        sl.graph = g;
-        URF_HIP(c, hipGraphInstantiate(&sl.exec, sl.graph, nullptr, nullptr, 0));
-        sl.key[0] = key[0];
-        sl.key[1] = key[1];
-        sl.key[2] = key[2];
-    }
     if (use_graph) {
-        URF_HIP(c, hipGraphLaunch(sl.exec, st));
+        /* The slot's sequence for this key.  One per slot; with urf_set_sweep_quantum up to URF_SWEEP_SEQS, the least recently used
+         * one making room for a new length.  Sequences of an earlier epoch go, all of them, whatever the key. */
+        const unsigned n_seqs = c->pol.sweep_quantum ? URF_SWEEP_SEQS : 1u;
+        urf_ctx::slot_t::seq_t *seq = nullptr, *room = nullptr;
+        for (auto& q : sl.seqs) {
+            if (q.exec && q.key[0] != key[0])
+                seq_drop(q);
+            if (q.exec && q.key[1] == key[1] && q.key[2] == key[2])
+                seq = &q;
+        }
+        if (!seq) {
+            for (unsigned i = 0; i < n_seqs; i++) {
+                urf_ctx::slot_t::seq_t& q = sl.seqs[i];
+                if (!q.exec) {
+                    room = &q;
+                    break;
+                }
+                if (!room || q.used < room->used)
+                    room = &q;
+            }
+            seq_drop(*room);
+            URF_HIP(c, hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+            rc = slot_launch(c, sl, n_run, point_step, off_x, off_y, off_z);
+            hipGraph_t g = nullptr;
+            const hipError_t e = hipStreamEndCapture(st, &g);
+            if (rc != URF_OK || e != hipSuccess) {
+                if (g)
+                    (void)hipGraphDestroy(g);
+                if (rc == URF_OK)
+                    URF_HIP(c, e);
+                return rc;
+            }
+            room->graph = g;
+            URF_HIP(c, hipGraphInstantiate(&room->exec, room->graph, nullptr, nullptr, 0));
+            room->key[0] = key[0];
+            room->key[1] = key[1];
+            room->key[2] = key[2];
+            room->cap_a = sl.cap_a;
+            room->cap_dp = sl.cap_dp;
+            room->cap_planned = sl.cap_planned;
+            c->n_captured++;
+            seq = room;
+        } else {   /* (what the sweep in this slot ran with: the readers' record, the rerun's parameters) */
+            sl.cap_a = seq->cap_a;
+            sl.cap_dp = seq->cap_dp;
+            sl.cap_planned = seq->cap_planned;
+        }
+        seq->used = ++c->seq_clock;
+        URF_HIP(c, hipGraphLaunch(seq->exec, st));
     } else {
-        rc = slot_launch(c, sl, n_points, point_step, off_x, off_y, off_z);
+        rc = slot_launch(c, sl, n_run, point_step, off_x, off_y, off_z);
         if (rc != URF_OK)
             return rc;
     }
@@ -1875,7 +2008,7 @@ extern "C" int urf_classify_pc2_wait(urf_ctx* c, uint32_t ticket, uint8_t* label
          * behind whatever the context's stream still does with the row */
         int rc = order_row_after_main(c, slot_row(c, sl), slot_stream(c, sl));
         if (rc == URF_OK)
-            rc = slot_launch(c, sl, sl.n_points, sl.point_step, sl.off_x, sl.off_y, sl.off_z, &sl.cap_dp, (int)sl.cap_a.capture);
+            rc = slot_launch(c, sl, sl.n_run, sl.point_step, sl.off_x, sl.off_y, sl.off_z, &sl.cap_dp, (int)sl.cap_a.capture);   /* (a padded sweep: pad and length word are still in place) */
         if (rc == URF_OK && hipStreamSynchronize(slot_stream(c, sl)) != hipSuccess) {
             c->last_error = "hipStreamSynchronize (rerun of a voided sweep)";
             rc = URF_ERR_HIP;
@@ -1887,6 +2020,7 @@ extern "C" int urf_classify_pc2_wait(urf_ctx* c, uint32_t ticket, uint8_t* label
     }
     /* only now is the sweep "the last call": its scratch row stays untouched until the row (or a batch call) is used again */
     publish_last(c, URF_LAST_SWEEP, 1, sl.cap_a, sl.cap_dp, sl.cap_planned, slot_row(c, sl), sl.gen);
+    c->last.sweep_n = sl.n_points;   /* (the readers answer for the caller's points, whatever length the sweep ran as) */
     if (labels_out)
         std::memcpy(labels_out, sl.h_labels.p, sl.n_points);
     if (info)
@@ -1960,13 +2094,13 @@ extern "C" int urf_result_ordered_indices(urf_ctx* c, uint32_t ticket, const uin
     const int rc = sweep_result_slot(c, ticket, URF_SWEEP_OUT_ORDER, "urf_result_ordered_indices", sl);
     if (rc != URF_OK)
         return rc;
-    const uint32_t* lists = sl->h_out.p + URF_SWEEP_HDR;   /* three lists at a stride of the sweep's n_points */
+    const uint32_t* lists = sl->h_out.p + URF_SWEEP_HDR;   /* three lists at a stride of the points the sweep ran as (urf_set_sweep_quantum: padded) */
     if (road)
         *road = lists;
     if (curb)
-        *curb = lists + sl->n_points;
+        *curb = lists + sl->n_run;
     if (ring10)
-        *ring10 = lists + 2 * (size_t)sl->n_points;
+        *ring10 = lists + 2 * (size_t)sl->n_run;
     if (sl->h_info.p->status != URF_OK)
         return URF_OK;
     const uint32_t* h = sl->h_out.p + URF_SWEEP_HDR_LCOUNTS;
@@ -2083,7 +2217,7 @@ extern "C" int urf_front_explain(urf_ctx* c, int layout, urf_front_why* out, uin
     const bool rows = layout == 1 && !l.dense.on;   /* (a dense call: the padded batch, firing order) */
     const bool lasers = L == 16u || L == 32u || L == 64u || L == 128u;   /* (other counts: no laser slots to speak of, the counters stay 0) */
     hipStream_t st = c->stream;
-    std::vector<uint32_t> rec((size_t)n * URF_FX_WORDS, 0u), ok(n), ncand(n), lens(n, a.n_per_scan);
+    std::vector<uint32_t> rec((size_t)n * URF_FX_WORDS, 0u), ok(n), ncand(n), lens(n, l.sweep_n ? l.sweep_n : a.n_per_scan);
     std::vector<urf_scan_info> info(n);
     if (lasers) {
         URF_HIP(c, hipMemsetAsync(c->fx_rec.p, 0, rec.size() * sizeof(uint32_t), st));
@@ -2574,7 +2708,7 @@ extern "C" int urf_read_stage(urf_ctx* c, urf_stage what, uint32_t scan, void* h
         if (len > k.max_len)
             len = k.max_len;
     } else {
-        len = k.n_per_scan;
+        len = l->sweep_n ? l->sweep_n : k.n_per_scan;   /* (a padded sweep: the caller's points) */
     }
     const unsigned C = (unsigned)l->dp.p.channels;
     const size_t sb = (size_t)scan * k.sstride;

@@ -37,6 +37,41 @@ __global__ __launch_bounds__(256) void k_pc2_to_soa(const uint8_t* __restrict__ 
     z[i] = fz;
 }
 
+/* The gather of a sweep padded to a quantum of points (urf_set_sweep_quantum): the grid covers the n_run points the captured sequence
+ * was built for, the sweep's own length comes from a device word of its slot -- a 4-byte copy in front of every launch of the sequence;
+ * a kernel argument would be frozen in the graph.  Records i < *n_real as k_pc2_to_soa gathers them, NaN behind them: the reference drops
+ * a non-finite point before it looks at anything else, so the pad changes no label and no summary. */
+__global__ __launch_bounds__(256) void k_pc2_to_soa_pad(const uint8_t* __restrict__ data, const unsigned* __restrict__ n_real, unsigned n_run,
+                                                        unsigned step, unsigned ox, unsigned oy, unsigned oz,
+                                                        float* __restrict__ x, float* __restrict__ y, float* __restrict__ z)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_run)
+        return;
+    float fx = __uint_as_float(0x7fc00000u), fy = fx, fz = fx;
+    if (i < *n_real) {
+        const uint8_t* p = data + (unsigned long long)i * step;
+        if ((((unsigned long long)(p + ox) | (unsigned long long)(p + oy) | (unsigned long long)(p + oz)) & 3ull) == 0) {
+            fx = *(const float*)(p + ox);
+            fy = *(const float*)(p + oy);
+            fz = *(const float*)(p + oz);
+        } else {
+            unsigned bx = 0, by = 0, bz = 0;
+            for (int b = 3; b >= 0; b--) {
+                bx = (bx << 8) | p[ox + b];
+                by = (by << 8) | p[oy + b];
+                bz = (bz << 8) | p[oz + b];
+            }
+            fx = __uint_as_float(bx);
+            fy = __uint_as_float(by);
+            fz = __uint_as_float(bz);
+        }
+    }
+    x[i] = fx;
+    y[i] = fy;
+    z[i] = fz;
+}
+
 /* ------------------------------------------------------------------------- */
 /* k_ring_table                                                                */
 /* ------------------------------------------------------------------------- */

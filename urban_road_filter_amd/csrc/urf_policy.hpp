@@ -86,6 +86,9 @@ struct __attribute__((visibility("hidden"))) urf_policy {
     /* urf_set_sweep_outputs (URF_SWEEP_OUT_*): a sweep's captured sequence also produces its marker points and / or ordered lists.  Part
      * of the epoch -- the slots capture again -- but not read by plan(): it decides no launch of the classification. */
     uint32_t sweep_outputs = 0;
+    /* urf_set_sweep_quantum: a sweep of the callback path runs as the next multiple of this many points, NaN behind its own, and a slot
+     * keeps a few captured sequences, one per padded length (0: off).  Part of the epoch, not read by plan(), as sweep_outputs. */
+    uint32_t sweep_quantum = 0;
     /* k_front hands a scan without the shape back to the general kernels: launched list-driven until a call has done so
      * (URF_FLAG_FRONT_HANDED_BACK: front_direct, full grids from then on); mode 1 stops trying once a whole batch has been handed back
      * (URF_FLAG_FRONT_ALL_HANDED_BACK: front_off, unorganised clouds).  forget_front() starts over. */
