@@ -77,7 +77,8 @@ extern "C" {
  * derived from the points' elevation on the device); urf_set_sweep_outputs with urf_result_marker_points / urf_result_ordered_indices
  * and URF_SWEEP_OUT_* (a sweep of the callback path brings its marker points and ordered lists along, read per ticket);
  * urf_set_sweep_quantum with urf_callback_path_captures and URF_SWEEP_SEQS (sweeps of varying length on the callback path: padded to a
- * quantum of points, one captured sequence per padded length).
+ * quantum of points, one captured sequence per padded length); urf_set_sweep_results_direct (those results stored by the kernels
+ * themselves into mapped pinned memory, the lists packed back to back: no copy of unused words).
  * WHICH std::sort (4 above): the one of libstdc++ as shipped with GCC 5 .. 13 (bits/stl_algo.h: __sort = __introsort_loop with
  * _S_threshold 16, __move_median_to_first on (first + 1, mid, last - 1), __unguarded_partition, depth limit 2 * floor(log2 n),
  * __partial_sort as the fallback, then __final_insertion_sort); tests/test_stdsort.py pins the restatement against the std::sort
@@ -348,6 +349,24 @@ int urf_result_ordered_indices(urf_ctx* ctx, uint32_t ticket, const uint32_t** r
 #define URF_SWEEP_SEQS 8
 int urf_set_sweep_quantum(urf_ctx* ctx, uint32_t points);
 int urf_callback_path_captures(const urf_ctx* ctx, uint32_t* n_captured, uint32_t* n_resident);
+
+/* The results of urf_set_sweep_outputs written to host memory at their own size (opt-in; additive under ABI 5).  Without this switch the
+ * sequence copies the three lists as three arrays of the sweep's length, 12 bytes per point whatever they hold.  With it the kernels that
+ * produce the marker points, their count, the three list counts and the lists store them themselves -- every word once, with plain stores --
+ * into a pinned buffer of the sweep's slot that is mapped into the device's address space and coherent (1448 header words +
+ * 2 * max_points list words: road and curb are disjoint sets of the sweep's points, ring 10 has at most all of them), and the sequence
+ * holds no device-to-host copy for these products (labels and summary are copied as before).  Only the entries that exist cross the link.
+ *   urf_set_sweep_results_direct   on: 0 (default) | 1, anything else URF_ERR_INVALID_ARG.  Decides something only together with bits of
+ *                           urf_set_sweep_outputs: with none set it allocates and launches nothing; whichever of the two setters comes
+ *                           second allocates the buffers (URF_ERR_OOM leaves the switch as it was), and a context that has the switch on
+ *                           before the first bit needs no device-side result buffer.  URF_ERR_BUSY while a sweep is in flight.  A change
+ *                           makes every slot capture its sequence again.  Off: every call launches and copies what it does without it.
+ * urf_result_marker_points and urf_result_ordered_indices keep signature and contract; they return pointers into that buffer.  The lists
+ * of a sweep submitted with the switch on lie back to back, independent of the sweep's length (and of its padded length under
+ * urf_set_sweep_quantum): *curb == *road + counts[0], *ring10 == *curb + counts[1]; the words behind them are never written.  A slot
+ * remembers how its sweep was submitted: the switch may change between the wait and the read.  Everything else -- labels, summaries,
+ * urf_marker_points, urf_ordered_indices, urf_read_stage, urf_front_explain, urf_front_scans, batch calls -- is what it is without it. */
+int urf_set_sweep_results_direct(urf_ctx* ctx, int on);
 
 /* ---- batch of scans, device-resident ---------------------------------------
  * n_scans independent scans of n_per_scan points each; scan s owns elements

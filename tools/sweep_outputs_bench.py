@@ -2,17 +2,19 @@
 """tools/sweep_outputs_bench.py -- what marker points and the reference order cost on the callback path, measured on one MI355X: read
 after the wait (today's way) against travelling with the sweep (urf_set_sweep_outputs).  Prints ONE JSON line and, with --out, writes it.
 
-    python tools/sweep_outputs_bench.py [--reps 200] [--windows 12] [--window 64] [--out profiles/sweep_outputs_bench.json]
+    python tools/sweep_outputs_bench.py [--reps 200] [--windows 12] [--window 64] [--reverse] [--out profiles/sweep_results_direct_bench.json]
 
 Two workloads: cfg2 64 x 2048 sweeps in firing order (the general kernels) and row-major 64 x 1024 sweeps (the fused front end, from the
 context's third sweep on), both as 32-byte PointCloud2 records through urf_classify_pc2_async / _wait on max_batch 4 contexts of the
-build with the test hooks.  Three arms, each on a context of its own, interleaved sweep by sweep (latency) and window by window
+build with the test hooks.  Four arms, each on a context of its own, interleaved sweep by sweep (latency) and window by window
 (throughput), behind an equality gate on labels, marker points and the three lists of every sweep:
   (a) wait, then urf_marker_points + urf_ordered_indices            (row-major: with urf_set_front_outputs on, so that the context stays fused)
   (b) urf_set_sweep_outputs(3) with the kernels of the two products launched one by one (debug flag 32 of the hooks build)
   (c) urf_set_sweep_outputs(3) with k_sweep_rings / k_sweep_lists
+  (d) (c) with urf_set_sweep_results_direct(1): the kernels store header results and packed lists into mapped pinned memory, no copy
 Per arm: latency with one sweep in flight (submit .. results in host arrays), sweeps/s with four in flight, median and p10-p90; per-pair
-ratios a/c and b/c (above 1: c is faster); the bytes per sweep that cross PCIe in each direction.  All arms pay the same ctypes / numpy
+ratios a/c and b/c (above 1: c is faster) and c/d (above 1: d is faster); the bytes per sweep that cross PCIe in each direction, for (d)
+computed from the counts of the gate's last sweep: labels + 32 + 4 * (c0 + c1 + c2) + 12 + 16 * m + 4.  All arms pay the same ctypes / numpy
 cost per call; the figures are the Python client's, not a C client's.
 """
 import argparse
@@ -52,6 +54,8 @@ class Arm:
         self.switch = name != "a"
         if name == "b":
             self.ctx._check(self.ctx._lib.urf_set_debug_flags(self.ctx._h, DBG_OLD_KERNELS), "urf_set_debug_flags")
+        if name == "d":
+            self.ctx.set_sweep_results_direct(1)
         if self.switch:
             self.ctx.set_sweep_outputs(3)
         elif rows:
@@ -86,7 +90,7 @@ class Arm:
 def workload(u, O, records, name, clouds, params, rows, args):
     n = len(clouds[0][0])
     recs = [records(*c) for c in clouds]
-    arms = [Arm(u, a, n, params, rows) for a in "abc"]
+    arms = [Arm(u, a, n, params, rows) for a in ("dcba" if args.reverse else "abcd")]   # (created, and taking their turns, in this order)
     for arm in arms:   # warm-up: capture, the row-major sighting, the first rerun
         for _ in range(3):
             for r in recs:
@@ -99,6 +103,7 @@ def workload(u, O, records, name, clouds, params, rows, args):
             outs.append((arm.lab.copy(),) + out)
         for o in outs[1:]:
             assert all(x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(o, outs[0])), name
+        assert all(len(o) == 5 for o in outs)   # labels, three lists, marker points
         gate += 1
     fused = [arm.ctx.front_scans() for arm in arms]
     lat = {a.name: [] for a in arms}
@@ -110,6 +115,7 @@ def workload(u, O, records, name, clouds, params, rows, args):
         for arm in arms:
             thr[arm.name].append(arm.window(recs, args.window))
     counts = [len(x) for x in outs[0][1:4]]
+    markers = len(outs[0][4])
     n4 = (n + 3) & ~3
     res = {"points": n, "sweeps_in_gate": gate, "fused_last_sweep": fused,
            "latency_ms_one_in_flight": {k: stats(v) for k, v in lat.items()},
@@ -121,9 +127,13 @@ def workload(u, O, records, name, clouds, params, rows, args):
                "device_to_host_labels_and_summary": n + 32,
                "device_to_host_a_readouts": 4 * (361 * 4 + 4) + 12 + 4 * sum(counts),
                "device_to_host_bc_results": 4 * (361 * 4 + 4) + 12 * n,
-               "lists_share_of_bc": 12 * n, "list_entries_used": counts}}
+               "lists_share_of_bc": 12 * n, "list_entries_used": counts,
+               "device_to_host_d_total": n + 32 + 4 * sum(counts) + 12 + 16 * markers + 4, "marker_points": markers}}
+    res["latency_ratio"]["c_over_d"] = stats(np.array(lat["c"]) / np.array(lat["d"]))
+    res["throughput_ratio"]["d_over_c"] = stats(np.array(thr["d"]) / np.array(thr["c"]))
     res["outcome"] = {"c_vs_a_latency": verdict(res["latency_ratio"]["a_over_c"]), "c_vs_b_latency": verdict(res["latency_ratio"]["b_over_c"]),
-                      "c_vs_a_throughput": verdict(res["throughput_ratio"]["c_over_a"]), "c_vs_b_throughput": verdict(res["throughput_ratio"]["c_over_b"])}
+                      "c_vs_a_throughput": verdict(res["throughput_ratio"]["c_over_a"]), "c_vs_b_throughput": verdict(res["throughput_ratio"]["c_over_b"]),
+                      "d_vs_c_latency": verdict(res["latency_ratio"]["c_over_d"]), "d_vs_c_throughput": verdict(res["throughput_ratio"]["d_over_c"])}
     for arm in arms:
         arm.ctx.close()
     return res
@@ -135,12 +145,14 @@ def main():
     ap.add_argument("--windows", type=int, default=12)
     ap.add_argument("--window", type=int, default=64)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--reverse", action="store_true", help="create the arms' contexts, and give them their turns, in the order d c b a")
     args = ap.parse_args()
     import oracles as O
     import urban_road_filter_amd as u
     from test_gpu_async import records
     from test_gpu_front import ring_major
     out = {"tool": "tools/sweep_outputs_bench.py", "reps": args.reps, "windows": args.windows, "window": args.window,
+           "arm_order": "dcba" if args.reverse else "abcd",
            "untimed": "16, 32 and 128 lasers per firing; curbPoints other than 5; a C client (the figures include ctypes / numpy per call)"}
     out["cfg2_64x2048"] = workload(u, O, records, "cfg2_64x2048", [O.cfg_cloud("cfg2", s) for s in (1, 2, 3, 4)], O.cfg_params("cfg2"), False, args)
     out["rows_64x1024"] = workload(u, O, records, "rows_64x1024", [ring_major(u.synth_cloud(64, 1024, 1, s)) for s in (5, 6, 7, 8)],

@@ -210,6 +210,7 @@ def lib(hooks=False):
         "urf_result_marker_points": [vp, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)],
         "urf_result_ordered_indices": [vp, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u32p],
         "urf_set_sweep_quantum": [vp, C.c_uint32],
+        "urf_set_sweep_results_direct": [vp, C.c_int],
         "urf_callback_path_captures": [vp, u32p, u32p],
         "urf_test_dense_ids": [vp, u8p, C.c_uint64],
         "urf_test_dense_ids_ms": [vp, C.c_uint32, C.POINTER(C.c_float)],
@@ -543,6 +544,13 @@ class Context:
         on any max_batch); 0 (default) off.  Allocates what the sequences need (UrfError -5 comes from here); -6 while a sweep is in
         flight (include/urf.h)."""
         self._check(self._lib.urf_set_sweep_outputs(self._h, int(bits)), "urf_set_sweep_outputs")
+
+    def set_sweep_results_direct(self, on):
+        """urf_set_sweep_results_direct: with bits of set_sweep_outputs set, the kernels of a sweep's sequence store marker points, counts
+        and the three lists themselves into mapped pinned memory of the sweep's slot, the lists back to back, and the sequence copies
+        none of them; 0 (default) off.  result_marker_points / result_ordered_indices read either layout.  UrfError -1 for another
+        value, -5 from the allocation, -7 while a sweep is in flight (include/urf.h)."""
+        self._check(self._lib.urf_set_sweep_results_direct(self._h, int(on)), "urf_set_sweep_results_direct")
 
     def set_sweep_quantum(self, points):
         """urf_set_sweep_quantum: a sweep of the callback path runs as the next multiple of `points` points (a multiple of 2048, at most

@@ -36,6 +36,8 @@ void Detector::applySweepOutputs(bool sweep, bool marker, bool order)
     sweep_bits_ = bits;
 }
 
+void Detector::setSweepResultsDirect(bool on) { check(urf_set_sweep_results_direct(ctx_, on ? 1 : 0), "urf_set_sweep_results_direct"); }
+
 void Detector::setSweepQuantum(uint32_t points) { check(urf_set_sweep_quantum(ctx_, points), "urf_set_sweep_quantum"); }
 
 void Detector::setParams(const urf_params& p) { check(urf_set_params(ctx_, &p), "urf_set_params"); }

@@ -149,7 +149,7 @@ public:
             { &urf_front_why::advice, URF_ADVICE_CURB_POINTS, "advice: urf_set_front_curb_points(ctx, 1)" },
             { &urf_front_why::advice, URF_ADVICE_MULTI_SECTOR, "advice: urf_set_front_multi_sector(ctx, 1)" },
             { &urf_front_why::advice, URF_ADVICE_MULTI_SECTOR_CP, "advice: urf_set_front_multi_sector_curb_points(ctx, 1)" },
-            { &urf_front_why::advice, URF_ADVICE_FRONT_OUTPUTS, "advice: urf_set_front_outputs(ctx, 1), so that read-outs leave the context fused (callback path: urf_set_sweep_outputs / Detector::setSweepOutputs, whose sweeps need no read-out)" },
+            { &urf_front_why::advice, URF_ADVICE_FRONT_OUTPUTS, "advice: urf_set_front_outputs(ctx, 1), so that read-outs leave the context fused (callback path: urf_set_sweep_outputs / Detector::setSweepOutputs, whose sweeps need no read-out; setSweepResultsDirect packs what they bring along)" },
             { &urf_front_why::advice, URF_ADVICE_RESET, "advice: call urf_set_front_mode again: it forgets the hand-backs and the read-out" },
             { &urf_front_why::advice, URF_ADVICE_CAPTURE_OFF, "advice: urf_enable_stage_capture(ctx, 0)" },
             { &urf_front_why::advice, URF_ADVICE_BATCH, "advice: classify the sweeps with a batch call (urf_classify_batch_*)" },
@@ -208,6 +208,11 @@ public:
         applySweepOutputs(on, marker_on_, reference_order_);
         sweep_outputs_ = on;
     }
+    /* urf_set_sweep_results_direct: on top of setSweepOutputs, the kernels of a sweep's sequence store marker points, counts and the lists
+     * themselves into mapped pinned memory of the sweep's slot, the lists back to back, instead of three copied arrays of the sweep's
+     * length; collect() reads either (urf_result_*), clouds and MarkerArray are the same byte for byte.  Off by default; decides nothing
+     * while setSweepOutputs is off.  Between sweeps only: with a sweep in flight it throws Error(URF_ERR_BUSY). */
+    void setSweepResultsDirect(bool on);
     /* urf_set_sweep_quantum: for streams whose messages differ in length (velodyne_pointcloud's default mode, any is_dense cloud).  A
      * sweep runs as the next multiple of `points` points (a multiple of 2048, at most max_points), NaN behind its own, so that one
      * captured launch sequence per padded length is replayed instead of a new one per message; clouds, labels and MarkerArray are the

@@ -52,6 +52,24 @@ struct lazy_buf {
         cap = 0;
     }
 };
+/* Pinned host memory that kernels write themselves (urf_set_sweep_results_direct): mapped into the device's address space and coherent,
+ * so that the host sees the stores once the event behind the kernel has completed, whatever the environment says about host memory. */
+struct mapped_buf {
+    uint32_t* p = nullptr;    /* the host's pointer */
+    uint32_t* dev = nullptr;  /* the device's (hipHostGetDevicePointer) */
+    size_t cap = 0;           /* words */
+    mapped_buf() = default;
+    mapped_buf(const mapped_buf&) = delete;
+    mapped_buf& operator=(const mapped_buf&) = delete;
+    ~mapped_buf() { release(); }
+    void release()
+    {
+        if (p)
+            (void)hipHostFree(p);
+        p = dev = nullptr;
+        cap = 0;
+    }
+};
 
 /* Every scratch array of urf_kargs, declared once with its elements per row: X(field, elements).  A row is one scan's slice of
  * each array -- scan r of a batch call, or the sweep of the callback path that runs on row r -- and starts r * elements into it
@@ -232,6 +250,11 @@ struct urf_ctx {
         lazy_buf<uint32_t> d_out;
         lazy_buf<uint32_t, true> h_out;
         uint32_t out_bits = 0;
+        /* urf_set_sweep_results_direct: the same products stored by the kernels themselves (URF_SWEEP_HDR words, then the three lists back
+         * to back: at most 2 x max_points entries -- road and curb are disjoint sets of the sweep's points, ring 10 has at most all of them);
+         * out_direct: whether the sweep in this slot was submitted that way, i.e. which buffer and which list layout its results have */
+        mapped_buf m_out;
+        bool out_direct = false;
     } slots[URF_ASYNC_SLOTS];
     /* urf_set_sweep_outputs: what launch_markers / launch_ordered / front_out_prepare keep as context-wide lazy buffers, once per scratch
      * row of the callback path (row r starts r * elements into each: sweep_row) -- a sweep's captured sequence produces its read-outs on
@@ -840,7 +863,7 @@ static uint32_t sweep_rows(const urf_ctx* c) { return c->max_batch < URF_ASYNC_S
 
 /* Everything the sequences will need, before any of them is captured: nothing may be allocated inside a stream capture.  The buffers are
  * of fixed size (rows, sstride, max_points): a second call finds them there. */
-static int sweep_outputs_alloc(urf_ctx* c)
+static int sweep_outputs_alloc(urf_ctx* c, bool direct)
 {
     const size_t rows = sweep_rows(c), cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS, ss = c->sstride;
     urf_ctx::sweep_scratch_t& w = c->sweep;
@@ -850,6 +873,23 @@ static int sweep_outputs_alloc(urf_ctx* c)
         (rc = grow(c, w.ord_pos, rows * ss)) != URF_OK || (rc = grow(c, w.ord_cls, rows * URF_MAX_CHANNELS * 2)) != URF_OK ||
         (rc = grow(c, w.fo_az, rows * ss)) != URF_OK || (rc = grow(c, w.fo_ent, rows * ss)) != URF_OK || (rc = grow(c, w.fo_d, rows * ss)) != URF_OK)
         return rc;
+    if (direct) {   /* (urf_set_sweep_results_direct: the kernels' own stores, no device-side result buffer) */
+        const size_t words = URF_SWEEP_HDR + 2 * (size_t)c->max_points;
+        for (auto& sl : c->slots) {
+            mapped_buf& m = sl.m_out;
+            if (m.cap >= words)
+                continue;
+            m.release();
+            void *hp = nullptr, *dp_ = nullptr;
+            URF_HIP(c, hipHostMalloc(&hp, words * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+            m.p = (uint32_t*)hp;
+            URF_HIP(c, hipHostGetDevicePointer(&dp_, hp, 0));
+            m.dev = (uint32_t*)dp_;
+            m.cap = words;
+            std::memset(m.p, 0, URF_SWEEP_HDR * sizeof(uint32_t));   /* (a sweep with one bit set leaves the other product's words alone) */
+        }
+        return URF_OK;
+    }
     const size_t words = URF_SWEEP_HDR + 3 * (size_t)c->max_points;
     for (auto& sl : c->slots) {
         const bool fresh = sl.d_out.cap < words;
@@ -878,11 +918,33 @@ extern "C" int urf_set_sweep_outputs(urf_ctx* c, uint32_t bits)
         }
     if (bits) {
         URF_HIP(c, hipSetDevice(c->device));
-        const int rc = sweep_outputs_alloc(c);
+        const int rc = sweep_outputs_alloc(c, c->pol.sweep_direct);
         if (rc != URF_OK)
             return rc;   /* (the switch stays as it was) */
     }
     c->pol.set(c->pol.sweep_outputs, bits);   /* (every slot captures its sequence again) */
+    return URF_OK;
+}
+
+/* ---- urf_set_sweep_results_direct (include/urf.h) ---------------------------------------------- */
+/* Whichever of the two setters comes second allocates the result buffers of the layout that is then in force (sweep_outputs_alloc), outside
+ * any capture; with no bit of urf_set_sweep_outputs set this one allocates nothing. */
+extern "C" int urf_set_sweep_results_direct(urf_ctx* c, int on)
+{
+    if (!c || (on != 0 && on != 1))
+        return URF_ERR_INVALID_ARG;
+    for (const auto& sl : c->slots)
+        if (sl.pending) {
+            c->last_error = "urf_set_sweep_results_direct: a sweep is in flight (urf_classify_pc2_wait it first)";
+            return URF_ERR_BUSY;
+        }
+    if (c->pol.sweep_outputs && (on != 0) != c->pol.sweep_direct) {
+        URF_HIP(c, hipSetDevice(c->device));
+        const int rc = sweep_outputs_alloc(c, on != 0);
+        if (rc != URF_OK)
+            return rc;   /* (the switch stays as it was) */
+    }
+    c->pol.set(c->pol.sweep_direct, on != 0);   /* (every slot captures its sequence again) */
     return URF_OK;
 }
 
@@ -1718,7 +1780,10 @@ static int sweep_outputs_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t row, h
     uint32_t* const fo_az = w.fo_az.p + row * ss;
     uint32_t* const fo_ent = w.fo_ent.p + row * ss;
     float* const fo_d = w.fo_d.p + row * ss;
-    uint32_t* const out = sl.d_out.p;
+    /* urf_set_sweep_results_direct: the slot's mapped pinned buffer as the device sees it -- the last kernels of the chain store header
+     * results and lists there themselves, the lists back to back (k_sweep_lists_direct / k_ordered_lists_direct), and nothing is copied */
+    const bool direct = c->pol.sweep_direct;
+    uint32_t* const out = direct ? sl.m_out.dev : sl.d_out.p;
     float* const d_pts = (float*)out;
     uint32_t* const d_mcount = out + URF_SWEEP_HDR_MCOUNT;
     uint32_t* const d_lcounts = out + URF_SWEEP_HDR_LCOUNTS;
@@ -1747,10 +1812,16 @@ static int sweep_outputs_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t row, h
             hipLaunchKernelGGL(k_marker_ring_literal_front, g_ring, b256, 0, st, a, dp, 0u, mk_lit, fo_az, fo_ent, fo_d, mk_d, mk_pos, mk_red);
     }
     if (merged) {
-        hipLaunchKernelGGL(k_sweep_lists, dim3((unsigned)dp.p.channels + 1u, 1), dim3(384), 0, st, a, dp,
-                           urf_sweep_lists_args{ ord_pos, ord_cls, d_road, d_curb, d_r10, d_lcounts, n_points, mk_d, mk_pos, mk_red, d_pts, d_mcount });
+        if (direct)
+            hipLaunchKernelGGL(k_sweep_lists_direct, dim3((unsigned)dp.p.channels + 1u, 1), dim3(384), 0, st, a, dp,
+                               urf_sweep_lists_args{ ord_pos, ord_cls, d_road, nullptr, nullptr, d_lcounts, 0u, mk_d, mk_pos, mk_red, d_pts, d_mcount });
+        else
+            hipLaunchKernelGGL(k_sweep_lists, dim3((unsigned)dp.p.channels + 1u, 1), dim3(384), 0, st, a, dp,
+                               urf_sweep_lists_args{ ord_pos, ord_cls, d_road, d_curb, d_r10, d_lcounts, n_points, mk_d, mk_pos, mk_red, d_pts, d_mcount });
     } else {
-        if (order)
+        if (order && direct)
+            hipLaunchKernelGGL(k_ordered_lists_direct, g_ring, b256, 0, st, a, dp, ord_pos, ord_cls, d_road, d_lcounts);
+        else if (order)
             hipLaunchKernelGGL(k_ordered_lists, g_ring, b256, 0, st, a, dp, 0u, ord_pos, ord_cls, d_road, d_curb, d_r10, n_points, d_lcounts);
         if (mark) {
             hipLaunchKernelGGL(k_marker_bins, dim3(1), dim3(384), 0, st, a, dp, 0u, mk_d, mk_pos, mk_red, d_pts, d_mcount);
@@ -1759,6 +1830,8 @@ static int sweep_outputs_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t row, h
         }
     }
     URF_HIP(c, hipGetLastError());
+    if (direct)
+        return URF_OK;   /* (the results are where the host reads them once the slot's event has completed) */
     URF_HIP(c, hipMemcpyAsync(sl.h_out.p, out, URF_SWEEP_HDR * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (order)
         URF_HIP(c, hipMemcpyAsync(sl.h_out.p + URF_SWEEP_HDR, d_road, 3 * (size_t)n_points * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -1977,6 +2050,7 @@ extern "C" int urf_classify_pc2_async(urf_ctx* c, const uint8_t* data, uint32_t 
     sl.off_z = off_z;
     sl.ticket = c->next_ticket;
     sl.out_bits = c->pol.sweep_outputs;   /* (it cannot change while the sweep is pending) */
+    sl.out_direct = c->pol.sweep_direct;
     sl.gen = ++c->row_gen[slot_row(c, sl)];
     *ticket = c->next_ticket++;
     return URF_OK;
@@ -2044,6 +2118,9 @@ extern "C" int urf_result_labels(urf_ctx* c, uint32_t ticket, const uint8_t** la
     return URF_OK;
 }
 
+/* where the results of the sweep in this slot are: the buffer of the way it was submitted (the switch may have changed since) */
+static const uint32_t* sweep_result_words(const urf_ctx::slot_t& sl) { return sl.out_direct ? sl.m_out.p : sl.h_out.p; }
+
 /* the ticket's slot for urf_result_marker_points / urf_result_ordered_indices: urf_result_labels' rules, and the sweep was submitted with `bit` */
 static int sweep_result_slot(urf_ctx* c, uint32_t ticket, uint32_t bit, const char* what, const urf_ctx::slot_t*& out)
 {
@@ -2052,7 +2129,7 @@ static int sweep_result_slot(urf_ctx* c, uint32_t ticket, uint32_t bit, const ch
         return URF_ERR_INVALID_ARG;   /* never issued, or its slot has been used again since */
     if (sl.pending)
         return URF_ERR_BUSY;          /* not waited for yet: the buffer is still being written */
-    if (!(sl.out_bits & bit) || !sl.h_out.p) {
+    if (!(sl.out_bits & bit) || !sweep_result_words(sl)) {
         c->last_error = std::string(what) + ": the sweep was submitted without " +
                         (bit == URF_SWEEP_OUT_ORDER ? "URF_SWEEP_OUT_ORDER" : "URF_SWEEP_OUT_MARKER_POINTS") + " (urf_set_sweep_outputs)";
         return URF_ERR_INVALID_ARG;
@@ -2071,10 +2148,11 @@ extern "C" int urf_result_marker_points(urf_ctx* c, uint32_t ticket, const float
     const int rc = sweep_result_slot(c, ticket, URF_SWEEP_OUT_MARKER_POINTS, "urf_result_marker_points", sl);
     if (rc != URF_OK)
         return rc;
-    *pts = (const float*)sl->h_out.p;
+    const uint32_t* const words = sweep_result_words(*sl);
+    *pts = (const float*)words;
     if (sl->h_info.p->status != URF_OK)
         return URF_OK;   /* nothing is published for such a sweep */
-    const uint32_t n = sl->h_out.p[URF_SWEEP_HDR_MCOUNT];
+    const uint32_t n = words[URF_SWEEP_HDR_MCOUNT];
     if (n > URF_DEG_CELLS)
         return URF_ERR_HIP;
     *count = n;
@@ -2094,18 +2172,22 @@ extern "C" int urf_result_ordered_indices(urf_ctx* c, uint32_t ticket, const uin
     const int rc = sweep_result_slot(c, ticket, URF_SWEEP_OUT_ORDER, "urf_result_ordered_indices", sl);
     if (rc != URF_OK)
         return rc;
-    const uint32_t* lists = sl->h_out.p + URF_SWEEP_HDR;   /* three lists at a stride of the points the sweep ran as (urf_set_sweep_quantum: padded) */
+    const uint32_t* const words = sweep_result_words(*sl);
+    const uint32_t* lists = words + URF_SWEEP_HDR;
+    const uint32_t* h = words + URF_SWEEP_HDR_LCOUNTS;
+    const bool ok = sl->h_info.p->status == URF_OK;
+    if (ok && (h[0] > sl->n_points || h[1] > sl->n_points || h[2] > sl->n_points || (uint64_t)h[0] + h[1] > sl->n_points))
+        return URF_ERR_HIP;
+    /* three lists at a stride of the points the sweep ran as (urf_set_sweep_quantum: padded); a sweep submitted direct: back to back */
+    const size_t at1 = sl->out_direct ? (ok ? h[0] : 0u) : sl->n_run, at2 = sl->out_direct ? (ok ? (size_t)h[0] + h[1] : 0u) : 2 * (size_t)sl->n_run;
     if (road)
         *road = lists;
     if (curb)
-        *curb = lists + sl->n_run;
+        *curb = lists + at1;
     if (ring10)
-        *ring10 = lists + 2 * (size_t)sl->n_run;
-    if (sl->h_info.p->status != URF_OK)
+        *ring10 = lists + at2;
+    if (!ok)
         return URF_OK;
-    const uint32_t* h = sl->h_out.p + URF_SWEEP_HDR_LCOUNTS;
-    if (h[0] > sl->n_points || h[1] > sl->n_points || h[2] > sl->n_points)
-        return URF_ERR_HIP;
     counts[0] = h[0];
     counts[1] = h[1];
     counts[2] = h[2];

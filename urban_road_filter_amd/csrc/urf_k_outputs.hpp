@@ -348,8 +348,14 @@ __global__ __launch_bounds__(256) void k_ring_order(urf_kargs a, urf_dev_params 
  * position, the point's input index and class, and per ring the number of road / curb points): workgroup
  * (ring, scan) finds where its ring starts in each list (the counts of the rings in front of it) and
  * appends its points in order -- ballot + prefix per 256 entries.  (One workgroup per SCAN walking all
- * ring points with three barriers per 1024 of them took 1.5 ms per 1024 sweeps.) */
-template <unsigned NT>   /* threads of the workgroup */
+ * ring points with three barriers per 1024 of them took 1.5 ms per 1024 sweeps.)
+ *
+ * PACKED (urf_set_sweep_results_direct; one scan per launch): the three lists lie back to back in ONE area at road_all -- road [0, c0), curb
+ * [c0, c0 + c1), road_probably [c0 + c1, c0 + c1 + c2) -- whatever the scan's length: every workgroup sums the road / curb counts of ALL
+ * the scan's rings (at most 128 pairs, beside the sums of the rings in front of it) and has the bases of curb and road_probably from
+ * that; `stride` is not read.  The area and the counts may be pinned host memory mapped into the device's address space: every word is
+ * written once, with a plain store, by the thread that writes it in the strided layout, and nothing is read back or updated atomically. */
+template <unsigned NT, bool PACKED = false>   /* threads of the workgroup */
 __device__ __forceinline__ void urf_ordered_lists(const urf_kargs& a, const urf_dev_params& dp, unsigned s0, const unsigned* rord_all,
                                                   const unsigned* rcls_all, unsigned* road_all, unsigned* curb_all, unsigned* ring10_all,
                                                   unsigned stride, unsigned* counts_all)
@@ -357,12 +363,14 @@ __device__ __forceinline__ void urf_ordered_lists(const urf_kargs& a, const urf_
     const unsigned c = blockIdx.x, s = s0 + blockIdx.y;
     const unsigned* rord = rord_all + (size_t)blockIdx.y * a.sstride;
     const unsigned* rcls = rcls_all + (size_t)blockIdx.y * URF_MAX_CHANNELS * 2;
-    unsigned* road = road_all ? road_all + (size_t)blockIdx.y * stride : nullptr;
-    unsigned* curb = curb_all ? curb_all + (size_t)blockIdx.y * stride : nullptr;
-    unsigned* ring10 = ring10_all ? ring10_all + (size_t)blockIdx.y * stride : nullptr;
+    unsigned* road = PACKED ? road_all : road_all ? road_all + (size_t)blockIdx.y * stride : nullptr;
+    unsigned* curb = PACKED ? nullptr : curb_all ? curb_all + (size_t)blockIdx.y * stride : nullptr;       /* (PACKED: below) */
+    unsigned* ring10 = PACKED ? nullptr : ring10_all ? ring10_all + (size_t)blockIdx.y * stride : nullptr;
     unsigned* counts = counts_all + (size_t)blockIdx.y * 3;
     __shared__ unsigned wsum[2][NT / 64];
     __shared__ unsigned base[2];
+    __shared__ unsigned total[PACKED ? 2 : 1];
+    static_assert(!PACKED || NT >= URF_MAX_CHANNELS, "one thread per ring sums the scan's counts");
     const unsigned tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const urf_scan_info in = a.info[s];
     const unsigned C = (unsigned)dp.p.channels;
@@ -374,12 +382,30 @@ __device__ __forceinline__ void urf_ordered_lists(const urf_kargs& a, const urf_
     }
     if (tid < 2)
         base[tid] = 0;
+    if constexpr (PACKED) {
+        if (tid < 2)
+            total[tid] = 0;
+    }
     __syncthreads();
-    if (tid < c) {   /* c <= 127 rings in front */
+    if constexpr (PACKED) {
+        if (tid < nR) {   /* every ring of the scan; those in front of this one into base as well */
+            const unsigned r0 = rcls[2 * tid], r1 = rcls[2 * tid + 1];
+            atomicAdd(&total[0], r0);
+            atomicAdd(&total[1], r1);
+            if (tid < c) {
+                atomicAdd(&base[0], r0);
+                atomicAdd(&base[1], r1);
+            }
+        }
+    } else if (tid < c) {   /* c <= 127 rings in front */
         atomicAdd(&base[0], rcls[2 * tid]);
         atomicAdd(&base[1], rcls[2 * tid + 1]);
     }
     __syncthreads();
+    if constexpr (PACKED) {
+        curb = road + total[0];
+        ring10 = curb + total[1];
+    }
     unsigned run0 = base[0], run1 = base[1];
     const unsigned n = a.ring_cnt[(size_t)s * C + c];
     const unsigned rel = a.ring_off[(size_t)s * (C + 1) + c];
@@ -425,6 +451,13 @@ __global__ __launch_bounds__(256) void k_ordered_lists(urf_kargs a, urf_dev_para
                                                        unsigned* ring10_all, unsigned stride, unsigned* counts_all)
 {
     urf_ordered_lists<256>(a, dp, s0, rord_all, rcls_all, road_all, curb_all, ring10_all, stride, counts_all);
+}
+/* ... with the packed layout, for the one scan of a sweep (urf_set_sweep_results_direct with URF_SWEEP_OUT_ORDER alone, or with the kernels of
+ * each product launched one by one): `area` holds all three lists, `counts` their three lengths */
+__global__ __launch_bounds__(256) void k_ordered_lists_direct(urf_kargs a, urf_dev_params dp, const unsigned* rord, const unsigned* rcls,
+                                                              unsigned* area, unsigned* counts)
+{
+    urf_ordered_lists<256, true>(a, dp, 0u, rord, rcls, area, nullptr, nullptr, 0u, counts);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -501,12 +534,9 @@ struct urf_sweep_lists_args {
     float* pts;            /* URF_DEG_CELLS x 4 */
     unsigned* pts_count;
 };
-__global__ __launch_bounds__(384) void k_sweep_lists(urf_kargs a, urf_dev_params dp, urf_sweep_lists_args o)
+/* the last workgroup of such a launch: the marker points of the sweep's one scan, of either kind */
+__device__ __forceinline__ void urf_sweep_marker_bins(const urf_kargs& a, const urf_sweep_lists_args& o)
 {
-    if (blockIdx.x < (unsigned)dp.p.channels) {   /* (uniform) */
-        urf_ordered_lists<384>(a, dp, 0u, o.rord, o.rcls, o.road, o.curb, o.ring10, o.stride, o.list_counts);
-        return;
-    }
     __shared__ unsigned wsum[6];
     const urf_scan_info in = a.info[0];
     if (urf_scan_fused(a, 0u, in)) {
@@ -515,6 +545,25 @@ __global__ __launch_bounds__(384) void k_sweep_lists(urf_kargs a, urf_dev_params
         urf_marker_bins<urf_ring_fused>(a, off, in.n_rings, o.m_d, o.m_pos, o.m_red, o.pts, o.pts_count, wsum);
     } else
         urf_marker_bins<urf_ring_sorted>(a, 0u, in.status == URF_OK ? in.n_rings : 0, o.m_d, o.m_pos, o.m_red, o.pts, o.pts_count, wsum);
+}
+__global__ __launch_bounds__(384) void k_sweep_lists(urf_kargs a, urf_dev_params dp, urf_sweep_lists_args o)
+{
+    if (blockIdx.x < (unsigned)dp.p.channels) {   /* (uniform) */
+        urf_ordered_lists<384>(a, dp, 0u, o.rord, o.rcls, o.road, o.curb, o.ring10, o.stride, o.list_counts);
+        return;
+    }
+    urf_sweep_marker_bins(a, o);
+}
+
+/* k_sweep_lists with the packed list layout (urf_set_sweep_results_direct): o.road is the list area, o.curb, o.ring10 and o.stride are
+ * not read; the marker workgroup is k_sweep_lists' -- its points and its count are plain stores already. */
+__global__ __launch_bounds__(384) void k_sweep_lists_direct(urf_kargs a, urf_dev_params dp, urf_sweep_lists_args o)
+{
+    if (blockIdx.x < (unsigned)dp.p.channels) {   /* (uniform) */
+        urf_ordered_lists<384, true>(a, dp, 0u, o.rord, o.rcls, o.road, nullptr, nullptr, 0u, o.list_counts);
+        return;
+    }
+    urf_sweep_marker_bins(a, o);
 }
 
 #ifdef URF_ENABLE_TEST_HOOKS   /* liburf_hip_test.so only (include/urf_test_hooks.h) */

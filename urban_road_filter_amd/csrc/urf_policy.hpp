@@ -86,6 +86,9 @@ struct __attribute__((visibility("hidden"))) urf_policy {
     /* urf_set_sweep_outputs (URF_SWEEP_OUT_*): a sweep's captured sequence also produces its marker points and / or ordered lists.  Part
      * of the epoch -- the slots capture again -- but not read by plan(): it decides no launch of the classification. */
     uint32_t sweep_outputs = 0;
+    /* urf_set_sweep_results_direct: the kernels of such a sequence store those products themselves into mapped pinned memory of the sweep's
+     * slot, the lists packed back to back, and the sequence holds no copy for them.  Part of the epoch, not read by plan(), as sweep_outputs. */
+    bool sweep_direct = false;
     /* urf_set_sweep_quantum: a sweep of the callback path runs as the next multiple of this many points, NaN behind its own, and a slot
      * keeps a few captured sequences, one per padded length (0: off).  Part of the epoch, not read by plan(), as sweep_outputs. */
     uint32_t sweep_quantum = 0;
