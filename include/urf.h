@@ -801,6 +801,64 @@ typedef struct urf_front_why {
 } urf_front_why;                      /* 64 bytes */
 int urf_front_explain(urf_ctx* ctx, int layout /* 0 firing order, 1 row-major */, urf_front_why* out /* host */, uint32_t n);
 
+/* ---- urf_set_front_auto: the context applies urf_front_explain's advice itself -----------------------------------
+ * One switch for the caller who wants "as fused as my sweeps allow": urf_set_front_mode(ctx, 2); urf_set_front_auto(ctx, 1).  0 (default):
+ * as today -- a context that never turns it on allocates and launches nothing for it.  1: below.  Anything else: URF_ERR_INVALID_ARG;
+ * URF_ERR_OOM (the pass's buffers, allocated by this call, outside any stream capture): it stays off.
+ *
+ * WHERE IT ACTS.  In front modes 2 and 3 only, like every other switch: mode 1's batch-size rule is a measured default and stays the
+ * caller's decision.  In modes 0 and 1 the switch is remembered and decides nothing (URF_AUTO_IDLE).
+ * BITS ARE ONLY EVER ADDED.  Auto turns switches on and raises mode 2 to 3; it never turns anything off.  urf_set_front_auto(ctx, 0) stops
+ * it and leaves what it applied: read `applied` and undo by hand what you do not want.  Turning it on again, even when it is on, is a new
+ * start.
+ * CALL-LEVEL ADVICE is applied at the call itself, on the host, before anything is launched: a batch call and urf_classify_pc2_async ask
+ * the policy why the call as it stands would keep the general kernels (urf_front_explain's `call` and `advice`) and apply the advice
+ * bits inside URF_ADVICE_AUTO_MASK unless the advice holds NEVER, CAPTURE_OFF or RESET (BATCH does not block: a sweep of the callback
+ * path may still be sighted row-major).  The bits go through the setters' own code, allocation included; a setter that answers
+ * URF_ERR_OOM puts its bit into `refused`, and the call goes on without it.  The call is then planned once, with the new settings.  (This
+ * happens before any scan has been looked at: a switch may be turned on for sweeps that then break a rule no setting lifts.)
+ * SCAN-LEVEL ADVICE needs evidence from the device: the learning pass.  While URF_AUTO_LEARNING, a call that launched the fused kernels
+ * is followed, on the same stream and inside the same API call, by k_front_explain and k_front_digest
+ * (urban_road_filter_amd/csrc/urf_k_front_digest.hpp): eight words in host-mapped memory that the NEXT call reads without waiting -- a
+ * digest that has not arrived is looked for again at the call after.  One pass is in flight at a time.  A call that did not launch the
+ * fused kernels launches no pass and changes no phase.  The pass reads the call's inputs behind the call's own kernels, in stream order:
+ * "the call has completed" already means the pass has, and the LIFETIME contract of the classify calls does not change.  On the callback
+ * path the pass runs on the sweep's stream between its launch sequence and the event urf_classify_pc2_wait waits for; it is no part of
+ * the captured sequence, a sweep that is voided and run again teaches nothing, and the re-run launches no pass.
+ * A digest that has arrived: scans its firings' sectors hand back (digest_helped > 0) while urf_set_front_multi_sector (curbPoints != 5:
+ * urf_set_front_multi_sector_curb_points too) is off -> both are applied, still learning.  Otherwise, nothing handed back, or every
+ * handed-back scan has a reason no setting lifts (digest_never + digest_candidates == digest_handed_back) -> URF_AUTO_SETTLED.  Otherwise,
+ * with OTHER or ROWS_SIGHTING among the bits (CALL_AGAIN: a repaired speculation, a first sighting) -> still learning, at most three
+ * times per new start, then settled.  At most five calls per new start carry a pass that counts (explained_calls); on the callback
+ * path a sweep that is voided carries one that is discarded and not counted -- once per kind of URF_STATUS_REDO_*, at most.
+ * A NEW START (learning again, explained_calls 0, `refused` cleared, `applied` kept): urf_set_params with other parameters,
+ * urf_set_front_mode with another mode or ending a sticky read-out, a switch setter that changes its switch, a row-major sighting,
+ * urf_set_front_auto(ctx, 1).
+ * SETTLED COSTS NOTHING: a settled context launches exactly what a context with the same switches set by hand launches.  It does not
+ * look again when the stream changes character: urf_set_front_auto(ctx, 1) starts it over.
+ * The sticky read-out (READOUT: RESET, FRONT_OUTPUTS), CAPACITY, BATCH, CAPTURE_OFF and NEVER are reported in `left` and never applied. */
+int urf_set_front_auto(urf_ctx* ctx, int on);
+#define URF_ADVICE_AUTO_MASK (URF_ADVICE_MODE_3 | URF_ADVICE_LASERS128 | URF_ADVICE_LONG_SWEEPS | URF_ADVICE_CURB_POINTS | \
+                              URF_ADVICE_MULTI_SECTOR | URF_ADVICE_MULTI_SECTOR_CP)
+#define URF_AUTO_IDLE     0u   /* off, or front mode 0 / 1 */
+#define URF_AUTO_LEARNING 1u
+#define URF_AUTO_SETTLED  2u
+typedef struct urf_front_auto_info {
+    uint32_t on, phase;
+    uint32_t applied;          /* URF_ADVICE_* bits the context turned on by itself since the switch was first turned on */
+    uint32_t refused;          /* bits it tried and could not have (URF_ERR_OOM): left off, not tried again before a new start */
+    uint32_t left;             /* advice of the last call / digest that auto never applies (NEVER, CAPACITY, BATCH, CAPTURE_OFF, RESET, FRONT_OUTPUTS, CALL_AGAIN) */
+    uint32_t explained_calls;  /* calls behind which the learning pass was launched since the last new start */
+    /* the last digest: its sequence number, scans with a result (URF_TOO_FEW_POINTS, an empty scan and a voided sweep count nowhere),
+     * those whose flag is cleared, the OR of their URF_WHY_SCAN_* bits, and how many of them have only MULTI_SECTOR / SECTORS_FALL,
+     * one of the four shape bits or ROWS_LENGTH, CANDIDATES, OTHER */
+    uint32_t digest_seq, digest_scans, digest_handed_back, digest_scan_bits, digest_helped, digest_never, digest_candidates, digest_other;
+    uint32_t reserved[2];
+} urf_front_auto_info;                /* 64 bytes */
+/* Synchronises the context's stream(s), then reports: the digest of a pass that has completed is shown whether or not a call has
+ * taken it yet.  Changes nothing.  With the switch off everything but `applied` reads 0. */
+int urf_front_auto_query(urf_ctx* ctx, urf_front_auto_info* out);
+
 /* ---- dense sweeps: put back into firing slots by laser id, on the device ---------
  * The fused front end above wants point f * L + l to be laser slot l of firing f (L = channels), non-returns left in place as holes.  A
  * driver that DROPS non-returns (velodyne_pointcloud's default mode, any is_dense cloud) publishes firings of unequal length back to

@@ -28,6 +28,7 @@ from .api import (  # noqa: F401
     ORDER_INPUT, ORDER_REFERENCE,
     SWEEP_OUT_MARKER_POINTS, SWEEP_OUT_ORDER,
     FRONT_WHY_DTYPE, WHY_CALL, WHY_SCAN, ADVICE,
+    FRONT_AUTO_DTYPE, AUTO_PHASE, ADVICE_AUTO_MASK,
     LABEL_MASK, LABEL_ROAD, LABEL_CURB, FLAG_ROI, FLAG_RING, FLAG_RING10,
     STAGE_VALPHA, STAGE_RING, STAGE_AZIMUTH, STAGE_RANGE2D, STAGE_DETECT, STAGE_SECTOR,
     STAGE_ANGLE_TABLE, STAGE_MAXDIST, STAGE_QUADRANTS, STAGE_BEAM_STOP,

@@ -95,6 +95,12 @@ WHY_SCAN = {name: 1 << k for k, name in enumerate(("LANE_TWO_RINGS", "RING_TWO_L
                                                    "CANDIDATES", "ROWS_SIGHTING", "OTHER"))}
 ADVICE = {name: 1 << k for k, name in enumerate(("MODE_2", "MODE_3", "LASERS128", "LONG_SWEEPS", "CURB_POINTS", "MULTI_SECTOR", "MULTI_SECTOR_CP",
                                                  "FRONT_OUTPUTS", "RESET", "CAPTURE_OFF", "BATCH", "NEVER", "CAPACITY", "CALL_AGAIN"))}
+# urf_set_front_auto (include/urf.h: urf_front_auto_info, URF_AUTO_*, URF_ADVICE_AUTO_MASK)
+FRONT_AUTO_DTYPE = np.dtype([(name, "<u4") for name in ("on", "phase", "applied", "refused", "left", "explained_calls", "digest_seq", "digest_scans",
+                                                        "digest_handed_back", "digest_scan_bits", "digest_helped", "digest_never",
+                                                        "digest_candidates", "digest_other")] + [("reserved", "<u4", (2,))])
+AUTO_PHASE = {"IDLE": 0, "LEARNING": 1, "SETTLED": 2}
+ADVICE_AUTO_MASK = sum(ADVICE[name] for name in ("MODE_3", "LASERS128", "LONG_SWEEPS", "CURB_POINTS", "MULTI_SECTOR", "MULTI_SECTOR_CP"))
 
 SWEEP_OUT_MARKER_POINTS, SWEEP_OUT_ORDER = 1, 2   # urf_set_sweep_outputs (include/urf.h: URF_SWEEP_OUT_*)
 
@@ -195,6 +201,8 @@ def lib(hooks=False):
         "urf_set_front_multi_sector_curb_points": [vp, C.c_int],
         "urf_set_front_outputs": [vp, C.c_int],
         "urf_front_explain": [vp, C.c_int, vp, C.c_uint32],
+        "urf_set_front_auto": [vp, C.c_int],
+        "urf_front_auto_query": [vp, vp],
         "urf_callback_path_preset": [vp, C.c_uint32],
         "urf_classify_batch_soa_dense": [vp, fp, fp, fp, vp, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, vp],
         "urf_classify_batch_pc2_dense": [vp, u8p, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -485,6 +493,20 @@ class Context:
         if n:
             self._check(self._lib.urf_front_explain(self._h, int(layout), out.ctypes.data, n), "urf_front_explain")
         return out
+
+    def set_front_auto(self, on):
+        """urf_set_front_auto: 1 lets the context apply front_explain's advice itself in front modes 2 and 3 -- the call's advice at the
+        call, the scans' from a learning pass behind its first few fused calls, read without waiting; switches are only ever turned on
+        (`applied` of front_auto() names them).  Turning it on again is a new start; 0 (default) stops it and leaves what it applied
+        (include/urf.h)."""
+        self._check(self._lib.urf_set_front_auto(self._h, int(on)), "urf_set_front_auto")
+
+    def front_auto(self):
+        """urf_front_auto_query: one FRONT_AUTO_DTYPE record -- `phase` (AUTO_PHASE), the ADVICE bits `applied`, `refused` and `left`,
+        the calls that carried the learning pass and the last digest.  Synchronises; changes nothing."""
+        out = np.zeros(1, FRONT_AUTO_DTYPE)
+        self._check(self._lib.urf_front_auto_query(self._h, out.ctypes.data), "urf_front_auto_query")
+        return out[0]
 
     def enable_kernel_timing(self, on=True):
         self._check(self._lib.urf_enable_kernel_timing(self._h, int(on)), "urf_enable_kernel_timing")

@@ -104,6 +104,27 @@ public:
     /* urf_set_front_multi_sector_curb_points: ... and, on top of setFrontMultiSector, with every curbPoints 1..8 that front mode 3 (and
      * setFrontCurbPoints) sends through the fused front end.  Decides nothing while setFrontMultiSector is off.  Times: profiles/front_multi_sector_cp_bench.json. */
     void setFrontMultiSectorCurbPoints(bool on) { set(urf_set_front_multi_sector_curb_points, "urf_set_front_multi_sector_curb_points", on); }
+    /* urf_set_front_auto: one switch instead of the five above and mode 3 -- with setFrontMode(2) the context turns on what its sweeps need
+     * to stay fused, the call's advice at the call, the scans' after a learning pass behind its first few fused calls (at most five).  It
+     * only ever adds; frontAuto().applied names what it turned on, and setFrontAuto(false) leaves that as it is. */
+    void setFrontAuto(bool on) { set(urf_set_front_auto, "urf_set_front_auto", on); }
+    /* urf_set_front_mode: 0 never, 1 (default) large batches of 64-laser sweeps, 2 every call the fused kernels apply to, 3 as 2 and
+     * curbPoints 1..8 -- setFrontAuto acts in modes 2 and 3 only. */
+    void setFrontMode(int mode)
+    {
+        const int rc = urf_set_front_mode(ctx_, mode);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_set_front_mode");
+    }
+    /* urf_front_auto_query: phase (URF_AUTO_*), the URF_ADVICE_* bits applied / refused / left, the last digest.  Synchronises. */
+    urf_front_auto_info frontAuto() const
+    {
+        urf_front_auto_info info;
+        const int rc = urf_front_auto_query(ctx_, &info);
+        if (rc != URF_OK)
+            throw Error(rc, "urf_front_auto_query");
+        return info;
+    }
 
     /* urf_front_explain: why each scan of the last call (Detector: the sweep waited for last; BatchDetector: the messages of the last
      * filtered()) left the fused front end, and which of the setters above keeps it.  layout: 0 firing order, 1 row-major organised.

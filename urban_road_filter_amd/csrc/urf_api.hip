@@ -30,6 +30,7 @@
 #include "urf_k_front_sectors.hpp"
 #include "urf_k_front_outputs.hpp"
 #include "urf_k_front_explain.hpp"
+#include "urf_k_front_digest.hpp"
 
 #define URF_ASYNC_SLOTS 4
 static_assert(URF_ASYNC_SLOTS == URF_MAX_IN_FLIGHT, "include/urf.h documents the number of sweeps in flight");
@@ -176,6 +177,13 @@ struct urf_planned {
     urf_policy::reasons call = { 0u, 0u };
     bool ms = false;
 };
+/* the call's part of the per-scan rule (urf_front_scan_rule): `rows`, the layout the records are counted in; sweep_n, a sweep's own length */
+static urf_fx_call fx_call_of(const urf_kargs& a, const urf_dev_params& dp, const urf_planned& planned, bool rows, uint32_t sweep_n)
+{
+    const uint32_t L = (uint32_t)dp.p.channels;
+    return urf_fx_call{ a.front, a.front_rows, a.front_cand_cap, rows ? 1u : 0u, (L == 16u || L == 32u || L == 64u || L == 128u) ? L : 0u,
+                        planned.ms ? 1u : 0u, dp.p.curbPoints != 5 ? 1u : 0u, planned.call.why, sweep_n };
+}
 struct urf_last_call {
     int kind = URF_LAST_NONE;
     uint32_t scans = 0;
@@ -349,6 +357,13 @@ struct urf_ctx {
     urf_planned planned;            /* run_pipeline: the call it planned last (its callers keep it with the call's arguments) */
     /* urf_front_explain: k_front_explain's per-scan records ([scans][URF_FX_WORDS]), grown by its first call */
     lazy_buf<uint32_t> fx_rec;
+    /* urf_set_front_auto's learning pass, allocated by the first call that turns the switch on: k_front_explain's records for a batch
+     * call (rows 0 .. max_batch - 1) and for the sweep of each slot (row max_batch + slot), k_front_digest's accumulators and its
+     * host-mapped digests ([1 + URF_ASYNC_SLOTS][URF_DG_WORDS] each: a batch call's first, then the slots') */
+    struct {
+        lazy_buf<uint32_t> rec, acc;
+        mapped_buf dig;
+    } au;
     std::string last_error;
     /* host-side cost of the callback path, phase by phase (only the build with the test hooks fills them:
      * URF_HOST_TIMES=1, printed by its benchmark loop; the context's layout is the same in both builds) */
@@ -448,6 +463,8 @@ static int scratch_alloc(urf_ctx* c, urf_scratch_group group)
 /* What the kernels of earlier calls reported, taken into the policy before a call's launches (never inside a stream capture: the first
  * row-major sighting lets the calls in flight on `st`, the stream the call launches on, finish -- what they handed back, possibly all
  * of their sweeps, says nothing about the calls to come -- and allocates the firing-order copies before the call takes its arguments). */
+static void auto_apply(urf_ctx* c, uint32_t bits);   /* (urf_set_front_auto: the setters' bodies, below) */
+
 int urf_policy::fold(urf_ctx* c, hipStream_t st)   /* (hipStream_t: ihipStream_t*) */
 {
     if (front_mode != 0 && !front_rows && !rows_oom && flags[URF_FLAG_ROWS_SIGHTED]) {
@@ -456,6 +473,7 @@ int urf_policy::fold(urf_ctx* c, hipStream_t st)   /* (hipStream_t: ihipStream_t
             set(front_rows, true);
             rows_probation = 16;
             forget_front();
+            auto_start();   /* (what a pass counted in firing order says nothing about these sweeps) */
         } else {
             set(rows_oom, true);   /* (such sweeps keep to the general kernels) */
             c->last_error.clear();
@@ -471,6 +489,31 @@ int urf_policy::fold(urf_ctx* c, hipStream_t st)   /* (hipStream_t: ihipStream_t
         set(front_direct, true);
     if (flags[URF_FLAG_FRONT_ALL_HANDED_BACK] && !every_batch())
         set(front_off, true);
+    /* urf_set_front_auto: the digest of the pass in flight, once its sequence word is the one the host handed to the pass (k_front_digest
+     * stores it last, behind a system-scope fence) -- never by waiting: a digest that has not arrived is looked for at the next call */
+    if (auto_on && auto_wait && auto_phase == URF_AUTO_LEARNING) {
+        const uint32_t which = auto_wait - 1u;
+        const volatile uint32_t* d = c->au.dig.p + (size_t)which * URF_DG_WORDS;
+        if (d[URF_DG_SEQ] == auto_seq) {
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);
+            uint32_t w[URF_DG_WORDS];
+            for (unsigned k = 0; k < URF_DG_WORDS; k++)
+                w[k] = d[k];
+            auto_wait = 0;
+            if (which == 0u || w[URF_DG_SCANS] != 0u) {   /* (a sweep without a result -- voided and run again --: discarded) */
+                std::memcpy(auto_digest_words, w, sizeof w);
+                const auto_step step = auto_digest(w, c->dp);
+                auto_left_digest = auto_digest_left(w);
+                auto_phase = step.phase;
+                if (step.again)
+                    auto_again++;
+                if (step.apply)
+                    auto_apply(c, step.apply);   /* (may allocate: before the call takes its arguments, outside any capture) */
+            } else if (auto_explained) {
+                auto_explained--;   /* (a pass that taught nothing does not count: at most five per new start that do) */
+            }
+        }
+    }
     return URF_OK;
 }
 
@@ -692,6 +735,7 @@ extern "C" int urf_set_params(urf_ctx* c, const urf_params* p)
     if (std::memcmp(&c->params, p, sizeof(*p)) != 0) {
         URF_HIP(c, hipMemsetAsync(c->k.ring_hint, 0, URF_ASYNC_SLOTS * sizeof(uint32_t), c->stream));
         c->pol.forget_front();   /* ... nor does what the fused front end made of them */
+        c->pol.auto_start();     /* ... nor what urf_set_front_auto learned from them */
     }
     c->params = *p;
     c->pol.epoch++;
@@ -772,21 +816,29 @@ extern "C" double urf_ring_threshold_cot(double angle_deg)
     return urf_cot_deg(angle_deg);
 }
 
-extern "C" int urf_set_front_mode(urf_ctx* c, int mode)
+/* by_auto: urf_set_front_auto's own application (auto_apply) -- everything the caller's setter does but the new start of the learning */
+static int set_front_mode(urf_ctx* c, int mode, bool by_auto)
 {
     if (!c || mode < 0 || mode > 3)
         return URF_ERR_INVALID_ARG;
+    const bool fresh = mode != c->pol.front_mode || (mode != 0 && c->pol.want_ring_sorted);
     if (mode != c->pol.front_mode && mode != 0)   /* (a new start) */
         c->pol.forget_front();
     c->pol.set(c->pol.front_mode, mode);
     if (mode != 0)
         c->pol.set(c->pol.want_ring_sorted, false);   /* (a caller that asks for ring-sorted results again pays for them again) */
+    if (fresh && !by_auto)
+        c->pol.auto_start();
     return URF_OK;
+}
+extern "C" int urf_set_front_mode(urf_ctx* c, int mode)
+{
+    return set_front_mode(c, mode, false);
 }
 
 /* The on / off switches of the fused front end that plan() reads: `prepare` (may be null) runs when the switch is turned on, before anything
  * changes, and may refuse; a change is a new start (forget_front); turning a switch on, like urf_set_front_mode, ends want_ring_sorted. */
-static int set_front_switch(urf_ctx* c, int on, bool urf_policy::*field, int (*prepare)(urf_ctx*))
+static int set_front_switch(urf_ctx* c, int on, bool urf_policy::*field, int (*prepare)(urf_ctx*), bool by_auto = false)
 {
     if (!c || (on != 0 && on != 1))
         return URF_ERR_INVALID_ARG;
@@ -796,17 +848,76 @@ static int set_front_switch(urf_ctx* c, int on, bool urf_policy::*field, int (*p
         if (rc != URF_OK)
             return rc;
     }
-    if ((on != 0) != c->pol.*field)   /* (a new start) */
+    if ((on != 0) != c->pol.*field) {   /* (a new start) */
         c->pol.forget_front();
+        if (!by_auto)
+            c->pol.auto_start();
+    }
     c->pol.set(c->pol.*field, on != 0);
     if (on)
         c->pol.set(c->pol.want_ring_sorted, false);
     return URF_OK;
 }
 
+/* the five switches, each with the URF_ADVICE_* bit that names it: the entry points below and auto_apply run the same row */
+static int long_sweeps_lds(urf_ctx* c);
+static int front_switch(urf_ctx* c, uint32_t advice_bit, int on, bool by_auto = false)
+{
+    switch (advice_bit) {
+    case URF_ADVICE_LASERS128:   /* what the fused kernels size for 64 lanes, sized for 128: allocated once, with the first call that turns the switch on */
+        return set_front_switch(c, on, &urf_policy::lasers128, [](urf_ctx* x) { return scratch_alloc(x, URF_SCR_LASERS128); }, by_auto);
+    case URF_ADVICE_LONG_SWEEPS:
+        return set_front_switch(c, on, &urf_policy::long_sweeps, long_sweeps_lds, by_auto);
+    case URF_ADVICE_CURB_POINTS:
+        return set_front_switch(c, on, &urf_policy::curb_points, nullptr, by_auto);
+    case URF_ADVICE_MULTI_SECTOR:   /* the star records' sectors, one per scratch element: allocated once, with the first call that turns the switch on */
+        return set_front_switch(c, on, &urf_policy::multi_sector, [](urf_ctx* x) { return scratch_alloc(x, URF_SCR_MULTI_SECTOR); }, by_auto);
+    case URF_ADVICE_MULTI_SECTOR_CP:   /* (allocates nothing: front_skey comes with urf_set_front_multi_sector, without which this switch decides nothing) */
+        return set_front_switch(c, on, &urf_policy::multi_sector_cp, nullptr, by_auto);
+    }
+    return URF_ERR_INVALID_ARG;
+}
+
+/* urf_set_front_auto applies advice: each bit through the code its setter runs, allocation included.  A bit that answers URF_ERR_OOM goes
+ * to auto_refused, the error text is cleared and the caller goes on without it; bits are only ever turned on. */
+static void auto_apply(urf_ctx* c, uint32_t bits)
+{
+    urf_policy& p = c->pol;
+    for (const uint32_t bit : { URF_ADVICE_LASERS128, URF_ADVICE_LONG_SWEEPS, URF_ADVICE_CURB_POINTS, URF_ADVICE_MULTI_SECTOR, URF_ADVICE_MULTI_SECTOR_CP })
+        if (bits & bit) {
+            if (front_switch(c, bit, 1, true) == URF_OK) {
+                p.auto_applied |= bit;
+            } else {
+                p.auto_refused |= bit;
+                c->last_error.clear();
+            }
+        }
+    if ((bits & URF_ADVICE_MODE_3) && set_front_mode(c, 3, true) == URF_OK)
+        p.auto_applied |= URF_ADVICE_MODE_3;
+}
+
+/* Call-level advice, at the call itself: behind fold(), in front of plan() and of the call's arguments (a switch may allocate a scratch
+ * group), outside any stream capture.  tiles, n_scans, capture: what plan() will read of the call. */
+static void auto_at_call(urf_ctx* c, uint32_t tiles, uint32_t n_scans, uint32_t capture, bool slot)
+{
+    urf_policy& p = c->pol;
+    if (!p.auto_on)
+        return;
+    urf_kargs a = c->k;
+    a.tiles = tiles;
+    a.n_scans = n_scans;
+    a.capture = capture;
+    urf_policy::reasons r = p.why(a, c->dp, slot, false);
+    if (const uint32_t bits = p.auto_call(r.why, r.advice)) {
+        auto_apply(c, bits);
+        r = p.why(a, c->dp, slot, false);
+    }
+    p.auto_left = r.advice & URF_ADVICE_LEFT_MASK;
+}
+
 extern "C" int urf_set_front_lasers128(urf_ctx* c, int on)
-{   /* what the fused kernels size for 64 lanes, sized for 128: allocated once, with the first call that turns the switch on */
-    return set_front_switch(c, on, &urf_policy::lasers128, [](urf_ctx* x) { return scratch_alloc(x, URF_SCR_LASERS128); });
+{
+    return front_switch(c, URF_ADVICE_LASERS128, on);
 }
 
 /* The finish kernels' dynamic LDS at URF_FRONT_LONG_MAX_TILES tiles: a device that does not grant a workgroup that much keeps the switch
@@ -825,22 +936,94 @@ static int long_sweeps_lds(urf_ctx* c)
 }
 extern "C" int urf_set_front_long_sweeps(urf_ctx* c, int on)
 {
-    return set_front_switch(c, on, &urf_policy::long_sweeps, long_sweeps_lds);
+    return front_switch(c, URF_ADVICE_LONG_SWEEPS, on);
 }
 
 extern "C" int urf_set_front_curb_points(urf_ctx* c, int on)
 {
-    return set_front_switch(c, on, &urf_policy::curb_points, nullptr);
+    return front_switch(c, URF_ADVICE_CURB_POINTS, on);
 }
 
 extern "C" int urf_set_front_multi_sector(urf_ctx* c, int on)
-{   /* the star records' sectors, one per scratch element: allocated once, with the first call that turns the switch on */
-    return set_front_switch(c, on, &urf_policy::multi_sector, [](urf_ctx* x) { return scratch_alloc(x, URF_SCR_MULTI_SECTOR); });
+{
+    return front_switch(c, URF_ADVICE_MULTI_SECTOR, on);
 }
 
 extern "C" int urf_set_front_multi_sector_curb_points(urf_ctx* c, int on)
-{   /* (allocates nothing: front_skey comes with urf_set_front_multi_sector, without which this switch decides nothing) */
-    return set_front_switch(c, on, &urf_policy::multi_sector_cp, nullptr);
+{
+    return front_switch(c, URF_ADVICE_MULTI_SECTOR_CP, on);
+}
+
+/* ---- urf_set_front_auto (include/urf.h) ------------------------------------------------------- */
+static_assert(sizeof(urf_front_auto_info) == 64 && offsetof(urf_front_auto_info, digest_seq) == 24, "include/urf.h: the digest's eight words in k_front_digest's order");
+/* Everything the learning pass will need, before any call launches it: nothing is allocated behind a call or inside a stream capture. */
+static int auto_alloc(urf_ctx* c)
+{
+    const size_t passes = 1 + URF_ASYNC_SLOTS;
+    int rc;
+    if ((rc = grow(c, c->au.rec, ((size_t)c->max_batch + URF_ASYNC_SLOTS) * URF_FX_WORDS)) != URF_OK || (rc = grow(c, c->au.acc, passes * URF_DG_WORDS)) != URF_OK)
+        return rc;
+    mapped_buf& m = c->au.dig;
+    if (!m.p) {
+        void *hp = nullptr, *dp_ = nullptr;
+        URF_HIP(c, hipHostMalloc(&hp, passes * URF_DG_WORDS * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+        m.p = (uint32_t*)hp;
+        m.cap = passes * URF_DG_WORDS;
+        std::memset(m.p, 0, m.cap * sizeof(uint32_t));
+        URF_HIP(c, hipHostGetDevicePointer(&dp_, hp, 0));
+        m.dev = (uint32_t*)dp_;
+    }
+    return URF_OK;
+}
+
+extern "C" int urf_set_front_auto(urf_ctx* c, int on)
+{
+    if (!c || (on != 0 && on != 1))
+        return URF_ERR_INVALID_ARG;
+    urf_policy& p = c->pol;
+    if (on) {
+        URF_HIP(c, hipSetDevice(c->device));
+        const int rc = auto_alloc(c);
+        if (rc != URF_OK) {
+            c->au.dig.release();   /* (all of it or none: a later call tries again) */
+            c->au.rec.release();
+            c->au.acc.release();
+            return rc;
+        }
+        p.auto_on = true;
+        p.auto_left = 0;
+        p.auto_start();   /* (turning it on again is a new start; a pass still in flight finishes into buffers that stay) */
+    } else {
+        p.auto_on = false;
+        p.auto_phase = URF_AUTO_IDLE;
+        p.auto_wait = 0;
+    }
+    return URF_OK;
+}
+
+extern "C" int urf_front_auto_query(urf_ctx* c, urf_front_auto_info* out)
+{
+    if (!c || !out)
+        return URF_ERR_INVALID_ARG;
+    const int rc = urf_synchronize(c);
+    if (rc != URF_OK)
+        return rc;
+    const urf_policy& p = c->pol;
+    std::memset(out, 0, sizeof *out);
+    out->applied = p.auto_applied;
+    if (!p.auto_on)
+        return URF_OK;
+    out->on = 1u;
+    out->phase = p.auto_phase;
+    out->refused = p.auto_refused;
+    out->left = p.auto_left | p.auto_left_digest;
+    out->explained_calls = p.auto_explained;
+    /* the pass in flight has completed with the stream: its digest as it stands, else the one fold() took last */
+    const uint32_t* d = p.auto_digest_words;
+    if (p.auto_wait && c->au.dig.p[(size_t)(p.auto_wait - 1u) * URF_DG_WORDS + URF_DG_SEQ] == p.auto_seq)
+        d = c->au.dig.p + (size_t)(p.auto_wait - 1u) * URF_DG_WORDS;
+    std::memcpy(&out->digest_seq, d, URF_DG_WORDS * sizeof(uint32_t));
+    return URF_OK;
 }
 
 extern "C" int urf_set_front_outputs(urf_ctx* c, int on)
@@ -1085,6 +1268,33 @@ static int order_row_after_main(urf_ctx* c, uint32_t row, hipStream_t st)
     return URF_OK;
 }
 
+/* urf_set_front_auto's learning pass behind a call that launched the fused kernels, on the call's stream: k_front_explain as
+ * urf_front_explain launches it -- layout 1 exactly when the call's sequence held the rows' probe and transpose --, then k_front_digest
+ * into digest `which` (0: a batch call's, 1 + i: slot i's).  rec_row: the first row of au.rec the call's records take; sweep_n: a sweep's
+ * own length.  One pass is in flight at a time; while learning is over, or the call kept the general kernels: nothing. */
+static int auto_pass(urf_ctx* c, const urf_kargs& a, const urf_dev_params& dp, const urf_planned& planned, hipStream_t st, uint32_t which,
+                     uint32_t rec_row, uint32_t sweep_n)
+{
+    urf_policy& p = c->pol;
+    if (!p.auto_on || p.auto_phase != URF_AUTO_LEARNING || p.auto_wait || !a.front || !c->au.dig.p)
+        return URF_OK;
+    const uint32_t n = a.n_scans;
+    uint32_t* const rec = c->au.rec.p + (size_t)rec_row * URF_FX_WORDS;
+    uint32_t* const acc = c->au.acc.p + (size_t)which * URF_DG_WORDS;
+    const bool rows = a.front_rows != 0u;
+    URF_HIP(c, hipMemsetAsync(rec, 0, (size_t)n * URF_FX_WORDS * sizeof(uint32_t), st));
+    URF_HIP(c, hipMemsetAsync(acc, 0, URF_DG_WORDS * sizeof(uint32_t), st));
+    if (++p.auto_seq == 0u)
+        p.auto_seq = 1u;   /* (0: what a fresh digest slot holds) */
+    hipLaunchKernelGGL(k_front_explain, dim3(a.tiles, n), dim3(64), 0, st, a, dp, rows ? 1u : 0u, rec);
+    hipLaunchKernelGGL(k_front_digest, dim3((n + 255u) / 256u), dim3(256), 0, st, a, fx_call_of(a, dp, planned, rows, sweep_n), rec, acc,
+                       c->au.dig.dev + (size_t)which * URF_DG_WORDS, p.auto_seq);
+    URF_HIP(c, hipGetLastError());
+    p.auto_wait = which + 1u;
+    p.auto_explained++;
+    return URF_OK;
+}
+
 /* ---- the pipeline ---------------------------------------------------------- */
 /* One call of the pipeline: a call of the public batch entry points (stream == nullptr: row 0 onwards, the context's stream), or one
  * sweep of the callback path on its row and stream.  Either caller publishes it as "the last call" (publish_last): a batch call at once,
@@ -1145,6 +1355,8 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
             rc = c->pol.fold(c, st);   /* (may allocate the row-major group: before the arguments are taken) */
         if (rc != URF_OK)
             return rc;
+        if (c->pol.auto_on && !call.general_only)   /* urf_set_front_auto: the call's advice, applied before it is planned (may allocate a scratch group) */
+            auto_at_call(c, std::max<uint32_t>((call.max_len + URF_TILE - 1) / URF_TILE, 1u), n_scans, (uint32_t)(call.capture >= 0 ? call.capture : c->capture), false);
     }
     urf_kargs a = kargs_row(c, call.row);
     a.x = call.x;
@@ -1302,6 +1514,11 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
     URF_HIP(c, hipGetLastError());
     if (call.info)
         URF_HIP(c, hipMemcpyAsync(call.info, a.info, (size_t)n_scans * sizeof(urf_scan_info), hipMemcpyDeviceToDevice, st));
+    if (!slot && !call.general_only) {   /* (a sweep of the callback path: urf_classify_pc2_async, behind its sequence) */
+        const int rc = auto_pass(c, a, dp, c->planned, st, 0u, call.row, 0u);
+        if (rc != URF_OK)
+            return rc;
+    }
     a_out = a;
     dp_out = dp;
     return URF_OK;
@@ -1977,6 +2194,8 @@ extern "C" int urf_classify_pc2_async(urf_ctx* c, const uint8_t* data, uint32_t 
     if (rc != URF_OK)
         return rc;
     c->pol.probation_sweep();
+    if (c->pol.auto_on)   /* urf_set_front_auto: the sweep's advice, applied before its sequence is chosen (a change bumps the epoch) */
+        auto_at_call(c, std::max<uint32_t>((n_run + URF_TILE - 1) / URF_TILE, 1u), 1u, (uint32_t)c->capture, true);
     /* the launch sequence of a sweep of this shape is captured once and replayed (one graph launch
      * instead of a dozen kernel launches per callback); anything it depends on bumps the epoch */
     const uint64_t key[3] = { c->pol.epoch,((uint64_t)n_run << 32) | point_step,
@@ -2039,6 +2258,13 @@ extern "C" int urf_classify_pc2_async(urf_ctx* c, const uint8_t* data, uint32_t 
             return rc;
     }
     HT(2, ht0);   /* graph launch (or the launches themselves) */
+    /* urf_set_front_auto's learning pass: no part of the captured sequence, on the sweep's stream behind it and in front of ev_done --
+     * the event urf_classify_pc2_wait waits for, the context's stream waits for before it touches a row (order_after_slots), and, on
+     * the same stream, whatever the row's next sweep launches (slots that share a row share its stream: max_batch < URF_ASYNC_SLOTS).
+     * The planes or staging rows it reads again belong to this slot resp. this row until then. */
+    rc = auto_pass(c, sl.cap_a, sl.cap_dp, sl.cap_planned, st, 1u + (uint32_t)(&sl - c->slots), c->max_batch + (uint32_t)(&sl - c->slots), n_points);
+    if (rc != URF_OK)
+        return rc;
     URF_HIP(c, hipEventRecord(sl.ev_done, st));
     HT(3, ht0);
     sl.pending = true;
@@ -2318,43 +2544,26 @@ extern "C" int urf_front_explain(urf_ctx* c, int layout, urf_front_why* out, uin
             lens[s] = std::min(offs[s + 1] - offs[s], a.max_len);
     }
     URF_HIP(c, hipStreamSynchronize(st));
-    const auto bits = [](const uint32_t* m) { return (uint32_t)(__builtin_popcount(m[0]) + __builtin_popcount(m[1]) + __builtin_popcount(m[2]) + __builtin_popcount(m[3])); };
+    const urf_fx_call k = fx_call_of(a, dp, l.planned, rows, 0u);
     for (uint32_t s = 0; s < n; s++) {
         const uint32_t* r = &rec[(size_t)s * URF_FX_WORDS];
+        const urf_fx_scan v = urf_front_scan_rule(k, r, ok[s], ncand[s], info[s].status, lens[s]);   /* (the rule k_front_digest applies on the device) */
         urf_front_why w;
         std::memset(&w, 0, sizeof w);
-        w.fused = (a.front && ok[s]) ? 1u : 0u;
+        w.fused = v.fused;
         w.call = l.planned.call.why;
-        w.advice = l.planned.call.advice;
+        w.advice = l.planned.call.advice | v.advice;
+        w.scan = v.scan;
         w.candidates = ncand[s];
         w.candidate_cap = a.front_cand_cap;
         if (info[s].status == URF_OK && lens[s] != 0u) {
-            w.lanes_two_rings = bits(r + URF_FX_LANE_MASK);
-            w.rings_two_lanes = bits(r + URF_FX_RING_MASK);
+            w.lanes_two_rings = urf_fx_bits4(r + URF_FX_LANE_MASK);
+            w.rings_two_lanes = urf_fx_bits4(r + URF_FX_RING_MASK);
             w.axis_points = r[URF_FX_AXIS];
             w.range_points = r[URF_FX_RANGE];
             w.multi_sector_firings = r[URF_FX_MULTI];
             w.max_sectors_per_firing = r[URF_FX_MAX_SECTORS];
             w.tiles_sectors_fall = r[URF_FX_FALL];
-            uint32_t scan = (w.lanes_two_rings ? URF_WHY_SCAN_LANE_TWO_RINGS : 0u) | (w.rings_two_lanes ? URF_WHY_SCAN_RING_TWO_LANES : 0u) |
-                            (w.axis_points ? URF_WHY_SCAN_AXIS : 0u) | (w.range_points ? URF_WHY_SCAN_RANGE : 0u);
-            if (rows && lasers && lens[s] % L != 0u)
-                scan |= URF_WHY_SCAN_ROWS_LENGTH;
-            if (scan)
-                w.advice |= URF_ADVICE_NEVER;
-            if (!l.planned.ms) {
-                const uint32_t ms = (w.multi_sector_firings ? URF_WHY_SCAN_MULTI_SECTOR : 0u) | (w.tiles_sectors_fall ? URF_WHY_SCAN_SECTORS_FALL : 0u);
-                if (ms)
-                    w.advice |= URF_ADVICE_MULTI_SECTOR | (dp.p.curbPoints != 5 ? URF_ADVICE_MULTI_SECTOR_CP : 0u);
-                scan |= ms;
-            }
-            if (a.front && ncand[s] > a.front_cand_cap)
-                scan |= URF_WHY_SCAN_CANDIDATES, w.advice |= URF_ADVICE_CAPACITY;
-            if (rows && a.front_rows == 0u)
-                scan |= URF_WHY_SCAN_ROWS_SIGHTING, w.advice |= URF_ADVICE_CALL_AGAIN;
-            if (!w.fused && !w.call && !scan)
-                scan = URF_WHY_SCAN_OTHER, w.advice |= URF_ADVICE_CALL_AGAIN;
-            w.scan = scan;
         }
         out[s] = w;
     }

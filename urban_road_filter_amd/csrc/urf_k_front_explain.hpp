@@ -1,6 +1,7 @@
 /*
  * urf_k_front_explain.hpp -- k_front_explain: which rules of the fused front end's march (urf_front.hpp) a scan of the LAST call breaks,
- * counted for urf_front_explain (urf_api.hip).  Off the hot path: launched by that entry point only, no classify call knows it.
+ * counted for urf_front_explain (urf_api.hip).  Off the hot path: launched by that entry point and, in a context that turned
+ * urf_set_front_auto on, behind the few calls that carry its learning pass (urf_k_front_digest.hpp); no other classify call knows it.
  *
  * It reads the call's points again and the scan's FINAL ring table (a.angle, info[s].n_rings) -- never the march's windows or its own
  * tables (front_lane_ring, front_ring_lane, the candidate lists), which a call without the fused kernels does not even fill -- and
@@ -34,6 +35,56 @@
 #define URF_FX_MAX_SECTORS 267u
 #define URF_FX_FALL 268u        /* tiles in which the sectors fall */
 #define URF_FX_WORDS 272u
+
+/* The per-scan rule: what a scan's record, its flag (front_ok), its candidate count, its status and its length say under the call's
+ * settings -- `fused`, the URF_WHY_SCAN_* bits and the URF_ADVICE_* they ask for.  One function for the host's loop (urf_front_explain)
+ * and for the device (k_front_digest, urf_k_front_digest.hpp).  The call's part: */
+struct urf_fx_call {
+    uint32_t front, front_rows, cand_cap;   /* a.front, a.front_rows, a.front_cand_cap */
+    uint32_t rows;        /* the layout the record was counted in: 1 row-major */
+    uint32_t lasers;      /* params.channels where it is 16, 32, 64 or 128, else 0 (no laser slots to speak of) */
+    uint32_t ms;          /* the march was, or would have been, the multi-sector one (urf_policy::ms_ok) */
+    uint32_t cp_other;    /* curbPoints != 5 */
+    uint32_t call_why;    /* URF_WHY_CALL_* of the call as planned */
+    uint32_t len;         /* a sweep of the callback path: the caller's number of points; 0: the scan's own length */
+};
+struct urf_fx_scan {
+    uint32_t fused, scan, advice;
+};
+__host__ __device__ inline uint32_t urf_fx_bits4(const uint32_t* m)
+{
+    uint32_t n = 0;
+    for (int k = 0; k < 4; k++)
+        for (uint32_t v = m[k]; v; v &= v - 1u)
+            n++;
+    return n;
+}
+__host__ __device__ inline urf_fx_scan urf_front_scan_rule(const urf_fx_call& k, const uint32_t* r, uint32_t ok, uint32_t ncand, int status, uint32_t len)
+{
+    urf_fx_scan o = { (k.front && ok) ? 1u : 0u, 0u, 0u };
+    if (status != URF_OK || len == 0u)
+        return o;   /* URF_TOO_FEW_POINTS, an empty scan, a voided sweep: no rule applies */
+    uint32_t scan = (urf_fx_bits4(r + URF_FX_LANE_MASK) ? URF_WHY_SCAN_LANE_TWO_RINGS : 0u) | (urf_fx_bits4(r + URF_FX_RING_MASK) ? URF_WHY_SCAN_RING_TWO_LANES : 0u) |
+                    (r[URF_FX_AXIS] ? URF_WHY_SCAN_AXIS : 0u) | (r[URF_FX_RANGE] ? URF_WHY_SCAN_RANGE : 0u);
+    if (k.rows && k.lasers && len % k.lasers != 0u)
+        scan |= URF_WHY_SCAN_ROWS_LENGTH;
+    if (scan)
+        o.advice |= URF_ADVICE_NEVER;
+    if (!k.ms) {
+        const uint32_t ms = (r[URF_FX_MULTI] ? URF_WHY_SCAN_MULTI_SECTOR : 0u) | (r[URF_FX_FALL] ? URF_WHY_SCAN_SECTORS_FALL : 0u);
+        if (ms)
+            o.advice |= URF_ADVICE_MULTI_SECTOR | (k.cp_other ? URF_ADVICE_MULTI_SECTOR_CP : 0u);
+        scan |= ms;
+    }
+    if (k.front && ncand > k.cand_cap)
+        scan |= URF_WHY_SCAN_CANDIDATES, o.advice |= URF_ADVICE_CAPACITY;
+    if (k.rows && k.front_rows == 0u)
+        scan |= URF_WHY_SCAN_ROWS_SIGHTING, o.advice |= URF_ADVICE_CALL_AGAIN;
+    if (!o.fused && !k.call_why && !scan)
+        scan = URF_WHY_SCAN_OTHER, o.advice |= URF_ADVICE_CALL_AGAIN;
+    o.scan = scan;
+    return o;
+}
 
 __global__ __launch_bounds__(64) void k_front_explain(urf_kargs a, urf_dev_params dp, unsigned layout, uint32_t* __restrict__ recs)
 {

@@ -42,6 +42,11 @@ struct ihipStream_t;   /* (hipStream_t is a pointer to it: fold() is the one mem
  * 255 x 2048 / 16 < 65536 (16 lasers per firing). */
 #define URF_FRONT_LONG_MAX_TILES 256u
 
+/* urf_set_front_auto (urf_policy::auto_call / auto_digest): how often a digest may say "call again" per new start -- the suite's own
+ * figure: its tests run three calls before they demand that every hand-back is explained --, and the advice auto never applies */
+#define URF_AUTO_AGAIN_MAX 3u
+#define URF_ADVICE_LEFT_MASK (URF_ADVICE_NEVER | URF_ADVICE_CAPACITY | URF_ADVICE_BATCH | URF_ADVICE_CAPTURE_OFF | URF_ADVICE_RESET | URF_ADVICE_FRONT_OUTPUTS | URF_ADVICE_CALL_AGAIN)
+
 /* The launch policy: which kernels a call launches, decided on the host from what the kernels of earlier calls reported through the
  * host-mapped flag words (enum urf_flag).  fold() is the only reader of the words: a batch call runs it in run_pipeline, a sweep of the
  * callback path in urf_classify_pc2_async, before either launches anything.  plan() turns the fields into a call's urf_kargs.  Every
@@ -102,6 +107,63 @@ struct __attribute__((visibility("hidden"))) urf_policy {
      * callback path take the fused kernels too. */
     bool front_rows = false, rows_oom = false, rows_used = false;
     uint32_t rows_probation = 0;
+
+    /* urf_set_front_auto: the context applies urf_front_explain's advice itself, in modes 2 and 3 (every_batch()).  plan() reads none of
+     * these fields; what auto applies goes through the setters' own code and reaches plan() as their fields.  auto_phase: URF_AUTO_*;
+     * auto_applied / auto_refused: URF_ADVICE_* bits it turned on / could not have (URF_ERR_OOM); auto_again: CALL_AGAIN digests taken
+     * since the last new start (at most URF_AUTO_AGAIN_MAX); auto_left / auto_left_digest: the advice of the last call / digest it never applies;
+     * auto_explained: calls that carried the learning pass since the last new start.  auto_wait: 1 + the digest slot of the one pass in
+     * flight (0: none), auto_seq: the sequence number handed to it -- fold() takes the digest once its first word is that number. */
+    bool auto_on = false;
+    uint32_t auto_phase = URF_AUTO_IDLE, auto_applied = 0, auto_refused = 0, auto_again = 0, auto_left = 0, auto_left_digest = 0, auto_explained = 0;
+    uint32_t auto_wait = 0, auto_seq = 0;
+    uint32_t auto_digest_words[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };   /* the digest fold() took last (urf_front_auto_query) */
+    /* A new start of the learning: urf_set_params with other parameters, urf_set_front_mode with another mode (or ending a sticky
+     * read-out), a switch setter that changes its switch, the row-major sighting, urf_set_front_auto(ctx, 1) -- whatever runs
+     * forget_front() for a reason other than auto's own application.  A pass still in flight teaches nothing any more. */
+    void auto_start()
+    {
+        if (!auto_on)
+            return;
+        auto_phase = every_batch() ? URF_AUTO_LEARNING : URF_AUTO_IDLE;
+        auto_refused = auto_again = auto_explained = auto_wait = auto_left_digest = 0;
+        for (uint32_t& w : auto_digest_words)   /* (the digest of other parameters or settings says nothing any more) */
+            w = 0;
+    }
+    /* The URF_ADVICE_* bits to apply at a call, on the host, before it is planned: why() of the call under the settings as they are.
+     * NEVER, CAPTURE_OFF and RESET name something auto does not touch, and with one of them missing no switch makes the call fused;
+     * BATCH does not block (a sweep of the callback path may still be sighted row-major). */
+    uint32_t auto_call(uint32_t why_bits, uint32_t advice) const
+    {
+        if (!auto_on || !every_batch() || !why_bits || (advice & (URF_ADVICE_NEVER | URF_ADVICE_CAPTURE_OFF | URF_ADVICE_RESET)))
+            return 0u;
+        return advice & URF_ADVICE_AUTO_MASK & ~auto_refused;
+    }
+    /* What a digest (k_front_digest: seq, scans, handed_back, scan_bits, helped, never, candidates, other) teaches: the bits to apply and
+     * the next phase; again: the digest was one of the URF_AUTO_AGAIN_MAX that may say "call again". */
+    struct auto_step { uint32_t apply, phase; bool again; };
+    auto_step auto_digest(const uint32_t* d, const urf_dev_params& dp) const
+    {
+        if (!auto_on || !every_batch())
+            return auto_step{ 0u, URF_AUTO_IDLE, false };
+        if (d[4] > 0u) {   /* helped: the multi-sector march keeps those scans */
+            const uint32_t want = URF_ADVICE_MULTI_SECTOR | (dp.p.curbPoints != 5 ? URF_ADVICE_MULTI_SECTOR_CP : 0u);
+            const uint32_t have = (multi_sector ? URF_ADVICE_MULTI_SECTOR : 0u) | (multi_sector_cp ? URF_ADVICE_MULTI_SECTOR_CP : 0u);
+            const uint32_t apply = want & ~have & ~auto_refused;
+            if (apply)
+                return auto_step{ apply, URF_AUTO_LEARNING, false };
+        }
+        if (d[2] == 0u || d[5] + d[6] == d[2])   /* nothing handed back, or nothing auto can lift */
+            return auto_step{ 0u, URF_AUTO_SETTLED, false };
+        if ((d[7] > 0u || (d[3] & URF_WHY_SCAN_ROWS_SIGHTING)) && auto_again < URF_AUTO_AGAIN_MAX)   /* a repaired speculation, a first sighting */
+            return auto_step{ 0u, URF_AUTO_LEARNING, true };
+        return auto_step{ 0u, URF_AUTO_SETTLED, false };
+    }
+    /* the advice in a digest that auto never applies (auto_left) */
+    static uint32_t auto_digest_left(const uint32_t* d)
+    {
+        return (d[5] ? URF_ADVICE_NEVER : 0u) | (d[6] ? URF_ADVICE_CAPACITY : 0u) | ((d[7] || (d[3] & URF_WHY_SCAN_ROWS_SIGHTING)) ? URF_ADVICE_CALL_AGAIN : 0u);
+    }
 
     template <class T>
     void set(T& field, T value)
