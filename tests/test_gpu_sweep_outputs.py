@@ -10,9 +10,10 @@ import pytest
 
 import oracles as O
 import urban_road_filter_amd as u
+from hipmem import DevBuf
 from test_gpu_async import records
 from test_gpu_front import ring_major
-from test_gpu_front_outputs import Soa, batch_readouts, lasers_params, nudged, repeated_firings, same
+from test_gpu_front_outputs import Soa, batch_readouts, check_labels, lasers_params, nudged, repeated_firings, same
 
 pytestmark = pytest.mark.gpu
 N = 64 * 2048
@@ -342,7 +343,66 @@ def test_a_batch_call_after_sweeps_with_the_switch_on():
             assert np.array_equal(a.view(np.uint32), c.view(np.uint32))
 
 
-# ---- 12. the A/B switch of the build with the test hooks ----
+# ---- 12. both users of the read-out launcher in one context ----
+def shuffled(cloud, seed):
+    """The sweep's points in random order: no firing order, no rows -- the fused front end hands such a scan back."""
+    perm = np.random.RandomState(seed).permutation(len(cloud[0]))
+    return tuple(np.ascontiguousarray(a[perm]) for a in cloud)
+
+
+@pytest.mark.parametrize("direct", [0, 1])
+def test_the_callback_path_and_the_batch_read_backs_share_one_launcher(direct):
+    """64 x 256 sweeps.  A sweep of the callback path with both products (captured); a fused batch of three scans whose middle one is
+    unorganised and handed back; urf_ordered_indices for each scan (the launcher from scan 0, 1 and 2) and urf_marker_points_batch; the
+    first sweep again, five times: once per slot and then in a slot that has captured it, a replay.  Every list and every marker point against oracle B, exact; the replay against the first
+    result, exact.  (A context of three scans: the batch needs three rows; its four slots still share them -- slot 3 runs on row 0.)"""
+    p = wide()
+    n = 64 * 256
+    key, sweep = small(0)
+    rs = ref(key, sweep, p)
+    named = [small(1), (("64x256", 3, 32, "shuffled"), shuffled(small(1)[1], 5)), small(2)]
+    refs = [ref(k, c, p) for k, c in named]
+    assert all(r[1]["status"] == 0 and r[1]["n_road"] > 1000 and len(r[2]["marker_pts"]) > 50 for r in refs + [rs])
+    b = Soa([c for _, c in named])
+    with u.Context(n, 3, params=p) as ctx:
+        ctx.set_front_mode(2)
+        ctx.set_front_outputs(1)
+        ctx.set_sweep_outputs(BOTH)
+        ctx.set_sweep_results_direct(direct)
+        t = submit(ctx, sweep)
+        check_ticket(ctx, t, sweep, rs, ("captured", direct))
+        first = [a.copy() for a in results(ctx, t)]
+        assert ctx.callback_path_captures()[0] == 1
+        b.classify(ctx)
+        assert ctx.front_scans() == 2                      # the middle scan went back to the general kernels
+        check_labels(b, refs)
+        for s in range(3):
+            got = ctx.ordered_indices(n, scan=s)
+            for g, name in zip(got, ("road_order", "curb_order", "ring10_order")):
+                assert np.array_equal(g, refs[s][2][name]), (direct, s, name)
+        dpts, dn = DevBuf(16 * 361 * 3), DevBuf(4 * 3)
+        dpts.fill(0xEE)
+        dn.fill(0xEE)
+        ctx.marker_points_batch(dpts, dn)
+        ctx.synchronize()
+        pts, cnt = dpts.to_numpy(np.float32).reshape(3, 361, 4), dn.to_numpy(np.uint32)
+        for s in range(3):
+            want = refs[s][2]["marker_pts"]
+            assert cnt[s] == len(want) and np.array_equal(pts[s][:cnt[s]].view(np.uint32), want.view(np.uint32)), (direct, s)
+        assert ctx.front_scans() == 2                      # (no second run of the batch)
+        # Submissions take the four slots in turn (the first sweep took slot 0), each slot keeps its own sequences, and what the batch
+        # reported may have bumped the epoch: reps 0-3 go to slots 1, 2, 3, 0 and may each capture; rep 4 is back in slot 1, which
+        # captured at rep 0 under the epoch that has stood since the batch, so it must replay.
+        for rep in range(5):
+            before = ctx.callback_path_captures()[0]
+            t = submit(ctx, sweep)
+            check_ticket(ctx, t, sweep, rs, ("again", direct, rep))
+            for a, f in zip(results(ctx, t), first):
+                assert a.shape == f.shape and np.array_equal(a.view(np.uint32), f.view(np.uint32)), (direct, rep)
+            assert rep < 4 or ctx.callback_path_captures()[0] == before, "rep 4: a replay"
+
+
+# ---- 13. the A/B switch of the build with the test hooks ----
 def test_both_bits_with_the_kernels_of_each_product_alone():
     """Debug flag 32 (include/urf_test_hooks.h): both bits set, the sequence launches k_ring_order, k_marker_ring, k_ordered_lists and
     k_marker_bins one by one instead of k_sweep_rings / k_sweep_lists -- the arm tools/sweep_outputs_bench.py measures against."""

@@ -49,7 +49,7 @@ def test_bits_above_three_are_refused():
     """With a context where there is a device; the refusal comes before any allocation.  Without one the rule is still in the
     source: the check on the bits stands in front of everything that needs the device."""
     from conftest import gpu_available
-    src = open(os.path.join(os.path.dirname(api.__file__), "csrc", "urf_api.hip")).read()
+    src = open(os.path.join(os.path.dirname(api.__file__), "csrc", "urf_api_sweep.hpp")).read()   # (the callback path's part of urf_api.hip)
     body = src[src.index('extern "C" int urf_set_sweep_outputs('):]
     body = body[:body.index("\n}\n")]
     assert body.index("bits & ~(URF_SWEEP_OUT_MARKER_POINTS | URF_SWEEP_OUT_ORDER)") < body.index("sweep_outputs_alloc(") < body.index("pol.set(")

@@ -48,17 +48,25 @@ def test_the_merged_ring_kernel_holds_what_its_two_parts_hold(table):
 
 
 def test_the_host_launches_them_and_names_them():
-    """The sequence launches the new kernels with both bits and the existing ones otherwise, as one linear chain; DESIGN.md section 4
-    names them.  (urf_kernel_name's table is the eight timed stages of the classification, URF_NUM_KERNELS, fixed by the ABI: the
-    read-out kernels never had a stage there.)"""
+    """The read-out chain (launch_readouts, urf_api.hip: the one launcher of the callback path's sequence and of the batch read-backs)
+    launches the new kernels with both bits and the existing ones otherwise, each from one place, as one linear chain;
+    sweep_outputs_launch (urf_api_sweep.hpp) is that chain and nothing that forks or joins; DESIGN.md section 4 names them.
+    (urf_kernel_name's table is the eight timed stages of the classification, URF_NUM_KERNELS, fixed by the ABI: the read-out kernels
+    never had a stage there.)"""
     csrc = os.path.join(ROOT, "urban_road_filter_amd", "csrc")
     api = open(os.path.join(csrc, "urf_api.hip")).read()
-    body = api[api.index("static int sweep_outputs_launch("):]
+    sweep = open(os.path.join(csrc, "urf_api_sweep.hpp")).read()
+    chain = api[api.index("static int launch_readouts("):]
+    chain = chain[:chain.index("\n}\n")]
+    body = sweep[sweep.index("static int sweep_outputs_launch("):]
     body = body[:body.index("\n}\n")]
     for k in NEW + ["k_ring_order", "k_marker_ring", "k_marker_ring_literal", "k_ordered_lists", "k_marker_bins", "k_front_out_prep",
                     "k_ring_order_front", "k_marker_ring_front", "k_marker_ring_literal_front", "k_marker_bins_front"]:
-        assert re.search(r"hipLaunchKernelGGL\(%s," % k, body), k
-    assert "hipStreamWaitEvent" not in body and "hipEventRecord" not in body   # one linear chain: no fork, no join
+        assert re.search(r"hipLaunchKernelGGL\(%s," % k, chain), k
+        assert len(re.findall(r"hipLaunchKernelGGL\(%s," % k, api + sweep)) == 1, k   # ... and from nowhere else
+    assert "launch_readouts(" in body and "hipLaunchKernelGGL" not in body
+    for text in (chain, body):
+        assert "hipStreamWaitEvent" not in text and "hipEventRecord" not in text   # one linear chain: no fork, no join
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     for k in NEW:
         assert k in design, k

@@ -45,7 +45,7 @@ def test_the_libraries_export_them_and_refuse_a_null_context_first(hooks):
 def test_the_checks_stand_in_front_of_the_switch():
     """The value, then the sweeps in flight, then the allocation, then the policy field -- in the source, and on a device where there is one."""
     from conftest import gpu_available
-    src = open(os.path.join(os.path.dirname(api.__file__), "csrc", "urf_api.hip")).read()
+    src = open(os.path.join(os.path.dirname(api.__file__), "csrc", "urf_api_sweep.hpp")).read()   # (the callback path's part of urf_api.hip)
     body = src[src.index('extern "C" int urf_set_sweep_quantum('):]
     body = body[:body.index("\n}\n")]
     assert body.index("points % URF_TILE") < body.index("sl.pending") < body.index("grow(") < body.index("pol.set(")

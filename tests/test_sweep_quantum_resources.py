@@ -40,12 +40,20 @@ def test_the_host_launches_it_in_a_padded_sequence_only():
     """slot_launch launches k_pc2_to_soa_pad for a padded sweep and k_pc2_to_soa otherwise; the sweep's length is no kernel argument
     frozen in the graph but a device word, copied in front of the launch; DESIGN.md names the kernel."""
     csrc = os.path.join(ROOT, "urban_road_filter_amd", "csrc")
-    api = open(os.path.join(csrc, "urf_api.hip")).read()
-    body = api[api.index("static int slot_launch("):]
-    body = body[:body.index("\n}\n")]
+    api = open(os.path.join(csrc, "urf_api_sweep.hpp")).read()   # (the callback path's part of urf_api.hip's translation unit)
+
+    def function(start):
+        text = api[api.index(start):]
+        return text[:text.index("\n}\n")]
+    body = function("static int slot_launch(")
     assert re.search(r"if \(sl\.pad\)[^;]*hipLaunchKernelGGL\(k_pc2_to_soa_pad,[^;]*sl\.d_n\.p", body, re.S)
     assert re.search(r"else\s+hipLaunchKernelGGL\(k_pc2_to_soa,", body)
-    sub = api[api.index('extern "C" int urf_classify_pc2_async('):]
-    sub = sub[:sub.index("\n}\n")]
-    assert sub.index("hipMemcpyAsync(sl.d_n.p, sl.h_n.p, sizeof(uint32_t)") < sub.index("hipStreamBeginCapture(")
+    # the path through urf_classify_pc2_async: the stage step, which holds the copy of the length word, stands in front of the sequence
+    # step, which holds the capture -- and the copy is nowhere else, so no captured sequence holds it
+    sub, stage, seq = function('extern "C" int urf_classify_pc2_async('), function("static int sweep_stage("), function("static int sweep_sequence(")
+    copy = "hipMemcpyAsync(sl.d_n.p, sl.h_n.p, sizeof(uint32_t)"
+    assert copy in stage and api.count(copy) == 1 and "hipStreamBeginCapture(" not in stage
+    assert "hipStreamBeginCapture(" in seq and api.count("hipStreamBeginCapture(") == 1
+    assert seq.index("hipStreamBeginCapture(") < seq.index("slot_launch(") < seq.index("hipStreamEndCapture(")
+    assert sub.index("sweep_stage(") < sub.index("sweep_sequence(") and "hipStreamBeginCapture(" not in sub
     assert "k_pc2_to_soa_pad" in open(os.path.join(ROOT, "DESIGN.md")).read()

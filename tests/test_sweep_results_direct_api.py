@@ -44,7 +44,7 @@ def test_the_libraries_export_it_and_refuse_bad_arguments_first(hooks):
 
 
 def test_other_values_are_refused_in_front_of_everything_that_needs_the_device():
-    src = open(os.path.join(os.path.dirname(api.__file__), "csrc", "urf_api.hip")).read()
+    src = open(os.path.join(os.path.dirname(api.__file__), "csrc", "urf_api_sweep.hpp")).read()   # (the callback path's part of urf_api.hip)
     body = _body(src, 'extern "C" int urf_set_sweep_results_direct(')
     assert body.index("on != 0 && on != 1") < body.index("URF_ERR_INVALID_ARG") < body.index("sl.pending") < body.index("URF_ERR_BUSY")
     assert body.index("URF_ERR_BUSY") < body.index("hipSetDevice") < body.index("sweep_outputs_alloc(") < body.index("pol.set(")

@@ -47,18 +47,24 @@ def test_the_packed_body_adds_two_words_of_lds(table, kernel):
 
 
 def test_the_host_launches_them_and_copies_nothing_for_them():
-    """sweep_outputs_launch launches the new kernels beside the ones it had, still as one linear chain, and returns in front of the two
-    copies when the switch is on; DESIGN.md section 4 names them."""
+    """The read-out chain (launch_readouts, urf_api.hip) launches the new kernels beside the ones it had, still as one linear chain,
+    and sweep_outputs_launch (urf_api_sweep.hpp), which is that chain and two copies, returns in front of the copies when the switch is
+    on; DESIGN.md section 4 names them."""
     csrc = os.path.join(ROOT, "urban_road_filter_amd", "csrc")
     api = open(os.path.join(csrc, "urf_api.hip")).read()
-    body = api[api.index("static int sweep_outputs_launch("):]
+    sweep = open(os.path.join(csrc, "urf_api_sweep.hpp")).read()
+    chain = api[api.index("static int launch_readouts("):]
+    chain = chain[:chain.index("\n}\n")]
+    body = sweep[sweep.index("static int sweep_outputs_launch("):]
     body = body[:body.index("\n}\n")]
     for k in NEW:
-        assert re.search(r"hipLaunchKernelGGL\(%s," % k, body), k
-    assert "hipStreamWaitEvent" not in body and "hipEventRecord" not in body
-    assert body.count("hipMemcpyAsync") == 2
-    assert body.index("if (direct)\n        return URF_OK;") < body.index("hipMemcpyAsync")
-    assert "hipHostMallocMapped | hipHostMallocCoherent" in api
+        assert re.search(r"hipLaunchKernelGGL\(%s," % k, chain), k
+    for text in (chain, body):
+        assert "hipStreamWaitEvent" not in text and "hipEventRecord" not in text
+    assert "hipMemcpy" not in chain and body.count("hipMemcpyAsync") == 2
+    assert body.index("launch_readouts(") < body.index("if (direct)\n        return URF_OK;") < body.index("hipMemcpyAsync")
+    alloc = sweep[sweep.index("static int sweep_outputs_alloc("):]
+    assert "hipHostMallocMapped | hipHostMallocCoherent" in alloc[:alloc.index("\n}\n")]
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     for k in NEW:
         assert k in design, k

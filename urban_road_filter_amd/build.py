@@ -24,7 +24,7 @@ LIB_TEST = os.path.join(HERE, "liburf_hip_test.so")
 SOURCES = ["urf_api.hip", "params.cpp", "detector.cpp", "marker.cpp"]
 HOOK_SOURCES = ["synth.cpp"]                 # liburf_hip_test.so only
 HOOK_DEFINES = ["URF_ENABLE_TEST_HOOKS=1"]
-HEADERS = ["urf_internal.hpp", "urf_policy.hpp", "urf_device.hpp", "urf_kernels.hpp", "urf_k_table.hpp", "urf_k_split.hpp", "urf_k_star.hpp", "urf_k_ring.hpp",
+HEADERS = ["urf_internal.hpp", "urf_policy.hpp", "urf_ctx.hpp", "urf_api_sweep.hpp", "urf_device.hpp", "urf_kernels.hpp", "urf_k_table.hpp", "urf_k_split.hpp", "urf_k_star.hpp", "urf_k_ring.hpp",
            "urf_k_beams_label.hpp", "urf_k_readouts.hpp", "urf_k_outputs.hpp", "urf_k_clouds.hpp", "urf_k_markers.hpp", "urf_k_dense.hpp", "urf_front.hpp", "urf_k_front_sectors.hpp", "urf_k_front_outputs.hpp", "urf_k_front_explain.hpp", "urf_k_front_digest.hpp", "detector.hpp", "marker.hpp",
            "../../include/urf.h", "../../include/urf_test_hooks.h", "../../include/urf_libm.h"]
 

@@ -32,86 +32,7 @@
 #include "urf_k_front_explain.hpp"
 #include "urf_k_front_digest.hpp"
 
-#define URF_ASYNC_SLOTS 4
-static_assert(URF_ASYNC_SLOTS == URF_MAX_IN_FLIGHT, "include/urf.h documents the number of sweeps in flight");
-
-/* A lazily sized buffer of T -- device memory, or pinned host memory (Host) --: grow() makes it large enough for the largest
- * request so far, and the context frees it with itself. */
-template <class T, bool Host = false>
-struct lazy_buf {
-    T* p = nullptr;
-    size_t cap = 0;   /* elements */
-    lazy_buf() = default;
-    lazy_buf(const lazy_buf&) = delete;
-    lazy_buf& operator=(const lazy_buf&) = delete;
-    ~lazy_buf() { release(); }
-    void release()
-    {
-        if (p)
-            (void)(Host ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-        cap = 0;
-    }
-};
-/* Pinned host memory that kernels write themselves (urf_set_sweep_results_direct): mapped into the device's address space and coherent,
- * so that the host sees the stores once the event behind the kernel has completed, whatever the environment says about host memory. */
-struct mapped_buf {
-    uint32_t* p = nullptr;    /* the host's pointer */
-    uint32_t* dev = nullptr;  /* the device's (hipHostGetDevicePointer) */
-    size_t cap = 0;           /* words */
-    mapped_buf() = default;
-    mapped_buf(const mapped_buf&) = delete;
-    mapped_buf& operator=(const mapped_buf&) = delete;
-    ~mapped_buf() { release(); }
-    void release()
-    {
-        if (p)
-            (void)hipHostFree(p);
-        p = dev = nullptr;
-        cap = 0;
-    }
-};
-
-/* Every scratch array of urf_kargs, declared once with its elements per row: X(field, elements).  A row is one scan's slice of
- * each array -- scan r of a batch call, or the sweep of the callback path that runs on row r -- and starts r * elements into it
- * (kargs_row).  Most arrays have max_batch rows; the two per-call counters (SLOTS: the URF_LIST_COUNT work-list lengths and the
- * ring-count hint) have URF_ASYNC_SLOTS, one per sweep in flight, whatever max_batch is.  urf_create allocates SCANS and SLOTS;
- * CAPTURE comes with the first urf_enable_stage_capture, ROW_MAJOR (the firing-order copies of row-major organised sweeps) once
- * such a sweep has been sighted (rows_state_update), LASERS128 (what the fused front end sizes for 64 lanes, sized for 128: urf_front.hpp)
- * with the first urf_set_front_lasers128(ctx, 1), MULTI_SECTOR (the star records' sectors, k_front*_ms -> k_front_sectors) with the first
- * urf_set_front_multi_sector(ctx, 1).  sstride, max_tiles and front_cand_cap are the context's (scratch_walk). */
-#define URF_SCRATCH_SCANS(X)                                                                                                     \
-    X(rx, sstride) X(ry, sstride) X(rz, sstride) X(rec, sstride)                                                                 \
-    X(sr, sstride) X(sz, sstride) X(sslot, sstride) X(ssrt16, sstride) X(ssrt, sstride) X(wsg, sstride)                          \
-    X(big_r, sstride) X(big_z, sstride) X(big_i, sstride)                                                                        \
-    X(tile_roi, max_tiles) X(roi_bits, max_tiles * (URF_TILE / 64)) X(troff, max_tiles * (URF_MAX_CHANNELS + 1))                 \
-    X(tsoff, max_tiles * (URF_MAX_SECTORS + 1)) X(tmaxs, max_tiles * URF_MAX_CHANNELS)                                           \
-    X(rpre, URF_MAX_CHANNELS * (max_tiles + 1)) X(rstart, URF_MAX_CHANNELS * max_tiles)                                          \
-    X(angle, URF_MAX_CHANNELS) X(ring_thr, URF_MAX_CHANNELS * 4) X(ring_lut, URF_LUT_CELLS) X(ring_cnt, URF_MAX_CHANNELS)        \
-    X(ring_off, URF_MAX_CHANNELS + 1)                                                                                            \
-    X(sec_cnt, URF_MAX_SECTORS) X(sec_run, URF_MAX_SECTORS) X(sec_off, URF_MAX_SECTORS + 1) X(star_hit, URF_MAX_SECTORS)         \
-    X(star_first, URF_MAX_SECTORS) X(star_list_mid, URF_MAX_SECTORS) X(star_list_big, URF_MAX_SECTORS)                           \
-    X(star_list_runs, URF_MAX_SECTORS) X(tie_list, URF_MAX_SECTORS) X(tie_post, URF_MAX_SECTORS)                                 \
-    X(table_upto, 1) X(table_redo, 1) X(redo_list, 1) X(table_cause, 1)                                                          \
-    X(nan_mask, 4) X(nan_list, 2 * URF_MAX_CHANNELS) X(vis, URF_MAX_CHANNELS)                                                    \
-    X(maxdist, URF_MAX_CHANNELS) X(quad, 4)                                                                                      \
-    X(curb_cnt, URF_MAX_CHANNELS) X(curb_az, URF_MAX_CHANNELS * URF_CURB_LIST)                                                   \
-    X(sufmin, URF_MAX_CHANNELS * URF_DEG_CELLS) X(premax, URF_MAX_CHANNELS * URF_DEG_CELLS)                                      \
-    X(stop_f, URF_DEG_CELLS) X(stop_b, URF_DEG_CELLS)                                                                            \
-    X(win, URF_MAX_CHANNELS * URF_DEG_CELLS)                                                                                     \
-    X(info, 1)                                                                                                                   \
-    X(front_ok, 1) X(front_pres, max_tiles * 64) X(front_maxs, max_tiles * 64) X(front_lane_ring, 64)                            \
-    X(front_ring_lane, URF_MAX_CHANNELS) X(front_cand, front_cand_cap) X(front_all, front_cand_cap) X(front_ncand, 1)             \
-    X(front_list, 1) X(front_st, URF_FRONT_ST_WORDS)
-#define URF_SCRATCH_SLOTS(X) X(list_len, URF_LIST_COUNT) X(ring_hint, 1)
-#define URF_SCRATCH_CAPTURE(X) X(valpha, sstride) X(seckey, sstride) X(ringkey, sstride) X(rd2, sstride) X(caz, sstride)
-#define URF_SCRATCH_ROW_MAJOR(X) X(tx, sstride) X(ty, sstride) X(tz, sstride) X(rows_v, 64) X(rows_ok, 1)
-#define URF_SCRATCH_LASERS128(X)                                                                                                  \
-    X(front_pres128, URF_FRONT128_TILES2(max_tiles) * 64) X(front_maxs128, URF_FRONT128_TILES2(max_tiles) * 64)                  \
-    X(front_lane_ring128, URF_FRONT128_L) X(front_st128, URF_FRONT128_ST_WORDS) X(rows_v128, URF_FRONT128_L)                     \
-    X(front_cand128, URF_FRONT128_CAND_CAP(max_points)) X(front_all128, URF_FRONT128_CAND_CAP(max_points))
-#define URF_SCRATCH_MULTI_SECTOR(X) X(front_skey, sstride)
-enum urf_scratch_group { URF_SCR_ALWAYS, URF_SCR_CAPTURE, URF_SCR_ROW_MAJOR, URF_SCR_LASERS128, URF_SCR_MULTI_SECTOR };
+#include "urf_ctx.hpp"
 
 /* The kernels of a call's fused family (urf_policy.hpp: urf_front_family), in one table.  An instance of the march and of the finish kernel
  * exists per curbPoints (the march twice: plain, and as the march of urf_set_front_multi_sector): the march per laser count -- 16, 32, 64, 128: the family's
@@ -168,296 +89,23 @@ static constexpr size_t urf_finish_lds_bytes(unsigned tiles)
 static_assert(urf_finish_lds_bytes(URF_FRONT_LONG_MAX_TILES) + sizeof(urf_finish_shared_t<URF_FRONT128_L>) <= 160u * 1024u, "a CU's LDS");
 static_assert(URF_FRONT128_TILES2(URF_FRONT_LONG_MAX_TILES) == URF_FRONT_LONG_MAX_TILES, "an even number: k_front_finish128's layout is as large");
 
-/* "The last call", for the entry points that take their input from it (urf_read_stage, urf_ordered_indices, urf_marker_points,
- * urf_clouds_batch_*): publish_last() is the only writer of the whole record, last_call() the readers' way to it. */
-enum urf_last_kind { URF_LAST_NONE, URF_LAST_SOA, URF_LAST_PC2, URF_LAST_SWEEP };   /* no call yet | the batch entry point | a sweep waited for */
-/* plan()'s decision about a call in words, kept for urf_front_explain: the terms that were false and the advice (urf_policy::why), and
- * whether the march was, or would have been, the multi-sector one (ms_ok) */
-struct urf_planned {
-    urf_policy::reasons call = { 0u, 0u };
-    bool ms = false;
-};
 /* the call's part of the per-scan rule (urf_front_scan_rule): `rows`, the layout the records are counted in; sweep_n, a sweep's own length */
-static urf_fx_call fx_call_of(const urf_kargs& a, const urf_dev_params& dp, const urf_planned& planned, bool rows, uint32_t sweep_n)
+static urf_fx_call fx_call_of(const urf_run& r, bool rows, uint32_t sweep_n)
 {
-    const uint32_t L = (uint32_t)dp.p.channels;
-    return urf_fx_call{ a.front, a.front_rows, a.front_cand_cap, rows ? 1u : 0u, (L == 16u || L == 32u || L == 64u || L == 128u) ? L : 0u,
-                        planned.ms ? 1u : 0u, dp.p.curbPoints != 5 ? 1u : 0u, planned.call.why, sweep_n };
+    const uint32_t L = (uint32_t)r.dp.p.channels;
+    return urf_fx_call{ r.a.front, r.a.front_rows, r.a.front_cand_cap, rows ? 1u : 0u, (L == 16u || L == 32u || L == 64u || L == 128u) ? L : 0u,
+                        r.planned.ms ? 1u : 0u, r.dp.p.curbPoints != 5 ? 1u : 0u, r.planned.call.why, sweep_n };
 }
-struct urf_last_call {
-    int kind = URF_LAST_NONE;
-    uint32_t scans = 0;
-    urf_kargs a;                    /* the kernel arguments and parameters it ran with */
-    urf_dev_params dp;
-    uint32_t row = 0;               /* the scratch row of a.* (a batch call: 0) */
-    uint64_t gen = 0;               /* a sweep: the row's submission number it was (urf_ctx::row_gen) */
-    urf_planned planned;            /* what the policy said about the call when it planned it (urf_front_explain) */
-    uint32_t sweep_n = 0;           /* a sweep: the caller's number of points (urf_set_sweep_quantum: a.n_per_scan is the padded length) */
-    /* a dense call (urf_classify_batch_*_dense): `a` is the padded batch -- staging, padded labels, all the context's own --, and
-     * this is what the caller handed in, for urf_clouds_batch_* in input order (offsets: the context's copy) */
-    struct {
-        bool on = false;
-        const float *x = nullptr, *y = nullptr, *z = nullptr;   /* a SoA call's */
-        uint8_t* labels = nullptr;
-        uint32_t max_len = 0;
-    } dense;
-};
-
-struct urf_ctx {
-    int device = 0;
-    uint32_t max_points = 0, max_batch = 0;
-    uint32_t max_tiles = 0;
-    uint32_t sstride = 0;           /* scratch elements per scan: max_tiles * URF_TILE + URF_SCAN_PAD */
-    uint32_t debug_flags = 0;       /* urf_set_debug_flags */
-    unsigned n_cus = 256;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    urf_params params;
-    urf_dev_params dp;
-    urf_kargs k;                    /* device pointers (context-owned part): the scratch arrays (URF_SCRATCH_*) at row 0 */
-    /* owned device memory of fixed size: the scratch arrays and the tables, freed by urf_destroy */
-    std::vector<void*> allocs;
-    lazy_buf<float> sx, sy, sz;     /* SoA staging for PointCloud2 input: max_batch x max_points */
-    /* The single-scan (callback) path: URF_ASYNC_SLOTS sweeps in flight, so that -- with a context created
-     * for several scans -- the copies and kernels of several sweeps overlap on the device (a single sweep's
-     * kernels are a few dozen workgroups each).  Per slot: pinned host staging for the message bytes and for the
-     * results, device copies of both, the captured launch sequence. */
-    struct slot_t {
-        lazy_buf<uint8_t, true> h_in;   /* the largest message so far */
-        lazy_buf<uint8_t> d_raw;        /* ... its device copy */
-        lazy_buf<uint8_t, true> h_labels;   /* max_points */
-        lazy_buf<uint8_t> d_labels;     /* max_points */
-        lazy_buf<urf_scan_info, true> h_info;
-        hipEvent_t ev_done = nullptr;
-        /* the captured launch sequences: one, or with urf_set_sweep_quantum up to URF_SWEEP_SEQS, one per padded length (seq_find) */
-        struct seq_t {
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            uint64_t key[3] = { 0, 0, 0 };  /* what the captured sequence was built for */
-            urf_kargs cap_a;                /* ... and the kernel arguments / parameters it runs with */
-            urf_dev_params cap_dp;
-            urf_planned cap_planned;        /* ... and what the policy said when it planned them */
-            uint64_t used = 0;              /* urf_ctx::seq_clock of its last launch: the least recently used one makes room */
-        } seqs[URF_SWEEP_SEQS];
-        urf_kargs cap_a;                /* the arguments / parameters / plan of the sweep in this slot (its sequence's, or its direct launches') */
-        urf_dev_params cap_dp;
-        urf_planned cap_planned;
-        bool pending = false, used = false;
-        uint64_t gen = 0;               /* the row's submission number of the sweep in this slot */
-        uint32_t n_points = 0, ticket = 0;
-        /* urf_set_sweep_quantum: the points the sweep runs as (n_points rounded up to the quantum, NaN behind the caller's; off: n_points),
-         * whether its sequence is a padded one, and the sweep's own length for k_pc2_to_soa_pad: a pinned word and its device copy */
-        uint32_t n_run = 0;
-        bool pad = false;
-        lazy_buf<uint32_t, true> h_n;
-        lazy_buf<uint32_t> d_n;
-        uint32_t point_step = 0, off_x = 0, off_y = 0, off_z = 0;   /* layout of the message in d_raw */
-        bool planes = false;            /* d_raw holds x[n] y[n] z[n] (a staged message) instead of the records */
-        /* urf_set_sweep_outputs: the sweep's marker points and ordered lists (sweep_out_words: URF_SWEEP_HDR words, then three
-         * lists of n_points entries), device and pinned; out_bits: the bits the sweep in this slot was submitted with */
-        lazy_buf<uint32_t> d_out;
-        lazy_buf<uint32_t, true> h_out;
-        uint32_t out_bits = 0;
-        /* urf_set_sweep_results_direct: the same products stored by the kernels themselves (URF_SWEEP_HDR words, then the three lists back
-         * to back: at most 2 x max_points entries -- road and curb are disjoint sets of the sweep's points, ring 10 has at most all of them);
-         * out_direct: whether the sweep in this slot was submitted that way, i.e. which buffer and which list layout its results have */
-        mapped_buf m_out;
-        bool out_direct = false;
-    } slots[URF_ASYNC_SLOTS];
-    /* urf_set_sweep_outputs: what launch_markers / launch_ordered / front_out_prepare keep as context-wide lazy buffers, once per scratch
-     * row of the callback path (row r starts r * elements into each: sweep_row) -- a sweep's captured sequence produces its read-outs on
-     * its own row.  Allocated by the first call that turns a bit on; empty in a context that never does. */
-    struct sweep_scratch_t {
-        lazy_buf<float> mk_d;               /* [rows][URF_MAX_CHANNELS * URF_DEG_CELLS] */
-        lazy_buf<uint32_t> mk_pos;
-        lazy_buf<uint8_t> mk_red;           /* ... + URF_MAX_CHANNELS literal flags (mk_lit) behind the cells of a row */
-        lazy_buf<unsigned long long> ord_keys;   /* [rows][sstride] */
-        lazy_buf<uint32_t> ord_pos;
-        lazy_buf<uint32_t> ord_cls;         /* [rows][URF_MAX_CHANNELS * 2] */
-        lazy_buf<uint32_t> fo_az, fo_ent;   /* [rows][sstride] */
-        lazy_buf<float> fo_d;
-    } sweep;
-    bool streams_made = false;
-    urf_policy pol;                 /* which kernels a call launches */
-    uint32_t n_rerun = 0;           /* sweeps urf_classify_pc2_wait had to run again */
-    uint32_t n_captured = 0;        /* launch sequences captured so far, all slots (urf_callback_path_captures) */
-    uint64_t seq_clock = 0;         /* launches of captured sequences so far (slot_t::seq_t::used) */
-    /* Slot i works on scratch row i % rows, rows = min(max_batch, URF_ASYNC_SLOTS); row 0 runs on the
-     * context's stream, every other row on a stream of its own (slots that share a row share its
-     * stream: they are serialised).  Everything else the context launches runs on `stream`; the two
-     * kinds of work are ordered against each other by events (order_after_slots / order_row_after_main). */
-    hipStream_t row_stream[URF_ASYNC_SLOTS] = { nullptr, nullptr, nullptr, nullptr };
-    hipEvent_t ev_main = nullptr;          /* recorded on `stream` for a row stream to wait on */
-    uint64_t main_seq = 1;                 /* bumped by every launch on `stream` that touches scratch rows >= 1 or the staging */
-    uint64_t row_seen[URF_ASYNC_SLOTS] = { 0, 0, 0, 0 };
-    /* Slots that share a scratch row (max_batch < URF_ASYNC_SLOTS) are serialised on the row's stream, and a later
-     * sweep overwrites the row.  Labels and summary of every sweep are safe (each slot has its own result buffers,
-     * filled in stream order); what reads the ROW afterwards (urf_read_stage / urf_ordered_indices /
-     * urf_marker_points) checks that the sweep published as "the last call" is still the row's latest submission (last_call). */
-    uint64_t row_gen[URF_ASYNC_SLOTS] = { 0, 0, 0, 0 };   /* submissions on the row so far */
-    uint32_t next_ticket = 0;
-    /* sized for the largest number of scans asked for so far: scratch of the index-list and marker-point outputs
-     * (sstride entries resp. channels x 361 cells per scan) */
-    lazy_buf<unsigned long long> ord_keys;
-    lazy_buf<uint32_t> ord_pos;
-    lazy_buf<uint32_t> ord_cls;     /* [scans][URF_MAX_CHANNELS][2] road / curb points per ring (k_ring_order -> k_ordered_lists) */
-    lazy_buf<uint32_t> ord_lists;   /* single-scan entry point: 3 x sstride + 4 */
-    /* the read-outs of a fused call (urf_k_front_outputs.hpp): [scans][sstride] per ring-major position the exact azimuth's bits, the entry
-     * input index | class << 30 and the planar distance.  k_front_out_prep fills them once per recorded call and range of scans (fo_prep:
-     * the call's number and the range they hold; nobody writes them afterwards), for urf_ordered_indices* and urf_marker_points* alike. */
-    lazy_buf<uint32_t> fo_az, fo_ent;
-    lazy_buf<float> fo_d;
-    struct { uint64_t seq = 0; uint32_t s0 = 0, n = 0; } fo_prep;
-    uint64_t last_seq = 0;          /* bumped whenever `last` is written */
-    lazy_buf<float> mk_d;
-    lazy_buf<uint32_t> mk_pos;
-    lazy_buf<uint8_t> mk_red;       /* ... and one flag per ring and scan behind the cells (k_marker_ring_literal) */
-    lazy_buf<float> mk_out;         /* single-scan entry point: 361 x 4 floats + 1 count */
-    lazy_buf<int32_t> mk_ghost;     /* urf_marker_strips_batch: the incoming ghost count (the call's last scan overwrites the caller's word) */
-    uint32_t* compact_cnt = nullptr;   /* [max_batch][max_tiles][4] */
-    /* the published clouds of a batch (urf_clouds_batch_*): per (scan, tile) counts and bases, and the ordered lists of the
-     * reference order: 3 x scans x stride entries + 3 counts per scan */
-    lazy_buf<urf_u32x4> cl_tiles;   /* 2 x [max_batch][max_tiles] */
-    lazy_buf<uint32_t> cl_lists;
-    /* dense sweeps put back into firing slots (urf_k_dense.hpp), grown by the first dense call: every dense point's position inside its
-     * padded scan and the padded batch's labels ([max_batch][max_points] each; the padded x / y / z are the SoA staging), the per-tile
-     * and per-scan words (2 x [max_batch][max_tiles] + [max_batch] + 1), the slot map's device copy */
-    lazy_buf<uint32_t> dn_pos;
-    lazy_buf<uint8_t> dn_labels;
-    lazy_buf<uint32_t> dn_words;
-    lazy_buf<uint8_t> dn_map;
-    /* urf_classify_batch_*_dense_elev: the ids derived from the points' elevation ([max_batch][max_points] bytes, indexed like the
-     * caller's arrays) and the device copy of dense_elev, both grown by the first such call */
-    lazy_buf<uint8_t> dn_ids;
-    lazy_buf<urf_dense_elev_table> dn_elev;
-    urf_dense_elev_table dense_elev;   /* urf_set_dense_elevations, for dense_elev_n slots (0: none) */
-    uint32_t dense_elev_n = 0;
-    bool dense_elev_dirty = true;      /* ... not yet in dn_elev */
-    struct { urf_dense_args d; urf_dense_ids_args e; uint32_t kind = URF_LAST_NONE; } dn_ids_call;   /* the last id launch (urf_test_dense_ids_ms) */
-    /* urf_set_dense_outputs: the inverse of dn_pos ([max_batch][max_points], k_dense_inverse), grown by the first read-out that needs it
-     * and built once per dense call: dn_calls counts those (a rerun of the padded batch writes `last` and leaves dn_pos as it is), dn_inv_of
-     * is the one dn_inv holds (0: none) */
-    lazy_buf<uint32_t> dn_inv;
-    uint64_t dn_calls = 0, dn_inv_of = 0;
-    bool dense_outputs = false;
-    uint8_t dense_map[256];         /* urf_set_dense_slots (urf_create: the identity); 0xff: no such id */
-    bool dense_map_dirty = true;    /* ... not yet in dn_map */
-    float* d_newY = nullptr;
-    urf_beam* d_beams = nullptr;
-    uint32_t beams_cap = 0;
-    int capture = 0;                /* urf_enable_stage_capture */
-    bool timing = false;
-    std::vector<std::vector<hipEvent_t>> timing_events;   /* sets of URF_NUM_KERNELS+1 events, created once and reused */
-    size_t timing_used = 0;         /* sets recorded since the last urf_kernel_timing() */
-    uint32_t* offsets_copy = nullptr;   /* [max_batch + 1] the ragged offsets of the last call (context-owned) */
-    /* k_front_finish's first part runs on a stream of its own next to the star-shaped search (side_fork): all three or none */
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    urf_last_call last;
-    urf_planned planned;            /* run_pipeline: the call it planned last (its callers keep it with the call's arguments) */
-    /* urf_front_explain: k_front_explain's per-scan records ([scans][URF_FX_WORDS]), grown by its first call */
-    lazy_buf<uint32_t> fx_rec;
-    /* urf_set_front_auto's learning pass, allocated by the first call that turns the switch on: k_front_explain's records for a batch
-     * call (rows 0 .. max_batch - 1) and for the sweep of each slot (row max_batch + slot), k_front_digest's accumulators and its
-     * host-mapped digests ([1 + URF_ASYNC_SLOTS][URF_DG_WORDS] each: a batch call's first, then the slots') */
-    struct {
-        lazy_buf<uint32_t> rec, acc;
-        mapped_buf dig;
-    } au;
-    std::string last_error;
-    /* host-side cost of the callback path, phase by phase (only the build with the test hooks fills them:
-     * URF_HOST_TIMES=1, printed by its benchmark loop; the context's layout is the same in both builds) */
-    double ht[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    bool ht_on = false;
-};
-
-#define URF_HIP(ctx, call)                                                              \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) {                                                         \
-            (ctx)->last_error = std::string(#call) + ": " + hipGetErrorString(e_);      \
-            return e_ == hipErrorOutOfMemory ? URF_ERR_OOM : URF_ERR_HIP;               \
-        }                                                                               \
-    } while (0)
-
-/* a slot's captured sequences: released one by one (seq_drop) or all of them (slot_forget); never while the slot's sweep is in flight */
-static void seq_drop(urf_ctx::slot_t::seq_t& q)
+static void seq_drop(urf_ctx::slot_t& sl, unsigned i)
 {
+    urf_ctx::slot_t::seq_t& q = sl.seqs[i];
     if (q.exec)
         (void)hipGraphExecDestroy(q.exec);
     if (q.graph)
         (void)hipGraphDestroy(q.graph);
     q.exec = nullptr;
     q.graph = nullptr;
-    q.key[0] = 0;
-}
-static void slot_forget(urf_ctx::slot_t& sl)
-{
-    for (auto& q : sl.seqs)
-        seq_drop(q);
-}
-
-template <class T>
-static int dev_alloc(urf_ctx* c, T** p, size_t count)
-{
-    void* v = nullptr;
-    URF_HIP(c, hipMalloc(&v, (count ? count : 1) * sizeof(T)));
-    c->allocs.push_back(v);
-    *p = (T*)v;
-    return URF_OK;
-}
-
-/* b holds at least `count` elements afterwards.  To grow, it waits for `st` first when one is given (work in flight there may still
- * read the old memory) and frees the old memory; a failed allocation leaves it empty. */
-template <class T, bool Host>
-static int grow(urf_ctx* c, lazy_buf<T, Host>& b, size_t count, hipStream_t st = nullptr)
-{
-    if (count <= b.cap)
-        return URF_OK;
-    if (st)
-        URF_HIP(c, hipStreamSynchronize(st));
-    b.release();
-    void* v = nullptr;
-    URF_HIP(c, Host ? hipHostMalloc(&v, count * sizeof(T), hipHostMallocDefault) : hipMalloc(&v, count * sizeof(T)));
-    b.p = (T*)v;
-    b.cap = count;
-    return URF_OK;
-}
-
-/* f(group, field, rows, elements per row) for every scratch array of `k` (URF_SCRATCH_*) */
-template <class F>
-static void scratch_walk(const urf_ctx* c, urf_kargs& k, F&& f)
-{
-    const size_t sstride = c->sstride, max_tiles = c->max_tiles, max_points = c->max_points, front_cand_cap = k.front_cand_cap;
-#define URF_X_SCANS(field, n) f(URF_SCR_ALWAYS, k.field, (size_t)c->max_batch, (size_t)(n));
-#define URF_X_SLOTS(field, n) f(URF_SCR_ALWAYS, k.field, (size_t)URF_ASYNC_SLOTS, (size_t)(n));
-#define URF_X_CAPTURE(field, n) f(URF_SCR_CAPTURE, k.field, (size_t)c->max_batch, (size_t)(n));
-#define URF_X_ROW_MAJOR(field, n) f(URF_SCR_ROW_MAJOR, k.field, (size_t)c->max_batch, (size_t)(n));
-#define URF_X_LASERS128(field, n) f(URF_SCR_LASERS128, k.field, (size_t)c->max_batch, (size_t)(n));
-#define URF_X_MULTI_SECTOR(field, n) f(URF_SCR_MULTI_SECTOR, k.field, (size_t)c->max_batch, (size_t)(n));
-    URF_SCRATCH_SCANS(URF_X_SCANS)
-    URF_SCRATCH_SLOTS(URF_X_SLOTS)
-    URF_SCRATCH_CAPTURE(URF_X_CAPTURE)
-    URF_SCRATCH_ROW_MAJOR(URF_X_ROW_MAJOR)
-    URF_SCRATCH_LASERS128(URF_X_LASERS128)
-    URF_SCRATCH_MULTI_SECTOR(URF_X_MULTI_SECTOR)
-#undef URF_X_SCANS
-#undef URF_X_SLOTS
-#undef URF_X_CAPTURE
-#undef URF_X_ROW_MAJOR
-#undef URF_X_LASERS128
-#undef URF_X_MULTI_SECTOR
-}
-
-/* Allocates the arrays of `group` that are missing (URF_OK: all of them are there). */
-static int scratch_alloc(urf_ctx* c, urf_scratch_group group)
-{
-    int rc = URF_OK;
-    scratch_walk(c, c->k, [&](urf_scratch_group g, auto*& p, size_t rows, size_t n) {
-        if (g == group && !p && rc == URF_OK)
-            rc = dev_alloc(c, &p, rows * n);
-    });
-    return rc;
+    sl.cache.drop(i);   /* (never while the slot's sweep is in flight) */
 }
 
 /* What the kernels of earlier calls reported, taken into the policy before a call's launches (never inside a stream capture: the first
@@ -632,7 +280,7 @@ extern "C" int urf_create(urf_ctx** out, int device_id, uint32_t max_points, uin
     }
     urf_default_params(&c->params);
     std::memset(&c->k, 0, sizeof(c->k));
-    std::memset(&c->last.a, 0, sizeof(c->last.a));
+    std::memset(&c->last.run.a, 0, sizeof(c->last.run.a));
     urf_kargs& k = c->k;
     k.front_cand_cap = max_points / 8 > 4096 ? max_points / 8 : 4096;
     if ((rc = scratch_alloc(c, URF_SCR_ALWAYS)) != URF_OK || (rc = dev_alloc(c, &c->offsets_copy, (size_t)max_batch + 1)) != URF_OK ||
@@ -705,7 +353,8 @@ extern "C" int urf_destroy(urf_ctx* c)
     if (c->pol.flags)
         (void)hipHostFree(c->pol.flags);
     for (auto& sl : c->slots) {
-        slot_forget(sl);
+        for (unsigned i = 0; i < URF_SWEEP_SEQS; i++)
+            seq_drop(sl, i);
         if (sl.ev_done)
             (void)hipEventDestroy(sl.ev_done);
     }
@@ -1030,145 +679,7 @@ extern "C" int urf_set_front_outputs(urf_ctx* c, int on)
 {
     if (!c || (on != 0 && on != 1))
         return URF_ERR_INVALID_ARG;
-    c->pol.front_outputs = on != 0;   /* (the read-outs' scratch grows with their first use: front_out_prepare) */
-    return URF_OK;
-}
-
-/* ---- urf_set_sweep_outputs (include/urf.h) ---------------------------------------------------- */
-/* A slot's result buffer, in 32-bit words: the marker points (URF_DEG_CELLS x 4 floats), their count, the three list counts -- one small
- * copy --, then the road, curb and ring-10 lists at a stride of the sweep's n_points (one copy of 3 x n_points words, sized at capture). */
-#define URF_SWEEP_HDR_MCOUNT (URF_DEG_CELLS * 4u)
-#define URF_SWEEP_HDR_LCOUNTS (URF_SWEEP_HDR_MCOUNT + 1u)
-#define URF_SWEEP_HDR (URF_SWEEP_HDR_LCOUNTS + 3u)
-#define URF_DBG_SWEEP_OLD_KERNELS 32u   /* test hook (urf_set_debug_flags): with both bits set the sequence launches the kernels of the two
-                                           products one by one instead of k_sweep_rings / k_sweep_lists (A/B, tools/sweep_outputs_bench.py) */
-static uint32_t sweep_rows(const urf_ctx* c) { return c->max_batch < URF_ASYNC_SLOTS ? c->max_batch : URF_ASYNC_SLOTS; }
-
-/* Everything the sequences will need, before any of them is captured: nothing may be allocated inside a stream capture.  The buffers are
- * of fixed size (rows, sstride, max_points): a second call finds them there. */
-static int sweep_outputs_alloc(urf_ctx* c, bool direct)
-{
-    const size_t rows = sweep_rows(c), cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS, ss = c->sstride;
-    urf_ctx::sweep_scratch_t& w = c->sweep;
-    int rc;
-    if ((rc = grow(c, w.mk_d, rows * cells)) != URF_OK || (rc = grow(c, w.mk_pos, rows * cells)) != URF_OK ||
-        (rc = grow(c, w.mk_red, rows * (cells + URF_MAX_CHANNELS))) != URF_OK || (rc = grow(c, w.ord_keys, rows * ss)) != URF_OK ||
-        (rc = grow(c, w.ord_pos, rows * ss)) != URF_OK || (rc = grow(c, w.ord_cls, rows * URF_MAX_CHANNELS * 2)) != URF_OK ||
-        (rc = grow(c, w.fo_az, rows * ss)) != URF_OK || (rc = grow(c, w.fo_ent, rows * ss)) != URF_OK || (rc = grow(c, w.fo_d, rows * ss)) != URF_OK)
-        return rc;
-    if (direct) {   /* (urf_set_sweep_results_direct: the kernels' own stores, no device-side result buffer) */
-        const size_t words = URF_SWEEP_HDR + 2 * (size_t)c->max_points;
-        for (auto& sl : c->slots) {
-            mapped_buf& m = sl.m_out;
-            if (m.cap >= words)
-                continue;
-            m.release();
-            void *hp = nullptr, *dp_ = nullptr;
-            URF_HIP(c, hipHostMalloc(&hp, words * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-            m.p = (uint32_t*)hp;
-            URF_HIP(c, hipHostGetDevicePointer(&dp_, hp, 0));
-            m.dev = (uint32_t*)dp_;
-            m.cap = words;
-            std::memset(m.p, 0, URF_SWEEP_HDR * sizeof(uint32_t));   /* (a sweep with one bit set leaves the other product's words alone) */
-        }
-        return URF_OK;
-    }
-    const size_t words = URF_SWEEP_HDR + 3 * (size_t)c->max_points;
-    for (auto& sl : c->slots) {
-        const bool fresh = sl.d_out.cap < words;
-        if ((rc = grow(c, sl.d_out, words)) != URF_OK || (rc = grow(c, sl.h_out, words)) != URF_OK)
-            return rc;
-        if (fresh) {   /* (a sweep with one bit set copies the whole header) */
-            URF_HIP(c, hipMemset(sl.d_out.p, 0, URF_SWEEP_HDR * sizeof(uint32_t)));
-            std::memset(sl.h_out.p, 0, URF_SWEEP_HDR * sizeof(uint32_t));
-        }
-    }
-    return URF_OK;
-}
-
-extern "C" int urf_set_sweep_outputs(urf_ctx* c, uint32_t bits)
-{
-    if (!c)
-        return URF_ERR_INVALID_ARG;
-    if (bits & ~(URF_SWEEP_OUT_MARKER_POINTS | URF_SWEEP_OUT_ORDER)) {
-        c->last_error = "urf_set_sweep_outputs: bits other than URF_SWEEP_OUT_MARKER_POINTS | URF_SWEEP_OUT_ORDER";
-        return URF_ERR_INVALID_ARG;
-    }
-    for (const auto& sl : c->slots)
-        if (sl.pending) {
-            c->last_error = "urf_set_sweep_outputs: a sweep is in flight (urf_classify_pc2_wait it first)";
-            return URF_ERR_BUSY;
-        }
-    if (bits) {
-        URF_HIP(c, hipSetDevice(c->device));
-        const int rc = sweep_outputs_alloc(c, c->pol.sweep_direct);
-        if (rc != URF_OK)
-            return rc;   /* (the switch stays as it was) */
-    }
-    c->pol.set(c->pol.sweep_outputs, bits);   /* (every slot captures its sequence again) */
-    return URF_OK;
-}
-
-/* ---- urf_set_sweep_results_direct (include/urf.h) ---------------------------------------------- */
-/* Whichever of the two setters comes second allocates the result buffers of the layout that is then in force (sweep_outputs_alloc), outside
- * any capture; with no bit of urf_set_sweep_outputs set this one allocates nothing. */
-extern "C" int urf_set_sweep_results_direct(urf_ctx* c, int on)
-{
-    if (!c || (on != 0 && on != 1))
-        return URF_ERR_INVALID_ARG;
-    for (const auto& sl : c->slots)
-        if (sl.pending) {
-            c->last_error = "urf_set_sweep_results_direct: a sweep is in flight (urf_classify_pc2_wait it first)";
-            return URF_ERR_BUSY;
-        }
-    if (c->pol.sweep_outputs && (on != 0) != c->pol.sweep_direct) {
-        URF_HIP(c, hipSetDevice(c->device));
-        const int rc = sweep_outputs_alloc(c, on != 0);
-        if (rc != URF_OK)
-            return rc;   /* (the switch stays as it was) */
-    }
-    c->pol.set(c->pol.sweep_direct, on != 0);   /* (every slot captures its sequence again) */
-    return URF_OK;
-}
-
-/* ---- urf_set_sweep_quantum, urf_callback_path_captures (include/urf.h) ------------------------- */
-extern "C" int urf_set_sweep_quantum(urf_ctx* c, uint32_t points)
-{
-    if (!c)
-        return URF_ERR_INVALID_ARG;
-    if (points % URF_TILE != 0u || points > c->max_points) {
-        c->last_error = "urf_set_sweep_quantum: not a multiple of URF_TILE (2048) points, or more than the context's max_points";
-        return URF_ERR_INVALID_ARG;
-    }
-    for (const auto& sl : c->slots)
-        if (sl.pending) {
-            c->last_error = "urf_set_sweep_quantum: a sweep is in flight (urf_classify_pc2_wait it first)";
-            return URF_ERR_BUSY;
-        }
-    if (points) {   /* the slots' length words, before any sequence is captured */
-        URF_HIP(c, hipSetDevice(c->device));
-        for (auto& sl : c->slots) {
-            int rc;
-            if ((rc = grow(c, sl.h_n, 1)) != URF_OK || (rc = grow(c, sl.d_n, 1)) != URF_OK)
-                return rc;   /* (the switch stays as it was) */
-        }
-    }
-    c->pol.set(c->pol.sweep_quantum, points);   /* (a change: every slot forgets its sequences with its next sweep) */
-    return URF_OK;
-}
-
-extern "C" int urf_callback_path_captures(const urf_ctx* c, uint32_t* n_captured, uint32_t* n_resident)
-{
-    if (!c)
-        return URF_ERR_INVALID_ARG;
-    if (n_captured)
-        *n_captured = c->n_captured;
-    if (n_resident) {   /* (a sequence of an earlier epoch is no sweep's any more: its slot's next submission releases it) */
-        *n_resident = 0;
-        for (const auto& sl : c->slots)
-            for (const auto& q : sl.seqs)
-                *n_resident += (q.exec && q.key[0] == c->pol.epoch) ? 1u : 0u;
-    }
+    c->pol.front_outputs = on != 0;   /* (the read-outs' scratch grows with their first use: readouts_of_last) */
     return URF_OK;
 }
 
@@ -1177,12 +688,12 @@ extern "C" int urf_front_scans(urf_ctx* c, uint32_t* n_fused)
     if (!c || !n_fused)
         return URF_ERR_INVALID_ARG;
     *n_fused = 0;
-    if (!c->last.a.front)   /* (or no call yet) */
+    if (!c->last.run.a.front)   /* (or no call yet) */
         return URF_OK;
     URF_HIP(c, hipSetDevice(c->device));
     URF_HIP(c, hipStreamSynchronize(c->stream));   /* (a sweep of the callback path has been waited for: its row is at rest) */
     std::vector<uint32_t> ok(c->last.scans);
-    URF_HIP(c, hipMemcpy(ok.data(), c->last.a.front_ok, ok.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    URF_HIP(c, hipMemcpy(ok.data(), c->last.run.a.front_ok, ok.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (uint32_t v : ok)
         *n_fused += v ? 1u : 0u;
     return URF_OK;
@@ -1228,20 +739,6 @@ extern "C" int urf_kernel_timing(urf_ctx* c, double* ms_sum, uint32_t* n_calls)
 
 extern "C" const char* urf_last_error(const urf_ctx* c) { return c ? c->last_error.c_str() : ""; }
 
-/* The context's scratch at row `row` (URF_SCRATCH_*): slot i of the callback path (URF_MAX_IN_FLIGHT slots) runs on row
- * i % min(max_batch, URF_MAX_IN_FLIGHT) and on that row's own stream, so that the sweeps in flight overlap.  Row 0 = the
- * context's own arguments; a lazy group that is not there stays NULL. */
-static urf_kargs kargs_row(const urf_ctx* c, uint32_t row)
-{
-    urf_kargs k = c->k;
-    if (row)
-        scratch_walk(c, k, [&](urf_scratch_group, auto*& p, size_t, size_t n) {
-            if (p)
-                p += row * n;
-        });
-    return k;
-}
-
 /* Work on the context's stream that reads or writes scratch (any row), the SoA staging or the results of
  * the last call must come after the sweeps of the callback path that are still in flight on OTHER
  * streams (a batch call overwrites their rows; urf_read_stage / urf_ordered_indices /
@@ -1272,10 +769,10 @@ static int order_row_after_main(urf_ctx* c, uint32_t row, hipStream_t st)
  * urf_front_explain launches it -- layout 1 exactly when the call's sequence held the rows' probe and transpose --, then k_front_digest
  * into digest `which` (0: a batch call's, 1 + i: slot i's).  rec_row: the first row of au.rec the call's records take; sweep_n: a sweep's
  * own length.  One pass is in flight at a time; while learning is over, or the call kept the general kernels: nothing. */
-static int auto_pass(urf_ctx* c, const urf_kargs& a, const urf_dev_params& dp, const urf_planned& planned, hipStream_t st, uint32_t which,
-                     uint32_t rec_row, uint32_t sweep_n)
+static int auto_pass(urf_ctx* c, const urf_run& r, hipStream_t st, uint32_t which, uint32_t rec_row, uint32_t sweep_n)
 {
     urf_policy& p = c->pol;
+    const urf_kargs& a = r.a;
     if (!p.auto_on || p.auto_phase != URF_AUTO_LEARNING || p.auto_wait || !a.front || !c->au.dig.p)
         return URF_OK;
     const uint32_t n = a.n_scans;
@@ -1286,8 +783,8 @@ static int auto_pass(urf_ctx* c, const urf_kargs& a, const urf_dev_params& dp, c
     URF_HIP(c, hipMemsetAsync(acc, 0, URF_DG_WORDS * sizeof(uint32_t), st));
     if (++p.auto_seq == 0u)
         p.auto_seq = 1u;   /* (0: what a fresh digest slot holds) */
-    hipLaunchKernelGGL(k_front_explain, dim3(a.tiles, n), dim3(64), 0, st, a, dp, rows ? 1u : 0u, rec);
-    hipLaunchKernelGGL(k_front_digest, dim3((n + 255u) / 256u), dim3(256), 0, st, a, fx_call_of(a, dp, planned, rows, sweep_n), rec, acc,
+    hipLaunchKernelGGL(k_front_explain, dim3(a.tiles, n), dim3(64), 0, st, a, r.dp, rows ? 1u : 0u, rec);
+    hipLaunchKernelGGL(k_front_digest, dim3((n + 255u) / 256u), dim3(256), 0, st, a, fx_call_of(r, rows, sweep_n), rec, acc,
                        c->au.dig.dev + (size_t)which * URF_DG_WORDS, p.auto_seq);
     URF_HIP(c, hipGetLastError());
     p.auto_wait = which + 1u;
@@ -1335,9 +832,10 @@ static bool side_fork(urf_ctx* c, hipStream_t st)
     return c->side_stream && hipEventRecord(c->ev_fork, st) == hipSuccess && hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) == hipSuccess;
 }
 
-/* The launch sequence of one call as the policy plans it; the arguments and parameters it ran with go to a_out / dp_out, last of all and
- * only for a call that succeeded and was not empty (call.dp may point at dp_out, the call's values may come from a_out: the two reruns) */
-static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_dev_params& dp_out)
+/* The launch sequence of one call as the policy plans it; what it ran with -- arguments, parameters, the policy's words -- goes to `out`,
+ * last of all and only for a call that succeeded and was not empty (call.dp may point into `out`, the call's values may come from out.a:
+ * the two reruns) */
+static int run_pipeline(urf_ctx* c, const urf_call& call, urf_run& out)
 {
     if (!call.x || !call.y || !call.z || !call.labels)
         return URF_ERR_INVALID_ARG;
@@ -1358,7 +856,9 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
         if (c->pol.auto_on && !call.general_only)   /* urf_set_front_auto: the call's advice, applied before it is planned (may allocate a scratch group) */
             auto_at_call(c, std::max<uint32_t>((call.max_len + URF_TILE - 1) / URF_TILE, 1u), n_scans, (uint32_t)(call.capture >= 0 ? call.capture : c->capture), false);
     }
-    urf_kargs a = kargs_row(c, call.row);
+    urf_run run;
+    urf_kargs& a = run.a;
+    a = kargs_row(c, call.row);
     a.x = call.x;
     a.y = call.y;
     a.z = call.z;
@@ -1384,12 +884,13 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
         a.rd2 = nullptr;
         a.caz = nullptr;
     }
-    const urf_dev_params dp = call.dp ? *call.dp : c->dp;
+    run.dp = call.dp ? *call.dp : c->dp;
+    const urf_dev_params& dp = run.dp;
     const unsigned C = (unsigned)dp.p.channels, K = (unsigned)dp.p.sectors;
     const bool star = dp.p.star_shaped_method != 0;
     const dim3 g_tiles(a.tiles, n_scans), g_scan(n_scans);
     c->pol.plan(a, dp, slot, call.general_only);
-    c->planned = urf_planned{ c->pol.why(a, dp, slot, call.general_only), c->pol.ms_ok(dp) };   /* (host words for urf_front_explain: decides nothing) */
+    run.planned = urf_planned{ c->pol.why(a, dp, slot, call.general_only), c->pol.ms_ok(dp) };   /* (host words for urf_front_explain: decides nothing) */
     if (!slot)
         c->pol.probation_batch(a);
 
@@ -1515,30 +1016,27 @@ static int run_pipeline(urf_ctx* c, const urf_call& call, urf_kargs& a_out, urf_
     if (call.info)
         URF_HIP(c, hipMemcpyAsync(call.info, a.info, (size_t)n_scans * sizeof(urf_scan_info), hipMemcpyDeviceToDevice, st));
     if (!slot && !call.general_only) {   /* (a sweep of the callback path: urf_classify_pc2_async, behind its sequence) */
-        const int rc = auto_pass(c, a, dp, c->planned, st, 0u, call.row, 0u);
+        const int rc = auto_pass(c, run, st, 0u, call.row, 0u);
         if (rc != URF_OK)
             return rc;
     }
-    a_out = a;
-    dp_out = dp;
+    out = run;
     return URF_OK;
 }
 
-static void publish_last(urf_ctx* c, int kind, uint32_t scans, const urf_kargs& a, const urf_dev_params& dp, const urf_planned& planned, uint32_t row = 0,
-                         uint64_t gen = 0)
+static void publish_last(urf_ctx* c, int kind, uint32_t scans, const urf_run& run, uint32_t row = 0, uint64_t gen = 0)
 {
-    c->last = urf_last_call{ kind, scans, a, dp, row, gen, planned };
+    c->last = urf_last_call{ kind, scans, run, row, gen };
     c->last_seq++;
 }
 
 /* a call of the public batch entry points: published after a successful call that was not empty (an empty one leaves the last call as it was) */
 static int classify_batch(urf_ctx* c, int kind, const urf_call& call)
 {
-    urf_kargs a;
-    urf_dev_params dp;
-    const int rc = run_pipeline(c, call, a, dp);
+    urf_run run;
+    const int rc = run_pipeline(c, call, run);
     if (rc == URF_OK && call.n_scans)
-        publish_last(c, kind, call.n_scans, a, dp, c->planned);
+        publish_last(c, kind, call.n_scans, run);
     return rc;
 }
 
@@ -1863,583 +1361,72 @@ extern "C" int urf_classify_batch_pc2_dense(urf_ctx* c, const uint8_t* d_data, c
     return classify_batch_dense(c, URF_LAST_PC2, d, d_offsets, max_len, n_scans, max_firings, d_labels, d_info);
 }
 
-/* ---- the callback path: one sweep, host buffers ------------------------------- */
-/* Slot i of the callback path works on scratch row i % rows, rows = min(max_batch, URF_ASYNC_SLOTS), and on
- * that row's compute stream (row 0: the context's stream): with a context created for several scans the
- * kernels of as many sweeps overlap on the device (a single sweep's kernels are a few dozen workgroups
- * each).  With max_batch == 1 all slots share row 0 and the context's stream: only the copies overlap. */
-static uint32_t slot_row(const urf_ctx* c, const urf_ctx::slot_t& sl)
-{
-    const uint32_t rows = c->max_batch < URF_ASYNC_SLOTS ? c->max_batch : URF_ASYNC_SLOTS;
-    return (uint32_t)(&sl - c->slots) % rows;
-}
-static hipStream_t slot_stream(urf_ctx* c, const urf_ctx::slot_t& sl)
-{
-    const uint32_t row = slot_row(c, sl);
-    return row ? c->row_stream[row] : c->stream;
-}
+/* ---- the read-out chain: published order and marker points of scans [s0, s0 + n) of a run ------------------------------- */
+struct urf_readout_dst {
+    uint32_t *road, *curb, *r10, stride, *lcounts;
+    float* pts;
+    uint32_t* mcount;
+};
 
-static int slot_prepare(urf_ctx* c, urf_ctx::slot_t& sl, size_t bytes)
+/* The one launch sequence of the read-out kernels, results to d: a sweep of the callback path behind its pipeline (sweep_outputs_launch:
+ * s0 = 0, n = 1, captured with the sweep) and the batch read-backs on the context's stream (readouts_of_last).  products: URF_SWEEP_OUT_ORDER | URF_SWEEP_OUT_MARKER_POINTS; prep: the pre-pass of a fused run's read-outs is to
+ * be launched; merged (both products, n == 1): the per-ring work of the two products is one launch (k_sweep_rings), lists and marker
+ * points another (k_sweep_lists); direct (n == 1): the last kernels store to d's mapped host memory themselves, the lists back to back.
+ * One linear chain on `st`, separate launches as the only synchronisation.  A fused run (r.a.front) holds the *_front siblings on the
+ * grids of the general kernels, in the order of the captured sequences: ring, ring_front, literal, literal_front.  Every general
+ * read-out kernel returns at once for a scan where urf_scan_fused holds and every *_front kernel where it does not (urf_k_outputs.hpp,
+ * urf_k_front_outputs.hpp): a scan is served by exactly one of each pair, so the order among them changes no result. */
+static int launch_readouts(urf_ctx* c, const urf_run& r, hipStream_t st, uint32_t s0, uint32_t n, const urf_readout_view& v, uint32_t products,
+                           bool prep, bool merged, bool direct, const urf_readout_dst& d)
 {
-    if (!c->streams_made) {
-        for (uint32_t r = 1; r < URF_ASYNC_SLOTS && r < c->max_batch; r++)
-            URF_HIP(c, hipStreamCreateWithFlags(&c->row_stream[r], hipStreamNonBlocking));
-        c->streams_made = true;
-    }
-    if (!sl.ev_done)
-        URF_HIP(c, hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
-    int rc;
-    if ((rc = grow(c, sl.h_labels, c->max_points)) != URF_OK || (rc = grow(c, sl.h_info, 1)) != URF_OK ||
-        (rc = grow(c, sl.d_labels, c->max_points)) != URF_OK)
-        return rc;
-    if (bytes > sl.h_in.cap || bytes > sl.d_raw.cap) {   /* grows to the largest message seen (a new buffer invalidates the captured sequences) */
-        for (auto& q : sl.seqs)
-            q.key[0] = 0;
-        const hipStream_t st = slot_stream(c, sl);   /* the slot's last sweep may still read d_raw */
-        if ((rc = grow(c, sl.h_in, bytes, st)) != URF_OK || (rc = grow(c, sl.d_raw, bytes, st)) != URF_OK)
-            return rc;
-    }
-    return URF_OK;
-}
-
-#ifdef URF_ENABLE_TEST_HOOKS
-static inline double ht_now()
-{
-    struct timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
-}
-#define HT_START double ht0 = c->ht_on ? ht_now() : 0.0
-#define HT(k, t0) do { if (c->ht_on) { const double ht_t = ht_now(); c->ht[k] += ht_t - (t0); (t0) = ht_t; } } while (0)
-#else
-#define HT_START
-#define HT(k, t0)
-#endif
-
-/* A message that has to be staged anyway is staged as three planes x[n4] y[n4] z[n4], n4 = n rounded up to 4: 12 of
- * its (typically) 32 bytes per point cross PCIe (84 -> 35 us for a 64 x 2048 sweep), and the device needs no
- * records -> SoA kernel.  Records whose x, y, z lie side by side with a fourth word behind them inside the record
- * (pcl::PointXYZI and every PointCloud2 layout of the lidar drivers) go four at a time through a 4 x 4 transpose and
- * leave with non-temporal stores (the planes are 16-byte aligned; on the test box's EPYC 9575F: memcpy of the 4 MiB
- * message 108 us, the transpose with ordinary stores 105, with streaming stores 67). */
-static void pc2_to_planes(const uint8_t* data, uint32_t i0, uint32_t n, uint32_t step, uint32_t ox, uint32_t oy, uint32_t oz, float* X,
-                          float* Y, float* Z)   /* points [i0, n); i0 a multiple of 4 */
-{
-    uint32_t i = i0;
-#if defined(__SSE2__)
-    if (oy == ox + 4 && oz == ox + 8 && (uint64_t)ox + 16 <= step) {
-        const uint8_t* p = data + (size_t)i0 * step + ox;
-        if ((((uintptr_t)(X + i0) | (uintptr_t)(Y + i0) | (uintptr_t)(Z + i0)) & 15u) == 0) {   /* (the pinned planes: always) */
-            for (; i + 4 <= n; i += 4, p += 4 * (size_t)step) {
-                __m128 r0 = _mm_loadu_ps((const float*)p), r1 = _mm_loadu_ps((const float*)(p + step));
-                __m128 r2 = _mm_loadu_ps((const float*)(p + 2 * (size_t)step)), r3 = _mm_loadu_ps((const float*)(p + 3 * (size_t)step));
-                _MM_TRANSPOSE4_PS(r0, r1, r2, r3);
-                _mm_stream_ps(X + i, r0);
-                _mm_stream_ps(Y + i, r1);
-                _mm_stream_ps(Z + i, r2);
-            }
-            _mm_sfence();   /* before the DMA engine is told to read them */
-        } else {
-            for (; i + 4 <= n; i += 4, p += 4 * (size_t)step) {
-                __m128 r0 = _mm_loadu_ps((const float*)p), r1 = _mm_loadu_ps((const float*)(p + step));
-                __m128 r2 = _mm_loadu_ps((const float*)(p + 2 * (size_t)step)), r3 = _mm_loadu_ps((const float*)(p + 3 * (size_t)step));
-                _MM_TRANSPOSE4_PS(r0, r1, r2, r3);
-                _mm_storeu_ps(X + i, r0);
-                _mm_storeu_ps(Y + i, r1);
-                _mm_storeu_ps(Z + i, r2);
-            }
-        }
-    }
-#endif
-    for (; i < n; i++) {
-        const uint8_t* p = data + (size_t)i * step;
-        std::memcpy(X + i, p + ox, 4);
-        std::memcpy(Y + i, p + oy, 4);
-        std::memcpy(Z + i, p + oz, 4);
-    }
-}
-
-/* the gather by itself (host only, no context): what urf_classify_pc2_async does with a message it stages */
-extern "C" int urf_pc2_to_planes(const uint8_t* data, uint32_t n_points, uint32_t point_step, uint32_t off_x, uint32_t off_y,
-                                 uint32_t off_z, float* x, float* y, float* z)
-{
-    if (!data || !x || !y || !z || !pc2_layout_ok(point_step, off_x, off_y, off_z))
-        return URF_ERR_INVALID_ARG;
-    pc2_to_planes(data, 0, n_points, point_step, off_x, off_y, off_z, x, y, z);
-    return URF_OK;
-}
-
-/* urf_set_sweep_outputs: the read-outs of the sweep run_pipeline has just launched on `st`, behind it on the same stream -- one linear
- * chain, separate launches as the only synchronisation -- with the sweep's own arguments and parameters (sl.cap_a: its scratch row, scan
- * 0), the row's read-out scratch and the slot's result buffers; then the copies to the slot's pinned buffer.  The kernels are
- * launch_markers' / launch_ordered's: a fused sequence (cap_a.front) holds the pre-pass and the *_front siblings as well and the scan
- * decides on the device which of each pair works; a sweep the short sequence voided leaves empty results (every kernel returns for a
- * status that is not URF_OK) and gets the right ones from its rerun.  With both bits set the per-ring work of the two products is one
- * launch (k_sweep_rings), lists and marker points another (k_sweep_lists).  c->fo_prep and want_ring_sorted are none of its business. */
-static int sweep_outputs_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t row, hipStream_t st, uint32_t n_points)
-{
-    const uint32_t bits = c->pol.sweep_outputs;
-    if (!bits)
-        return URF_OK;
-    const urf_kargs& a = sl.cap_a;
-    const urf_dev_params& dp = sl.cap_dp;
-    const bool mark = (bits & URF_SWEEP_OUT_MARKER_POINTS) != 0, order = (bits & URF_SWEEP_OUT_ORDER) != 0, fused = a.front != 0;
-    const bool merged = mark && order && !(c->debug_flags & URF_DBG_SWEEP_OLD_KERNELS);
-    const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS, ss = c->sstride;
-    urf_ctx::sweep_scratch_t& w = c->sweep;
-    float* const mk_d = w.mk_d.p + row * cells;
-    uint32_t* const mk_pos = w.mk_pos.p + row * cells;
-    uint8_t* const mk_red = w.mk_red.p + row * (cells + URF_MAX_CHANNELS);
-    uint8_t* const mk_lit = mk_red + cells;
-    unsigned long long* const ord_keys = w.ord_keys.p + row * ss;
-    uint32_t* const ord_pos = w.ord_pos.p + row * ss;
-    uint32_t* const ord_cls = w.ord_cls.p + (size_t)row * URF_MAX_CHANNELS * 2;
-    uint32_t* const fo_az = w.fo_az.p + row * ss;
-    uint32_t* const fo_ent = w.fo_ent.p + row * ss;
-    float* const fo_d = w.fo_d.p + row * ss;
-    /* urf_set_sweep_results_direct: the slot's mapped pinned buffer as the device sees it -- the last kernels of the chain store header
-     * results and lists there themselves, the lists back to back (k_sweep_lists_direct / k_ordered_lists_direct), and nothing is copied */
-    const bool direct = c->pol.sweep_direct;
-    uint32_t* const out = direct ? sl.m_out.dev : sl.d_out.p;
-    float* const d_pts = (float*)out;
-    uint32_t* const d_mcount = out + URF_SWEEP_HDR_MCOUNT;
-    uint32_t* const d_lcounts = out + URF_SWEEP_HDR_LCOUNTS;
-    uint32_t* const d_road = out + URF_SWEEP_HDR;
-    uint32_t* const d_curb = d_road + n_points;
-    uint32_t* const d_r10 = d_curb + n_points;
-    const dim3 g_ring((unsigned)dp.p.channels, 1), b256(256);
+    const urf_kargs& a = r.a;
+    const urf_dev_params& dp = r.dp;
+    const bool mark = (products & URF_SWEEP_OUT_MARKER_POINTS) != 0, order = (products & URF_SWEEP_OUT_ORDER) != 0, fused = a.front != 0;
+    uint8_t* const mk_lit = v.mk_red + n * (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;   /* one flag per ring and scan behind the cells */
+    const dim3 g_ring((unsigned)dp.p.channels, n), g_lists((unsigned)dp.p.channels + 1u, n), b256(256);
     const size_t map_lds = (2 * (size_t)a.tiles + 1) * sizeof(unsigned);
-    if (fused)
-        hipLaunchKernelGGL(k_front_out_prep, dim3(a.tiles, 1), b256, 0, st, a, dp, 0u, fo_az, fo_ent, fo_d);
+    if (prep)
+        hipLaunchKernelGGL(k_front_out_prep, dim3(a.tiles, n), b256, 0, st, a, dp, s0, v.fo_az, v.fo_ent, v.fo_d);
     if (merged) {
-        hipLaunchKernelGGL(k_sweep_rings, g_ring, b256, map_lds, st, a, dp, urf_ring_outs{ ord_keys, ord_pos, ord_cls, mk_d, mk_pos, mk_red, mk_lit });
+        hipLaunchKernelGGL(k_sweep_rings, g_ring, b256, map_lds, st, a, dp, urf_ring_outs{ v.ord_keys, v.ord_pos, v.ord_cls, v.mk_d, v.mk_pos, v.mk_red, mk_lit });
     } else {
         if (order)
-            hipLaunchKernelGGL(k_ring_order, g_ring, b256, map_lds, st, a, dp, 0u, ord_keys, ord_pos, ord_cls);
+            hipLaunchKernelGGL(k_ring_order, g_ring, b256, map_lds, st, a, dp, s0, v.ord_keys, v.ord_pos, v.ord_cls);
         if (mark)
-            hipLaunchKernelGGL(k_marker_ring, g_ring, b256, map_lds, st, a, dp, 0u, mk_d, mk_pos, mk_red, mk_lit);
+            hipLaunchKernelGGL(k_marker_ring, g_ring, b256, map_lds, st, a, dp, s0, v.mk_d, v.mk_pos, v.mk_red, mk_lit);
     }
     if (fused && order)
-        hipLaunchKernelGGL(k_ring_order_front, g_ring, b256, 0, st, a, dp, 0u, fo_az, fo_ent, ord_pos, ord_cls);
+        hipLaunchKernelGGL(k_ring_order_front, g_ring, b256, 0, st, a, dp, s0, v.fo_az, v.fo_ent, v.ord_pos, v.ord_cls);
     if (fused && mark)
-        hipLaunchKernelGGL(k_marker_ring_front, g_ring, b256, 0, st, a, dp, 0u, fo_az, fo_ent, fo_d, mk_d, mk_pos, mk_red, mk_lit);
+        hipLaunchKernelGGL(k_marker_ring_front, g_ring, b256, 0, st, a, dp, s0, v.fo_az, v.fo_ent, v.fo_d, v.mk_d, v.mk_pos, v.mk_red, mk_lit);
     if (mark) {   /* rings in which the ORDER of equal azimuths decides a marker point (normally none: every workgroup returns at once) */
-        hipLaunchKernelGGL(k_marker_ring_literal, g_ring, b256, 0, st, a, dp, 0u, mk_lit, mk_d, mk_pos, mk_red);
+        hipLaunchKernelGGL(k_marker_ring_literal, g_ring, b256, 0, st, a, dp, s0, mk_lit, v.mk_d, v.mk_pos, v.mk_red);
         if (fused)
-            hipLaunchKernelGGL(k_marker_ring_literal_front, g_ring, b256, 0, st, a, dp, 0u, mk_lit, fo_az, fo_ent, fo_d, mk_d, mk_pos, mk_red);
+            hipLaunchKernelGGL(k_marker_ring_literal_front, g_ring, b256, 0, st, a, dp, s0, mk_lit, v.fo_az, v.fo_ent, v.fo_d, v.mk_d, v.mk_pos, v.mk_red);
     }
     if (merged) {
         if (direct)
-            hipLaunchKernelGGL(k_sweep_lists_direct, dim3((unsigned)dp.p.channels + 1u, 1), dim3(384), 0, st, a, dp,
-                               urf_sweep_lists_args{ ord_pos, ord_cls, d_road, nullptr, nullptr, d_lcounts, 0u, mk_d, mk_pos, mk_red, d_pts, d_mcount });
+            hipLaunchKernelGGL(k_sweep_lists_direct, g_lists, dim3(384), 0, st, a, dp,
+                               urf_sweep_lists_args{ v.ord_pos, v.ord_cls, d.road, nullptr, nullptr, d.lcounts, 0u, v.mk_d, v.mk_pos, v.mk_red, d.pts, d.mcount });
         else
-            hipLaunchKernelGGL(k_sweep_lists, dim3((unsigned)dp.p.channels + 1u, 1), dim3(384), 0, st, a, dp,
-                               urf_sweep_lists_args{ ord_pos, ord_cls, d_road, d_curb, d_r10, d_lcounts, n_points, mk_d, mk_pos, mk_red, d_pts, d_mcount });
+            hipLaunchKernelGGL(k_sweep_lists, g_lists, dim3(384), 0, st, a, dp,
+                               urf_sweep_lists_args{ v.ord_pos, v.ord_cls, d.road, d.curb, d.r10, d.lcounts, d.stride, v.mk_d, v.mk_pos, v.mk_red, d.pts, d.mcount });
     } else {
         if (order && direct)
-            hipLaunchKernelGGL(k_ordered_lists_direct, g_ring, b256, 0, st, a, dp, ord_pos, ord_cls, d_road, d_lcounts);
+            hipLaunchKernelGGL(k_ordered_lists_direct, g_ring, b256, 0, st, a, dp, v.ord_pos, v.ord_cls, d.road, d.lcounts);
         else if (order)
-            hipLaunchKernelGGL(k_ordered_lists, g_ring, b256, 0, st, a, dp, 0u, ord_pos, ord_cls, d_road, d_curb, d_r10, n_points, d_lcounts);
+            hipLaunchKernelGGL(k_ordered_lists, g_ring, b256, 0, st, a, dp, s0, v.ord_pos, v.ord_cls, d.road, d.curb, d.r10, d.stride, d.lcounts);
         if (mark) {
-            hipLaunchKernelGGL(k_marker_bins, dim3(1), dim3(384), 0, st, a, dp, 0u, mk_d, mk_pos, mk_red, d_pts, d_mcount);
+            hipLaunchKernelGGL(k_marker_bins, dim3(n), dim3(384), 0, st, a, dp, s0, v.mk_d, v.mk_pos, v.mk_red, d.pts, d.mcount);
             if (fused)
-                hipLaunchKernelGGL(k_marker_bins_front, dim3(1), dim3(384), 0, st, a, dp, 0u, mk_d, mk_pos, mk_red, d_pts, d_mcount);
+                hipLaunchKernelGGL(k_marker_bins_front, dim3(n), dim3(384), 0, st, a, dp, s0, v.mk_d, v.mk_pos, v.mk_red, d.pts, d.mcount);
         }
     }
     URF_HIP(c, hipGetLastError());
-    if (direct)
-        return URF_OK;   /* (the results are where the host reads them once the slot's event has completed) */
-    URF_HIP(c, hipMemcpyAsync(sl.h_out.p, out, URF_SWEEP_HDR * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (order)
-        URF_HIP(c, hipMemcpyAsync(sl.h_out.p + URF_SWEEP_HDR, d_road, 3 * (size_t)n_points * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     return URF_OK;
 }
 
-/* what one sweep of the callback path launches on the compute stream: records -> SoA (unless the message was
- * staged as planes), the pipeline, results to the pinned host buffers */
-static int slot_launch(urf_ctx* c, urf_ctx::slot_t& sl, uint32_t n_points, uint32_t point_step, uint32_t off_x,
-                       uint32_t off_y, uint32_t off_z, const urf_dev_params* dp_in = nullptr, int capture_in = -1)
-{
-    const uint32_t row = slot_row(c, sl);
-    hipStream_t st = slot_stream(c, sl);
-    float *sx, *sy, *sz;
-    if (sl.planes) {
-        const size_t n4 = ((size_t)n_points + 3) & ~(size_t)3;
-        sx = (float*)sl.d_raw.p;
-        sy = sx + n4;
-        sz = sy + n4;
-    } else {
-        sx = c->sx.p + (size_t)row * c->max_points;   /* (ensure_soa_staging: the caller) */
-        sy = c->sy.p + (size_t)row * c->max_points;
-        sz = c->sz.p + (size_t)row * c->max_points;
-        if (sl.pad)   /* (urf_set_sweep_quantum: n_points is the padded length, the sweep's own stands in the slot's device word) */
-            hipLaunchKernelGGL(k_pc2_to_soa_pad, dim3((n_points + 255) / 256), dim3(256), 0, st, sl.d_raw.p, sl.d_n.p, n_points, point_step,
-                               off_x, off_y, off_z, sx, sy, sz);
-        else
-            hipLaunchKernelGGL(k_pc2_to_soa, dim3((n_points + 255) / 256), dim3(256), 0, st, sl.d_raw.p, (unsigned long long)n_points,
-                               point_step, off_x, off_y, off_z, sx, sy, sz);
-    }
-    const int rc = run_pipeline(c, urf_call{ sx, sy, sz, nullptr, n_points, n_points, 1, sl.d_labels.p, nullptr, row, st, dp_in, capture_in },
-                                sl.cap_a, sl.cap_dp);
-    if (rc != URF_OK)
-        return rc;
-    sl.cap_planned = c->planned;
-    URF_HIP(c, hipMemcpyAsync(sl.h_labels.p, sl.d_labels.p, n_points, hipMemcpyDeviceToHost, st));
-    URF_HIP(c, hipMemcpyAsync(sl.h_info.p, kargs_row(c, row).info, sizeof(urf_scan_info), hipMemcpyDeviceToHost, st));
-    return sweep_outputs_launch(c, sl, row, st, n_points);   /* (urf_set_sweep_outputs; off: nothing) */
-}
-
-extern "C" int urf_pinned_input(urf_ctx* c, size_t bytes, uint8_t** ptr)
-{
-    if (!c || !ptr || bytes == 0)
-        return URF_ERR_INVALID_ARG;
-    urf_ctx::slot_t& sl = c->slots[c->next_ticket % URF_ASYNC_SLOTS];   /* the slot the next submission uses */
-    if (sl.pending)
-        return URF_ERR_BUSY;
-    URF_HIP(c, hipSetDevice(c->device));
-    const int rc = slot_prepare(c, sl, bytes);
-    if (rc != URF_OK)
-        return rc;
-    *ptr = sl.h_in.p;
-    return URF_OK;
-}
-
-extern "C" int urf_classify_pc2_async(urf_ctx* c, const uint8_t* data, uint32_t n_points, uint32_t point_step,
-                                      uint32_t off_x, uint32_t off_y, uint32_t off_z, uint32_t* ticket)
-{
-    if (!c || !data || !ticket || n_points == 0 || !pc2_layout_ok(point_step, off_x, off_y, off_z))
-        return URF_ERR_INVALID_ARG;   /* before any byte of the message is copied */
-    if (n_points > c->max_points)
-        return URF_ERR_CAPACITY;
-    urf_ctx::slot_t& sl = c->slots[c->next_ticket % URF_ASYNC_SLOTS];
-    if (sl.pending)
-        return URF_ERR_BUSY;          /* every slot in flight: urf_classify_pc2_wait() the oldest one first */
-    URF_HIP(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)n_points * point_step;
-    HT_START;
-    /* a message inside the slot's pinned buffer must be the buffer urf_pinned_input() handed out, and
-     * fit it: a larger one would make slot_prepare() free the very memory it is about to read */
-    if (sl.h_in.p && data >= sl.h_in.p && data < sl.h_in.p + sl.h_in.cap && (data != sl.h_in.p || bytes > sl.h_in.cap))
-        return URF_ERR_INVALID_ARG;
-    const bool planes = data != sl.h_in.p;   /* (a producer that filled the pinned buffer itself wrote records) */
-    /* urf_set_sweep_quantum: the sweep runs as the next multiple of the quantum, (NaN, NaN, NaN) behind its own points -- the reference
-     * drops non-finite points before anything else, so labels and summary are those of the unpadded sweep -- and every sweep of that
-     * padded length replays one captured sequence.  A padded length beyond max_points: unpadded, under its own key. */
-    uint32_t n_run = n_points;
-    bool pad = false;
-    if (const uint32_t q = c->pol.sweep_quantum) {
-        const uint64_t up = ((uint64_t)n_points + q - 1) / q * q;
-        if (up <= c->max_points) {
-            n_run = (uint32_t)up;
-            pad = true;   /* (a multiple of the quantum too: it shares the padded sequence of its length) */
-        }
-    }
-    const size_t n4 = ((size_t)n_run + 3) & ~(size_t)3;
-    const size_t plane_bytes = 3 * sizeof(float) * n4;
-    size_t want = planes && plane_bytes > bytes ? plane_bytes : bytes;
-    if (pad && (want > sl.h_in.cap || want > sl.d_raw.cap)) {
-        /* a new buffer forgets the slot's sequences, and the messages of such a stream keep growing by a few points: room for twice the
-         * padded length (at most max_points), so that the lengths to come fit the buffer this one gets */
-        const size_t room = std::min<size_t>(2 * (size_t)n_run, c->max_points);
-        want = std::max(want, ((room + 3) & ~(size_t)3) * std::max<size_t>(point_step, 3 * sizeof(float)));
-    }
-    int rc = slot_prepare(c, sl, want);
-    if (rc == URF_OK && !planes)
-        rc = ensure_soa_staging(c);   /* where the device gathers the records' x / y / z */
-    if (rc != URF_OK)
-        return rc;
-    hipStream_t st = slot_stream(c, sl);
-    rc = order_row_after_main(c, slot_row(c, sl), st);
-    if (rc != URF_OK)
-        return rc;
-    /* The message goes to the device on the slot's own stream, in front of the sweep's kernels.  (r2 / r3 used a copy
-     * stream of its own and an event per sweep for the slot's stream to wait on: 7 870 -> 8 670 sweeps/s with a pinned
-     * producer, 6 460 -> 7 540 staged without them.  The four streams still map to three hardware queues -- kernel
-     * trace, profiles/r3_callback_trace_after.txt --, but more queues made things worse, see profiles/README.md.)
-     * Sweeps of other slots run beside the copy as before. */
-    if (planes) {
-        /* gathered into the pinned planes (pc2_to_planes) in two halves, so that the first one is on its way while the
-         * second one is gathered (one 2-D copy per half: its columns of the three planes; 35 us for the whole, 22 per
-         * half).  (urf_pinned_input() lets a producer write its records into the pinned buffer directly: no staging.) */
-        float* X = (float*)sl.h_in.p;
-        const size_t real4 = ((size_t)n_points + 3) & ~(size_t)3;   /* (the halves are halves of the sweep's own points; no pad: n4) */
-        const uint32_t mid = n_points >= 32768 ? (uint32_t)((real4 / 2) & ~(size_t)3) : 0u;
-        const uint32_t cut[3] = { 0u, mid, n_points };
-        for (int h = mid ? 0 : 1; h < 2; h++) {
-            pc2_to_planes(data, cut[h], cut[h + 1], point_step, off_x, off_y, off_z, X, X + n4, X + 2 * n4);
-            if (h == 1 && n_run != n_points) {   /* the pad: the planes' tails, which the second copy's columns [mid, n_run) carry */
-                const float nan = std::numeric_limits<float>::quiet_NaN();
-                for (float* P : { X, X + n4, X + 2 * n4 })
-                    std::fill(P + n_points, P + n_run, nan);
-            }
-            const size_t w = (h == 1 ? n4 - cut[1] : cut[1]) * sizeof(float), o = cut[h] * sizeof(float);
-            URF_HIP(c, hipMemcpy2DAsync(sl.d_raw.p + o, n4 * sizeof(float), sl.h_in.p + o, n4 * sizeof(float), w, 3, hipMemcpyHostToDevice, st));
-        }
-    } else {
-        URF_HIP(c, hipMemcpyAsync(sl.d_raw.p, sl.h_in.p, bytes, hipMemcpyHostToDevice, st));
-        if (pad) {   /* the sweep's own length for k_pc2_to_soa_pad: a word of the slot, copied in front of every launch of the sequence */
-            *sl.h_n.p = n_points;
-            URF_HIP(c, hipMemcpyAsync(sl.d_n.p, sl.h_n.p, sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        }
-    }
-    if (planes != sl.planes)
-        for (auto& q : sl.seqs)
-            q.key[0] = 0;   /* the captured sequences read the other format */
-    sl.planes = planes;
-    sl.n_run = n_run;
-    sl.pad = pad;
-    HT(0, ht0);   /* staging + H2D enqueue */
-    /* what earlier calls reported, for this sweep and the replayed sequences (outside the stream capture: fold may synchronise) */
-    rc = c->pol.fold(c, st);
-    if (rc != URF_OK)
-        return rc;
-    c->pol.probation_sweep();
-    if (c->pol.auto_on)   /* urf_set_front_auto: the sweep's advice, applied before its sequence is chosen (a change bumps the epoch) */
-        auto_at_call(c, std::max<uint32_t>((n_run + URF_TILE - 1) / URF_TILE, 1u), 1u, (uint32_t)c->capture, true);
-    /* the launch sequence of a sweep of this shape is captured once and replayed (one graph launch
-     * instead of a dozen kernel launches per callback); anything it depends on bumps the epoch */
-    const uint64_t key[3] = { c->pol.epoch,((uint64_t)n_run << 32) | point_step,
-                              ((uint64_t)off_x << 42) ^ ((uint64_t)off_y << 21) ^ off_z };
-    const bool use_graph = !c->timing && !(c->debug_flags & 8u);
-    HT(1, ht0);   /* event record, ordering, stream wait */
-    if (use_graph) {
-        /* The slot's sequence for this key.  One per slot; with urf_set_sweep_quantum up to URF_SWEEP_SEQS, the least recently used
-         * one making room for a new length.  Sequences of an earlier epoch go, all of them, whatever the key. */
-        const unsigned n_seqs = c->pol.sweep_quantum ? URF_SWEEP_SEQS : 1u;
-        urf_ctx::slot_t::seq_t *seq = nullptr, *room = nullptr;
-        for (auto& q : sl.seqs) {
-            if (q.exec && q.key[0] != key[0])
-                seq_drop(q);
-            if (q.exec && q.key[1] == key[1] && q.key[2] == key[2])
-                seq = &q;
-        }
-        if (!seq) {
-            for (unsigned i = 0; i < n_seqs; i++) {
-                urf_ctx::slot_t::seq_t& q = sl.seqs[i];
-                if (!q.exec) {
-                    room = &q;
-                    break;
-                }
-                if (!room || q.used < room->used)
-                    room = &q;
-            }
-            seq_drop(*room);
-            URF_HIP(c, hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-            rc = slot_launch(c, sl, n_run, point_step, off_x, off_y, off_z);
-            hipGraph_t g = nullptr;
-            const hipError_t e = hipStreamEndCapture(st, &g);
-            if (rc != URF_OK || e != hipSuccess) {
-                if (g)
-                    (void)hipGraphDestroy(g);
-                if (rc == URF_OK)
-                    URF_HIP(c, e);
-                return rc;
-            }
-            room->graph = g;
-            URF_HIP(c, hipGraphInstantiate(&room->exec, room->graph, nullptr, nullptr, 0));
-            room->key[0] = key[0];
-            room->key[1] = key[1];
-            room->key[2] = key[2];
-            room->cap_a = sl.cap_a;
-            room->cap_dp = sl.cap_dp;
-            room->cap_planned = sl.cap_planned;
-            c->n_captured++;
-            seq = room;
-        } else {   /* (what the sweep in this slot ran with: the readers' record, the rerun's parameters) */
-            sl.cap_a = seq->cap_a;
-            sl.cap_dp = seq->cap_dp;
-            sl.cap_planned = seq->cap_planned;
-        }
-        seq->used = ++c->seq_clock;
-        URF_HIP(c, hipGraphLaunch(seq->exec, st));
-    } else {
-        rc = slot_launch(c, sl, n_run, point_step, off_x, off_y, off_z);
-        if (rc != URF_OK)
-            return rc;
-    }
-    HT(2, ht0);   /* graph launch (or the launches themselves) */
-    /* urf_set_front_auto's learning pass: no part of the captured sequence, on the sweep's stream behind it and in front of ev_done --
-     * the event urf_classify_pc2_wait waits for, the context's stream waits for before it touches a row (order_after_slots), and, on
-     * the same stream, whatever the row's next sweep launches (slots that share a row share its stream: max_batch < URF_ASYNC_SLOTS).
-     * The planes or staging rows it reads again belong to this slot resp. this row until then. */
-    rc = auto_pass(c, sl.cap_a, sl.cap_dp, sl.cap_planned, st, 1u + (uint32_t)(&sl - c->slots), c->max_batch + (uint32_t)(&sl - c->slots), n_points);
-    if (rc != URF_OK)
-        return rc;
-    URF_HIP(c, hipEventRecord(sl.ev_done, st));
-    HT(3, ht0);
-    sl.pending = true;
-    sl.used = true;
-    sl.n_points = n_points;
-    sl.point_step = point_step;
-    sl.off_x = off_x;
-    sl.off_y = off_y;
-    sl.off_z = off_z;
-    sl.ticket = c->next_ticket;
-    sl.out_bits = c->pol.sweep_outputs;   /* (it cannot change while the sweep is pending) */
-    sl.out_direct = c->pol.sweep_direct;
-    sl.gen = ++c->row_gen[slot_row(c, sl)];
-    *ticket = c->next_ticket++;
-    return URF_OK;
-}
-
-extern "C" int urf_classify_pc2_wait(urf_ctx* c, uint32_t ticket, uint8_t* labels_out, urf_scan_info* info)
-{
-    if (!c)
-        return URF_ERR_INVALID_ARG;
-    urf_ctx::slot_t& sl = c->slots[ticket % URF_ASYNC_SLOTS];
-    if (!sl.pending || sl.ticket != ticket)
-        return URF_ERR_INVALID_ARG;
-    URF_HIP(c, hipSetDevice(c->device));
-    HT_START;
-    URF_HIP(c, hipEventSynchronize(sl.ev_done));
-    HT(4, ht0);
-    /* the short launch sequence left out something this sweep needed (urf_policy::plan): once more, with it --
-     * the message is still in the slot's device buffer -- and from now on for every sweep (on_redo) */
-    for (int tries = 0; c->pol.on_redo(sl.h_info.p->status); tries++) {
-        if (tries == 6) {
-            sl.pending = false;
-            return URF_ERR_HIP;   /* (cannot happen: the full sequence raises none) */
-        }
-        c->n_rerun++;
-        /* the rerun is the row's LATEST submission: with fewer rows than sweeps in flight a later sweep shares this row, and
-         * what it left there is overwritten now -- its read-backs of the row must answer URF_ERR_BUSY, not this sweep's data */
-        sl.gen = ++c->row_gen[slot_row(c, sl)];
-        /* with the parameters and capture mode the sweep was submitted with (urf_set_params may have been called since),
-         * behind whatever the context's stream still does with the row */
-        int rc = order_row_after_main(c, slot_row(c, sl), slot_stream(c, sl));
-        if (rc == URF_OK)
-            rc = slot_launch(c, sl, sl.n_run, sl.point_step, sl.off_x, sl.off_y, sl.off_z, &sl.cap_dp, (int)sl.cap_a.capture);   /* (a padded sweep: pad and length word are still in place) */
-        if (rc == URF_OK && hipStreamSynchronize(slot_stream(c, sl)) != hipSuccess) {
-            c->last_error = "hipStreamSynchronize (rerun of a voided sweep)";
-            rc = URF_ERR_HIP;
-        }
-        if (rc != URF_OK) {
-            sl.pending = false;   /* the slot must not stay busy for ever */
-            return rc;
-        }
-    }
-    /* only now is the sweep "the last call": its scratch row stays untouched until the row (or a batch call) is used again */
-    publish_last(c, URF_LAST_SWEEP, 1, sl.cap_a, sl.cap_dp, sl.cap_planned, slot_row(c, sl), sl.gen);
-    c->last.sweep_n = sl.n_points;   /* (the readers answer for the caller's points, whatever length the sweep ran as) */
-    if (labels_out)
-        std::memcpy(labels_out, sl.h_labels.p, sl.n_points);
-    if (info)
-        *info = *sl.h_info.p;
-    sl.pending = false;
-    HT(5, ht0);
-    return URF_OK;
-}
-
-extern "C" int urf_result_labels(urf_ctx* c, uint32_t ticket, const uint8_t** labels)
-{
-    if (!c || !labels)
-        return URF_ERR_INVALID_ARG;
-    *labels = nullptr;
-    const urf_ctx::slot_t& sl = c->slots[ticket % URF_ASYNC_SLOTS];
-    if (!sl.used || sl.ticket != ticket || !sl.h_labels.p)
-        return URF_ERR_INVALID_ARG;   /* never issued, or its slot has been used again since */
-    if (sl.pending)
-        return URF_ERR_BUSY;          /* not waited for yet: the buffer is still being written */
-    *labels = sl.h_labels.p;
-    return URF_OK;
-}
-
-/* where the results of the sweep in this slot are: the buffer of the way it was submitted (the switch may have changed since) */
-static const uint32_t* sweep_result_words(const urf_ctx::slot_t& sl) { return sl.out_direct ? sl.m_out.p : sl.h_out.p; }
-
-/* the ticket's slot for urf_result_marker_points / urf_result_ordered_indices: urf_result_labels' rules, and the sweep was submitted with `bit` */
-static int sweep_result_slot(urf_ctx* c, uint32_t ticket, uint32_t bit, const char* what, const urf_ctx::slot_t*& out)
-{
-    const urf_ctx::slot_t& sl = c->slots[ticket % URF_ASYNC_SLOTS];
-    if (!sl.used || sl.ticket != ticket)
-        return URF_ERR_INVALID_ARG;   /* never issued, or its slot has been used again since */
-    if (sl.pending)
-        return URF_ERR_BUSY;          /* not waited for yet: the buffer is still being written */
-    if (!(sl.out_bits & bit) || !sweep_result_words(sl)) {
-        c->last_error = std::string(what) + ": the sweep was submitted without " +
-                        (bit == URF_SWEEP_OUT_ORDER ? "URF_SWEEP_OUT_ORDER" : "URF_SWEEP_OUT_MARKER_POINTS") + " (urf_set_sweep_outputs)";
-        return URF_ERR_INVALID_ARG;
-    }
-    out = &sl;
-    return URF_OK;
-}
-
-extern "C" int urf_result_marker_points(urf_ctx* c, uint32_t ticket, const float** pts, uint32_t* count)
-{
-    if (!c || !pts || !count)
-        return URF_ERR_INVALID_ARG;
-    *pts = nullptr;
-    *count = 0;
-    const urf_ctx::slot_t* sl = nullptr;
-    const int rc = sweep_result_slot(c, ticket, URF_SWEEP_OUT_MARKER_POINTS, "urf_result_marker_points", sl);
-    if (rc != URF_OK)
-        return rc;
-    const uint32_t* const words = sweep_result_words(*sl);
-    *pts = (const float*)words;
-    if (sl->h_info.p->status != URF_OK)
-        return URF_OK;   /* nothing is published for such a sweep */
-    const uint32_t n = words[URF_SWEEP_HDR_MCOUNT];
-    if (n > URF_DEG_CELLS)
-        return URF_ERR_HIP;
-    *count = n;
-    return URF_OK;
-}
-
-extern "C" int urf_result_ordered_indices(urf_ctx* c, uint32_t ticket, const uint32_t** road, const uint32_t** curb, const uint32_t** ring10,
-                                          uint32_t counts[3])
-{
-    if (!c || !counts)
-        return URF_ERR_INVALID_ARG;
-    counts[0] = counts[1] = counts[2] = 0;
-    for (const uint32_t** p : { road, curb, ring10 })
-        if (p)
-            *p = nullptr;
-    const urf_ctx::slot_t* sl = nullptr;
-    const int rc = sweep_result_slot(c, ticket, URF_SWEEP_OUT_ORDER, "urf_result_ordered_indices", sl);
-    if (rc != URF_OK)
-        return rc;
-    const uint32_t* const words = sweep_result_words(*sl);
-    const uint32_t* lists = words + URF_SWEEP_HDR;
-    const uint32_t* h = words + URF_SWEEP_HDR_LCOUNTS;
-    const bool ok = sl->h_info.p->status == URF_OK;
-    if (ok && (h[0] > sl->n_points || h[1] > sl->n_points || h[2] > sl->n_points || (uint64_t)h[0] + h[1] > sl->n_points))
-        return URF_ERR_HIP;
-    /* three lists at a stride of the points the sweep ran as (urf_set_sweep_quantum: padded); a sweep submitted direct: back to back */
-    const size_t at1 = sl->out_direct ? (ok ? h[0] : 0u) : sl->n_run, at2 = sl->out_direct ? (ok ? (size_t)h[0] + h[1] : 0u) : 2 * (size_t)sl->n_run;
-    if (road)
-        *road = lists;
-    if (curb)
-        *curb = lists + at1;
-    if (ring10)
-        *ring10 = lists + at2;
-    if (!ok)
-        return URF_OK;
-    counts[0] = h[0];
-    counts[1] = h[1];
-    counts[2] = h[2];
-    return URF_OK;
-}
-
-extern "C" int urf_classify_pc2(urf_ctx* c, const uint8_t* data, uint32_t n_points, uint32_t point_step,
-                                uint32_t off_x, uint32_t off_y, uint32_t off_z, uint8_t* labels_out, urf_scan_info* info)
-{
-    if (!c || !data || !labels_out || !pc2_layout_ok(point_step, off_x, off_y, off_z))
-        return URF_ERR_INVALID_ARG;   /* before any byte of the message is copied */
-    if (n_points > c->max_points)
-        return URF_ERR_CAPACITY;
-    if (n_points == 0) {
-        if (info) {
-            std::memset(info, 0, sizeof(*info));
-            info->status = URF_TOO_FEW_POINTS;
-        }
-        return URF_OK;
-    }
-    uint32_t ticket = 0;
-    const int rc = urf_classify_pc2_async(c, data, n_points, point_step, off_x, off_y, off_z, &ticket);
-    if (rc != URF_OK)
-        return rc;
-    return urf_classify_pc2_wait(c, ticket, labels_out, info);
-}
+#include "urf_api_sweep.hpp"
 
 /* Step 1 of last_call(), on its own for the entry points that check sizes of theirs against the call before any HIP call: a last call
  * exists, holds `scan` (a batch read-out: 0) and is of `kind` where that matters (urf_clouds_batch_*).  nullptr: URF_ERR_INVALID_ARG. */
@@ -2451,7 +1438,7 @@ static const urf_last_call* last_valid(urf_ctx* c, uint32_t scan = 0, int kind =
                                                                          : "the last classify call was no batch call (urf_classify_batch_*)";
         return nullptr;
     }
-    return scan < l.scans && l.a.labels ? &l : nullptr;   /* (no call yet: no scans) */
+    return scan < l.scans && l.run.a.labels ? &l : nullptr;   /* (no call yet: no scans) */
 }
 
 /* After a dense call (urf_classify_batch_*_dense) the record is the PADDED batch: what answers in padded indices -- urf_ordered_indices*,
@@ -2481,19 +1468,18 @@ static int last_call(urf_ctx* c, uint32_t scan, const urf_last_call*& out, urf_l
         return URF_ERR_BUSY;
     }
     int rc = URF_OK;
-    if (l.a.front && !(need == URF_NEED_RING_ORDER && c->pol.front_outputs)) {
+    if (l.run.a.front && !(need == URF_NEED_RING_ORDER && c->pol.front_outputs)) {
         /* the last call went through the fused front end (urf_front.hpp), which keeps no ring-sorted copies: once more on its row through
          * the general kernels, as a batch call with every repair kernel in the sequence (same inputs -- a batch caller's arrays must still
          * be alive, a sweep of the callback path is still in its slot's device buffer and its row has not been resubmitted (checked
          * above) --, same parameters, same labels), and the context stays with them: a caller that reads ring-sorted results pays for
-         * them once, not per call.  Only the record's arguments and parameters change: a sweep stays the sweep it was.
+         * them once, not per call.  Only the record's run changes: a sweep stays the sweep it was (row, gen, sweep_n, dense).
          * With urf_set_front_outputs on, the entry points that only need the rings' points in order (URF_NEED_RING_ORDER) take the fused
          * call as it is: launch_ordered / launch_markers run the kernels of urf_k_front_outputs.hpp next to the general ones. */
         c->pol.set(c->pol.want_ring_sorted, true);
-        rc = run_pipeline(c, urf_call{ l.a.x, l.a.y, l.a.z, l.a.offsets, l.a.n_per_scan, l.a.max_len, l.a.n_scans, l.a.labels, nullptr, l.row,
-                                       nullptr, &l.dp, (int)l.a.capture, true }, l.a, l.dp);
-        if (rc == URF_OK)
-            l.planned = c->planned;
+        const urf_kargs& a = l.run.a;
+        rc = run_pipeline(c, urf_call{ a.x, a.y, a.z, a.offsets, a.n_per_scan, a.max_len, a.n_scans, a.labels, nullptr, l.row, nullptr, &l.run.dp,
+                                       (int)a.capture, true }, l.run);
         c->last_seq++;
     }
     return rc != URF_OK ? rc : order_after_slots(c);
@@ -2519,8 +1505,8 @@ extern "C" int urf_front_explain(urf_ctx* c, int layout, urf_front_why* out, uin
     int rc = grow(c, c->fx_rec, (size_t)n * URF_FX_WORDS, c->stream);
     if (rc != URF_OK || (rc = order_after_slots(c)) != URF_OK)
         return rc;
-    const urf_kargs& a = l.a;
-    const urf_dev_params& dp = l.dp;
+    const urf_kargs& a = l.run.a;
+    const urf_dev_params& dp = l.run.dp;
     const unsigned L = (unsigned)dp.p.channels;
     const bool rows = layout == 1 && !l.dense.on;   /* (a dense call: the padded batch, firing order) */
     const bool lasers = L == 16u || L == 32u || L == 64u || L == 128u;   /* (other counts: no laser slots to speak of, the counters stay 0) */
@@ -2544,15 +1530,15 @@ extern "C" int urf_front_explain(urf_ctx* c, int layout, urf_front_why* out, uin
             lens[s] = std::min(offs[s + 1] - offs[s], a.max_len);
     }
     URF_HIP(c, hipStreamSynchronize(st));
-    const urf_fx_call k = fx_call_of(a, dp, l.planned, rows, 0u);
+    const urf_fx_call k = fx_call_of(l.run, rows, 0u);
     for (uint32_t s = 0; s < n; s++) {
         const uint32_t* r = &rec[(size_t)s * URF_FX_WORDS];
         const urf_fx_scan v = urf_front_scan_rule(k, r, ok[s], ncand[s], info[s].status, lens[s]);   /* (the rule k_front_digest applies on the device) */
         urf_front_why w;
         std::memset(&w, 0, sizeof w);
         w.fused = v.fused;
-        w.call = l.planned.call.why;
-        w.advice = l.planned.call.advice | v.advice;
+        w.call = l.run.planned.call.why;
+        w.advice = l.run.planned.call.advice | v.advice;
         w.scan = v.scan;
         w.candidates = ncand[s];
         w.candidate_cap = a.front_cand_cap;
@@ -2603,36 +1589,32 @@ extern "C" int urf_compact_indices(urf_ctx* c, const uint8_t* d_labels, uint32_t
     return urf_compact_indices_batch(c, d_labels, n_points, 1, d_road, d_curb, d_roi, d_ring10, d_counts);
 }
 
-static int ensure_order_scratch(urf_ctx* c, uint32_t n_scans)
+/* The read-out chain for scans [s0, s0 + n) of the last classify call (l: from last_call) on the context's stream: the scratch of the
+ * wanted products grown to n scans, for a fused record (last_call: only with urf_set_front_outputs on) the pre-pass's too; then
+ * launch_readouts, with the pre-pass unless its arrays already hold exactly that (same recorded call, same range). */
+static int readouts_of_last(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t n, uint32_t products, const urf_readout_dst& d)
 {
-    const size_t n = (size_t)n_scans * c->sstride;
-    int rc;
-    if ((rc = grow(c, c->ord_keys, n, c->stream)) != URF_OK || (rc = grow(c, c->ord_pos, n, c->stream)) != URF_OK)
+    urf_readout_scratch& w = c->ro;
+    const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS, ss = (size_t)n * c->sstride;
+    hipStream_t st = c->stream;
+    int rc = URF_OK;
+    if ((products & URF_SWEEP_OUT_ORDER) && ((rc = grow(c, w.ord_keys, ss, st)) != URF_OK || (rc = grow(c, w.ord_pos, ss, st)) != URF_OK ||
+                                             (rc = grow(c, w.ord_cls, (size_t)n * URF_MAX_CHANNELS * 2, st)) != URF_OK))
         return rc;
-    return grow(c, c->ord_cls, (size_t)n_scans * URF_MAX_CHANNELS * 2, c->stream);
-}
-
-/* The pre-pass of the read-outs of a fused call (urf_k_front_outputs.hpp) for scans [s0, s0 + n) of the last call: scratch, then
- * k_front_out_prep unless the arrays already hold exactly that (same recorded call, same range). */
-static int front_out_prepare(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t n)
-{
-    const size_t cnt = (size_t)n * c->sstride;
-    const bool regrow = cnt > c->fo_az.cap || cnt > c->fo_ent.cap || cnt > c->fo_d.cap;
-    int rc;
-    if ((rc = grow(c, c->fo_az, cnt, c->stream)) != URF_OK || (rc = grow(c, c->fo_ent, cnt, c->stream)) != URF_OK ||
-        (rc = grow(c, c->fo_d, cnt, c->stream)) != URF_OK) {
-        c->fo_prep.seq = 0;
+    if ((products & URF_SWEEP_OUT_MARKER_POINTS) && ((rc = grow(c, w.mk_d, n * cells, st)) != URF_OK || (rc = grow(c, w.mk_pos, n * cells, st)) != URF_OK ||
+                                                     (rc = grow(c, w.mk_red, n * (cells + URF_MAX_CHANNELS), st)) != URF_OK))
         return rc;
+    bool prep = false;
+    if (l.run.a.front) {
+        prep = ss > w.fo_az.cap || ss > w.fo_ent.cap || ss > w.fo_d.cap || c->fo_prep.seq != c->last_seq || c->fo_prep.s0 != s0 || c->fo_prep.n != n;
+        if (prep)
+            c->fo_prep.seq = 0;
+        if ((rc = grow(c, w.fo_az, ss, st)) != URF_OK || (rc = grow(c, w.fo_ent, ss, st)) != URF_OK || (rc = grow(c, w.fo_d, ss, st)) != URF_OK)
+            return rc;
     }
-    if (!regrow && c->fo_prep.seq == c->last_seq && c->fo_prep.s0 == s0 && c->fo_prep.n == n)
-        return URF_OK;
-    c->fo_prep.seq = 0;
-    hipLaunchKernelGGL(k_front_out_prep, dim3(l.a.tiles, n), dim3(256), 0, c->stream, l.a, l.dp, s0, c->fo_az.p, c->fo_ent.p, c->fo_d.p);
-    URF_HIP(c, hipGetLastError());   /* (the mark only behind a launch that was accepted) */
-    c->fo_prep.seq = c->last_seq;
-    c->fo_prep.s0 = s0;
-    c->fo_prep.n = n;
-    return URF_OK;
+    if ((rc = launch_readouts(c, l.run, st, s0, n, w.view(0, c->sstride), products, prep, false, false, d)) == URF_OK && prep)
+        c->fo_prep = { c->last_seq, s0, n };   /* (the mark only behind a launch that was accepted) */
+    return rc;
 }
 
 /* The lists k_ordered_lists wrote for scans [s0, s0 + n) of a dense call, from padded positions to the caller's dense indices, in place
@@ -2647,7 +1629,7 @@ static int dense_unmap(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t
     const int rc = grow(c, c->dn_inv, (size_t)c->max_points * c->max_batch, st);
     if (rc != URF_OK)
         return rc;
-    const uint32_t WL = l.a.max_len, max_len = l.dense.max_len;   /* (the padded call's scans are W * L points each) */
+    const uint32_t WL = l.run.a.max_len, max_len = l.dense.max_len;   /* (the padded call's scans are W * L points each) */
     urf_dense_unmap_args u{ c->offsets_copy, max_len, WL, c->dn_pos.p, c->dn_inv.p };
     if (c->dn_inv_of != c->dn_calls) {
         c->dn_inv_of = 0;
@@ -2667,22 +1649,9 @@ static int dense_unmap(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t
 static int launch_ordered(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t n, uint32_t* d_road, uint32_t* d_curb, uint32_t* d_r10,
                           uint32_t stride, uint32_t* d_counts)
 {
-    const urf_kargs& a = l.a;   /* the call's own arguments and parameters, whatever was set since */
-    const urf_dev_params& dp = l.dp;
-    const bool fused = a.front != 0;   /* (last_call: only with urf_set_front_outputs on) a scan is either kind's, decided on the device */
-    int rc = ensure_order_scratch(c, n);
-    if (rc == URF_OK && fused)
-        rc = front_out_prepare(c, l, s0, n);
+    const int rc = readouts_of_last(c, l, s0, n, URF_SWEEP_OUT_ORDER, urf_readout_dst{ d_road, d_curb, d_r10, stride, d_counts, nullptr, nullptr });
     if (rc != URF_OK)
         return rc;
-    hipLaunchKernelGGL(k_ring_order, dim3((unsigned)dp.p.channels, n), dim3(256), (2 * (size_t)a.tiles + 1) * sizeof(unsigned), c->stream, a, dp,
-                       s0, c->ord_keys.p, c->ord_pos.p, c->ord_cls.p);
-    if (fused)
-        hipLaunchKernelGGL(k_ring_order_front, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, c->fo_az.p, c->fo_ent.p,
-                           c->ord_pos.p, c->ord_cls.p);
-    hipLaunchKernelGGL(k_ordered_lists, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, c->ord_pos.p, c->ord_cls.p, d_road,
-                       d_curb, d_r10, stride, d_counts);
-    URF_HIP(c, hipGetLastError());
     return l.dense.on ? dense_unmap(c, l, s0, n, d_road, d_curb, d_r10, stride, d_counts) : URF_OK;   /* (refuse_dense: the switch is on) */
 }
 
@@ -2690,7 +1659,7 @@ extern "C" int urf_ordered_indices_batch(urf_ctx* c, uint32_t* d_road, uint32_t*
                                          uint32_t* d_counts)
 {
     const urf_last_call* l = c ? last_valid(c) : nullptr;
-    if (!l || !d_counts || refuse_dense(c, "urf_ordered_indices_batch", true) || stride < (l->dense.on ? l->dense.max_len : l->a.max_len))
+    if (!l || !d_counts || refuse_dense(c, "urf_ordered_indices_batch", true) || stride < (l->dense.on ? l->dense.max_len : l->run.a.max_len))
         return URF_ERR_INVALID_ARG;   /* (a dense call's lists hold dense points: none is longer than its max_len) */
     const int rc = last_call(c, 0, l, URF_NEED_RING_ORDER);
     return rc != URF_OK ? rc : launch_ordered(c, *l, 0, l->scans, d_road, d_curb, d_ring10, stride, d_counts);
@@ -2751,7 +1720,7 @@ static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, ur
     const bool dense = l->dense.on;
     if (dense && order == URF_ORDER_REFERENCE && refuse_dense(c, "urf_clouds_batch_* with URF_ORDER_REFERENCE", true))
         return URF_ERR_INVALID_ARG;
-    const uint32_t S = l->scans, max_len = dense ? l->dense.max_len : l->a.max_len, stride = max_len ? max_len : 1u;
+    const uint32_t S = l->scans, max_len = dense ? l->dense.max_len : l->run.a.max_len, stride = max_len ? max_len : 1u;
     if (d_records && capacity < 3ull * S * max_len)
         return URF_ERR_CAPACITY;
     URF_HIP(c, hipSetDevice(c->device));
@@ -2768,7 +1737,7 @@ static int clouds_batch(urf_ctx* c, int kind, urf_clouds_args src, int order, ur
     }
     if (rc != URF_OK)
         return rc;
-    const urf_kargs& a = l->a;   /* (after a rerun: the same labels, inputs and offsets) */
+    const urf_kargs& a = l->run.a;   /* (after a rerun: the same labels, inputs and offsets) */
     src.labels = a.labels;
     src.offsets = a.offsets;
     src.info = a.info;
@@ -2827,9 +1796,9 @@ extern "C" int urf_clouds_batch_soa(urf_ctx* c, const float* d_intensity, int or
         return URF_ERR_INVALID_ARG;
     urf_clouds_args src{};
     src.src = URF_SRC_SOA;
-    src.x = (const unsigned*)c->last.a.x;
-    src.y = (const unsigned*)c->last.a.y;
-    src.z = (const unsigned*)c->last.a.z;
+    src.x = (const unsigned*)c->last.run.a.x;
+    src.y = (const unsigned*)c->last.run.a.y;
+    src.z = (const unsigned*)c->last.run.a.z;
     src.in = (const unsigned*)d_intensity;
     src.oi = -1;
     return clouds_batch(c, URF_LAST_SOA, src, order, d_records, capacity, d_counts, d_offsets);
@@ -2861,32 +1830,7 @@ extern "C" int urf_clouds_batch_pc2(urf_ctx* c, const uint8_t* d_data, uint32_t 
 
 static int launch_markers(urf_ctx* c, const urf_last_call& l, uint32_t s0, uint32_t n, float* d_pts, uint32_t* d_counts)
 {
-    const size_t cells = (size_t)URF_MAX_CHANNELS * URF_DEG_CELLS;
-    int rc;
-    if ((rc = grow(c, c->mk_d, n * cells, c->stream)) != URF_OK || (rc = grow(c, c->mk_pos, n * cells, c->stream)) != URF_OK ||
-        (rc = grow(c, c->mk_red, n * (cells + URF_MAX_CHANNELS), c->stream)) != URF_OK)
-        return rc;
-    const urf_kargs& a = l.a;
-    const urf_dev_params& dp = l.dp;
-    const bool fused = a.front != 0;   /* (as in launch_ordered) */
-    if (fused && (rc = front_out_prepare(c, l, s0, n)) != URF_OK)
-        return rc;
-    uint8_t* const mk_lit = c->mk_red.p + n * cells;
-    hipLaunchKernelGGL(k_marker_ring, dim3((unsigned)dp.p.channels, n), dim3(256), (2 * (size_t)a.tiles + 1) * sizeof(unsigned), c->stream, a, dp, s0,
-                       c->mk_d.p, c->mk_pos.p, c->mk_red.p, mk_lit);
-    /* rings in which the ORDER of equal azimuths decides a marker point (normally none: every workgroup returns at once) */
-    hipLaunchKernelGGL(k_marker_ring_literal, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, mk_lit, c->mk_d.p, c->mk_pos.p, c->mk_red.p);
-    if (fused) {
-        hipLaunchKernelGGL(k_marker_ring_front, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, c->fo_az.p, c->fo_ent.p,
-                           c->fo_d.p, c->mk_d.p, c->mk_pos.p, c->mk_red.p, mk_lit);
-        hipLaunchKernelGGL(k_marker_ring_literal_front, dim3((unsigned)dp.p.channels, n), dim3(256), 0, c->stream, a, dp, s0, mk_lit, c->fo_az.p,
-                           c->fo_ent.p, c->fo_d.p, c->mk_d.p, c->mk_pos.p, c->mk_red.p);
-    }
-    hipLaunchKernelGGL(k_marker_bins, dim3(n), dim3(384), 0, c->stream, a, dp, s0, c->mk_d.p, c->mk_pos.p, c->mk_red.p, d_pts, d_counts);
-    if (fused)
-        hipLaunchKernelGGL(k_marker_bins_front, dim3(n), dim3(384), 0, c->stream, a, dp, s0, c->mk_d.p, c->mk_pos.p, c->mk_red.p, d_pts, d_counts);
-    URF_HIP(c, hipGetLastError());
-    return URF_OK;
+    return readouts_of_last(c, l, s0, n, URF_SWEEP_OUT_MARKER_POINTS, urf_readout_dst{ nullptr, nullptr, nullptr, 0u, nullptr, d_pts, d_counts });
 }
 
 extern "C" int urf_marker_points_batch(urf_ctx* c, float* d_pts, uint32_t* d_counts)
@@ -2963,8 +1907,8 @@ static int fetch(urf_ctx* c, std::vector<T>& dst, const T* src, size_t count)
  * fills its first troff[t][C] slots. */
 static int ring_slot_sources(urf_ctx* c, const urf_last_call& l, uint32_t scan, uint32_t len, std::vector<uint32_t>& slot, std::vector<uint32_t>& src)
 {
-    const urf_kargs& k = l.a;
-    const unsigned C = (unsigned)l.dp.p.channels;
+    const urf_kargs& k = l.run.a;
+    const unsigned C = (unsigned)l.run.dp.p.channels;
     const unsigned ntiles = (len + URF_TILE - 1) / URF_TILE;
     std::vector<uint16_t> troff;
     std::vector<uint32_t> rec;
@@ -2990,7 +1934,7 @@ extern "C" int urf_read_stage(urf_ctx* c, urf_stage what, uint32_t scan, void* h
     if (rc != URF_OK)
         return rc;
     URF_HIP(c, hipStreamSynchronize(c->stream));
-    const urf_kargs& k = l->a;   /* the arguments and parameters of the call whose results are read */
+    const urf_kargs& k = l->run.a;   /* the arguments and parameters of the call whose results are read */
     uint32_t len;
     if (k.offsets) {
         uint32_t o2[2];
@@ -3001,7 +1945,7 @@ extern "C" int urf_read_stage(urf_ctx* c, urf_stage what, uint32_t scan, void* h
     } else {
         len = l->sweep_n ? l->sweep_n : k.n_per_scan;   /* (a padded sweep: the caller's points) */
     }
-    const unsigned C = (unsigned)l->dp.p.channels;
+    const unsigned C = (unsigned)l->run.dp.p.channels;
     const size_t sb = (size_t)scan * k.sstride;
     urf_scan_info in;
     URF_HIP(c, hipMemcpy(&in, k.info + scan, sizeof(in), hipMemcpyDeviceToHost));
@@ -3132,79 +2076,6 @@ extern "C" int urf_selftest_fast(urf_ctx* c, uint64_t n_samples, float* err)
         e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);
     URF_HIP(c, e);
-    return URF_OK;
-}
-
-/* Benchmark helper: the submit / collect loop of a C or C++ client of the callback path (a ROS node's
- * subscriber callback and publisher), timed natively -- `n_sweeps` messages (taken round robin from
- * `msgs`), at most `in_flight` of them submitted before the oldest is collected. */
-extern "C" int urf_bench_callback_stream(urf_ctx* c, const uint8_t* const* msgs, uint32_t n_msgs, uint32_t n_points,
-                                         uint32_t point_step, uint32_t off_x, uint32_t off_y, uint32_t off_z,
-                                         uint32_t n_sweeps, uint32_t in_flight, int producer_pinned, uint8_t* labels_out,
-                                         double* seconds)
-{
-    if (!c || !msgs || n_msgs == 0 || !seconds || in_flight == 0 || in_flight > URF_ASYNC_SLOTS)
-        return URF_ERR_INVALID_ARG;
-    for (uint32_t k = 0; k < n_msgs; k++)
-        if (!msgs[k])
-            return URF_ERR_INVALID_ARG;
-    const size_t bytes = (size_t)n_points * point_step;
-    uint32_t tickets[URF_ASYNC_SLOTS];
-    uint32_t head = 0, count = 0;   /* ring of tickets in flight */
-    urf_scan_info info;
-    struct timespec t0, t1;
-    c->ht_on = getenv("URF_HOST_TIMES") != nullptr;
-    for (double& v : c->ht)
-        v = 0.0;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    auto loop = [&]() -> int {
-        for (uint32_t k = 0; k < n_sweeps; k++) {
-            if (count == in_flight) {
-                const int rc = urf_classify_pc2_wait(c, tickets[head], labels_out, &info);
-                if (rc != URF_OK)
-                    return rc;
-                head = (head + 1) % URF_ASYNC_SLOTS;
-                count--;
-            }
-            const uint8_t* data = msgs[k % n_msgs];
-            if (producer_pinned) {   /* the producer fills the library's pinned buffer itself (each slot's once: producing the data is not what is timed) */
-                uint8_t* pin = nullptr;
-                const int rc = urf_pinned_input(c, bytes, &pin);
-                if (rc != URF_OK)
-                    return rc;
-                if (k < URF_ASYNC_SLOTS)
-                    std::memcpy(pin, data, bytes);
-                data = pin;
-            }
-            uint32_t t = 0;
-            const int rc = urf_classify_pc2_async(c, data, n_points, point_step, off_x, off_y, off_z, &t);
-            if (rc != URF_OK)
-                return rc;
-            tickets[(head + count) % URF_ASYNC_SLOTS] = t;
-            count++;
-        }
-        while (count) {
-            const int rc = urf_classify_pc2_wait(c, tickets[head], labels_out, &info);
-            if (rc != URF_OK)
-                return rc;
-            head = (head + 1) % URF_ASYNC_SLOTS;
-            count--;
-        }
-        return URF_OK;
-    };
-    const int lrc = loop();
-    if (lrc != URF_OK) {
-        c->ht_on = false;   /* (every exit path: a later call must not pay for the clock reads) */
-        return lrc;
-    }
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    *seconds = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
-    if (c->ht_on) {
-        fprintf(stderr, "host us per sweep (pinned %d, in flight %u): total %.1f | stage+h2d %.1f order %.1f launch %.1f record %.1f wait %.1f rest-of-wait %.1f\n",
-                producer_pinned, in_flight, 1e6 * *seconds / n_sweeps, 1e6 * c->ht[0] / n_sweeps, 1e6 * c->ht[1] / n_sweeps, 1e6 * c->ht[2] / n_sweeps,
-                1e6 * c->ht[3] / n_sweeps, 1e6 * c->ht[4] / n_sweeps, 1e6 * c->ht[5] / n_sweeps);
-        c->ht_on = false;
-    }
     return URF_OK;
 }
 

@@ -1,9 +1,11 @@
 /* urf_policy.hpp -- the launch policy of the host API: which kernels a call launches (urf_policy::plan) and which family of the fused
- * front end they belong to (urf_front_family_of).  Host code without a HIP call: it compiles with a plain C++17 compiler, and
- * tests/cpp/policy_table.cpp walks its decisions without a GPU. */
+ * front end they belong to (urf_front_family_of); the callback path's urf_sweep_shape and urf_seq_cache.  Host code without a HIP call:
+ * it compiles with a plain C++17 compiler, and tests/cpp/policy_*.cpp walk its decisions without a GPU. */
 #ifndef URF_POLICY_HPP
 #define URF_POLICY_HPP
 
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 
 #include "urf_internal.hpp"
@@ -356,5 +358,72 @@ static inline urf_front_family urf_front_family_of(uint32_t front, uint32_t fron
     return urf_front_family{ 1, (uint8_t)(front_lsh - 4u), wide, (uint8_t)(other ? cp : 5), front_ms != 0u, front_rows != 0u,
                              wide ? URF_FRONT128_TILES2(tiles) : tiles };
 }
+
+/* ---- the callback path's host decisions (urf_classify_pc2_async; tests/cpp/policy_sweep.cpp) ----
+ * The shape a sweep runs as and the bytes to ask its slot's message buffers for (cap: what the smaller of them holds).  urf_set_sweep_quantum:
+ * the sweep runs as the next multiple of the quantum, (NaN, NaN, NaN) behind its own points -- the reference drops non-finite points before
+ * anything else -- and every sweep of that padded length replays one captured sequence; beyond max_points: unpadded, under its own key. */
+struct urf_sweep_dims { uint32_t n_run; bool pad; size_t want; };   /* the points it runs as | in a padded sequence | bytes for slot_prepare */
+static inline urf_sweep_dims urf_sweep_shape(uint32_t n_points, uint32_t point_step, uint32_t quantum, uint32_t max_points, bool planes, size_t cap)
+{
+    uint32_t n_run = n_points;
+    bool pad = false;
+    if (const uint32_t q = quantum) {
+        const uint64_t up = ((uint64_t)n_points + q - 1) / q * q;
+        if (up <= max_points) {
+            n_run = (uint32_t)up;
+            pad = true;   /* (a multiple of the quantum too: it shares the padded sequence of its length) */
+        }
+    }
+    const size_t bytes = (size_t)n_points * point_step;
+    const size_t n4 = ((size_t)n_run + 3) & ~(size_t)3;
+    const size_t plane_bytes = 3 * sizeof(float) * n4;
+    size_t want = planes && plane_bytes > bytes ? plane_bytes : bytes;
+    if (pad && want > cap) {
+        /* a new buffer forgets the slot's sequences, and the messages of such a stream keep growing by a few points: room for twice the
+         * padded length (at most max_points), so that the lengths to come fit the buffer this one gets */
+        const size_t room = std::min<size_t>(2 * (size_t)n_run, max_points);
+        want = std::max(want, ((room + 3) & ~(size_t)3) * std::max<size_t>(point_step, 3 * sizeof(float)));
+    }
+    return urf_sweep_dims{ n_run, pad, want };
+}
+
+/* A slot's captured launch sequences as the host decides about them: entry i is live (captured into), was built for key[3] = { epoch,
+ * n_run << 32 | point_step, the offsets } and ran last at `used` (urf_ctx::seq_clock); graph and run: urf_ctx::slot_t::seqs[i]. */
+struct urf_seq_cache {
+    struct entry { bool live = false; uint64_t key[3] = { 0, 0, 0 }, used = 0; } e[URF_SWEEP_SEQS];
+    void take(unsigned i, const uint64_t* key) { e[i] = entry{ true, { key[0], key[1], key[2] }, 0 }; }
+    void drop(unsigned i) { e[i] = entry{}; }
+    /* the sequences are no sweep's any more (a new message buffer, the other staging format): the slot's next submission drops them */
+    void invalidate() { for (entry& q : e) q.key[0] = 0; }
+    /* The entry a sweep of `key` runs from.  release(i), which ends in drop(i), is called for every entry of another epoch, whatever its key;
+     * hit = false: the caller releases, captures into and take()s the one returned -- the first free of the first n_seqs, else their LRU. */
+    template <class F>
+    unsigned acquire(const uint64_t* key, unsigned n_seqs, bool& hit, F&& release)
+    {
+        unsigned at = 0;
+        hit = false;
+        for (unsigned i = 0; i < URF_SWEEP_SEQS; i++) {
+            if (e[i].live && e[i].key[0] != key[0])
+                release(i);
+            if (e[i].live && e[i].key[1] == key[1] && e[i].key[2] == key[2]) {
+                at = i;
+                hit = true;
+            }
+        }
+        for (unsigned i = 0; !hit && i < n_seqs && e[at].live; i++)   /* (no entry holds the key: room) */
+            if (!e[i].live || e[i].used < e[at].used)
+                at = i;
+        return at;
+    }
+    /* the sequences a sweep of `epoch` can still replay (urf_callback_path_captures) */
+    unsigned resident(uint64_t epoch) const
+    {
+        unsigned n = 0;
+        for (const entry& q : e)
+            n += (q.live && q.key[0] == epoch) ? 1u : 0u;
+        return n;
+    }
+};
 
 #endif /* URF_POLICY_HPP */
